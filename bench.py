@@ -21,6 +21,11 @@ sits in the timed data path (independent systems); RCCL carries the
 outside the timed region, one all-gather of the densities (`marshalling_ms`).
 
 Prints ONE JSON line on rank 0 (fields per the driver contract, plus `roofline`, `fill` and `cpu_baseline`).
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned, the densities of the job's systems,
+as DIR/density_real.npy and DIR/density_imag.npy (float64, batch axis first).  The inputs depend on the arguments alone, so two
+builds run with the same arguments can be compared output for output.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of
+the systems is written instead (their batch indices in DIR/density_index.npy).
 """
 from __future__ import annotations
 
@@ -42,6 +47,8 @@ FP64_MFMA_PEAK_TFLOPS = 78.6      # MI355X FP64 matrix, vendor spec (256 CU x 4 
 HBM_PEAK_GBS = 8000.0
 CLASSES = ["tables", "fill", "rhs", "panel", "swap", "trsm", "gemm", "back", "gemm_small"]
 DEFAULT_SYSTEMS = {1: 4096, 2: 512, 3: 256, 4: 64, 5: 512}
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 0
 
 
 # ------------------------------------------------------------------------------------------------
@@ -172,6 +179,28 @@ def cpu_baseline(w, n_sys: int, reps: int, one_thread: bool):
     return res, idx, out
 
 
+def dump_outputs(out_dir: str, density) -> None:
+    """Write the densities (complex, batch axis first) as float64 real / imaginary parts; a seeded sample of the systems
+    when the whole would exceed DUMP_LIMIT_BYTES."""
+    import torch
+
+    d = density.detach()
+    n = int(d.shape[0])
+    per_system = 2 * 8 * (d[0].numel() if n else 0)
+    keep = n if per_system == 0 else min(n, DUMP_LIMIT_BYTES // per_system)
+    index = None
+    if keep < n:
+        index = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        d = d[torch.as_tensor(index, dtype=torch.long, device=d.device)]
+    a = d.cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "density_real.npy"), np.ascontiguousarray(a.real, dtype=np.float64))
+    np.save(os.path.join(out_dir, "density_imag.npy"), np.ascontiguousarray(a.imag, dtype=np.float64))
+    if index is not None:
+        np.save(os.path.join(out_dir, "density_index.npy"), index.astype(np.float64))
+    print(f"bench.py: wrote {'all ' + str(n) if index is None else f'{keep} of {n}'} systems' densities to {out_dir}", file=sys.stderr)
+
+
 # ------------------------------------------------------------------------------------------------
 def _spawn_ranks(args) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks as child processes.  This parent never initialises a GPU
@@ -215,7 +244,10 @@ def main() -> int:
     ap.add_argument("--sym-vs-lu-systems", type=int, default=16, help="systems of the timed batch re-solved with the pivoted LU for the whole-batch accuracy figure")
     ap.add_argument("--single-system", action="store_true", help="also for cfg 3 / 5 (batches of different systems): latency of the first system alone, one system per call (default only for the one-system configs 1, 2, 4: its small launches would enter a profiler's per-kernel averages of the default run)")
     ap.add_argument("--no-single-system", action="store_true", help="skip the one-system-per-call latency measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's densities under DIR as .npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return _spawn_ranks(args)
@@ -304,6 +336,7 @@ def main() -> int:
     launches = (C.c_longlong * 9)()
     L.check(lib.biem_profile_end(ms, work, launches))
     marshalling_ms, rccl_ranks = None, None
+    dump = calc.density if dist is None else None     # (several ranks: the gathered densities of the whole job, below)
     if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if share else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -318,12 +351,17 @@ def main() -> int:
         barrier()
         marshalling_ms = (time.perf_counter() - tg) * 1e3
         assert full.shape[0] == n_total
+        if args.dump_outputs and rank == 0:
+            dump = full
         del full
 
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
         return 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dump)
+    del dump
 
     systems_per_step = n_total
     stats_timed = dict(impl._last_solve_stats)
