@@ -216,6 +216,13 @@ int biem_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long ld
   return launch_sym_factor_solve(nb, n_pad, nrhs, d_A, lda, sys_stride, d_info, d_work, work_bytes, (hipStream_t)stream, false);
 }
 
+int biem_sym_factor_solve_n(int nb, int n_pad, int n_active, int nrhs, double* d_A, long long lda, long long sys_stride, int* d_info,
+                            void* d_work, size_t work_bytes, void* stream) {
+  NEED(d_A, "d_A"); NEED(d_info, "d_info"); NEED(d_work, "d_work");
+  if (n_active < 1 || n_active > n_pad) { set_error("%s: n_active=%d outside 1 .. n_pad=%d", __func__, n_active, n_pad); return BIEM_ERR_ARG; }
+  return launch_sym_factor_solve(nb, n_pad, nrhs, d_A, lda, sys_stride, d_info, d_work, work_bytes, (hipStream_t)stream, false, n_active);
+}
+
 int biem_density(const biem_plan* plan, int nb, int B, int nrhs, const double* d_x, long long sys_stride, long long elem_stride,
                  long long rhs_stride, const double* d_tab, double* d_density, void* stream) {
   NEED_DEV(plan); NEED(d_x, "d_x"); NEED(d_tab, "d_tab"); NEED(d_density, "d_density");

@@ -180,6 +180,13 @@ int biem_ldlt_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long l
  * growth: -(Npad + 1)) and acceptance tests as biem_ldlt_factor_solve. */
 int biem_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long lda, long long sys_stride, int* d_info /*[nb]*/,
                           void* d_work, size_t work_bytes, void* stream);
+/* biem_sym_factor_solve for systems of n_active <= n_pad unknowns (1 <= n_active): rows and columns n_active .. n_pad-1 of every
+ * system are identity padding (the caller's promise) and the right-hand sides' padding rows are zero.  Where the whole system fits
+ * the one-launch LDS-resident path (n_active <= 128, nrhs <= 8, n_active + nrhs <= 128; what biem_solve_ldlt runs for small
+ * systems) the padding rows and columns are neither read nor written; otherwise the blocked factorisation runs over all n_pad
+ * rows as biem_sym_factor_solve does.  Arguments, workspace and d_info as biem_sym_factor_solve. */
+int biem_sym_factor_solve_n(int nb, int n_pad, int n_active, int nrhs, double* d_A, long long lda, long long sys_stride,
+                            int* d_info /*[nb]*/, void* d_work, size_t work_bytes, void* stream);
 
 /* density[s][r][b][h] = x / (gh * blc): the reference's `density` from the equilibrated unknowns (also the
  * single-ball shortcut _biem.py:648-691 with x = f).  x element (s, r, i) at d_x[s*sys_stride + i*elem_stride + r*rhs_stride]. */
