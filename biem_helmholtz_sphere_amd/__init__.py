@@ -7,11 +7,13 @@ typing helpers, plus the coordinate-tree factory the reference imports from ``ul
 __version__ = "0.1.0"
 
 from ._biem import (
+    BIEMFactorization,
     BIEMKwargs,
     BIEMResultCalculator,
     BIEMResultCalculatorProtocol,
     UinCallable,
     biem,
+    biem_factorize,
     biem_u,
     max_memory,
     max_n_end,
@@ -21,11 +23,13 @@ from ._biem import (
 from ._coords import SphericalCoordinates, create_from_branching_types
 
 __all__ = [
+    "BIEMFactorization",
     "BIEMKwargs",
     "BIEMResultCalculator",
     "BIEMResultCalculatorProtocol",
     "UinCallable",
     "biem",
+    "biem_factorize",
     "biem_u",
     "max_memory",
     "max_n_end",

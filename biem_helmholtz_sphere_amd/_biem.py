@@ -36,8 +36,8 @@ warnings.filterwarnings("error", category=ComplexWarning)
 Array = Any
 
 __all__ = [
-    "BIEMKwargs", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem", "biem_u",
-    "max_memory", "max_n_end", "plane_wave", "point_source",
+    "BIEMFactorization", "BIEMKwargs", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
+    "biem_factorize", "biem_u", "max_memory", "max_n_end", "plane_wave", "point_source",
 ]
 
 
@@ -886,3 +886,227 @@ def biem_u(res: Any, x: Array, /, far_field: bool = False, per_ball: bool = Fals
                                    flags, _ptr(out), _ptr(work), wb, _stream_ptr(dev)), "biem_uscat")
     out = out.reshape(xshape + batch + ((B,) if per_ball else ()))
     return origin.give(out)
+
+
+# --------------------------------------------------------------------------------------
+# factor once, solve many (an extension: the reference factors again on every call, :797)
+# --------------------------------------------------------------------------------------
+class BIEMFactorization:
+    """The factored operator of one :func:`biem_factorize` call: solve any number of incident fields against it.
+
+    The operator (geometry, k, eta, alpha, beta, kind) is fixed; :meth:`solve` takes ``uin`` / ``uin_grad`` and returns what
+    ``biem(..., uin=uin, uin_grad=uin_grad)`` returns for the same arguments.  Systems are kept in U^T U form (``n_symmetric``)
+    or, where the symmetric factorisation rejected them (or with ``BIEM_SOLVER=lu``), in pivoted LU form (``n_lu``).  The
+    factors stay in device memory (``nbytes``) until the object is dropped or :meth:`close` is called; solving never
+    modifies them.
+    """
+
+    def __init__(self, *, c, n_end, kind, origin, dev, batch, perm, plan, fl, centers_t, radii_t, k_t, eta_t, k_complex,
+                 alpha_zero, beta_zero, tab, factors, ipiv, lu_runs, n_symmetric, n_lu, chunk):
+        self.c, self.n_end, self.kind = c, n_end, kind
+        self._origin, self._dev, self._batch, self._perm, self._plan, self._fl = origin, dev, tuple(batch), perm, plan, fl
+        self._centers_t, self._radii_t, self._k_t, self._eta_t, self._k_complex = centers_t, radii_t, k_t, eta_t, k_complex
+        self._alpha_zero, self._beta_zero = alpha_zero, beta_zero
+        self._tab, self._factors, self._ipiv, self._lu_runs = tab, factors, ipiv, lu_runs
+        self.n_symmetric, self.n_lu, self._chunk = n_symmetric, n_lu, chunk
+        self._closed = False
+
+    @property
+    def nbytes(self) -> int:
+        """Device bytes held: factors, pivots of the LU-form systems and the per-ball tables."""
+        return sum(int(t.numel() * t.element_size()) for t in (self._tab, self._factors, self._ipiv) if t is not None)
+
+    def close(self) -> None:
+        """Release the device memory now; :meth:`solve` raises afterwards."""
+        self._tab = self._factors = self._ipiv = None
+        self._closed = True
+
+    def __repr__(self) -> str:
+        return (f"BIEMFactorization(c={self.c!r}, n_end={self.n_end}, kind={self.kind!r}, batch={self._batch}, "
+                f"n_symmetric={self.n_symmetric}, n_lu={self.n_lu}, nbytes={self.nbytes}{', closed' if self._closed else ''})")
+
+    def solve(self, *, uin: Callable[[Array], Array] | None = None,
+              uin_grad: Callable[[Array], Array] | None = None) -> BIEMResultCalculator:
+        """Densities of the incident field (uin, uin_grad) against the stored factors: ``biem()``'s result for the same field."""
+        if self._closed:
+            raise ValueError("BIEMFactorization is closed")
+        origin, dev, plan, fl, batch = self._origin, self._dev, self._plan, self._fl, self._batch
+        lib = L.load()
+        B, H, n_end, nb = fl.B, plan.H, self.n_end, fl.nb
+        has_rhs = not (uin is None and uin_grad is None)
+        density = None
+        if has_rhs:
+            if uin is None and not self._alpha_zero:
+                raise ValueError("alpha is not zero, but uin is None. uin must be provided to compute the boundary condition.")
+            if uin_grad is None and not self._beta_zero:
+                raise ValueError("beta is not zero, but uin_grad is None. uin_grad must be provided to compute the boundary condition.")
+            g, full, op_axes, rhs_axes = _boundary_samples(plan, origin, fl, batch, uin, uin_grad, self._perm)
+            nrhs = int(g.shape[1])
+            density_t = torch.empty((nb, nrhs, B, H), dtype=torch.complex128, device=dev)
+            sp = _stream_ptr(dev)
+            with torch.cuda.device(dev):
+                if nb > 0 and self._factors is None:
+                    # single ball: density = f / (blc (alpha h + beta k h'))    (reference :648-691, as biem())
+                    f = torch.empty((nb, nrhs, B * H), dtype=torch.complex128, device=dev)
+                    L.check(lib.biem_rhs_project(plan.handle, nb, B, nrhs, _ptr(g), _ptr(f), nrhs * B * H, 1, B * H, sp), "biem_rhs_project")
+                    L.check(lib.biem_density(plan.handle, nb, B, nrhs, _ptr(f), nrhs * B * H, 1, B * H, _ptr(self._tab), _ptr(density_t), sp),
+                            "biem_density")
+                elif nb > 0:
+                    n_pad = int(self._factors.shape[-1])
+                    sst = n_pad * n_pad
+                    if self.n_symmetric > 0:
+                        wb = int(lib.biem_solve_factored_workspace_bytes(plan.handle, nb, B, nrhs))
+                        work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+                        L.check(lib.biem_solve_factored(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab), _ptr(g),
+                                                        _ptr(density_t), _ptr(work), wb, sp), "biem_solve_factored")
+                        del work
+                    # LU-form systems (runs of consecutive systems): equilibrated right-hand sides in natural order, stored LU, density
+                    ldx = nrhs
+                    for s0, s1 in self._lu_runs:
+                        n = s1 - s0
+                        x = torch.zeros((n, n_pad, ldx), dtype=torch.complex128, device=dev)
+                        xs = n_pad * ldx
+                        L.check(lib.biem_rhs_project(plan.handle, n, B, nrhs, _ptr(g[s0:s1]), _ptr(x), xs, ldx, 1, sp), "biem_rhs_project")
+                        L.check(lib.biem_lu_solve(n, n_pad, nrhs, _ptr(self._factors[s0]), n_pad, sst, _ptr(self._ipiv[s0]), _ptr(x), ldx, xs, sp),
+                                "biem_lu_solve")
+                        L.check(lib.biem_density(plan.handle, n, B, nrhs, _ptr(x), xs, ldx, 1, _ptr(self._tab[s0]), _ptr(density_t[s0]), sp),
+                                "biem_density")
+            density = origin.give(_restore_batch(density_t, full, op_axes, rhs_axes).contiguous())
+
+        ndim_first = self._k_t.ndim
+        if uin is None:
+            uin_wrapped = None
+        else:
+            def uin_wrapped(x: Array, /, *, expand_x: bool = True) -> Array:   # reference :803-806
+                if expand_x:
+                    x = x[(...,) + (None,) * ndim_first]
+                return uin(x)
+
+        real_out = lambda t: origin.give(t.to(origin.real_dtype), complex_out=False)
+        return BIEMResultCalculator(
+            c=self.c,
+            centers=real_out(torch.movedim(self._centers_t, -1, 0)),
+            radii=real_out(self._radii_t),
+            k=(origin.give(self._k_t) if self._k_complex else real_out(self._k_t.real)),
+            n_end=n_end,
+            eta=real_out(self._eta_t),
+            kind=self.kind,
+            uin=uin_wrapped,
+            density=density,
+            matrix=(self._matrix if (B > 1 or not has_rhs) else None),
+        )
+
+    def _matrix(self) -> Array:
+        """The reference-scaled matrix of every system (as ``BIEMResultCalculator.matrix`` of ``biem()``), assembled on demand."""
+        plan, fl, dev, lib = self._plan, self._fl, self._dev, L.load()
+        nb, B, H, n_end = fl.nb, fl.B, plan.H, self.n_end
+        with torch.cuda.device(dev):
+            N = B * H
+            tab = torch.empty((nb, B, 3, n_end), dtype=torch.complex128, device=dev)
+            L.check(lib.biem_ball_tables(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
+                                         _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), _stream_ptr(dev)), "biem_ball_tables")
+            wb = int(lib.biem_fill_workspace_bytes(plan.handle, nb, B))
+            work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+            A = torch.empty((nb, N, N), dtype=torch.complex128, device=dev)
+            L.check(lib.biem_fill(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.centers), fl.geom_batched, _ptr(tab), L.FILL_REFERENCE,
+                                  _ptr(A), N, N * N, N, _ptr(work), wb, _stream_ptr(dev)), "biem_fill")
+            return self._origin.give(A.reshape(self._batch + (B, H, B, H)))
+
+
+def biem_factorize(
+    c: Any,
+    /,
+    *,
+    centers: Array,
+    radii: Array,
+    k: Array,
+    n_end: int,
+    alpha: Array | complex = 1.0,
+    beta: Array | complex = 0.0,
+    eta: Array | None = None,
+    kind: Literal["inner", "outer"] = "outer",
+    chunk: int = 0,
+) -> BIEMFactorization:
+    r"""Factor the BIEM operator of :func:`biem` once; solve incident fields against it later with ``.solve(uin=, uin_grad=)``.
+
+    Arguments and their checks are those of :func:`biem` without the incident field; alpha and beta belong to the operator.
+    The factors of all systems of the batch are kept on the device, ``nb x n_pad^2 x 16`` bytes (n_pad = B H rounded up to
+    64); if they do not fit, ``torch.OutOfMemoryError`` states the bytes needed - the batch is never split silently, since
+    factors that are not kept cannot be reused.  ``chunk`` bounds how many systems are filled and factored at once (0 =
+    choose); it sizes the workspace on top of the factors, not the factors.  A single ball keeps only its tables (the
+    shortcut of :func:`biem`).
+    """
+    origin, dev, batch, centers_t, radii_t, k_t, eta_t, alpha_t, beta_t = _check_biem_inputs(c, centers, radii, k, eta, alpha, beta)
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    lib = L.load()
+    B = int(radii_t.shape[-1])
+    plan = _plan(tree, n_end, dev)
+    H = plan.H
+    fl = _flatten(batch, B, centers_t if list(perm) == list(range(len(perm))) else centers_t[..., list(perm)], radii_t, k_t, eta_t, alpha_t, beta_t)
+    nb = fl.nb
+    sp = _stream_ptr(dev)
+    _all_zero = lambda v, v_t: (v == 0) if isinstance(v, (int, float, complex)) else bool(torch.all(v_t == 0))
+    solver = os.environ.get("BIEM_SOLVER", "ldlt")
+    if solver not in ("ldlt", "lu"):
+        raise ValueError(f"BIEM_SOLVER must be 'ldlt' or 'lu', got {solver!r}")
+    factors = ipiv = None
+    lu_runs: list = []
+    n_sym = n_lu = 0
+    chunk = int(chunk)
+    with torch.cuda.device(dev):
+        tab = torch.empty((nb, B, 3, n_end), dtype=torch.complex128, device=dev)
+        if nb > 0 and B == 1:
+            L.check(lib.biem_ball_tables(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
+                                         _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), sp), "biem_ball_tables")
+        elif nb > 0:
+            n_pad = int(lib.biem_lu_npad(B * H))
+            fbytes = nb * n_pad * n_pad * 16
+            wb = int(lib.biem_factor_workspace_bytes(plan.handle, nb, B, chunk))
+            free, _total = torch.cuda.mem_get_info(dev)
+            avail = free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            if fbytes + wb > avail:
+                raise torch.OutOfMemoryError(
+                    f"biem_factorize: the factors of {nb} systems of {n_pad} unknowns need {fbytes} bytes "
+                    f"(+ {wb} bytes of workspace), {avail} bytes are available on {dev}; factor fewer systems per call")
+            try:
+                factors = torch.empty((nb, n_pad, n_pad), dtype=torch.complex128, device=dev)
+            except torch.OutOfMemoryError as e:
+                raise torch.OutOfMemoryError(f"biem_factorize: the factors of {nb} systems need {fbytes} bytes: {e}") from e
+            info = torch.zeros(nb, dtype=torch.int32, device=dev)
+            work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+            L.check(lib.biem_factor_ldlt(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
+                                         _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(factors), n_pad, n_pad * n_pad, _ptr(tab),
+                                         _ptr(info), chunk, _ptr(work), wb, sp), "biem_factor_ldlt")
+            del work
+            # systems the symmetric factorisation rejected (or all of them with BIEM_SOLVER=lu): pivoted LU of the equilibrated
+            # system in the same slot, as biem() re-solves them
+            redo = np.ones(nb, dtype=bool) if solver == "lu" else (info.cpu().numpy() < 0)
+            n_lu = int(redo.sum())
+            n_sym = nb - n_lu
+            if n_lu > 0:
+                ipiv = torch.zeros((nb, n_pad), dtype=torch.int32, device=dev)
+                idx = np.flatnonzero(redo)
+                starts = [int(i) for i in idx if i == 0 or not redo[i - 1]]
+                ends = [int(i) + 1 for i in idx if i == nb - 1 or not redo[i + 1]]
+                per_chunk = chunk if chunk > 0 else max(1, min(nb, (4 << 30) // max(1, int(lib.biem_lu_workspace_bytes(1, n_pad, 0))
+                                                                                        + int(lib.biem_fill_workspace_bytes(plan.handle, 1, B)))))
+                for r0, r1 in zip(starts, ends):
+                    for s0 in range(r0, r1, per_chunk):
+                        s1 = min(r1, s0 + per_chunk)
+                        lu_runs.append((s0, s1))
+                        n = s1 - s0
+                        fwb = int(lib.biem_fill_workspace_bytes(plan.handle, n, B))
+                        lwb = int(lib.biem_lu_workspace_bytes(n, n_pad, 0))
+                        work = torch.empty(max(fwb, lwb, 16), dtype=torch.uint8, device=dev)
+                        cen = _ptr(fl.centers[s0]) if fl.geom_batched else _ptr(fl.centers)
+                        L.check(lib.biem_fill(plan.handle, n, B, _ptr(fl.k[s0:]), cen, fl.geom_batched, _ptr(tab[s0]), L.FILL_EQUILIBRATED,
+                                              _ptr(factors[s0]), n_pad, n_pad * n_pad, n_pad, _ptr(work), fwb, sp), "biem_fill")
+                        L.check(lib.biem_lu_factor(n, n_pad, _ptr(factors[s0]), n_pad, n_pad * n_pad, _ptr(ipiv[s0]), _ptr(info[s0:]),
+                                                   _ptr(work), lwb, sp), "biem_lu_factor")
+                        del work
+        alpha_zero = _all_zero(alpha, alpha_t)
+        beta_zero = _all_zero(beta, beta_t)
+    return BIEMFactorization(c=c, n_end=n_end, kind=kind, origin=origin, dev=dev, batch=batch, perm=perm, plan=plan, fl=fl,
+                             centers_t=centers_t, radii_t=radii_t, k_t=k_t, eta_t=eta_t, k_complex=_is_complex(k),
+                             alpha_zero=alpha_zero, beta_zero=beta_zero, tab=tab, factors=factors, ipiv=ipiv, lu_runs=lu_runs,
+                             n_symmetric=n_sym, n_lu=n_lu, chunk=chunk)

@@ -57,6 +57,12 @@ SIGNATURES = {
     "biem_ldlt_factor_solve": (_i, [_i, _i, _i, _dp, _ll, _ll, _ip, _ip, _vp, _sz, _vp]),
     "biem_sym_factor_solve": (_i, [_i, _i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
     "biem_sym_factor_solve_n": (_i, [_i, _i, _i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
+    "biem_sym_factor": (_i, [_i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
+    "biem_sym_solve": (_i, [_i, _i, _i, _dp, _ll, _ll, _dp, _ll, _ll, _vp]),
+    "biem_factor_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "biem_factor_ldlt": (_i, [_vp, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _ll, _ll, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_solve_factored_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "biem_solve_factored": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _vp, _sz, _vp]),
     "biem_profile_begin": (_i, []),
     "biem_profile_end": (_i, [_vp, _vp, _vp]),
     "biem_bench_mfma_f64": (_i, [_i, C.POINTER(C.c_double), _vp]),

@@ -363,6 +363,129 @@ int biem_solve_ldlt(const biem_plan* plan, int nb, int B, int nrhs, const double
                     chunk, d_work, work_bytes, stream, true);
 }
 
+// ---- factor now, solve later: the symmetric path split at the factorisation -------------------------------------------------
+int biem_sym_factor(int nb, int n_pad, double* d_A, long long lda, long long sys_stride, int* d_info, void* d_work, size_t work_bytes,
+                    void* stream) {
+  NEED(d_A, "d_A"); NEED(d_info, "d_info"); NEED(d_work, "d_work");
+  return launch_sym_factor_solve(nb, n_pad, 0, d_A, lda, sys_stride, d_info, d_work, work_bytes, (hipStream_t)stream, false);
+}
+
+int biem_sym_solve(int nb, int n_pad, int nrhs, const double* d_U, long long lda, long long sys_stride, double* d_B, long long ldb,
+                   long long b_stride, void* stream) {
+  NEED(d_U, "d_U"); NEED(d_B, "d_B");
+  return launch_sym_solve(nb, n_pad, nrhs, d_U, lda, sys_stride, d_B, ldb, b_stride, (hipStream_t)stream);
+}
+
+namespace {
+struct FactorLayout {
+  int N, n_pad, chunk;
+  size_t off_T, off_P, total;
+};
+FactorLayout make_factor_layout(const biem_plan* p, int nb, int B, int chunk) {
+  FactorLayout L;
+  L.N = B * p->H;
+  L.n_pad = lu_npad(L.N);
+  if (chunk <= 0) {
+    // fill and factorisation workspace of ~4 GiB at most: the factors themselves are the caller's, all of them resident
+    const size_t per = fill_workspace_bytes(p, 1, B) + lu_workspace_bytes(1, L.n_pad, 0);
+    const size_t fit = ((size_t)4 << 30) / (per ? per : 1);
+    chunk = (int)(fit < 1 ? 1 : (fit > (size_t)nb ? (size_t)nb : fit));
+  }
+  if (chunk > nb) chunk = nb;
+  if (chunk < 1) chunk = 1;
+  L.chunk = chunk;
+  size_t o = 0;
+  L.off_T = o; o = align256(o + fill_workspace_bytes(p, chunk, B));
+  L.off_P = o; o = align256(o + lu_workspace_bytes(chunk, L.n_pad, 0));
+  L.total = o;
+  return L;
+}
+inline long long solve_ldx(int nrhs) { return ((long long)nrhs + 7) / 8 * 8; }   // rows of the right-hand sides 128-byte aligned
+}  // namespace
+
+size_t biem_factor_workspace_bytes(const biem_plan* plan, int nb, int B, int chunk) {
+  if (!plan || nb <= 0 || B <= 0) return 0;
+  return make_factor_layout(plan, nb, B, chunk).total;
+}
+
+int biem_factor_ldlt(const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_centers,
+                     const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, double* d_F,
+                     long long lda, long long sys_stride, double* d_tab, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                     void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_eta, "d_eta"); NEED(d_centers, "d_centers"); NEED(d_radii, "d_radii");
+  NEED(d_alpha, "d_alpha"); NEED(d_beta, "d_beta"); NEED(d_F, "d_F"); NEED(d_tab, "d_tab"); NEED(d_info, "d_info"); NEED(d_work, "d_work");
+  if (nb < 0 || nb > 65535 || B < 0) { set_error("%s: 0 .. 65535 systems per call and B >= 0 (got nb=%d, B=%d)", __func__, nb, B); return BIEM_ERR_ARG; }
+  if (nb == 0 || B == 0) return BIEM_OK;
+  const FactorLayout L = make_factor_layout(plan, nb, B, chunk);
+  if (lda < L.n_pad || sys_stride < (long long)L.n_pad * lda) {
+    set_error("%s: lda=%lld < n_pad=%d or sys_stride=%lld < n_pad * lda", __func__, lda, L.n_pad, sys_stride);
+    return BIEM_ERR_ARG;
+  }
+  if (work_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, L.total); return BIEM_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)d_work;
+  void* T = w + L.off_T;
+  void* Pw = w + L.off_P;
+  const int d = plan->d;
+  int rc = launch_ball_tables(plan, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_tab, st);
+  if (rc) return rc;
+  const FillDedupe dd = {d_radii, d_alpha, d_beta};
+  for (int s0 = 0; s0 < nb; s0 += L.chunk) {
+    const int c = (nb - s0 < L.chunk) ? nb - s0 : L.chunk;
+    const double* ks = d_k + 2 * (size_t)s0;
+    const double* cen = d_centers + (geom_batched ? (size_t)s0 * B * d : 0);
+    const double* tb = d_tab + (size_t)s0 * B * 3 * plan->n_end * 2;
+    double* A = d_F + 2 * (size_t)s0 * sys_stride;
+    // identity padding written (no_padding = false) even where the one-launch path factors the active rows only: the solve runs
+    // over all n_pad rows and finds U = I there
+    rc = launch_fill_sym(plan, c, B, ks, cen, geom_batched, tb, A, lda, sys_stride, L.n_pad, T, fill_workspace_bytes(plan, c, B), st, false,
+                         (!geom_batched && !ab_batched) ? &dd : nullptr);
+    if (rc) return rc;
+    rc = lu_growth_init(Pw, c, L.n_pad, 1.0, st);     // max |A~| >= 1 (unit diagonal), as in biem_solve_ldlt
+    if (rc) return rc;
+    rc = launch_sym_factor_solve(c, L.n_pad, 0, A, lda, sys_stride, d_info + s0, Pw, lu_workspace_bytes(c, L.n_pad, 0), st, true, L.N);
+    if (rc) return rc;
+  }
+  return BIEM_OK;
+}
+
+size_t biem_solve_factored_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs) {
+  if (!plan || nb <= 0 || B <= 0 || nrhs <= 0) return 0;
+  return (size_t)nb * lu_npad(B * plan->H) * solve_ldx(nrhs) * sizeof(cplx);
+}
+
+int biem_solve_factored(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                        const double* d_tab, const double* d_g, double* d_density, void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_F, "d_F"); NEED(d_tab, "d_tab"); NEED(d_g, "d_g"); NEED(d_density, "d_density"); NEED(d_work, "d_work");
+  if (nb < 0 || nb > 65535 || nrhs < 0 || nrhs > 65535 || B < 0) {
+    set_error("%s: 0 .. 65535 systems / right-hand sides per call and B >= 0 (got nb=%d, nrhs=%d, B=%d)", __func__, nb, nrhs, B);
+    return BIEM_ERR_ARG;
+  }
+  if (nb == 0 || nrhs == 0 || B == 0) return BIEM_OK;
+  const int n_pad = lu_npad(B * plan->H);
+  if (lda < n_pad || sys_stride < (long long)n_pad * lda) {
+    set_error("%s: lda=%lld < n_pad=%d or sys_stride=%lld < n_pad * lda", __func__, lda, n_pad, sys_stride);
+    return BIEM_ERR_ARG;
+  }
+  const size_t need = biem_solve_factored_workspace_bytes(plan, nb, B, nrhs);
+  if (work_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, need); return BIEM_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  // right-hand sides X[s][row][q] (row-major, ldx columns), rows in the slot order of the symmetric form; padding rows zero
+  double* X = (double*)d_work;
+  const long long ldx = solve_ldx(nrhs), xs = (long long)n_pad * ldx;
+  double* Xaug = X - 2 * (size_t)n_pad;      // X seen as the augmented columns n_pad .. of a matrix with leading dimension ldx
+  BIEM_HIPCHK(hipMemsetAsync(X, 0, need, st));
+  int rc = launch_rhs_project(plan, nb, B, nrhs, d_g, X, xs, ldx, 1, st, true);
+  if (rc) return rc;
+  rc = launch_sym_rhs(plan, nb, B, nrhs, n_pad, d_tab, Xaug, ldx, xs, false, st);
+  if (rc) return rc;
+  rc = launch_sym_solve(nb, n_pad, nrhs, d_F, lda, sys_stride, X, ldx, xs, st);
+  if (rc) return rc;
+  rc = launch_sym_rhs(plan, nb, B, nrhs, n_pad, d_tab, Xaug, ldx, xs, true, st);
+  if (rc) return rc;
+  return launch_density(plan, nb, B, nrhs, X, xs, ldx, 1, d_tab, d_density, st, true);
+}
+
 int biem_profile_begin(void) {
   Profiler& p = profiler();
   for (auto& r : p.recs) { p.pool.push_back(r.a); p.pool.push_back(r.b); }

@@ -112,6 +112,9 @@ int lu_growth_init(void* d_work, int nb, int n_pad, double amax, hipStream_t st)
 // right-hand-side columns (slot order): f~ = R W^H f in place; inverse_on_solution: x = W R^-1 x~
 int launch_sym_rhs(const biem_plan* p, int nb, int B, int nrhs, int n_pad, const double* d_tab, double* d_A, long long lda,
                    long long sys_stride, bool inverse_on_solution, hipStream_t st);
+// solve with a stored U^T U factor (upper triangle, identity-padded): forward U^T y = f, back U x = y, B row-major [n_pad][ldb] per system
+int launch_sym_solve(int nb, int n_pad, int nrhs, const double* d_U, long long lda, long long sys_stride, double* d_B, long long ldb,
+                     long long b_stride, hipStream_t st);
 int launch_lu_solve(int nb, int n_pad, int nrhs, const double* d_LU, long long lda, long long sys_stride, const int* d_ipiv, double* d_B,
                     long long ldb, long long b_stride, hipStream_t st);
 int bench_mfma_f64(int iters, double* tflops, hipStream_t st, int variant = 0);

@@ -2400,6 +2400,128 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
   return BIEM_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Solve with a stored U^T U factor (biem_sym_solve, biem_solve_factored): U^T y = f, then U x = y.  The fused path gets the forward
+// elimination for free inside its trailing updates; a factor kept for later right-hand sides needs it on its own.  Per 64-row
+// block j, top down:
+//   k_fwd_utu_diag    y_j = U[j,j]^{-T} f_j (lower triangular): the block in LDS once per workgroup, one wave per right-hand side
+//   k_fwd_utu_update  f[r] -= sum_{c in block j} U[c, r] y_c for every r right of the block: a 64-row strip of U, contiguous along r
+//                     in the row-major factor.  TR columns per workgroup; each U element is loaded once, into registers, and used for
+//                     every right-hand side (register tiles of FWD_NQ, the 64 rows c split over 256 / TR thread groups and summed in
+//                     LDS in a fixed order, so two solves of the same data agree bit for bit).
+// Launch form: TR = 64 when the step has enough 64-column tiles over all systems to fill the chip, else TR = 16 (four times the
+// workgroups per system: one system alone spreads its strip over ~n_pad / 16 workgroups).  Back substitution: the column form of
+// the fused path (k_back_diag + k_back_update, without the checks the factorisation already took).  4 n_pad / 64 launches in all.
+// Each U element takes 8 nrhs flops per 16 bytes read: the update is bound by memory bandwidth below ~20 right-hand sides (78.6
+// FP64 TFLOP/s over 8 TB/s) and by the VALU above.
+// ---------------------------------------------------------------------------------------------
+constexpr int FWD_RG = 4;          // right-hand sides per workgroup of the diagonal step (one per wave)
+constexpr int FWD_NQ = 8;          // right-hand sides per register tile of the strip update
+constexpr long long FWD_WIDE_MIN = 1024;   // workgroups of the TR = 64 form from which it is used (4 per CU)
+
+__global__ void __launch_bounds__(256) k_fwd_utu_diag(const cplx* __restrict__ A, long long lda, long long sys_stride, cplx* __restrict__ F,
+                                                       long long ldf, long long f_stride, int nrhs, int j) {
+  __shared__ cplx sU[NB][NB + 1];
+  const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const cplx* Ub = A + (size_t)s * sys_stride + (size_t)j * lda + j;
+  for (int e = threadIdx.x; e < NB * NB; e += 256) { const int r = e >> 6, c = e & 63; if (c >= r) sU[r][c] = Ub[(size_t)r * lda + c]; }
+  __syncthreads();
+  const int q = blockIdx.y * FWD_RG + wave;
+  if (q >= nrhs) return;
+  cplx* Fq = F + (size_t)s * f_stride + (size_t)j * ldf + q;
+  cplx y = Fq[(size_t)lane * ldf];
+  const cplx inv = crecip(sU[lane][lane]);
+  // (U^T)[r][c] = u_cr: x_c = y_c / u_cc, then every row r > c takes u_cr x_c off (one wave: x_c travels by a lane broadcast)
+  for (int c = 0; c < NB; ++c) {
+    const cplx t = cmul(y, inv);
+    const cplx xc = make_double2(lane_bcast(t.x, c), lane_bcast(t.y, c));
+    if (lane == c) y = xc;
+    if (lane > c) y = cfnma(sU[c][lane], xc, y);
+  }
+  Fq[(size_t)lane * ldf] = y;
+}
+
+template <int TR>
+__global__ void __launch_bounds__(256) k_fwd_utu_update(const cplx* __restrict__ A, long long lda, long long sys_stride, cplx* __restrict__ F,
+                                                         long long ldf, long long f_stride, int nrhs, int j, int n_pad) {
+  constexpr int KG = 256 / TR;       // thread groups over the 64 rows c of the strip
+  constexpr int KR = NB / KG;        // rows c per group
+  __shared__ cplx sy[NB][FWD_NQ];
+  __shared__ cplx sred[KG][FWD_NQ][TR + 1];
+  const int s = blockIdx.y, t = threadIdx.x, col = t % TR, kg = t / TR;
+  const int r0 = j + NB + blockIdx.x * TR;
+  const cplx* As = A + (size_t)s * sys_stride;
+  cplx* Fs = F + (size_t)s * f_stride;
+  cplx u[KR];
+#pragma unroll
+  for (int k = 0; k < KR; ++k) u[k] = r0 + col < n_pad ? As[(size_t)(j + kg * KR + k) * lda + r0 + col] : make_double2(0.0, 0.0);
+  for (int q0 = 0; q0 < nrhs; q0 += FWD_NQ) {
+    const int nq = nrhs - q0 < FWD_NQ ? nrhs - q0 : FWD_NQ;
+    if (q0 > 0) __syncthreads();                  // the previous tile's sums have been read
+    for (int e = t; e < NB * FWD_NQ; e += 256) {
+      const int c = e / FWD_NQ, q = e % FWD_NQ;
+      sy[c][q] = q < nq ? Fs[(size_t)(j + c) * ldf + q0 + q] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    cplx acc[FWD_NQ];
+#pragma unroll
+    for (int q = 0; q < FWD_NQ; ++q) acc[q] = make_double2(0.0, 0.0);
+#pragma unroll
+    for (int k = 0; k < KR; ++k)
+#pragma unroll
+      for (int q = 0; q < FWD_NQ; ++q) acc[q] = cfma(u[k], sy[kg * KR + k][q], acc[q]);
+#pragma unroll
+    for (int q = 0; q < FWD_NQ; ++q) sred[kg][q][col] = acc[q];
+    __syncthreads();
+    // consecutive threads take consecutive right-hand sides of one row: the stores run along the row of F
+    for (int o = t; o < TR * FWD_NQ; o += 256) {
+      const int q = o % FWD_NQ, cc = o / FWD_NQ, r = r0 + cc;
+      if (q >= nq || r >= n_pad) continue;
+      cplx sum = sred[0][q][cc];
+#pragma unroll
+      for (int g = 1; g < KG; ++g) sum = cadd(sum, sred[g][q][cc]);
+      cplx* y = Fs + (size_t)r * ldf + q0 + q;
+      *y = csub(*y, sum);
+    }
+  }
+}
+
+int launch_sym_solve(int nb, int n_pad, int nrhs, const double* d_U, long long lda, long long sys_stride, double* d_B, long long ldb,
+                     long long b_stride, hipStream_t st) {
+  if (n_pad <= 0 || n_pad % NB) { set_error("biem_sym_solve: n_pad=%d is not a positive multiple of %d (use biem_lu_npad)", n_pad, NB); return BIEM_ERR_ARG; }
+  if (lda < n_pad || ldb < nrhs) { set_error("biem_sym_solve: lda < n_pad or ldb < nrhs"); return BIEM_ERR_ARG; }
+  if (nb < 0 || nrhs < 0 || nb > 65535 || nrhs > 65535) {
+    set_error("biem_sym_solve: 0 .. 65535 systems / right-hand sides per call (got %d / %d)", nb, nrhs);
+    return BIEM_ERR_ARG;
+  }
+  if (nb == 0 || nrhs == 0) return BIEM_OK;
+  const cplx* A = (const cplx*)d_U;
+  cplx* F = (cplx*)d_B;
+  {
+    ProfScope ps(PK_TRSM, st, 4.0 * (double)nb * n_pad * (double)n_pad * nrhs);
+    for (int j = 0; j < n_pad; j += NB) {
+      hipLaunchKernelGGL(k_fwd_utu_diag, dim3(nb, (nrhs + FWD_RG - 1) / FWD_RG), dim3(256), 0, st, A, lda, sys_stride, F, ldb, b_stride, nrhs, j);
+      const int rem = n_pad - (j + NB);
+      if (rem <= 0) continue;
+      if ((long long)nb * ((rem + 63) / 64) >= FWD_WIDE_MIN)
+        hipLaunchKernelGGL(k_fwd_utu_update<64>, dim3((rem + 63) / 64, nb), dim3(256), 0, st, A, lda, sys_stride, F, ldb, b_stride, nrhs, j, n_pad);
+      else
+        hipLaunchKernelGGL(k_fwd_utu_update<16>, dim3((rem + 15) / 16, nb), dim3(256), 0, st, A, lda, sys_stride, F, ldb, b_stride, nrhs, j, n_pad);
+    }
+  }
+  {
+    ProfScope ps(PK_BACK, st, 4.0 * (double)nb * n_pad * (double)n_pad * nrhs);
+    for (int jr = n_pad - BS; jr >= 0; jr -= BS) {
+      hipLaunchKernelGGL(k_back_diag, dim3(nb, nrhs), dim3(64), 0, st, A, lda, sys_stride, F, ldb, b_stride, jr);
+      if (jr > 0)
+        hipLaunchKernelGGL(k_back_update, dim3((jr + BACK_ROWS - 1) / BACK_ROWS, nb), dim3(256), 0, st, A, lda, sys_stride, F, ldb, b_stride,
+                           nrhs, jr, 0, jr);
+    }
+  }
+  BIEM_LAUNCHCHK();
+  return BIEM_OK;
+}
+
 // Solve with the stored factors of launch_lu_factor_solve(keep_multipliers = true): the multipliers of a panel are stored in the
 // row order its own 64 interchanges left (later panels' interchanges are not applied to them), so the forward substitution
 // interleaves interchanges and eliminations panel by panel; L D L^T factors are the case ipiv = identity, U = D L^T.

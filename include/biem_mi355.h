@@ -224,6 +224,38 @@ int biem_solve_ldlt(const biem_plan* plan, int nb, int B, int nrhs, const double
                     int ab_batched, const double* d_g, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
                     void* stream);
 
+/* ---- factor now, solve later: the symmetric path split at its factorisation (the reference factors again on every call,
+ *      _biem.py:797).  A factor is kept and solved against any number of times; the solve reads it and never writes it. ----
+ * biem_sym_factor: biem_sym_factor_solve with no right-hand side (lda >= n_pad suffices): on return the upper triangle of every
+ * system holds U with A = U^T U, for every n_pad (the one-launch path of n_pad <= 128 stores the whole U too); d_info and workspace
+ * as biem_sym_factor_solve (biem_lu_workspace_bytes(nb, n_pad, 0)).
+ * biem_sym_solve: U^T U x = b with such a factor (only its upper triangle is read): B row-major [n_pad][ldb] per system (nrhs <= ldb
+ * columns, system s at d_B + 2*s*b_stride doubles; rows of an identity-padded system past its size must hold zeros), overwritten by
+ * the solutions.  Forward solve U^T y = b by 64-row blocks (diagonal step, then an update of the rows below from the 64-row strip of U
+ * right of the block, each U element read once for all right-hand sides), back solve by the column form of biem_sym_factor_solve.
+ * No workspace; n_pad a multiple of 64, lda >= n_pad, ldb >= nrhs, at most 65535 systems and right-hand sides. */
+int biem_sym_factor(int nb, int n_pad, double* d_A, long long lda, long long sys_stride, int* d_info /*[nb]*/, void* d_work,
+                    size_t work_bytes, void* stream);
+int biem_sym_solve(int nb, int n_pad, int nrhs, const double* d_U, long long lda, long long sys_stride, double* d_B, long long ldb,
+                   long long b_stride, void* stream);
+/* biem_factor_ldlt: ball tables (into d_tab [nb][B][3][n_end], which the solve needs), symmetric fill and U^T U factorisation of the
+ * systems of biem_solve_ldlt, without right-hand sides, into the caller's factor buffer d_F (n_pad = biem_lu_npad(B H) rows, lda >=
+ * n_pad, system s at d_F + 2*s*sys_stride doubles, sys_stride >= n_pad lda; identity padding written).  Same chunking of the fill and
+ * factorisation workspace (`chunk` systems at a time, 0 = choose; the factors of ALL nb systems stay in d_F), pair-block dedupe and
+ * d_info codes as biem_solve_ldlt: a system with d_info[s] < 0 is to be factored by the pivoted LU instead (biem_fill with
+ * BIEM_FILL_EQUILIBRATED into the same slot, biem_lu_factor; solved by biem_lu_solve).  Workspace: biem_factor_workspace_bytes.
+ * biem_solve_factored: densities [nb][nrhs][B][H] of the right-hand sides d_g [nb][nrhs][B][Q] (as biem_solve_ldlt) against such
+ * factors: biem_rhs_project in slot order, f~ = R W^H f, biem_sym_solve, x = W R^-1 x~, biem_density.  Systems in LU form are not
+ * told apart: their densities are the caller's to replace.  Workspace: biem_solve_factored_workspace_bytes (the right-hand sides). */
+size_t biem_factor_workspace_bytes(const biem_plan* plan, int nb, int B, int chunk);
+int biem_factor_ldlt(const biem_plan* plan, int nb, int B, const double* d_k /*c128*/, const double* d_eta, const double* d_centers,
+                     const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, double* d_F,
+                     long long lda, long long sys_stride, double* d_tab, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                     void* stream);
+size_t biem_solve_factored_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs);
+int biem_solve_factored(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                        const double* d_tab, const double* d_g, double* d_density, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- per-kernel-class timing with HIP events on the launch stream (thread-local; used by bench.py for the
  *      live `roofline` figures).  Between begin and end every launch of the calling thread is bracketed by two
  *      events; end synchronises on them and returns, per class, elapsed ms, algorithmic work and launch count.
