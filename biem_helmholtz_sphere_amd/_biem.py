@@ -469,7 +469,32 @@ def _warn_biem_inputs(k: Any, eta: Any) -> None:
         warnings.warn("The solution may be incorrectif not (Im k >= 0 and eta Re k >= 0).", UserWarning, stacklevel=4)
 
 
-def _check_biem_inputs(c, centers, radii, k, eta, alpha, beta):
+@dataclass
+class _Operator:
+    """Everything of one biem() / biem_factorize() call that does not depend on the incident field."""
+
+    c: Any
+    n_end: int
+    kind: str
+    origin: _Origin
+    dev: torch.device
+    batch: Tuple[int, ...]
+    perm: Tuple[int, ...]    # canonical axis i = the caller's axis perm[i]
+    plan: _Plan
+    fl: _Flat                # in canonical axes
+    centers_t: torch.Tensor  # the caller's arrays on the device, caller's axes
+    radii_t: torch.Tensor
+    k_t: torch.Tensor
+    eta_t: torch.Tensor
+    k_complex: bool
+    alpha: Any               # alpha / beta as given (Python scalars are tested for zero on the host) and on the device
+    beta: Any
+    alpha_t: torch.Tensor
+    beta_t: torch.Tensor
+
+
+def _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind) -> _Operator:
+    """Input checks of reference :240-326, the operands on the device and the plan."""
     batch = _validate_biem_inputs(c, centers, radii, k, eta, alpha, beta)
     _warn_biem_inputs(k, eta)
     origin, dev = _origin_of(centers, radii, k, eta, alpha, beta)
@@ -487,7 +512,13 @@ def _check_biem_inputs(c, centers, radii, k, eta, alpha, beta):
     beta_t = _to_dev(beta, dev, torch.complex128)
     if beta_t.ndim == 0:
         beta_t = beta_t[(None,) * (k_t.ndim + 1)]
-    return origin, dev, batch, centers_t, radii_t, k_t, eta_t, alpha_t, beta_t
+    # trees with primed nodes run as their canonical tree in permuted axes (canonical component i = original perm[i])
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    plan = _plan(tree, n_end, dev)
+    fl = _flatten(batch, centers_t if list(perm) == list(range(len(perm))) else centers_t[..., list(perm)], radii_t, k_t, eta_t,
+                  alpha_t, beta_t)
+    return _Operator(c, n_end, kind, origin, dev, tuple(batch), perm, plan, fl, centers_t, radii_t, k_t, eta_t, _is_complex(k),
+                     alpha, beta, alpha_t, beta_t)
 
 
 # --------------------------------------------------------------------------------------
@@ -495,7 +526,7 @@ def _check_biem_inputs(c, centers, radii, k, eta, alpha, beta):
 # --------------------------------------------------------------------------------------
 @dataclass
 class _Flat:
-    """Flattened, contiguous device operands of one biem() call."""
+    """Flattened, contiguous device operands of one biem() call (biem_u: the geometry only, alpha / beta None)."""
 
     nb: int
     B: int
@@ -504,14 +535,14 @@ class _Flat:
     centers: torch.Tensor    # [nb or 1, B, d]
     radii: torch.Tensor      # [nb or 1, B]
     geom_batched: int
-    alpha: torch.Tensor      # [nb or 1, B] complex128
-    beta: torch.Tensor
-    ab_batched: int
+    alpha: Optional[torch.Tensor] = None     # [nb or 1, B] complex128
+    beta: Optional[torch.Tensor] = None
+    ab_batched: int = 0
 
 
-def _flatten(batch, B, centers_t, radii_t, k_t, eta_t, alpha_t, beta_t) -> _Flat:
+def _flatten(batch, centers_t, radii_t, k_t, eta_t, alpha_t=None, beta_t=None) -> _Flat:
     nb = int(np.prod(batch)) if len(batch) else 1
-    d = centers_t.shape[-1]
+    B, d = int(radii_t.shape[-1]), centers_t.shape[-1]
     kf = k_t.expand(batch).reshape(nb).contiguous()
     ef = eta_t.expand(batch).reshape(nb).contiguous()
     geom_b = any(s != 1 for s in tuple(centers_t.shape[:-2]) + tuple(radii_t.shape[:-1]))
@@ -520,7 +551,9 @@ def _flatten(batch, B, centers_t, radii_t, k_t, eta_t, alpha_t, beta_t) -> _Flat
         rf = radii_t.expand(tuple(batch) + (B,)).reshape(nb, B).contiguous()
     else:
         cf = centers_t.reshape(1, B, d).contiguous()
-        rf = radii_t.expand(radii_t.shape[:-1] + (B,)).reshape(1, B).contiguous()
+        rf = radii_t.reshape(1, B).contiguous()
+    if alpha_t is None:
+        return _Flat(nb, B, kf, ef, cf, rf, int(geom_b))
     ab_b = any(s != 1 for s in tuple(alpha_t.shape[:-1]) + tuple(beta_t.shape[:-1]))
     if ab_b:
         af = alpha_t.expand(tuple(batch) + (B,)).reshape(nb, B).contiguous()
@@ -531,10 +564,98 @@ def _flatten(batch, B, centers_t, radii_t, k_t, eta_t, alpha_t, beta_t) -> _Flat
     return _Flat(nb, B, kf, ef, cf, rf, int(geom_b), af, bf, int(ab_b))
 
 
-def _boundary_samples(plan: _Plan, origin: _Origin, fl: _Flat, batch, uin, uin_grad, perm) -> torch.Tensor:
+def _check_incident(op: _Operator, uin, uin_grad) -> None:
+    """The boundary condition needs uin where alpha != 0 and uin_grad where beta != 0.  The zero tests run only when the matching
+    callable is missing; Python scalars are decided on the host (a device tensor costs a synchronisation)."""
+    def all_zero(v, v_t):
+        return (v == 0) if isinstance(v, (int, float, complex)) else bool(torch.all(v_t == 0))
+    if uin is None and not all_zero(op.alpha, op.alpha_t):
+        raise ValueError("alpha is not zero, but uin is None. uin must be provided to compute the boundary condition.")
+    if uin_grad is None and not all_zero(op.beta, op.beta_t):
+        raise ValueError("beta is not zero, but uin_grad is None. uin_grad must be provided to compute the boundary condition.")
+
+
+def _solver() -> str:
+    solver = os.environ.get("BIEM_SOLVER", "ldlt")
+    if solver not in ("ldlt", "lu"):
+        raise ValueError(f"BIEM_SOLVER must be 'ldlt' or 'lu', got {solver!r}")
+    return solver
+
+
+def _available_bytes(dev: torch.device) -> int:
+    """Device memory this process can still get: free plus what torch's caching allocator holds unused."""
+    free, _total = torch.cuda.mem_get_info(dev)
+    return free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+
+
+def _ball_tables(op: _Operator, sp: int, fill: bool = True) -> torch.Tensor:
+    """The per-ball tables [nb, B, 3, n_end] of biem_ball_tables (fill=False: only allocated, for an entry that writes them)."""
+    fl, plan = op.fl, op.plan
+    tab = torch.empty((fl.nb, fl.B, 3, op.n_end), dtype=torch.complex128, device=op.dev)
+    if fill:
+        L.check(L.load().biem_ball_tables(plan.handle, fl.nb, fl.B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
+                                          _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), sp), "biem_ball_tables")
+    return tab
+
+
+def _single_ball_density(op: _Operator, g: torch.Tensor, tab: torch.Tensor, density_t: torch.Tensor, sp: int) -> None:
+    """Single ball: density = f / (blc (alpha h + beta k h'))    (reference :648-691)."""
+    lib, plan, nb, B = L.load(), op.plan, op.fl.nb, op.fl.B
+    H, nrhs = plan.H, int(g.shape[1])
+    f = torch.empty((nb, nrhs, B * H), dtype=torch.complex128, device=op.dev)
+    L.check(lib.biem_rhs_project(plan.handle, nb, B, nrhs, _ptr(g), _ptr(f), nrhs * B * H, 1, B * H, sp), "biem_rhs_project")
+    L.check(lib.biem_density(plan.handle, nb, B, nrhs, _ptr(f), nrhs * B * H, 1, B * H, _ptr(tab), _ptr(density_t), sp), "biem_density")
+
+
+def _reference_matrix(op: _Operator) -> Array:
+    """The matrix of every system in the reference's scaling (``BIEMResultCalculator.matrix``), assembled on demand."""
+    plan, fl, dev, lib = op.plan, op.fl, op.dev, L.load()
+    nb, B, H = fl.nb, fl.B, plan.H
+    with torch.cuda.device(dev):
+        N = B * H
+        tab = _ball_tables(op, _stream_ptr(dev))
+        wb = int(lib.biem_fill_workspace_bytes(plan.handle, nb, B))
+        work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+        A = torch.empty((nb, N, N), dtype=torch.complex128, device=dev)
+        L.check(lib.biem_fill(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.centers), fl.geom_batched, _ptr(tab), L.FILL_REFERENCE,
+                              _ptr(A), N, N * N, N, _ptr(work), wb, _stream_ptr(dev)), "biem_fill")
+        return op.origin.give(A.reshape(op.batch + (B, H, B, H)))
+
+
+def _result(op: _Operator, uin, density_t: Optional[torch.Tensor], axes, with_matrix: bool) -> BIEMResultCalculator:
+    """What biem() returns: the operands and the density (axes: the layout _boundary_samples returned) in the caller's namespace."""
+    origin = op.origin
+    density = None if density_t is None else origin.give(_restore_batch(density_t, *axes).contiguous())
+    if uin is None:
+        uin_wrapped = None
+    else:
+        ndim_first = op.k_t.ndim
+
+        def uin_wrapped(x: Array, /, *, expand_x: bool = True) -> Array:   # reference :803-806
+            if expand_x:
+                x = x[(...,) + (None,) * ndim_first]
+            return uin(x)
+
+    real_out = lambda t: origin.give(t.to(origin.real_dtype), complex_out=False)
+    return BIEMResultCalculator(
+        c=op.c,
+        centers=real_out(torch.movedim(op.centers_t, -1, 0)),       # [..., B, v] -> [v, ..., B]  (reference :588)
+        radii=real_out(op.radii_t),
+        k=(origin.give(op.k_t) if op.k_complex else real_out(op.k_t.real)),
+        n_end=op.n_end,
+        eta=real_out(op.eta_t),
+        kind=op.kind,
+        uin=uin_wrapped,
+        density=density,
+        matrix=(lambda: _reference_matrix(op)) if with_matrix else None,
+    )
+
+
+def _boundary_samples(op: _Operator, uin, uin_grad) -> torch.Tensor:
     """g[nb, B, Q] = (-alpha u_in - beta d_n u_in)(c_b + rho_b y_q): the closure `f` of reference :611-624.
 
     fl.centers are in the plan's canonical axes; the user's callables see ORIGINAL axes (x_orig[perm[i]] = x_canon[i])."""
+    plan, origin, fl, batch, perm = op.plan, op.origin, op.fl, op.batch, op.perm
     dev, d, Q, B, nb = plan.dev, plan.d, plan.Q, fl.B, fl.nb
     qshape = plan.quad_shape()
     nbt = len(batch)
@@ -644,25 +765,18 @@ def biem(
     """
     if translational_coefficients_method not in (None, "gumerov", "plane_wave", "triplet"):
         raise ValueError(f"Invalid translational_coefficients_method: {translational_coefficients_method}")
-    origin, dev, batch, centers_t, radii_t, k_t, eta_t, alpha_t, beta_t = _check_biem_inputs(c, centers, radii, k, eta, alpha, beta)
-    # trees with primed nodes run as their canonical tree in permuted axes (canonical component i = original perm[i])
-    tree, perm = canonical_tree(c.branching_types_expression_str)
+    op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind)
     lib = L.load()
-    B = int(radii_t.shape[-1])
-    ndim_first = k_t.ndim
-    plan = _plan(tree, n_end, dev)
-    H, Q = plan.H, plan.Q
-    fl = _flatten(batch, B, centers_t if list(perm) == list(range(len(perm))) else centers_t[..., list(perm)], radii_t, k_t, eta_t, alpha_t, beta_t)
-    nb = fl.nb
+    plan, fl, dev = op.plan, op.fl, op.dev
+    B, nb, H = fl.B, fl.nb, plan.H
     sp = _stream_ptr(dev)
 
     has_rhs = not (uin is None and uin_grad is None)
-    g = None
-    full, op_axes, rhs_axes, nrhs = tuple(batch), list(range(len(batch))), [], 1
+    g = axes = None
     # A repeated call of the same shape takes its workspace FIRST, before the boundary samples: the block the previous call
     # returned to torch's caching allocator is then still whole.  Taken after them, one of their mid-size temporaries may have
     # been carved out of it - and a second block of that size need not exist (cfg 3's whole batch: 164 of 288 GB).
-    ws_key = (tree, int(n_end), int(nb), int(B), int(chunk), os.environ.get("BIEM_MAX_RESIDENT_BYTES"))
+    ws_key = (plan.tree, int(n_end), int(nb), int(B), int(chunk), os.environ.get("BIEM_MAX_RESIDENT_BYTES"))
     work_pre = None
     if has_rhs and nb > 0 and (B > 1 or force_matrix):
         memo = _ws_memo.get(dev)
@@ -673,14 +787,8 @@ def biem(
             except torch.OutOfMemoryError:
                 work_pre = None
     if has_rhs:
-        # (the all-zero tests are only needed when the matching callable is missing; Python scalars are decided on the host)
-        def _all_zero(v, v_t):
-            return (v == 0) if isinstance(v, (int, float, complex)) else bool(torch.all(v_t == 0))
-        if uin is None and not _all_zero(alpha, alpha_t):
-            raise ValueError("alpha is not zero, but uin is None. uin must be provided to compute the boundary condition.")
-        if uin_grad is None and not _all_zero(beta, beta_t):
-            raise ValueError("beta is not zero, but uin_grad is None. uin_grad must be provided to compute the boundary condition.")
-        g, full, op_axes, rhs_axes = _boundary_samples(plan, origin, fl, batch, uin, uin_grad, perm)
+        _check_incident(op, uin, uin_grad)
+        g, *axes = _boundary_samples(op, uin, uin_grad)
         nrhs = int(g.shape[1])
 
     use_matrix = (not has_rhs) or B > 1 or force_matrix          # reference :643-645
@@ -690,15 +798,8 @@ def biem(
             # an empty batch axis: nothing to solve, results of the right (empty) shape
             density_t = torch.empty((0, nrhs, B, H), dtype=torch.complex128, device=dev) if has_rhs else None
         elif not use_matrix:
-            # single ball: density = f / (blc (alpha h + beta k h'))    (reference :648-691)
-            tab = torch.empty((nb, B, 3, n_end), dtype=torch.complex128, device=dev)
-            L.check(lib.biem_ball_tables(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
-                                         _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), sp), "biem_ball_tables")
-            f = torch.empty((nb, nrhs, B * H), dtype=torch.complex128, device=dev)
-            L.check(lib.biem_rhs_project(plan.handle, nb, B, nrhs, _ptr(g), _ptr(f), nrhs * B * H, 1, B * H, sp), "biem_rhs_project")
             density_t = torch.empty((nb, nrhs, B, H), dtype=torch.complex128, device=dev)
-            L.check(lib.biem_density(plan.handle, nb, B, nrhs, _ptr(f), nrhs * B * H, 1, B * H, _ptr(tab), _ptr(density_t), sp),
-                    "biem_density")
+            _single_ball_density(op, g, _ball_tables(op, sp), density_t, sp)
         elif has_rhs:
             chunk = int(chunk)
             if chunk <= 0:
@@ -709,8 +810,7 @@ def biem(
                 if nb * per <= (1 << 30) and not os.environ.get("BIEM_MAX_RESIDENT_BYTES"):
                     chunk = nb                     # small jobs: everything resident, no memory query (it costs more than the solve)
                 else:
-                    free, _total = torch.cuda.mem_get_info(dev)
-                    avail = free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+                    avail = _available_bytes(dev)
                     if work_pre is not None:
                         avail += int(work_pre.numel())     # (the block taken in advance above is this call's own)
                     budget = int(0.85 * avail)
@@ -735,9 +835,7 @@ def biem(
             # U^T U factorisation without interchanges, half the flops of the LU.  Systems whose diagonal pivots were rejected
             # (info < 0: close to a resonance of a sphere, or strongly coupled spheres) are solved again with the pivoted LU,
             # which is what the reference's linalg.solve does for every system (_biem.py:797).  BIEM_SOLVER=lu: LU only.
-            solver = os.environ.get("BIEM_SOLVER", "ldlt")
-            if solver not in ("ldlt", "lu"):
-                raise ValueError(f"BIEM_SOLVER must be 'ldlt' or 'lu', got {solver!r}")
+            solver = _solver()
             entry = lib.biem_solve_ldlt if solver == "ldlt" else lib.biem_solve
             L.check(entry(plan.handle, nb, B, nrhs, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
                           _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(g), _ptr(density_t), _ptr(info), chunk,
@@ -768,44 +866,7 @@ def biem(
             if solver == "ldlt" and redo.numel() > 0:
                 _last_solve_stats["rejected_info"] = info_h[redo_h].tolist()[:64]
             del work
-
-    def make_matrix():
-        with torch.cuda.device(dev):
-            N = B * H
-            tab = torch.empty((nb, B, 3, n_end), dtype=torch.complex128, device=dev)
-            L.check(lib.biem_ball_tables(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
-                                         _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), _stream_ptr(dev)), "biem_ball_tables")
-            wb = int(lib.biem_fill_workspace_bytes(plan.handle, nb, B))
-            work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
-            A = torch.empty((nb, N, N), dtype=torch.complex128, device=dev)
-            L.check(lib.biem_fill(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.centers), fl.geom_batched, _ptr(tab), L.FILL_REFERENCE,
-                                  _ptr(A), N, N * N, N, _ptr(work), wb, _stream_ptr(dev)), "biem_fill")
-            return origin.give(A.reshape(tuple(batch) + (B, H, B, H)))
-
-    matrix = make_matrix if use_matrix else None
-    density = None if density_t is None else origin.give(_restore_batch(density_t, full, op_axes, rhs_axes).contiguous())
-
-    if uin is None:
-        uin_wrapped = None
-    else:
-        def uin_wrapped(x: Array, /, *, expand_x: bool = True) -> Array:   # reference :803-806
-            if expand_x:
-                x = x[(...,) + (None,) * ndim_first]
-            return uin(x)
-
-    real_out = lambda t: origin.give(t.to(origin.real_dtype), complex_out=False)
-    return BIEMResultCalculator(
-        c=c,
-        centers=real_out(torch.movedim(centers_t, -1, 0)),       # [..., B, v] -> [v, ..., B]  (reference :588)
-        radii=real_out(radii_t),
-        k=(origin.give(k_t) if _is_complex(k) else real_out(k_t.real)),
-        n_end=n_end,
-        eta=real_out(eta_t),
-        kind=kind,
-        uin=uin_wrapped,
-        density=density,
-        matrix=matrix,
-    )
+    return _result(op, uin, density_t, axes, use_matrix)
 
 
 # --------------------------------------------------------------------------------------
@@ -832,13 +893,13 @@ def biem_u(res: Any, x: Array, /, far_field: bool = False, per_ball: bool = Fals
     rad_t = _to_dev(res.radii, dev, f64)            # [...(first), B]
     dens_t = _to_dev(res.density, dev, torch.complex128)
     d = c.c_ndim
-    B = int(rad_t.shape[-1])
     H = int(dens_t.shape[-1])
     n_end = n_end_from_harm(tree, H)
     ndim_first = k_t.ndim
     batch = tuple(np.broadcast_shapes(tuple(k_t.shape), tuple(eta_t.shape), tuple(cen_t.shape[1:-1]), tuple(rad_t.shape[:-1]),
                                       tuple(dens_t.shape[:-2])))
-    nb = int(np.prod(batch)) if batch else 1
+    fl = _flatten(batch, torch.movedim(cen_t, 0, -1), rad_t, k_t, eta_t)
+    nb, B = fl.nb, fl.B
     plan = _plan(tree, n_end, dev)
 
     if isinstance(x, (list, tuple)):
@@ -866,24 +927,14 @@ def biem_u(res: Any, x: Array, /, far_field: bool = False, per_ball: bool = Fals
     if res.kind == "inner":
         flags |= L.USCAT_KIND_INNER
 
-    kf = k_t.expand(batch).reshape(nb).contiguous()
-    ef = eta_t.expand(batch).reshape(nb).contiguous()
-    geom_b = any(s != 1 for s in tuple(cen_t.shape[1:-1]) + tuple(rad_t.shape[:-1]))
-    cen_bd = torch.movedim(cen_t, 0, -1)            # [...(first), B, d]
-    if geom_b:
-        cf = cen_bd.expand(batch + (B, d)).reshape(nb, B, d).contiguous()
-        rf = rad_t.expand(batch + (B,)).reshape(nb, B).contiguous()
-    else:
-        cf = cen_bd.reshape(1, B, d).contiguous()
-        rf = rad_t.reshape(1, B).contiguous()
     df = dens_t.expand(batch + (B, H)).reshape(nb, B, H).contiguous()
     out = torch.empty((P, nb, B) if per_ball else (P, nb), dtype=torch.complex128, device=dev)
     with torch.cuda.device(dev):
         wb = int(lib.biem_uscat_workspace_bytes(plan.handle, nb, B))
         work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
         if P > 0 and nb > 0:
-            L.check(lib.biem_uscat(plan.handle, nb, B, P, _ptr(kf), _ptr(ef), _ptr(cf), _ptr(rf), int(geom_b), _ptr(df), _ptr(pts),
-                                   flags, _ptr(out), _ptr(work), wb, _stream_ptr(dev)), "biem_uscat")
+            L.check(lib.biem_uscat(plan.handle, nb, B, P, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
+                                   _ptr(df), _ptr(pts), flags, _ptr(out), _ptr(work), wb, _stream_ptr(dev)), "biem_uscat")
     out = out.reshape(xshape + batch + ((B,) if per_ball else ()))
     return origin.give(out)
 
@@ -901,12 +952,10 @@ class BIEMFactorization:
     modifies them.
     """
 
-    def __init__(self, *, c, n_end, kind, origin, dev, batch, perm, plan, fl, centers_t, radii_t, k_t, eta_t, k_complex,
-                 alpha_zero, beta_zero, tab, factors, ipiv, lu_runs, n_symmetric, n_lu, chunk):
-        self.c, self.n_end, self.kind = c, n_end, kind
-        self._origin, self._dev, self._batch, self._perm, self._plan, self._fl = origin, dev, tuple(batch), perm, plan, fl
-        self._centers_t, self._radii_t, self._k_t, self._eta_t, self._k_complex = centers_t, radii_t, k_t, eta_t, k_complex
-        self._alpha_zero, self._beta_zero = alpha_zero, beta_zero
+    def __init__(self, op: _Operator, *, tab, factors, ipiv, lu_runs, n_symmetric, n_lu, chunk):
+        self._op = op
+        self.c, self.n_end, self.kind = op.c, op.n_end, op.kind
+        self._plan = op.plan                   # (read by tools/time_factorized_solve.py)
         self._tab, self._factors, self._ipiv, self._lu_runs = tab, factors, ipiv, lu_runs
         self.n_symmetric, self.n_lu, self._chunk = n_symmetric, n_lu, chunk
         self._closed = False
@@ -922,7 +971,7 @@ class BIEMFactorization:
         self._closed = True
 
     def __repr__(self) -> str:
-        return (f"BIEMFactorization(c={self.c!r}, n_end={self.n_end}, kind={self.kind!r}, batch={self._batch}, "
+        return (f"BIEMFactorization(c={self.c!r}, n_end={self.n_end}, kind={self.kind!r}, batch={self._op.batch}, "
                 f"n_symmetric={self.n_symmetric}, n_lu={self.n_lu}, nbytes={self.nbytes}{', closed' if self._closed else ''})")
 
     def solve(self, *, uin: Callable[[Array], Array] | None = None,
@@ -930,27 +979,20 @@ class BIEMFactorization:
         """Densities of the incident field (uin, uin_grad) against the stored factors: ``biem()``'s result for the same field."""
         if self._closed:
             raise ValueError("BIEMFactorization is closed")
-        origin, dev, plan, fl, batch = self._origin, self._dev, self._plan, self._fl, self._batch
-        lib = L.load()
-        B, H, n_end, nb = fl.B, plan.H, self.n_end, fl.nb
+        op, lib = self._op, L.load()
+        plan, fl, dev = op.plan, op.fl, op.dev
+        B, H, nb = fl.B, plan.H, fl.nb
         has_rhs = not (uin is None and uin_grad is None)
-        density = None
+        density_t = axes = None
         if has_rhs:
-            if uin is None and not self._alpha_zero:
-                raise ValueError("alpha is not zero, but uin is None. uin must be provided to compute the boundary condition.")
-            if uin_grad is None and not self._beta_zero:
-                raise ValueError("beta is not zero, but uin_grad is None. uin_grad must be provided to compute the boundary condition.")
-            g, full, op_axes, rhs_axes = _boundary_samples(plan, origin, fl, batch, uin, uin_grad, self._perm)
+            _check_incident(op, uin, uin_grad)
+            g, *axes = _boundary_samples(op, uin, uin_grad)
             nrhs = int(g.shape[1])
             density_t = torch.empty((nb, nrhs, B, H), dtype=torch.complex128, device=dev)
             sp = _stream_ptr(dev)
             with torch.cuda.device(dev):
                 if nb > 0 and self._factors is None:
-                    # single ball: density = f / (blc (alpha h + beta k h'))    (reference :648-691, as biem())
-                    f = torch.empty((nb, nrhs, B * H), dtype=torch.complex128, device=dev)
-                    L.check(lib.biem_rhs_project(plan.handle, nb, B, nrhs, _ptr(g), _ptr(f), nrhs * B * H, 1, B * H, sp), "biem_rhs_project")
-                    L.check(lib.biem_density(plan.handle, nb, B, nrhs, _ptr(f), nrhs * B * H, 1, B * H, _ptr(self._tab), _ptr(density_t), sp),
-                            "biem_density")
+                    _single_ball_density(op, g, self._tab, density_t, sp)
                 elif nb > 0:
                     n_pad = int(self._factors.shape[-1])
                     sst = n_pad * n_pad
@@ -971,46 +1013,7 @@ class BIEMFactorization:
                                 "biem_lu_solve")
                         L.check(lib.biem_density(plan.handle, n, B, nrhs, _ptr(x), xs, ldx, 1, _ptr(self._tab[s0]), _ptr(density_t[s0]), sp),
                                 "biem_density")
-            density = origin.give(_restore_batch(density_t, full, op_axes, rhs_axes).contiguous())
-
-        ndim_first = self._k_t.ndim
-        if uin is None:
-            uin_wrapped = None
-        else:
-            def uin_wrapped(x: Array, /, *, expand_x: bool = True) -> Array:   # reference :803-806
-                if expand_x:
-                    x = x[(...,) + (None,) * ndim_first]
-                return uin(x)
-
-        real_out = lambda t: origin.give(t.to(origin.real_dtype), complex_out=False)
-        return BIEMResultCalculator(
-            c=self.c,
-            centers=real_out(torch.movedim(self._centers_t, -1, 0)),
-            radii=real_out(self._radii_t),
-            k=(origin.give(self._k_t) if self._k_complex else real_out(self._k_t.real)),
-            n_end=n_end,
-            eta=real_out(self._eta_t),
-            kind=self.kind,
-            uin=uin_wrapped,
-            density=density,
-            matrix=(self._matrix if (B > 1 or not has_rhs) else None),
-        )
-
-    def _matrix(self) -> Array:
-        """The reference-scaled matrix of every system (as ``BIEMResultCalculator.matrix`` of ``biem()``), assembled on demand."""
-        plan, fl, dev, lib = self._plan, self._fl, self._dev, L.load()
-        nb, B, H, n_end = fl.nb, fl.B, plan.H, self.n_end
-        with torch.cuda.device(dev):
-            N = B * H
-            tab = torch.empty((nb, B, 3, n_end), dtype=torch.complex128, device=dev)
-            L.check(lib.biem_ball_tables(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
-                                         _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), _stream_ptr(dev)), "biem_ball_tables")
-            wb = int(lib.biem_fill_workspace_bytes(plan.handle, nb, B))
-            work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
-            A = torch.empty((nb, N, N), dtype=torch.complex128, device=dev)
-            L.check(lib.biem_fill(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.centers), fl.geom_batched, _ptr(tab), L.FILL_REFERENCE,
-                                  _ptr(A), N, N * N, N, _ptr(work), wb, _stream_ptr(dev)), "biem_fill")
-            return self._origin.give(A.reshape(self._batch + (B, H, B, H)))
+        return _result(op, uin, density_t, axes, B > 1 or not has_rhs)
 
 
 def biem_factorize(
@@ -1036,34 +1039,23 @@ def biem_factorize(
     choose); it sizes the workspace on top of the factors, not the factors.  A single ball keeps only its tables (the
     shortcut of :func:`biem`).
     """
-    origin, dev, batch, centers_t, radii_t, k_t, eta_t, alpha_t, beta_t = _check_biem_inputs(c, centers, radii, k, eta, alpha, beta)
-    tree, perm = canonical_tree(c.branching_types_expression_str)
+    op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind)
     lib = L.load()
-    B = int(radii_t.shape[-1])
-    plan = _plan(tree, n_end, dev)
-    H = plan.H
-    fl = _flatten(batch, B, centers_t if list(perm) == list(range(len(perm))) else centers_t[..., list(perm)], radii_t, k_t, eta_t, alpha_t, beta_t)
-    nb = fl.nb
+    plan, fl, dev = op.plan, op.fl, op.dev
+    B, nb, H = fl.B, fl.nb, plan.H
     sp = _stream_ptr(dev)
-    _all_zero = lambda v, v_t: (v == 0) if isinstance(v, (int, float, complex)) else bool(torch.all(v_t == 0))
-    solver = os.environ.get("BIEM_SOLVER", "ldlt")
-    if solver not in ("ldlt", "lu"):
-        raise ValueError(f"BIEM_SOLVER must be 'ldlt' or 'lu', got {solver!r}")
+    solver = _solver()
     factors = ipiv = None
     lu_runs: list = []
     n_sym = n_lu = 0
     chunk = int(chunk)
     with torch.cuda.device(dev):
-        tab = torch.empty((nb, B, 3, n_end), dtype=torch.complex128, device=dev)
-        if nb > 0 and B == 1:
-            L.check(lib.biem_ball_tables(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
-                                         _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), sp), "biem_ball_tables")
-        elif nb > 0:
+        tab = _ball_tables(op, sp, fill=nb > 0 and B == 1)       # (biem_factor_ldlt writes them for B > 1)
+        if nb > 0 and B > 1:
             n_pad = int(lib.biem_lu_npad(B * H))
             fbytes = nb * n_pad * n_pad * 16
             wb = int(lib.biem_factor_workspace_bytes(plan.handle, nb, B, chunk))
-            free, _total = torch.cuda.mem_get_info(dev)
-            avail = free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            avail = _available_bytes(dev)
             if fbytes + wb > avail:
                 raise torch.OutOfMemoryError(
                     f"biem_factorize: the factors of {nb} systems of {n_pad} unknowns need {fbytes} bytes "
@@ -1104,9 +1096,4 @@ def biem_factorize(
                         L.check(lib.biem_lu_factor(n, n_pad, _ptr(factors[s0]), n_pad, n_pad * n_pad, _ptr(ipiv[s0]), _ptr(info[s0:]),
                                                    _ptr(work), lwb, sp), "biem_lu_factor")
                         del work
-        alpha_zero = _all_zero(alpha, alpha_t)
-        beta_zero = _all_zero(beta, beta_t)
-    return BIEMFactorization(c=c, n_end=n_end, kind=kind, origin=origin, dev=dev, batch=batch, perm=perm, plan=plan, fl=fl,
-                             centers_t=centers_t, radii_t=radii_t, k_t=k_t, eta_t=eta_t, k_complex=_is_complex(k),
-                             alpha_zero=alpha_zero, beta_zero=beta_zero, tab=tab, factors=factors, ipiv=ipiv, lu_runs=lu_runs,
-                             n_symmetric=n_sym, n_lu=n_lu, chunk=chunk)
+    return BIEMFactorization(op, tab=tab, factors=factors, ipiv=ipiv, lu_runs=lu_runs, n_symmetric=n_sym, n_lu=n_lu, chunk=chunk)
