@@ -18,9 +18,15 @@ Multi-GPU: one process per GPU.  Under torchrun (WORLD_SIZE set) the ranks are u
 starts N child processes itself (the parent never touches a GPU).  --scaling weak (default): every GPU owns S systems, the k's
 of the whole job are one linspace of S*N values; --scaling strong: the config's S systems are split S/N per GPU.  No collective
 sits in the timed data path (independent systems); RCCL carries the barrier / max-reduce of the timing and,
-outside the timed region, one all-gather of the densities (`marshalling_ms`).
+outside the timed region, one all-gather of the densities (timed as `marshalling_ms` with --full; a plain run gathers only for
+--dump-outputs).
 
-Prints ONE JSON line on rank 0 (fields per the driver contract, plus `roofline`, `fill` and `cpu_baseline`).
+Prints ONE JSON line on rank 0 (fields per the driver contract, plus `roofline`, `fill` and `stage_ms_per_step`, which come from the
+library's event timing of the timed steps).  A plain run does only what that line's headline needs: set-up, warm-up, the timed
+steps, --dump-outputs, the line.  --full adds what takes work of its own after the timed steps, each still shaped by its own
+options: the CPU baseline and the u_scat error vs the oracle (`cpu_baseline`, `max_rel_err_uscat`), the pivoted-LU re-solve
+(`sym_vs_lu`), the one-system-per-call latency (`single_system_ms`), the pure MFMA stream (`roofline.pure_mfma_stream_tflops`) and,
+with several ranks, the timed all-gather of the densities (`marshalling_ms`).  Without --full these fields are null.
 
 --dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned, the densities of the job's systems,
 as DIR/density_real.npy and DIR/density_imag.npy (float64, batch axis first).  The inputs depend on the arguments alone, so two
@@ -238,16 +244,20 @@ def main() -> int:
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--systems-per-gpu", type=int, default=0, help="0 = the config's batch (cfg3: 256, cfg5: 512; one-system configs: copies)")
     ap.add_argument("--chunk", type=int, default=0, help="resident matrices per pass (0 = library default)")
+    ap.add_argument("--full", action="store_true", help="also run the CPU baseline, the accuracy checks and the latency, MFMA-stream and "
+                    "marshalling figures after the timed steps (the options below shape them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-systems", type=int, default=4)
     ap.add_argument("--cpu-baseline-reps", type=int, default=5, help="BASELINE.md section 3: median of 5 repetitions after one warm-up")
     ap.add_argument("--sym-vs-lu-systems", type=int, default=16, help="systems of the timed batch re-solved with the pivoted LU for the whole-batch accuracy figure")
-    ap.add_argument("--single-system", action="store_true", help="also for cfg 3 / 5 (batches of different systems): latency of the first system alone, one system per call (default only for the one-system configs 1, 2, 4: its small launches would enter a profiler's per-kernel averages of the default run)")
+    ap.add_argument("--single-system", action="store_true", help="with --full, also for cfg 3 / 5 (batches of different systems): latency of the first system alone, one system per call (by default --full measures it only for the one-system configs 1, 2, 4: its small launches would enter a profiler's per-kernel averages of a cfg 3 run)")
     ap.add_argument("--no-single-system", action="store_true", help="skip the one-system-per-call latency measurement")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's densities under DIR as .npy (float64)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.single_system and not args.full:
+        ap.error("--single-system is a --full figure")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return _spawn_ranks(args)
@@ -341,19 +351,23 @@ def main() -> int:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if share else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-        # output marshalling (outside the timed region): all-gather of the densities, as _dist.biem_sharded does
+        # output marshalling (outside the timed region): all-gather of the densities, as _dist.biem_sharded does; timed with --full,
+        # and a plain run gathers only what --dump-outputs writes
         rccl_ranks = dist.get_world_size()
-        dens = calc.density if not share else calc.density.cpu()
-        D.gather_batch(dens, n_total if args.scaling == "strong" else S * world)          # warm-up (communicator set-up)
-        barrier()
-        tg = time.perf_counter()
-        full = D.gather_batch(dens, n_total if args.scaling == "strong" else S * world)
-        barrier()
-        marshalling_ms = (time.perf_counter() - tg) * 1e3
-        assert full.shape[0] == n_total
-        if args.dump_outputs and rank == 0:
-            dump = full
-        del full
+        if args.full or args.dump_outputs:
+            dens = calc.density if not share else calc.density.cpu()
+            if args.full:
+                D.gather_batch(dens, n_total if args.scaling == "strong" else S * world)          # warm-up (communicator set-up)
+                barrier()
+            tg = time.perf_counter()
+            full = D.gather_batch(dens, n_total if args.scaling == "strong" else S * world)
+            barrier()
+            if args.full:
+                marshalling_ms = (time.perf_counter() - tg) * 1e3
+            assert full.shape[0] == n_total
+            if args.dump_outputs and rank == 0:
+                dump = full
+            del full
 
     if rank != 0:
         if dist is not None:
@@ -376,7 +390,7 @@ def main() -> int:
 
     # latency of a single system per call (what the reference's own drivers do; cfg 3 / 5 - the first system of the batch - with --single-system), rank 0 only
     single_ms = None
-    if rank == 0 and not args.no_single_system and (cfg in (1, 2, 4) or args.single_system):
+    if args.full and rank == 0 and not args.no_single_system and (cfg in (1, 2, 4) or args.single_system):
         u1, g1 = amd.plane_wave(k=k_t[:1], direction=t(dirs[:, :1]))
         kw1 = dict(kw)
         if w["beta"] != 0:
@@ -393,7 +407,7 @@ def main() -> int:
     # whole-batch accuracy figure (cheap): systems spread over the timed batch solved again by the pivoted LU (the reference's
     # algorithm, _biem.py:797) and compared with the timed run's densities, max over systems of max |d_sym - d_lu| / max |d_lu|
     sym_vs_lu = None
-    if solver == "ldlt" and args.sym_vs_lu_systems > 0 and rank == 0:
+    if args.full and solver == "ldlt" and args.sym_vs_lu_systems > 0 and rank == 0:
         pick = sorted(set(int(round(v)) for v in np.linspace(0, nloc - 1, min(args.sym_vs_lu_systems, nloc))))
         pt = torch.as_tensor(pick, device=dev)
         u2, g2 = amd.plane_wave(k=k_t[pt], direction=t(dirs[:, pick]))
@@ -414,7 +428,7 @@ def main() -> int:
 
     # accuracy of this run's densities vs the CPU oracle at probe points (the metric's second half) + the CPU baseline
     cpu, relerr = None, None
-    if not args.no_cpu_baseline and world == 1:     # rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:     # rank 0 at N = 1 only
         from oracle import biem_oracle as O
 
         res, idx, cpu = cpu_baseline(w, args.cpu_baseline_systems, args.cpu_baseline_reps, one_thread=True)
@@ -459,7 +473,7 @@ def main() -> int:
     # what a pure stream of the same MFMA instruction sustains on THIS box (0.3 s, after the timed region): context for `frac`,
     # which stays priced against the nominal 78.6 TFLOP/s
     sustained = None
-    if rank == 0:
+    if args.full and rank == 0:
         tf = C.c_double()
         L.check(lib.biem_bench_mfma_f64_ex(2000000, 1, C.byref(tf), None))
         sustained = tf.value

@@ -6,9 +6,9 @@ OUT=gpurun_out/ab; mkdir -p $OUT
 rm -rf /tmp/r2 && mkdir -p /tmp/r2 && tar -C /tmp/r2 -xf tools/_r2src.tar
 (cd /tmp/r2 && python -m biem_helmholtz_sphere_amd._build > /dev/null 2>&1)
 for c in 1 2; do
-  python bench.py --config $c --steps 10 --warmup 3 --no-cpu-baseline --sym-vs-lu-systems 0 > $OUT/new_cfg$c.json 2>/dev/null
+  python bench.py --full --config $c --steps 10 --warmup 3 --no-cpu-baseline --sym-vs-lu-systems 0 > $OUT/new_cfg$c.json 2>/dev/null
   (cd /tmp/r2 && python bench.py --config $c --steps 10 --warmup 3 --no-cpu-baseline > $OLDPWD/$OUT/old_cfg$c.json 2>/dev/null)
-  python bench.py --config $c --steps 10 --warmup 3 --no-cpu-baseline --sym-vs-lu-systems 0 > $OUT/new2_cfg$c.json 2>/dev/null
+  python bench.py --full --config $c --steps 10 --warmup 3 --no-cpu-baseline --sym-vs-lu-systems 0 > $OUT/new2_cfg$c.json 2>/dev/null
 done
 python - <<'PY'
 import json,glob

@@ -5,9 +5,9 @@ set -o pipefail
 OUT=gpurun_out/ev; mkdir -p $OUT; export TMPDIR=/tmp
 part=${1:-main}
 if [ "$part" = main ]; then
-  python bench.py --steps 10 --warmup 3 --single-system > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err; echo "bench cfg3 rc=$?"
+  python bench.py --full --steps 10 --warmup 3 --single-system > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err; echo "bench cfg3 rc=$?"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --sym-vs-lu-systems 0 --no-single-system > $OUT/bench_under_rocprof.json 2> $OUT/kt.err; echo "kernel trace rc=$?"
-  BIEM_FILL_NO_DEDUPE=1 python bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg3_no_pair_classes.json 2> $OUT/bench_cfg3_nd.err; echo "bench cfg3 no pair classes rc=$?"
+  BIEM_FILL_NO_DEDUPE=1 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg3_no_pair_classes.json 2> $OUT/bench_cfg3_nd.err; echo "bench cfg3 no pair classes rc=$?"
 fi
 if [ "$part" = pmc ]; then
   for c in "WRITE_SIZE" "FETCH_SIZE" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVES" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
@@ -24,15 +24,15 @@ if [ "$part" = pmc ]; then
   done
 fi
 if [ "$part" = configs ]; then
-  for c in 1 2 4 5; do timeout -k 10 420 python bench.py --config $c --steps 5 --warmup 2 --cpu-baseline-reps 1 > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err; echo "bench cfg$c rc=$?"; done
-  for c in 4 5; do BIEM_FILL_NO_DEDUPE=1 python bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg${c}_no_pair_classes.json 2> $OUT/bench_cfg${c}_nd.err; echo "bench cfg$c no pair classes rc=$?"; done
+  for c in 1 2 4 5; do timeout -k 10 420 python bench.py --full --config $c --steps 5 --warmup 2 --cpu-baseline-reps 1 > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err; echo "bench cfg$c rc=$?"; done
+  for c in 4 5; do BIEM_FILL_NO_DEDUPE=1 python bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg${c}_no_pair_classes.json 2> $OUT/bench_cfg${c}_nd.err; echo "bench cfg$c no pair classes rc=$?"; done
 fi
 if [ "$part" = extra ]; then
-  BIEM_SOLVER=lu python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg3_lu.json 2> $OUT/bench_cfg3_lu.err; echo "lu rc=$?"
-  BIEM_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 1 --warmup 1 --systems-per-gpu 32 --no-cpu-baseline > $OUT/bench_2ranks_weak_shared_gpu.json 2> $OUT/b2w.err; echo "2-rank weak rc=$?"
-  BIEM_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --scaling strong --steps 1 --warmup 1 --systems-per-gpu 64 --no-cpu-baseline > $OUT/bench_2ranks_strong_shared_gpu.json 2> $OUT/b2s.err; echo "2-rank strong rc=$?"
-  BIEM_BENCH_FORCE_DIST=1 python bench.py --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_rccl_1rank.json 2> $OUT/b1r.err; echo "rccl 1 rank rc=$?"
-  BIEM_BENCH_FORCE_DIST=1 python bench.py --gpus 1 --config 5 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_rccl_1rank_cfg5.json 2> $OUT/b1r5.err; echo "rccl 1 rank cfg5 rc=$?"
+  BIEM_SOLVER=lu python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg3_lu.json 2> $OUT/bench_cfg3_lu.err; echo "lu rc=$?"
+  BIEM_BENCH_SHARE_GPU=1 python bench.py --full --gpus 2 --steps 1 --warmup 1 --systems-per-gpu 32 --no-cpu-baseline > $OUT/bench_2ranks_weak_shared_gpu.json 2> $OUT/b2w.err; echo "2-rank weak rc=$?"
+  BIEM_BENCH_SHARE_GPU=1 python bench.py --full --gpus 2 --scaling strong --steps 1 --warmup 1 --systems-per-gpu 64 --no-cpu-baseline > $OUT/bench_2ranks_strong_shared_gpu.json 2> $OUT/b2s.err; echo "2-rank strong rc=$?"
+  BIEM_BENCH_FORCE_DIST=1 python bench.py --full --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_rccl_1rank.json 2> $OUT/b1r.err; echo "rccl 1 rank rc=$?"
+  BIEM_BENCH_FORCE_DIST=1 python bench.py --full --gpus 1 --config 5 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_rccl_1rank_cfg5.json 2> $OUT/b1r5.err; echo "rccl 1 rank cfg5 rc=$?"
   for s in 32 64 128; do python bench.py --systems-per-gpu $s --steps 4 --warmup 2 --no-cpu-baseline --sym-vs-lu-systems 0 --no-single-system > $OUT/bench_cfg3_${s}sys.json 2> $OUT/b$s.err; echo "cfg3 $s systems rc=$?"; done
 fi
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*.db" -delete; find $OUT -name "*counter_collection.csv" -size +3M -delete

@@ -3,7 +3,7 @@
 O=gpurun_out/r03_eval; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -q > $O/t_full.log 2>&1; echo "tests exit $?"; tail -3 $O/t_full.log
 for cfg in 1 2 4 5; do
-  timeout -k 10 300 python bench.py --config $cfg --no-cpu-baseline > $O/bench_cfg$cfg.json 2> $O/bench_cfg$cfg.err || { echo "bench $cfg failed"; tail -3 $O/bench_cfg$cfg.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $cfg --no-cpu-baseline > $O/bench_cfg$cfg.json 2> $O/bench_cfg$cfg.err || { echo "bench $cfg failed"; tail -3 $O/bench_cfg$cfg.err; exit 1; }
   python - <<PY
 import json
 d=json.loads(open("$O/bench_cfg$cfg.json").read().strip().splitlines()[-1])
