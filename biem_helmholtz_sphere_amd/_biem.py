@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._coords import SphericalCoordinates, canonical_tree, harm_count, n_end_from_harm
+from ._coords import SphericalCoordinates, canonical_tree, chain_dim, harm_count, n_end_from_harm
 
 try:  # numpy >= 1.25
     from numpy.exceptions import ComplexWarning
@@ -186,15 +186,27 @@ def _ptr(t: Optional[torch.Tensor]) -> int:
 # --------------------------------------------------------------------------------------
 # plans (tables per (tree, n_end, device)), cached for the life of the process
 # --------------------------------------------------------------------------------------
+def _chain_plan_dim(tree: str) -> int:
+    """d if the tree's plan is built by the generic chain code: the chains d >= 5 always, ba / bba under BIEM_TREE_CHAIN=1 (tests)."""
+    d = chain_dim(tree)
+    if not d and tree in ("ba", "bba") and os.environ.get("BIEM_TREE_CHAIN") == "1":
+        d = 3 if tree == "ba" else 4
+    return d
+
+
 class _Plan:
     def __init__(self, tree: str, n_end: int, dev: torch.device):
         lib = L.load()
-        if tree not in L.TREE_IDS:
-            raise NotImplementedError(f"coordinate tree {tree!r} is not built (available: {sorted(L.TREE_IDS)})")
-        self.tree, self.n_end, self.dev = tree, n_end, dev
+        chain = _chain_plan_dim(tree)
+        if tree not in L.TREE_IDS and not chain:
+            raise NotImplementedError(f"coordinate tree {tree!r} is not built (available: {sorted(L.TREE_IDS)} and the standard chains)")
+        self.tree, self.n_end, self.dev, self.chain = tree, n_end, dev, chain
         h = C.c_void_p()
         with torch.cuda.device(dev):
-            L.check(lib.biem_plan_create(L.TREE_IDS[tree], n_end, C.byref(h)), "biem_plan_create")
+            if chain:
+                L.check(lib.biem_plan_create_chain(chain, n_end, C.byref(h)), "biem_plan_create_chain")
+            else:
+                L.check(lib.biem_plan_create(L.TREE_IDS[tree], n_end, C.byref(h)), "biem_plan_create")
         self.handle = h
         d, H, Q, H2, nt = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
         L.check(lib.biem_plan_info(h, C.byref(d), C.byref(H), C.byref(Q), C.byref(H2), C.byref(nt)))
@@ -204,14 +216,17 @@ class _Plan:
         L.check(lib.biem_plan_quadrature(h, y.ctypes.data, w.ctypes.data))
         self.quad_y = torch.as_tensor(y, device=dev)          # [Q, d] unit vectors
         self.y_by_axes: dict = {}                              # the same, [d, ...(quadrature axes)] per axis order of the caller's tree
-        lab = np.zeros((self.H, 3), dtype=np.int32)
+        width = self.d - 1 if chain else 3
+        lab = np.zeros((self.H, width), dtype=np.int32)
         deg = np.zeros(self.H, dtype=np.int32)
-        L.check(lib.biem_plan_labels(h, lab.ctypes.data, deg.ctypes.data))
+        L.check(lib.biem_plan_labels_n(h, width, lab.ctypes.data, deg.ctypes.data))
         self.labels, self.degrees = lab, deg
 
     def quad_shape(self) -> Tuple[int, ...]:
         """Tensor-product shape of the rule, one axis per spherical node (the reference's ...(f) axes)."""
         n = self.n_end
+        if self.chain:
+            return (n,) * (self.d - 2) + (2 * n,)
         return {"a": (2 * n,), "ba": (n, 2 * n), "bba": (n, n, 2 * n), "caa": (n, 2 * n, 2 * n)}[self.tree]
 
 
@@ -219,7 +234,7 @@ _PLANS: dict = {}
 
 
 def _plan(tree: str, n_end: int, dev: torch.device) -> _Plan:
-    key = (tree, int(n_end), dev.index if dev.index is not None else torch.cuda.current_device())
+    key = (tree, int(n_end), dev.index if dev.index is not None else torch.cuda.current_device(), _chain_plan_dim(tree))
     p = _PLANS.get(key)
     if p is None:
         p = _PLANS[key] = _Plan(tree, int(n_end), torch.device("cuda", key[2]))
@@ -776,7 +791,7 @@ def biem(
     # A repeated call of the same shape takes its workspace FIRST, before the boundary samples: the block the previous call
     # returned to torch's caching allocator is then still whole.  Taken after them, one of their mid-size temporaries may have
     # been carved out of it - and a second block of that size need not exist (cfg 3's whole batch: 164 of 288 GB).
-    ws_key = (plan.tree, int(n_end), int(nb), int(B), int(chunk), os.environ.get("BIEM_MAX_RESIDENT_BYTES"))
+    ws_key = (plan.tree, plan.chain, int(n_end), int(nb), int(B), int(chunk), os.environ.get("BIEM_MAX_RESIDENT_BYTES"))
     work_pre = None
     if has_rhs and nb > 0 and (B > 1 or force_matrix):
         memo = _ws_memo.get(dev)

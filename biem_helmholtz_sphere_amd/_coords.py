@@ -28,11 +28,38 @@ NEXT = ()
 CANONICAL = {"bpa": ("ba", (2, 1, 0)), "bpbpa": ("bba", (3, 1, 2, 0))}
 
 
+# Standard chain trees "b" * (d - 2) + "a" (the reference's create_standard(d - 1)) of every dimension d >= 5 up to CHAIN_DIM_MAX (ba and
+# bba are its d = 3, 4 members, built above): the generic chain branches of to_cartesian / from_cartesian below.
+CHAIN_DIM_MAX = 10
+
+
+def chain_dim(branching_types: str) -> int:
+    """d of a standard chain tree "b" * (d - 2) + "a" with 5 <= d <= CHAIN_DIM_MAX, else 0."""
+    d = len(branching_types) + 1
+    if 5 <= d <= CHAIN_DIM_MAX and branching_types == "b" * (d - 2) + "a":
+        return d
+    return 0
+
+
+def tree_dim(branching_types: str) -> int:
+    """c_ndim of a built tree; NotImplementedError naming the built ones otherwise."""
+    if branching_types in SUPPORTED:
+        return SUPPORTED[branching_types]
+    d = chain_dim(branching_types)
+    if d:
+        return d
+    extra = " (planned: %s)" % ", ".join(NEXT) if branching_types in NEXT else ""
+    raise NotImplementedError(
+        f"coordinate tree {branching_types!r} is not built in this MI355X implementation; "
+        f"available: {sorted(SUPPORTED)} and the standard chains 'b' * (d - 2) + 'a' for 5 <= d <= {CHAIN_DIM_MAX}{extra}"
+    )
+
+
 def canonical_tree(branching_types: str):
-    """(canonical tree name, perm) with canonical component i = original component perm[i]; identity for a / ba / bba."""
+    """(canonical tree name, perm) with canonical component i = original component perm[i]; identity for a / ba / bba / chains."""
     if branching_types in CANONICAL:
         return CANONICAL[branching_types]
-    return branching_types, tuple(range(SUPPORTED[branching_types]))
+    return branching_types, tuple(range(tree_dim(branching_types)))
 
 
 def _xp(a: Any):
@@ -52,14 +79,8 @@ class SphericalCoordinates:
     """Coordinate tree described by its branching-types string (root first)."""
 
     def __init__(self, branching_types: str):
-        if branching_types not in SUPPORTED:
-            extra = " (planned: %s)" % ", ".join(NEXT) if branching_types in NEXT else ""
-            raise NotImplementedError(
-                f"coordinate tree {branching_types!r} is not built in this MI355X implementation; "
-                f"available: {sorted(SUPPORTED)}{extra}"
-            )
+        self.c_ndim = tree_dim(branching_types)
         self.branching_types_expression_str = branching_types
-        self.c_ndim = SUPPORTED[branching_types]
         self.s_ndim = self.c_ndim - 1
         self.root = 0
         # adjacency of the tree, enough for display purposes (the reference's plot/CLI read c.G)
@@ -163,6 +184,9 @@ def harm_count(branching_types: str, n_end: int) -> int:
         return n_end * n_end
     if branching_types in ("bba", "caa"):
         return n_end * (n_end + 1) * (2 * n_end + 1) // 6
+    d = chain_dim(branching_types)
+    if d:
+        return math.comb(n_end + d - 2, d - 1) + math.comb(n_end + d - 3, d - 1)
     raise NotImplementedError(branching_types)
 
 

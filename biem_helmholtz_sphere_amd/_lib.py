@@ -27,9 +27,12 @@ SIGNATURES = {
     "biem_plan_create_host": (_i, [_i, _i, C.POINTER(_vp)]),
     "biem_plan_upload": (_i, [_vp]),
     "biem_plan_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "biem_plan_create_chain_host": (_i, [_i, _i, C.POINTER(_vp)]),
+    "biem_plan_create_chain": (_i, [_i, _i, C.POINTER(_vp)]),
     "biem_plan_destroy": (_i, [_vp]),
     "biem_plan_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_ll)]),
     "biem_plan_labels": (_i, [_vp, _vp, _vp]),
+    "biem_plan_labels_n": (_i, [_vp, _i, _vp, _vp]),
     "biem_plan_symmetric_order": (_i, [_vp, _vp, _vp]),
     "biem_plan_fill_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "biem_plan_quadrature": (_i, [_vp, _vp, _vp]),

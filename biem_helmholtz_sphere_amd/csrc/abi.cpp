@@ -59,6 +59,33 @@ int biem_plan_create_host(int tree, int n_end, biem_plan** plan) {
 
 int biem_plan_upload(biem_plan* plan) { NEED(plan, "plan"); return plan_upload(plan); }
 
+int biem_plan_create_chain_host(int d, int n_end, biem_plan** plan) {
+  NEED(plan, "plan");
+  biem_plan* p = new (std::nothrow) biem_plan();
+  if (!p) { set_error("out of host memory"); return BIEM_ERR_ALLOC; }
+  int rc = BIEM_OK;
+  try {
+    rc = plan_build_chain_host(p, d, n_end);
+  } catch (const std::bad_alloc&) {
+    set_error("out of host memory building chain tables for d=%d n_end=%d", d, n_end);
+    rc = BIEM_ERR_ALLOC;
+  }
+  if (rc != BIEM_OK) { delete p; *plan = nullptr; return rc; }
+  *plan = p;
+  return BIEM_OK;
+}
+
+int biem_plan_create_chain(int d, int n_end, biem_plan** plan) {
+  int n = 0;
+  int rc = biem_device_count(&n);
+  if (rc != BIEM_OK) return rc;
+  rc = biem_plan_create_chain_host(d, n_end, plan);
+  if (rc != BIEM_OK) return rc;
+  rc = plan_upload(*plan);
+  if (rc != BIEM_OK) { plan_free(*plan); *plan = nullptr; }
+  return rc;
+}
+
 int biem_plan_create(int tree, int n_end, biem_plan** plan) {
   int n = 0;
   int rc = biem_device_count(&n);
@@ -84,7 +111,18 @@ int biem_plan_info(const biem_plan* plan, int* d, int* n_harm, int* n_quad, int*
 
 int biem_plan_labels(const biem_plan* plan, int* h_labels, int* h_deg) {
   NEED(plan, "plan");
+  if (plan->lw != 3) { set_error("biem_plan_labels: this plan's labels have %d entries; use biem_plan_labels_n", plan->lw); return BIEM_ERR_UNSUPPORTED; }
   if (h_labels) memcpy(h_labels, plan->labels.data(), plan->labels.size() * sizeof(int));
+  if (h_deg) memcpy(h_deg, plan->deg.data(), plan->deg.size() * sizeof(int));
+  return BIEM_OK;
+}
+
+int biem_plan_labels_n(const biem_plan* plan, int width, int* h_labels, int* h_deg) {
+  NEED(plan, "plan");
+  if (width < plan->lw) { set_error("biem_plan_labels_n: width %d < the plan's label width %d", width, plan->lw); return BIEM_ERR_ARG; }
+  if (h_labels)
+    for (int h = 0; h < plan->H; ++h)
+      for (int j = 0; j < width; ++j) h_labels[(size_t)h * width + j] = j < plan->lw ? plan->labels[(size_t)h * plan->lw + j] : 0;
   if (h_deg) memcpy(h_deg, plan->deg.data(), plan->deg.size() * sizeof(int));
   return BIEM_OK;
 }

@@ -26,6 +26,10 @@ __global__ void k_radial(int d, int nmax, int count, const double* __restrict__ 
     bessel_jy_int(nmax + 1, xi, lj, ly);
     double f = kSqrtHalfPi / xi;
     for (int n = 0; n <= nmax; ++n) { J[n] = lj[n + 1] * f; Y[n] = ly[n + 1] * f; }
+  } else if (d >= 5) {
+    double lj[kMaxRad + 2 + kRadShiftMax], ly[kMaxRad + 2 + kRadShiftMax];
+    radial_d(d, nmax, x[i], lj, ly);
+    for (int n = 0; n <= nmax; ++n) { J[n] = lj[n]; Y[n] = ly[n]; }
   } else {
     radial_d(d, nmax, x[i], J, Y);
   }
@@ -35,7 +39,7 @@ __global__ void k_radial(int d, int nmax, int count, const double* __restrict__ 
 __global__ void k_radial_c(int d, int nmax, int count, const cplx* __restrict__ z, cplx* __restrict__ out) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  cplx lj[kMaxRad + 3], lh[kMaxRad + 3];
+  cplx lj[kMaxRad + 3 + kRadShiftMax], lh[kMaxRad + 3 + kRadShiftMax];
   radial_jh(d, nmax, z[i], lj, lh);
   cplx* J = out + (size_t)i * 2 * (nmax + 1);
   cplx* Hh = J + (nmax + 1);
@@ -43,7 +47,7 @@ __global__ void k_radial_c(int d, int nmax, int count, const cplx* __restrict__ 
 }
 
 int launch_radial_c(int d, int nmax, int count, const double* d_z, double* d_out, hipStream_t st) {
-  if (nmax < 0 || nmax > kMaxRad || (d != 2 && d != 3 && d != 4)) { set_error("biem_radial_complex: bad d/nmax"); return BIEM_ERR_ARG; }
+  if (nmax < 0 || nmax > kMaxRad || d < 2 || d > kChainDimMax) { set_error("biem_radial_complex: bad d/nmax"); return BIEM_ERR_ARG; }
   if (count <= 0) return BIEM_OK;
   hipLaunchKernelGGL(k_radial_c, dim3((count + 63) / 64), dim3(64), 0, st, d, nmax, count, (const cplx*)d_z, (cplx*)d_out);
   BIEM_LAUNCHCHK();
@@ -51,7 +55,7 @@ int launch_radial_c(int d, int nmax, int count, const double* d_z, double* d_out
 }
 
 int launch_radial(int d, int nmax, int count, const double* d_x, double* d_out, hipStream_t st) {
-  if (nmax < 0 || nmax > kMaxRad || (d != 2 && d != 3 && d != 4)) { set_error("biem_radial: bad d/nmax"); return BIEM_ERR_ARG; }
+  if (nmax < 0 || nmax > kMaxRad || d < 2 || d > kChainDimMax) { set_error("biem_radial: bad d/nmax"); return BIEM_ERR_ARG; }
   if (count <= 0) return BIEM_OK;
   hipLaunchKernelGGL(k_radial, dim3((count + 63) / 64), dim3(64), 0, st, d, nmax, count, d_x, d_out);
   BIEM_LAUNCHCHK();
@@ -75,8 +79,26 @@ __global__ void k_harmonics(int tree, int d, int H, const int* __restrict__ labe
   }
 }
 
+// chain trees: every label from scratch (test entry; the fill and the field evaluation use node tables)
+__global__ void k_harmonics_chain(int d, int H, const int* __restrict__ labels, int count, const double* __restrict__ u, cplx* __restrict__ Y) {
+  int p = blockIdx.x;
+  if (p >= count) return;
+  double c[kChainDimMax], s[kChainDimMax], phi;
+  chain_angles(d, u + (size_t)p * d, c, s, &phi);
+  for (int h = threadIdx.x; h < H; h += blockDim.x) {
+    double re, im;
+    chain_harmonic(d, labels + (size_t)h * (d - 1), c, s, phi, &re, &im);
+    Y[(size_t)p * H + h] = make_double2(re, im);
+  }
+}
+
 int launch_harmonics(const biem_plan* p, int count, const double* d_u, double* d_Y, hipStream_t st) {
   if (count <= 0) return BIEM_OK;
+  if (p->tree == TREE_CHAIN) {
+    hipLaunchKernelGGL(k_harmonics_chain, dim3(count), dim3(128), 0, st, p->d, p->H, p->d_labels, count, d_u, (cplx*)d_Y);
+    BIEM_LAUNCHCHK();
+    return BIEM_OK;
+  }
   hipLaunchKernelGGL(k_harmonics, dim3(count), dim3(128), 0, st, p->tree, p->d, p->H, p->d_labels, count, d_u, (cplx*)d_Y);
   BIEM_LAUNCHCHK();
   return BIEM_OK;
@@ -275,6 +297,104 @@ __global__ void __launch_bounds__(64) k_pair_tables(int tree, int d, int n2, int
   }
 }
 
+// Pair tables of the chain trees (same outputs and arguments as k_pair_tables).  Every label is a product of d - 2 polar node
+// factors F_j[l_j][l_{j+1}] = sin^{l_{j+1}} t_j Gbar_{l_j - l_{j+1}}^{(l_{j+1} + (d-j-2)/2)}(cos t_j) (l_{d-2} = |m|) and one phase: one
+// lane per (node j, l_{j+1}) runs the Gegenbauer degree recurrence once per (pair, system) into LDS, then every label is d - 2
+// lookups - the pattern of the ba branch above, one table per node.
+__global__ void __launch_bounds__(64) k_pair_tables_chain(int tree, int d, int n2, int H2, double Cd, const int* __restrict__ labels2,
+                                                           const int* __restrict__ deg2, int B, const cplx* __restrict__ k,
+                                                           const double* __restrict__ centers, int geom_batched, cplx* __restrict__ T,
+                                                           int lower, int nbp, const int* __restrict__ lin2, int H2lin,
+                                                           const int* __restrict__ red_of, const int* __restrict__ red_first,
+                                                           const int* __restrict__ ph_mu, int E, int NP,
+                                                           const cplx* __restrict__ tab, int n_end, cplx* __restrict__ rad_scratch,
+                                                           const int* __restrict__ rep_flag) {
+  __shared__ cplx sJ[kMaxRad * 2 + 6], sH[kMaxRad * 2 + 6];
+  __shared__ double sF[kChainNodeTab];                 // [j][L][L1], n2 x n2 per node
+  __shared__ double sC[kChainDimMax], sS[kChainDimMax], sPhi;
+  (void)tree; (void)rad_scratch;
+  int pair = blockIdx.x, s = blockIdx.y;
+  int b = pair / B, bp = pair % B;
+  if (lower ? b <= bp : b >= bp) return;
+  if (rep_flag != nullptr && !rep_flag[b * B + bp]) return;
+  const double* cb = centers + ((geom_batched ? (size_t)s * B : 0) + b) * d;
+  const double* cp = centers + ((geom_batched ? (size_t)s * B : 0) + bp) * d;
+  const int np = d - 2, lw = d - 1;
+  if (threadIdx.x == 0) {
+    double t[kChainDimMax];
+    double r2 = 0.0;
+    for (int i = 0; i < d; ++i) { t[i] = cb[i] - cp[i]; r2 += t[i] * t[i]; }
+    radial_jh(d, n2 - 1, cscale(k[s], sqrt(r2)), sJ, sH);
+    double phi;
+    chain_angles(d, t, sC, sS, &phi);
+    sPhi = phi;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < np * n2; i += 64) {
+    const int j = i / n2, L1 = i - j * n2;
+    const double lam = (double)L1 + 0.5 * (d - j - 2), c = sC[j], sn = sS[j];
+    double sl = 1.0;
+    for (int q = 0; q < L1; ++q) sl *= sn;
+    // orthonormal Gegenbauer recurrence of gbar_lam in the degree k = L - L1
+    double p0 = sl / sqrt(sqrt(kPi) * exp(lgamma(lam + 0.5) - lgamma(lam + 1.0))), p1 = 0.0, aprev = 0.0;
+    double* F = sF + ((size_t)j * n2) * n2 + L1;
+    for (int L = L1; L < n2; ++L) {
+      const int kq = L - L1;
+      if (kq > 0) {
+        const double aq = 0.5 * sqrt((double)kq * ((double)kq + 2.0 * lam - 1.0) / (((double)kq + lam - 1.0) * ((double)kq + lam)));
+        const double p2 = (c * p0 - aprev * p1) / aq;
+        p1 = p0; p0 = p2; aprev = aq;
+      }
+      F[(size_t)L * n2] = p0;
+    }
+  }
+  __syncthreads();
+  auto amp_of = [&](int l) {
+    const int* lb = labels2 + (size_t)l * lw;
+    double a = Cd * kInvSqrt2Pi;
+    for (int j = 0; j < np; ++j) {
+      const int L1 = j + 1 < np ? lb[j + 1] : (lb[lw - 1] < 0 ? -lb[lw - 1] : lb[lw - 1]);
+      a *= sF[((size_t)j * n2 + lb[j]) * n2 + L1];
+    }
+    return a;
+  };
+  if (red_of != nullptr) {
+    cplx* o = T + ((size_t)s * B * B + pair) * (size_t)(E + NP + 2 * n_end);
+    for (int i = threadIdx.x; i < 2 * n_end; i += 64) {
+      const int which = i >= n_end, n = i - which * n_end;
+      const cplx* tb = tab + ((size_t)s * B + (which ? bp : b)) * 3 * n_end;
+      o[E + NP + i] = cmul(tb[n], crecip(zsqrt(cmul(tb[n], tb[n_end + n]))));
+    }
+    for (int l = threadIdx.x; l < H2; l += 64) {
+      if (!red_first[l]) continue;
+      o[red_of[l]] = cscale(sH[deg2[l]], amp_of(l));
+    }
+    for (int i = threadIdx.x; i < NP; i += 64) {
+      double sn, cs;
+      sincos((double)ph_mu[2 * i] * sPhi, &sn, &cs);
+      o[E + i] = make_double2(cs, sn);
+    }
+    return;
+  }
+  cplx* out = nbp > 0 ? T + (((size_t)(s >> 6) * (B * (B - 1) / 2) + (bp * (bp - 1) / 2 + b)) * H2) * 64 + (s & 63) : T + ((size_t)s * B * B + pair) * H2;
+  const size_t ostride = nbp > 0 ? 64 : 1;
+  for (int l = threadIdx.x; l < H2; l += 64) {
+    const int m = labels2[(size_t)l * lw + lw - 1];
+    double sn, cs;
+    sincos((double)m * sPhi, &sn, &cs);
+    const cplx val = cmul(cscale(sH[deg2[l]], amp_of(l)), make_double2(cs, sn));
+    if (lin2 == nullptr) { out[(size_t)l * ostride] = val; continue; }
+    cplx* o2 = T + ((size_t)s * B * B + pair) * H2lin;
+    const int i = lin2[l];
+    o2[i] = val;
+    if (m == 0) o2[i + 1] = val;
+  }
+}
+
+typedef decltype(&k_pair_tables) PairTablesKernel;
+// the pair-table kernel of a plan: the chain trees have their own (node tables), every other tree k_pair_tables
+static PairTablesKernel pair_tables_kernel(const biem_plan* p) { return p->tree == TREE_CHAIN ? &k_pair_tables_chain : &k_pair_tables; }
+
 // ---------------------------------------------------------------------------------------------
 // K1-K3: generic fill.  For every ordered pair block (b, b') and every entry (h, h'):
 //   off-diagonal:  A = R_b[n(h)] * Cc_{b'}[n(h')] * sum_p coef[p] T_{bb'}[tidx[p]]        ((S|R)^T, _biem.py:769)
@@ -442,7 +562,7 @@ static int launch_pair_tables_red(const biem_plan* p, int nb, int B, const doubl
     if (p->tree != TREE_A) { set_error("n_end=%d exceeds the built table size", p->n_end); return BIEM_ERR_UNSUPPORTED; }
     BIEM_HIPCHK(hipMallocAsync((void**)&scratch, (size_t)nb * B * B * 2 * (p->n2 + 6) * sizeof(cplx), st));
   }
-  hipLaunchKernelGGL(k_pair_tables, dim3(B * B, nb), dim3(64), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2, p->d_deg2, B,
+  hipLaunchKernelGGL(pair_tables_kernel(p), dim3(B * B, nb), dim3(64), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2, p->d_deg2, B,
                      (const cplx*)d_k, d_centers, geom_batched, T, 0, 0, nullptr, 0, p->d_red_of, p->d_red_first, p->d_ph_mu, p->E, p->NP,
                      (const cplx*)d_tab, p->n_end, scratch, rep_flag);
   BIEM_LAUNCHCHK();
@@ -484,8 +604,9 @@ int launch_fill(const biem_plan* p, int nb, int B, const double* d_k, const doub
   }
   if (2 * p->n_end > kMaxRad) { set_error("n_end=%d exceeds the built table size", p->n_end); return BIEM_ERR_UNSUPPORTED; }
   if (B > 1) {
-    hipLaunchKernelGGL(k_pair_tables, dim3(B * B, nb), dim3(64), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2,
-                       p->d_deg2, B, (const cplx*)d_k, d_centers, geom_batched, T, 0, 0, nullptr, 0);
+    hipLaunchKernelGGL(pair_tables_kernel(p), dim3(B * B, nb), dim3(64), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2,
+                       p->d_deg2, B, (const cplx*)d_k, d_centers, geom_batched, T, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0,
+                       nullptr, 0, nullptr, nullptr);
     BIEM_LAUNCHCHK();
   }
   size_t shm = (size_t)((p->fill_table_global ? 0 : p->H2) + 2 * H) * sizeof(cplx) + (size_t)p->chunk_terms_max * 10 + (size_t)(p->chunk_ents_max + 1) * 4 + 16;
@@ -1272,8 +1393,8 @@ int launch_fill_sym(const biem_plan* p, int nb, int B, const double* d_k, const 
     const size_t shm = (size_t)(p->schunk_terms_max + 1) * 12 + (size_t)(4 * p->schunk_pairs_max + 1) * 4 + (size_t)p->schunk_pairs_max * 12 + 16;
     if (p->H2 > 65536) { set_error("biem_fill (symmetric, systems in lanes): n_end=%d has %d table labels, the 16-bit term indices hold 65536", p->n_end, p->H2); return BIEM_ERR_UNSUPPORTED; }
     if (shm > 64 * 1024 || (size_t)p->H2 * 64 >= (1ull << 32)) { set_error("biem_fill (symmetric, systems in lanes): a unit pair of n_end=%d has %d terms", p->n_end, p->schunk_terms_max); return BIEM_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(k_pair_tables, dim3(B * B, nb), dim3(64), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2, p->d_deg2, B,
-                       (const cplx*)d_k, d_centers, geom_batched, T, 0, nbp, nullptr, 0);
+    hipLaunchKernelGGL(pair_tables_kernel(p), dim3(B * B, nb), dim3(64), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2, p->d_deg2, B,
+                       (const cplx*)d_k, d_centers, geom_batched, T, 0, nbp, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr);
     const int nq = B * p->n_end * nbp;
     hipLaunchKernelGGL(k_qfactors_t, dim3((nq + 255) / 256), dim3(256), 0, st, p->n_end, B, nb, nbp, (const cplx*)d_tab, Qt);
     BIEM_LAUNCHCHK();
@@ -1316,7 +1437,7 @@ int launch_fill_sym(const biem_plan* p, int nb, int B, const double* d_k, const 
       const int rc = launch_pair_tables_red(p, nb, B, d_k, d_centers, geom_batched, d_tab, T, st, rep_flag);
       if (rc) return rc;
     } else {
-      hipLaunchKernelGGL(k_pair_tables, dim3(B * B, nb), dim3(64), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2, p->d_deg2, B,
+      hipLaunchKernelGGL(pair_tables_kernel(p), dim3(B * B, nb), dim3(64), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2, p->d_deg2, B,
                          (const cplx*)d_k, d_centers, geom_batched, T, 0, 0, p->d_lin2, p->H2lin, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, rep_flag);
       BIEM_LAUNCHCHK();
     }

@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(256) k_uscat(int tree, int d, int H, int n_end
         if ((!inner && r < rho) || (inner && r > rho)) atomicOr(&sBad, 1);
         if (r > 0.0) radial_jh(d, n_end - 1, cscale(kk, r), sJ[wave], sH[wave]);
         else {   // centre of a ball (inner kind): z_n(0) = delta_{n0} sqrt(pi/2) 2^{1-d/2} / Gamma(d/2); the exterior form has no value there
-          const double z0 = d == 2 ? kSqrtHalfPi : d == 3 ? 1.0 : 0.5 * kSqrtHalfPi;
+          const double z0 = radial_z0_at_zero(d);
           const double qn = __longlong_as_double(0x7ff8000000000000LL);
           for (int n = 0; n < n_end; ++n) { sJ[wave][n] = make_double2(n == 0 ? z0 : 0.0, 0.0); sH[wave][n] = make_double2(qn, qn); }
         }
@@ -254,7 +254,7 @@ __global__ void __launch_bounds__(256) k_uscat_fast(int d, int H, int n_end, con
     if (INNER) {
       if (r > 0.0) radial_jh(d, n_end - 1, cscale(kk, r), (zc*)sJl, nullptr);
       else {                                // centre of the ball: z_n(0) = delta_{n0} sqrt(pi/2) 2^{1-d/2} / Gamma(d/2)
-        const double z0 = d == 2 ? kSqrtHalfPi : d == 3 ? 1.0 : 0.5 * kSqrtHalfPi;
+        const double z0 = radial_z0_at_zero(d);
         for (int n = 0; n < n_end; ++n) sJl[n] = make_double2(n == 0 ? z0 : 0.0, 0.0);
       }
     } else if (!FAR) {
@@ -448,6 +448,129 @@ __global__ void __launch_bounds__(256) k_uscat_fast(int d, int H, int n_end, con
   } else out[(size_t)p * nb + s] = bad ? make_double2(qnan, 0.0) : make_double2(tr, ti);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Chain trees (any depth): one workgroup of 4 waves per (point, system), a wave per ball as in k_uscat, but the harmonics come from
+// node tables: lane 0 runs the radial functions and the angles, the lanes fill F_j[L][L1] (one lane per (node j, L1): the Gegenbauer
+// degree recurrence once) and the phases e^{i m phi}, then every harmonic is d - 2 LDS lookups and one phase.
+// ---------------------------------------------------------------------------------------------
+constexpr int kChainRadU = 64;                  // radial orders per wave (n_end + 1 + shift)
+constexpr int kChainTabU = 1024;                // node-table doubles per wave ((d - 2) n_end^2)
+__global__ void __launch_bounds__(256) k_uscat_chain(int d, int H, int n_end, const int* __restrict__ labels,
+                                                      const int* __restrict__ deg, int nb, int B, int P, const cplx* __restrict__ k,
+                                                      const double* __restrict__ centers, const double* __restrict__ radii,
+                                                      int geom_batched, const cplx* __restrict__ c, const double* __restrict__ pts,
+                                                      int flags, cplx* __restrict__ out) {
+  __shared__ cplx sJ[4][kChainRadU], sH[4][kChainRadU], sPh[4][kChainRadU];
+  __shared__ double sF[4][kChainTabU];
+  __shared__ double sC[4][kChainDimMax], sS[4][kChainDimMax], sPhi[4];
+  __shared__ int sBad;
+  extern __shared__ cplx sBall[];   // [B]
+  const int p = blockIdx.x, s = blockIdx.y;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool far = (flags & BIEM_USCAT_FAR_FIELD) != 0, per_ball = (flags & BIEM_USCAT_PER_BALL) != 0;
+  const bool inner = (flags & BIEM_USCAT_KIND_INNER) != 0, pb = (flags & BIEM_USCAT_POINTS_BATCHED) != 0;
+  const int np = d - 2, lw = d - 1;
+  if (threadIdx.x == 0) sBad = 0;
+  const cplx kk = k[s];
+  __syncthreads();
+  for (int bb = 0; bb < B; bb += 4) {
+    const int b = bb + wave;
+    const bool act = b < B;
+    double xc = 0.0;
+    if (act && lane == 0) {
+      const double* cb = centers + ((geom_batched ? (size_t)s * B : 0) + b) * d;
+      const double rho = radii[(geom_batched ? (size_t)s * B : 0) + b];
+      double rel[kChainDimMax];
+      double r2 = 0.0;
+      for (int i = 0; i < d; ++i) {
+        const double xi = pb ? pts[((size_t)i * P + p) * nb + s] : pts[(size_t)i * P + p];
+        rel[i] = xi - cb[i]; r2 += rel[i] * rel[i]; xc += xi * cb[i];
+      }
+      const double r = sqrt(r2);
+      double phi;
+      chain_angles(d, rel, sC[wave], sS[wave], &phi);
+      sPhi[wave] = phi;
+      if (!far) {
+        if ((!inner && r < rho) || (inner && r > rho)) atomicOr(&sBad, 1);
+        if (r > 0.0) radial_jh(d, n_end - 1, cscale(kk, r), sJ[wave], sH[wave]);
+        else {   // centre of a ball (inner kind): z_n(0) = delta_{n0} z_0(0); the exterior form has no value there
+          const double z0 = radial_z0_at_zero(d);
+          const double qn = __longlong_as_double(0x7ff8000000000000LL);
+          for (int n = 0; n < n_end; ++n) { sJ[wave][n] = make_double2(n == 0 ? z0 : 0.0, 0.0); sH[wave][n] = make_double2(qn, qn); }
+        }
+      }
+    }
+    __syncthreads();
+    if (act) {
+      for (int i = lane; i < np * n_end; i += 64) {
+        const int j = i / n_end, L1 = i - j * n_end;
+        const double lam = (double)L1 + 0.5 * (d - j - 2), cj = sC[wave][j], sn = sS[wave][j];
+        double sl = 1.0;
+        for (int q = 0; q < L1; ++q) sl *= sn;
+        double p0 = sl / sqrt(sqrt(kPi) * exp(lgamma(lam + 0.5) - lgamma(lam + 1.0))), p1 = 0.0, aprev = 0.0;
+        double* F = sF[wave] + ((size_t)j * n_end) * n_end + L1;
+        for (int L = L1; L < n_end; ++L) {
+          const int kq = L - L1;
+          if (kq > 0) {
+            const double aq = 0.5 * sqrt((double)kq * ((double)kq + 2.0 * lam - 1.0) / (((double)kq + lam - 1.0) * ((double)kq + lam)));
+            const double p2 = (cj * p0 - aprev * p1) / aq;
+            p1 = p0; p0 = p2; aprev = aq;
+          }
+          F[(size_t)L * n_end] = p0;
+        }
+      }
+      for (int m = lane; m < n_end; m += 64) {
+        double sn, cs;
+        sincos((double)m * sPhi[wave], &sn, &cs);
+        sPh[wave][m] = make_double2(cs, sn);
+      }
+    }
+    __syncthreads();
+    if (act) {
+      const cplx* cs = c + ((size_t)s * B + b) * H;
+      double ar = 0.0, ai = 0.0;
+      for (int h = lane; h < H; h += 64) {
+        const int* lb = labels + (size_t)h * lw;
+        const int m = lb[lw - 1], am = m < 0 ? -m : m;
+        double amp = kInvSqrt2Pi;
+        for (int j = 0; j < np; ++j) amp *= sF[wave][((size_t)j * n_end + lb[j]) * n_end + (j + 1 < np ? lb[j + 1] : am)];
+        const cplx ph = sPh[wave][am];
+        const int n = deg[h];
+        cplx rad;
+        if (far) {
+          const int q = n & 3;
+          rad = q == 0 ? make_double2(1, 0) : q == 1 ? make_double2(0, -1) : q == 2 ? make_double2(-1, 0) : make_double2(0, 1);
+        } else {
+          rad = inner ? sJ[wave][n] : sH[wave][n];
+        }
+        const cplx v = cmul(cmul(cs[h], rad), make_double2(amp * ph.x, m < 0 ? -amp * ph.y : amp * ph.y));
+        ar += v.x; ai += v.y;
+      }
+      ar = wave_sum(ar); ai = wave_sum(ai);
+      if (lane == 0) {
+        cplx v = make_double2(ar, ai);
+        if (far) {
+          const double pw = 0.5 * (d - 1);
+          const cplx lik = zlog(make_double2(-kk.y, kk.x));                    // log(i k)
+          v = cmul(v, zexp(make_double2(kk.y * xc - pw * lik.x, -kk.x * xc - pw * lik.y)));
+        }
+        sBall[b] = v;
+      }
+    }
+    __syncthreads();
+  }
+  const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+  const bool bad = !far && sBad;
+  if (per_ball) {
+    for (int b = threadIdx.x; b < B; b += 256)
+      out[((size_t)p * nb + s) * B + b] = bad ? make_double2(qnan, 0.0) : sBall[b];
+  } else if (threadIdx.x == 0) {
+    double ar = 0.0, ai = 0.0;
+    for (int b = 0; b < B; ++b) { ar += sBall[b].x; ai += sBall[b].y; }
+    out[(size_t)p * nb + s] = bad ? make_double2(qnan, 0.0) : make_double2(ar, ai);
+  }
+}
+
 int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
                  const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
                  double* d_out, void* d_work, size_t work_bytes, hipStream_t st) {
@@ -468,6 +591,16 @@ int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, co
                      geom_batched, (const cplx*)d_density, c, scratch);
   BIEM_LAUNCHCHK();
   if (scratch) BIEM_HIPCHK(hipFreeAsync(scratch, st));
+  if (p->tree == TREE_CHAIN) {
+    if (p->n_end + 1 + kRadShiftMax > kChainRadU || (p->d - 2) * p->n_end * p->n_end > kChainTabU || nb > 65535 ||
+        (size_t)B * sizeof(cplx) > 64 * 1024) {
+      set_error("biem_uscat: chain tree d=%d n_end=%d (%d balls) exceeds the field kernel's tables", p->d, p->n_end, B); return BIEM_ERR_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL(k_uscat_chain, dim3(P, nb), dim3(256), (size_t)B * sizeof(cplx), st, p->d, p->H, p->n_end, p->d_labels,
+                       p->d_deg, nb, B, P, (const cplx*)d_k, d_centers, d_radii, geom_batched, (const cplx*)c, d_points, flags, (cplx*)d_out);
+    BIEM_LAUNCHCHK();
+    return BIEM_OK;
+  }
   // the far field does not depend on the kind; the near field of kind inner reads j_n from a per-lane LDS row (INNER)
   const bool far = (flags & BIEM_USCAT_FAR_FIELD) != 0;
   const bool inner = !far && (flags & BIEM_USCAT_KIND_INNER);

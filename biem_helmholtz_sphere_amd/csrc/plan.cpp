@@ -6,7 +6,9 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <map>
+#include <unordered_map>
 #include <tuple>
 
 namespace biem {
@@ -100,6 +102,8 @@ struct Gaunt3 {
     return acc * kInvSqrt2Pi;
   }
 };
+
+static int plan_build_tail(biem_plan* p);
 
 int plan_build_host(biem_plan* p, int tree, int n_end) {
   if (tree < 0 || tree > 3) { set_error("unsupported coordinate tree id %d (built: a, ba, bba, caa)", tree); return BIEM_ERR_UNSUPPORTED; }
@@ -280,6 +284,13 @@ int plan_build_host(biem_plan* p, int tree, int n_end) {
       p->ptr[(size_t)h * H + hp + 1] = (uint32_t)p->coef.size();
     }
   }
+  return plan_build_tail(p);
+}
+
+// the tree-independent tables behind the labels and term lists: fill chunks, unit-pair lists, the reduced-table form
+static int plan_build_tail(biem_plan* p) {
+  const int tree = p->tree, n_end = p->n_end, H = p->H, lw = p->lw;
+  const bool lists = p->lists_built;
   // ---- entry chunks of the fill kernel: term slice + row pointers + pair table + column factors must fit LDS ----
   p->tidx16.resize(p->tidx.size());
   for (size_t i = 0; i < p->tidx.size(); ++i) p->tidx16[i] = (uint16_t)p->tidx[i];
@@ -335,15 +346,16 @@ int plan_build_host(biem_plan* p, int tree, int n_end) {
       }
     // ---- the two-list form of the entry-per-lane kernel ----
     {
-      std::map<std::tuple<int, int, int>, int> pos2;
+      std::map<std::vector<int>, int> pos2;
       const int H2 = p->H2;
-      for (int l = 0; l < H2; ++l) pos2[std::make_tuple(p->labels2[3 * l], p->labels2[3 * l + 1], p->labels2[3 * l + 2])] = l;
+      for (int l = 0; l < H2; ++l) pos2[std::vector<int>(&p->labels2[(size_t)lw * l], &p->labels2[(size_t)lw * l] + lw)] = l;
       std::vector<int> partner2(H2, -1);
       bool ok = true;
       for (int l = 0; l < H2 && ok; ++l) {
-        int a = p->labels2[3 * l], b = p->labels2[3 * l + 1], c = p->labels2[3 * l + 2];
-        if (tree == TREE_A) a = -a; else if (tree == TREE_BA) b = -b; else if (tree == TREE_BBA) c = -c; else { b = -b; c = -c; }
-        auto it = pos2.find(std::make_tuple(a, b, c));
+        std::vector<int> c(&p->labels2[(size_t)lw * l], &p->labels2[(size_t)lw * l] + lw);
+        if (tree == TREE_A) c[0] = -c[0]; else if (tree == TREE_BA) c[1] = -c[1]; else if (tree == TREE_BBA) c[2] = -c[2];
+        else if (tree == TREE_CHAIN) c[lw - 1] = -c[lw - 1]; else { c[1] = -c[1]; c[2] = -c[2]; }
+        auto it = pos2.find(c);
         if (it == pos2.end()) ok = false; else partner2[l] = it->second;
       }
       p->lin2.assign(H2, 0);
@@ -392,8 +404,9 @@ int plan_build_host(biem_plan* p, int tree, int n_end) {
       }
       // phase ids: one per distinct azimuthal order vector of the first members
       auto az_of = [&](int l, int& m1, int& m2) {
-        const int a = p->labels2[3 * l], b = p->labels2[3 * l + 1], c = p->labels2[3 * l + 2];
         m2 = 0;
+        if (tree == TREE_CHAIN) { m1 = p->labels2[(size_t)lw * l + lw - 1]; return; }
+        const int a = p->labels2[3 * l], b = p->labels2[3 * l + 1], c = p->labels2[3 * l + 2];
         if (tree == TREE_A) m1 = a; else if (tree == TREE_BA) m1 = b; else if (tree == TREE_BBA) m1 = c; else { m1 = b; m2 = c; }
       };
       std::map<std::pair<int, int>, int> phid;
@@ -606,6 +619,198 @@ int plan_build_host(biem_plan* p, int tree, int n_end) {
     }
   }
   return BIEM_OK;
+}
+
+// ---- chain trees "b" * (d - 2) + "a" ----------------------------------------------------------
+// n-point Gauss-Jacobi(a, a) rule (weight (1-x^2)^a; a = 0, 1/2 take the rules above, so a chain plan of ba / bba has their rule):
+// nodes by Sturm-sequence bisection on the Jacobi matrix of the orthonormal Gegenbauer polynomials (lam = a + 1/2), weights by
+// the Christoffel numbers 1 / sum_{k<n} p_k(x)^2
+static void gauss_sym(int n, double a, std::vector<double>& t, std::vector<double>& w) {
+  if (a == 0.0) { gauss_legendre(n, t, w); return; }
+  if (a == 0.5) { gauss_cheb2(n, t, w); return; }
+  const double lam = a + 0.5;
+  std::vector<double> b2(n, 0.0);                 // squared off-diagonal a_k^2, k = 1 .. n-1
+  for (int k = 1; k < n; ++k) b2[k] = 0.25 * (double)k * (k + 2.0 * lam - 1.0) / ((k + lam - 1.0) * (k + lam));
+  auto below = [&](double x) {                    // number of eigenvalues < x
+    int cnt = 0; double q = -x;
+    if (q < 0) ++cnt;
+    for (int k = 1; k < n; ++k) {
+      if (q == 0.0) q = 1e-300;
+      q = -x - b2[k] / q;
+      if (q < 0) ++cnt;
+    }
+    return cnt;
+  };
+  t.assign(n, 0.0); w.assign(n, 0.0);
+  const double h0 = sqrt(kPi) * exp(lgamma(lam + 0.5) - lgamma(lam + 1.0));
+  for (int i = 0; i < n; ++i) {
+    double lo = -1.0, hi = 1.0;
+    for (int it = 0; it < 200 && hi - lo > 0.0; ++it) {
+      const double mid = 0.5 * (lo + hi);
+      if (mid <= lo || mid >= hi) break;
+      if (below(mid) > i) hi = mid; else lo = mid;
+    }
+    const double x = 0.5 * (lo + hi);
+    t[i] = x;
+    double p0 = 1.0 / sqrt(h0), s = p0 * p0, p1 = 0.0, aprev = 0.0;
+    for (int k = 1; k < n; ++k) {
+      const double ak = sqrt(b2[k]);
+      const double p2 = (x * p0 - aprev * p1) / ak;
+      p1 = p0; p0 = p2; aprev = ak; s += p0 * p0;
+    }
+    w[i] = 1.0 / s;
+  }
+}
+
+// labels of degree < n in n-major order: (n, l_1 .. l_{d-3}, m), each label entry from 0 to the previous one, m from -l to l
+static void chain_labels(int d, int n, std::vector<int>& lab, std::vector<int>& deg) {
+  lab.clear(); deg.clear();
+  const int lw = d - 1;
+  std::vector<int> cur(lw, 0);
+  std::function<void(int, int)> rec = [&](int j, int up) {
+    if (j == lw - 1) {
+      for (int m = -up; m <= up; ++m) { cur[j] = m; lab.insert(lab.end(), cur.begin(), cur.end()); deg.push_back(cur[0]); }
+      return;
+    }
+    for (int l = 0; l <= up; ++l) { cur[j] = l; rec(j + 1, l); }
+  };
+  for (int q = 0; q < n; ++q) { cur[0] = q; rec(1, q); }
+}
+
+int plan_build_chain_host(biem_plan* p, int d, int n_end) {
+  if (d < 3 || d > kChainDimMax) { set_error("unsupported chain tree dimension d=%d (built: 3 <= d <= %d)", d, kChainDimMax); return BIEM_ERR_UNSUPPORTED; }
+  if (n_end < 1) { set_error("n_end=%d out of range", n_end); return BIEM_ERR_ARG; }
+  const int n2 = 2 * n_end - 1, lw = d - 1;
+  const long long H2ll = harm_count_d(d, n2);
+  // every 16-bit index the fills keep (tidx16, qidx16, q2idx16, ridx) addresses the H2 table labels or fewer
+  if (H2ll > 65535) {
+    set_error("chain tree d=%d n_end=%d: %lld table labels (degree < 2 n_end - 1) exceed the 16-bit table index limit 65535 of the fill", d, n_end, H2ll);
+    return BIEM_ERR_UNSUPPORTED;
+  }
+  // the chain kernels keep (d - 2) node tables of n2 x n2 doubles in LDS (pair tables) and the radial functions up to order n2 + shift
+  if ((long long)(d - 2) * n2 * n2 > kChainNodeTab || n2 + kRadShiftMax + 6 > 2 * 320) {
+    set_error("chain tree d=%d n_end=%d: the node tables (%d x %d x %d doubles) exceed the chain kernels' LDS limit %d", d, n_end, d - 2, n2, n2, kChainNodeTab);
+    return BIEM_ERR_UNSUPPORTED;
+  }
+  p->tree = TREE_CHAIN; p->d = d; p->lw = lw; p->n_end = n_end; p->n2 = n2;
+  p->H = (int)harm_count_d(d, n_end); p->H2 = (int)H2ll;
+  p->Cd = pow(2.0 * kPi, 0.5 * d) * sqrt(2.0 / kPi);
+  chain_labels(d, n_end, p->labels, p->deg);
+  chain_labels(d, n2, p->labels2, p->deg2);
+  const int H = p->H, n = n_end, np = d - 2;        // np polar nodes
+  auto lab = [&](const std::vector<int>& L, int h, int j) { return j < lw - 1 ? L[(size_t)lw * h + j] : iabs(L[(size_t)lw * h + lw - 1]); };
+  {
+    // conjugate partners: the azimuthal order negated
+    std::map<std::vector<int>, int> pos;
+    for (int h = 0; h < H; ++h) pos[std::vector<int>(&p->labels[(size_t)lw * h], &p->labels[(size_t)lw * h] + lw)] = h;
+    p->units.clear();
+    for (int h = 0; h < H; ++h) {
+      std::vector<int> c(&p->labels[(size_t)lw * h], &p->labels[(size_t)lw * h] + lw);
+      c[lw - 1] = -c[lw - 1];
+      auto it = pos.find(c);
+      if (it == pos.end()) { set_error("internal: harmonic %d has no conjugate partner", h); return BIEM_ERR_ARG; }
+      if (h <= it->second) { p->units.push_back(h); p->units.push_back(it->second); }
+    }
+  }
+  // ---- boundary-data quadrature: n-point Gauss-Jacobi((d-j-3)/2, (d-j-3)/2) at polar node j, 2 n equispaced azimuths ----
+  std::vector<std::vector<double>> tq(np), wq(np);
+  for (int j = 0; j < np; ++j) gauss_sym(n, 0.5 * (d - j - 3), tq[j], wq[j]);
+  const int na = 2 * n;
+  long long Qll = na;
+  for (int j = 0; j < np; ++j) Qll *= n;
+  if (Qll * H > (1LL << 31)) { set_error("chain tree d=%d n_end=%d: projection matrix of %lld x %d entries too large", d, n_end, Qll, H); return BIEM_ERR_UNSUPPORTED; }
+  p->Q = (int)Qll;
+  p->qy.resize((size_t)p->Q * d); p->qw.resize(p->Q);
+  // node factors of the harmonics at the rule's nodes: Fq[j][i][L][L1], L < n_end
+  std::vector<double> Fq((size_t)np * n * n * n, 0.0);
+  for (int j = 0; j < np; ++j)
+    for (int i = 0; i < n; ++i) {
+      const double c = tq[j][i], s = sqrt(1.0 - c * c);
+      for (int L = 0; L < n; ++L) for (int L1 = 0; L1 <= L; ++L1) Fq[(((size_t)j * n + i) * n + L) * n + L1] = chain_node_factor(d, j, L, L1, c, s);
+    }
+  p->W.resize((size_t)p->Q * H * 2);
+  std::vector<int> idx(np, 0);
+  for (int q = 0; q < p->Q; ++q) {
+    int r = q / na; const int jp = q % na;
+    for (int j = np - 1; j >= 0; --j) { idx[j] = r % n; r /= n; }
+    double* y = &p->qy[(size_t)q * d];
+    double sp = 1.0, wt = kPi / n;
+    for (int j = 0; j < np; ++j) {
+      const double c = tq[j][idx[j]];
+      y[j] = sp * c; sp *= sqrt(1.0 - c * c); wt *= wq[j][idx[j]];
+    }
+    const double ph = jp * kPi / n;
+    y[d - 2] = sp * cos(ph); y[d - 1] = sp * sin(ph);
+    p->qw[q] = wt;
+    for (int h = 0; h < H; ++h) {
+      double amp = kInvSqrt2Pi;
+      for (int j = 0; j < np; ++j) amp *= Fq[(((size_t)j * n + idx[j]) * n + lab(p->labels, h, j)) * n + lab(p->labels, h, j + 1)];
+      const double ang = p->labels[(size_t)lw * h + lw - 1] * ph;
+      p->W[((size_t)q * H + h) * 2] = wt * amp * cos(ang);
+      p->W[((size_t)q * H + h) * 2 + 1] = -wt * amp * sin(ang);
+    }
+  }
+  // ---- translation terms ----
+  // int Y' conj(Y) conj(Y'') = delta(m'' = m' - m) / sqrt(2 pi) * prod_j I_j, I_j = int (1-x^2)^{(d-j-3)/2} f'_j f_j f''_j dx over
+  // the node factors f_j = sin^{l_{j+1}} Gbar_{l_j - l_{j+1}}: for the kept terms the powers of sin sum to an even number, so the
+  // integrand is a polynomial of degree <= 4 n_end - 4 times the weight and the 2 n_end-point Gauss-Jacobi rule of the node is exact.
+  // Terms are selected by the selection rules alone - at every node the triangle |l_j - l'_j| <= l''_j <= l_j + l'_j (l''_{j+1} <= l''_j)
+  // and an even (l_j - l_{j+1}) + (l'_j - l'_{j+1}) + (l''_j - l''_{j+1}); at the azimuth |m''| <= l''_{d-3}.
+  const int nq = 2 * n;
+  std::vector<double> Ft((size_t)np * n2 * n2 * nq, 0.0), wt_((size_t)np * nq);
+  for (int j = 0; j < np; ++j) {
+    std::vector<double> t, w; gauss_sym(nq, 0.5 * (d - j - 3), t, w);
+    for (int i = 0; i < nq; ++i) {
+      wt_[(size_t)j * nq + i] = w[i];
+      const double c = t[i], s = sqrt(1.0 - c * c);
+      for (int L = 0; L < n2; ++L) for (int L1 = 0; L1 <= L; ++L1) Ft[(((size_t)j * n2 + L) * n2 + L1) * nq + i] = chain_node_factor(d, j, L, L1, c, s);
+    }
+  }
+  auto node_int = [&](int j, int a0, int a1, int b0, int b1, int c0, int c1) {
+    const double* fa = &Ft[(((size_t)j * n2 + a0) * n2 + a1) * nq];
+    const double* fb = &Ft[(((size_t)j * n2 + b0) * n2 + b1) * nq];
+    const double* fc = &Ft[(((size_t)j * n2 + c0) * n2 + c1) * nq];
+    const double* w = &wt_[(size_t)j * nq];
+    double acc = 0.0;
+    for (int i = 0; i < nq; ++i) acc += w[i] * fa[i] * fb[i] * fc[i];
+    return acc;
+  };
+  std::unordered_map<unsigned long long, int> pos2;           // label key -> index among the degrees < n2
+  const unsigned long long base = 2ULL * n2 + 1;
+  auto key = [&](const int* l) { unsigned long long k = 0; for (int j = 0; j < lw; ++j) k = k * base + (unsigned long long)(l[j] + n2); return k; };
+  for (int l = 0; l < p->H2; ++l) pos2[key(&p->labels2[(size_t)lw * l])] = l;
+  p->lists_built = true;
+  p->ptr.assign((size_t)H * H + 1, 0);
+  p->coef.clear(); p->tidx.clear();
+  std::vector<int> a(np + 1), b(np + 1), c(lw);
+  std::vector<double> pre(np + 1);
+  bool too_many = false;
+  for (int h = 0; h < H && !too_many; ++h)
+    for (int hp = 0; hp < H; ++hp) {
+      for (int j = 0; j <= np; ++j) { b[j] = lab(p->labels, h, j); a[j] = lab(p->labels, hp, j); }
+      const int m = p->labels[(size_t)lw * h + lw - 1], mp = p->labels[(size_t)lw * hp + lw - 1], mu = mp - m;
+      c[lw - 1] = mu;
+      // choose l''_j node by node; pre[j] = product of the node integrals 0 .. j-1
+      std::function<void(int)> rec = [&](int j) {
+        const int lo = iabs(a[j] - b[j]), hi = std::min(a[j] + b[j], j == 0 ? n2 - 1 : c[j - 1]);
+        for (int l2 = lo; l2 <= hi; ++l2) {
+          if (j > 0 && (((a[j - 1] - a[j]) + (b[j - 1] - b[j]) + (c[j - 1] - l2)) & 1)) continue;
+          c[j] = l2;
+          pre[j] = j == 0 ? 1.0 : pre[j - 1] * node_int(j - 1, a[j - 1], a[j], b[j - 1], b[j], c[j - 1], l2);
+          if (j < np - 1) { rec(j + 1); continue; }
+          // last polar node: l''_{d-2} = |m''|
+          if (l2 < iabs(mu) || (((a[j] - a[j + 1]) + (b[j] - b[j + 1]) + (l2 - iabs(mu))) & 1)) continue;
+          const double v = pre[j] * node_int(j, a[j], a[j + 1], b[j], b[j + 1], l2, iabs(mu));
+          p->coef.push_back(isign_even(b[0] + c[0] - a[0]) * v * kInvSqrt2Pi);
+          p->tidx.push_back(pos2.at(key(c.data())));
+        }
+      };
+      rec(0);
+      if (p->coef.size() > 0x7fffffffULL) { too_many = true; break; }
+      p->ptr[(size_t)h * H + hp + 1] = (uint32_t)p->coef.size();
+    }
+  if (too_many) { set_error("chain tree d=%d n_end=%d: more than 2^31 translation terms", d, n_end); return BIEM_ERR_UNSUPPORTED; }
+  return plan_build_tail(p);
 }
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error("%s failed: %s", #x, hipGetErrorString(e_)); return BIEM_ERR_HIP; } } while (0)

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include "special.hpp"
 
+constexpr int kChainNodeTab = 4096;        // doubles of node-factor tables the chain kernels keep in LDS
 constexpr int kLists2dMax = 160;            // 2-D plans up to this order also carry term lists (tests, the generic fill forms)
 
 struct biem_plan {
@@ -12,8 +13,9 @@ struct biem_plan {
   int H = 0, H2 = 0, Q = 0;
   double Cd = 0.0;                          // (2 pi)^{d/2} sqrt(2/pi)
   // host tables
-  std::vector<int> labels, deg;             // [H][3], [H]
-  std::vector<int> labels2, deg2;           // [H2][3], [H2]
+  int lw = 3;                               // label width: 3 (a, ba, bba, caa), d - 1 (chain trees)
+  std::vector<int> labels, deg;             // [H][lw], [H]
+  std::vector<int> labels2, deg2;           // [H2][lw], [H2]
   std::vector<int> units;                   // [U][2]: harmonics (h, p) with conj Y_h = Y_p, h <= p (h == p: real harmonic)
   std::vector<double> qy, qw;               // [Q][d], [Q]
   std::vector<double> W;                    // [Q][H] complex128 interleaved
@@ -92,6 +94,7 @@ struct biem_plan {
 
 namespace biem {
 int plan_build_host(biem_plan* p, int tree, int n_end);   // returns BIEM_* status
+int plan_build_chain_host(biem_plan* p, int d, int n_end);  // the standard chain tree "b" * (d - 2) + "a", 3 <= d <= kChainDimMax
 int plan_upload(biem_plan* p);
 void plan_free(biem_plan* p);
 void set_error(const char* fmt, ...);

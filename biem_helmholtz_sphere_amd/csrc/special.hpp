@@ -17,7 +17,10 @@ constexpr double kEulerGamma = 0.57721566490153286061;
 constexpr double kSqrtHalfPi = 1.25331413731550025121;   // sqrt(pi/2)
 constexpr double kInvSqrt2Pi = 0.39894228040143267794;   // 1/sqrt(2 pi)
 
-enum Tree { TREE_A = 0, TREE_BA = 1, TREE_BBA = 2, TREE_CAA = 3 };
+enum Tree { TREE_A = 0, TREE_BA = 1, TREE_BBA = 2, TREE_CAA = 3, TREE_CHAIN = 4 };
+// standard chain trees "b" * (d - 2) + "a" (TREE_CHAIN; ba and bba are its d = 3, 4 members): labels (l_0 = n >= l_1 >= ... >= l_{d-3} >= |m|)
+constexpr int kChainDimMax = 10;
+constexpr int kRadShiftMax = kChainDimMax / 2 - 1;        // order shift of the d-dimensional radial functions (below)
 
 BIEM_HD int tree_dim(int tree) { return tree == TREE_A ? 2 : (tree == TREE_BA ? 3 : 4); }   // bba, caa: 4
 
@@ -28,6 +31,16 @@ BIEM_HD int harm_count(int tree, int n) {
   if (tree == TREE_BA) return n * n;
   return n * (n + 1) * (2 * n + 1) / 6;
 }
+
+// number of harmonics of degree < n on S^{d-1}: C(n + d - 2, d - 1) + C(n + d - 3, d - 1) (any d >= 2; long long: callers check ranges)
+BIEM_HD long long harm_count_d(int d, int n) {
+  if (n <= 0) return 0;
+  auto binom = [](long long a, int b) { long long r = 1; for (int i = 1; i <= b; ++i) r = r * (a - b + i) / i; return a < b ? 0LL : r; };
+  return binom(n + d - 2, d - 1) + binom(n + d - 3, d - 1);
+}
+
+// order shift of z_n^{(d)}: odd d -> j_{n+s}(x) / x^s, s = (d-3)/2;  even d -> sqrt(pi/2) J_{n+s}(x) / x^s, s = d/2 - 1
+BIEM_HD int radial_shift(int d) { return (d & 1) ? (d - 3) / 2 : d / 2 - 1; }
 
 // ---------------------------------------------------------------------------------------------
 // Integer-order cylindrical Bessel functions J_0..J_nmax, Y_0..Y_nmax at real x > 0.
@@ -117,17 +130,24 @@ BIEM_HD void bessel_jy_sph(int nmax, double x, double* J, double* Y) {
   }
 }
 
-// d-dimensional z_n, n = 0..nmax. For d = 4 the caller must provide nmax+2 slots (order n+1 is needed).
+// d-dimensional z_n, n = 0..nmax. For d >= 4 the caller must provide nmax + 1 + radial_shift(d) slots (orders up to n + shift
+// are needed).
 BIEM_HD void radial_d(int d, int nmax, double x, double* J, double* Y) {
   if (d == 3) {
     bessel_jy_sph(nmax, x, J, Y);
   } else if (d == 2) {
     bessel_jy_int(nmax, x, J, Y);
     for (int n = 0; n <= nmax; ++n) { J[n] *= kSqrtHalfPi; if (Y) Y[n] *= kSqrtHalfPi; }
-  } else {  // d == 4: sqrt(pi/2) Z_{n+1}(x) / x
+  } else if (d == 4) {  // sqrt(pi/2) Z_{n+1}(x) / x
     bessel_jy_int(nmax + 1, x, J, Y);
     double f = kSqrtHalfPi / x;
     for (int n = 0; n <= nmax; ++n) { J[n] = J[n + 1] * f; if (Y) Y[n] = Y[n + 1] * f; }
+  } else {  // d >= 5: the order shift of radial_shift
+    const int sh = radial_shift(d);
+    double f = (d & 1) ? 1.0 : kSqrtHalfPi;
+    for (int i = 0; i < sh; ++i) f /= x;
+    if (d & 1) bessel_jy_sph(nmax + sh, x, J, Y); else bessel_jy_int(nmax + sh, x, J, Y);
+    for (int n = 0; n <= nmax; ++n) { J[n] = J[n + sh] * f; if (Y) Y[n] = Y[n + sh] * f; }
   }
 }
 
@@ -316,7 +336,7 @@ BIEM_HD void bessel_jh_int_c(int nmax, zc z, zc* J, zc* H) {
 }
 
 // d-dimensional regular and outgoing radial functions at a complex argument; real arguments (Im z == 0) take the real
-// routines above (bit-identical to the real-k path).  J, H: nmax + 1 entries (d = 4: nmax + 2 slots each).  H == nullptr: the
+// routines above (bit-identical to the real-k path).  J, H: nmax + 1 entries (d >= 4: nmax + 1 + radial_shift(d) slots each).  H == nullptr: the
 // regular functions only (the outgoing ones are not computed).
 BIEM_HD void radial_jh(int d, int nmax, zc z, zc* J, zc* H) {
   if (z.y == 0.0) {
@@ -331,11 +351,23 @@ BIEM_HD void radial_jh(int d, int nmax, zc z, zc* J, zc* H) {
   } else if (d == 2) {
     bessel_jh_int_c(nmax, z, J, H);
     for (int n = 0; n <= nmax; ++n) { J[n] = zscl(J[n], kSqrtHalfPi); if (H) H[n] = zscl(H[n], kSqrtHalfPi); }
-  } else {
+  } else if (d == 4) {
     bessel_jh_int_c(nmax + 1, z, J, H);
     zc f = zscl(zinv(z), kSqrtHalfPi);
     for (int n = 0; n <= nmax; ++n) { J[n] = zmul(J[n + 1], f); if (H) H[n] = zmul(H[n + 1], f); }
+  } else {  // d >= 5: the order shift of radial_shift
+    const int sh = radial_shift(d);
+    const zc iz = zinv(z);
+    zc f = zmk((d & 1) ? 1.0 : kSqrtHalfPi, 0.0);
+    for (int i = 0; i < sh; ++i) f = zmul(f, iz);
+    if (d & 1) bessel_jh_sph_c(nmax + sh, z, J, H); else bessel_jh_int_c(nmax + sh, z, J, H);
+    for (int n = 0; n <= nmax; ++n) { J[n] = zmul(J[n + sh], f); if (H) H[n] = zmul(H[n + sh], f); }
   }
+}
+
+// z_n(0) = delta_{n0} sqrt(pi/2) 2^{1-d/2} / Gamma(d/2): the regular function at the centre of a ball
+BIEM_HD double radial_z0_at_zero(int d) {
+  return d == 2 ? kSqrtHalfPi : d == 3 ? 1.0 : d == 4 ? 0.5 * kSqrtHalfPi : kSqrtHalfPi * exp2(1.0 - 0.5 * d) / tgamma(0.5 * d);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -374,6 +406,56 @@ BIEM_HD double gbar_single(int k, int l, double x) {
     p0 = p1; p1 = p2; aprev = aq;
   }
   return p1;
+}
+
+// orthonormal Gegenbauer p_k^{(lam)}(x) for any lam > 0 (integer or half-integer in the chain trees), weight (1-x^2)^{lam-1/2}:
+// the recurrence of gbar_single with h_0 = int (1-x^2)^{lam-1/2} = sqrt(pi) Gamma(lam + 1/2) / Gamma(lam + 1)
+BIEM_HD double gbar_lam(int k, double lam, double x) {
+  const double h0 = sqrt(kPi) * exp(lgamma(lam + 0.5) - lgamma(lam + 1.0));
+  double p0 = 1.0 / sqrt(h0);
+  if (k == 0) return p0;
+  double a1 = 0.5 * sqrt((2.0 * lam) / (lam * (1.0 + lam)));
+  double p1 = x * p0 / a1;
+  double aprev = a1;
+  for (int q = 2; q <= k; ++q) {
+    double aq = 0.5 * sqrt((double)q * ((double)q + 2.0 * lam - 1.0) / (((double)q + lam - 1.0) * ((double)q + lam)));
+    double p2 = (x * p1 - aprev * p0) / aq;
+    p0 = p1; p1 = p2; aprev = aq;
+  }
+  return p1;
+}
+
+// Chain-tree polar angles of a direction u[d]: cos t_j = u_j / |u_{j..}|, sin t_j = |u_{j+1..}| / |u_{j..}| (j = 0 .. d-3) and the
+// azimuth phi = atan2(u_{d-1}, u_{d-2}); c, s hold d - 2 entries.  (ba, bba: make_dir below, the same angles.)
+BIEM_HD void chain_angles(int d, const double* u, double* c, double* s, double* phi) {
+  double tail = u[d - 1] * u[d - 1] + u[d - 2] * u[d - 2];
+  for (int j = d - 3; j >= 0; --j) {
+    const double rho1 = sqrt(tail);
+    tail += u[j] * u[j];
+    const double rho = sqrt(tail);
+    c[j] = 1.0; s[j] = 0.0;
+    if (rho > 0.0) { c[j] = u[j] / rho; s[j] = rho1 / rho; }
+  }
+  *phi = atan2(u[d - 1], u[d - 2]);
+}
+
+// node factor of a chain harmonic at polar node j: sin^{L1} t_j Gbar_{L - L1}^{(L1 + (d-j-2)/2)}(cos t_j)
+BIEM_HD double chain_node_factor(int d, int j, int L, int L1, double c, double s) {
+  double sl = 1.0;
+  for (int i = 0; i < L1; ++i) sl *= s;
+  return sl * gbar_lam(L - L1, (double)L1 + 0.5 * (d - j - 2), c);
+}
+
+// One chain harmonic Y_label(u), label = (l_0 .. l_{d-3}, m) (d - 1 entries); u need not be normalised
+BIEM_HD void chain_harmonic(int d, const int* lab, const double* c, const double* s, double phi, double* re, double* im) {
+  double amp = kInvSqrt2Pi;
+  for (int j = 0; j <= d - 3; ++j) {
+    const int L = lab[j], L1 = j + 1 <= d - 3 ? lab[j + 1] : (lab[d - 2] < 0 ? -lab[d - 2] : lab[d - 2]);
+    amp *= chain_node_factor(d, j, L, L1, c[j], s[j]);
+  }
+  const double ang = (double)lab[d - 2] * phi;
+  *re = amp * cos(ang);
+  *im = amp * sin(ang);
 }
 
 // Angles of a direction for the harmonics of one tree (computed once per direction).

@@ -76,11 +76,21 @@ int biem_plan_create_host(int tree, int n_end, biem_plan** plan);
 int biem_plan_upload(biem_plan* plan);
 /* = create_host + upload */
 int biem_plan_create(int tree, int n_end, biem_plan** plan);
+/* the standard chain tree "b" * (d - 2) + "a" of dimension d (3 <= d <= 10; d = 3, 4 give the labels and rules of ba / bba through
+ * the generic chain code): harmonics Y = prod_j sin^{l_{j+1}} t_j Gbar_{l_j - l_{j+1}}^{(l_{j+1} + (d-j-2)/2)}(cos t_j) e^{i m phi} / sqrt(2 pi)
+ * (Gbar: orthonormal Gegenbauer, no Condon-Shortley phase), boundary rule = n_end-point Gauss-Jacobi((d-j-3)/2, (d-j-3)/2) per polar
+ * node x 2 n_end azimuths.  Orders whose tables pass a 16-bit index or LDS limit fail with BIEM_ERR_UNSUPPORTED naming it. */
+int biem_plan_create_chain_host(int d, int n_end, biem_plan** plan);
+int biem_plan_create_chain(int d, int n_end, biem_plan** plan);
 int biem_plan_destroy(biem_plan* plan);
 /* d, H (degree < n_end), Q quadrature points per ball, H2 (degree < 2 n_end - 1), number of translation terms */
 int biem_plan_info(const biem_plan* plan, int* d, int* n_harm, int* n_quad, int* n_harm2, long long* n_terms);
 /* h_labels[H][3]: a:(m,0,0)  ba:(n,m,0)  bba:(n,l,m)  caa:(n,m1,m2);  h_deg[H]: degree n */
+/* (a chain plan - biem_plan_create_chain - has wider labels: BIEM_ERR_UNSUPPORTED, nothing is written) */
 int biem_plan_labels(const biem_plan* plan, int* h_labels, int* h_deg);
+/* h_labels[H][width], width >= the plan's label width (3; chain plans: d - 1), entries beyond it 0.  Chain labels:
+ * (n = l_0 >= l_1 >= ... >= l_{d-3} >= |m|, m) in n-major order (l_1 from 0 to n, then the next entry, ..., m from -l to l) */
+int biem_plan_labels_n(const biem_plan* plan, int width, int* h_labels, int* h_deg);
 /* the real-harmonic form used by the symmetric path: h_partner[h] = p with conj Y_h = Y_p (p == h: a real harmonic); h_slot[h] =
  * internal position of harmonic h among its ball's H unknowns in that path: for a unit (h <= p) the "cosine" combination
  * (Y_h + Y_p)/sqrt2 sits in slot h_slot[h], the "sine" combination i (Y_p - Y_h)/sqrt2 in slot h_slot[p] */
