@@ -15,6 +15,7 @@ from ._biem import (
     biem,
     biem_factorize,
     biem_u,
+    biem_u_grad,
     max_memory,
     max_n_end,
     plane_wave,
@@ -31,6 +32,7 @@ __all__ = [
     "biem",
     "biem_factorize",
     "biem_u",
+    "biem_u_grad",
     "max_memory",
     "max_n_end",
     "plane_wave",

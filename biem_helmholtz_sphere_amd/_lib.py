@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libbiem_mi355.so")
 
 BIEM_OK = 0
+BIEM_ERR_UNSUPPORTED = 3
 TREE_IDS = {"a": 0, "ba": 1, "bba": 2, "caa": 3}
 FILL_REFERENCE, FILL_EQUILIBRATED, FILL_SYMMETRIC = 0, 1, 2
 USCAT_FAR_FIELD, USCAT_PER_BALL, USCAT_KIND_INNER, USCAT_POINTS_BATCHED = 1, 2, 4, 8
@@ -54,6 +55,7 @@ SIGNATURES = {
     "biem_density": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _ll, _dp, _dp, _vp]),
     "biem_uscat_workspace_bytes": (_sz, [_vp, _i, _i]),
     "biem_uscat": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _vp, _sz, _vp]),
+    "biem_uscat_grad": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _vp, _sz, _vp]),
     "biem_solve_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "biem_solve": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_ldlt": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _ip, _i, _vp, _sz, _vp]),

@@ -95,6 +95,9 @@ double fill_sym_bytes(int n_pad);
 int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
                  const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
                  double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
+int launch_uscat_grad(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                      const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
+                      double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
 int lu_npad(int N);
 size_t lu_workspace_bytes(int nb, int n_pad, int nrhs);
 int launch_lu_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long lda, long long sys_stride, int* d_ipiv,

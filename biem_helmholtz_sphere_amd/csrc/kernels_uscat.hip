@@ -156,74 +156,92 @@ constexpr int kFastNendMaxCaa = 12;        // 4-D (caa): c in a dense [n][m1][m2
 // INNER (kind = "inner", near field): the radial factor is the regular function j_n(k r), whose upward recurrence is unstable
 // for n > |k r|: each lane computes j_0 .. j_{n_end-1} once per ball by the backward recurrence of radial_jh into its own LDS row
 // (64-thread workgroups; odd row stride: conflict-free 16-byte reads) and the harmonic loops read it by degree.
+// The LDS layout, the recurrence tables and the staging of a ball's coefficients of the per-lane kernels.  k_uscat_fast and the gradient
+// kernel k_uscat_grad_fast share them as ONE text expanded in both (macros, not device functions: the compiler contracts multiply-adds
+// after inlining, and a value kernel built from inlined helpers differed from its predecessor in the last bit of some results; the
+// expansion is token for token the text the value kernel had, so its code object does not change).
+// They expect n_end, H, labels, tid, T and (staging) cs in scope and define ra, rb, cmm, ga, gia, g0, jA, jB, jC, jN, sC, K2, ncaa, ms, nC.
+#define BIEM_FAST_LAYOUT() \
+  extern __shared__ double sfast[]; \
+  /* 3-D: ra[q * n_end + m], rb[q * n_end + m] (q > m), cm[m]; then the ball's coefficients sC[pos] */ \
+  constexpr bool LEG = TREE == TREE_BA || TREE == TREE_BBA;   /* a Legendre factor Pbar_l^m */ \
+  double* ra = sfast; \
+  double* rb = ra + (LEG ? n_end * n_end : 0); \
+  double* cmm = rb + (LEG ? n_end * n_end : 0); \
+  double* ga = cmm + (LEG ? ((n_end + 1) & ~1) : 0);   /* bba: Gegenbauer a_q of order lam = l + 1 at [l * n_end + q] */ \
+  double* gia = ga + (TREE == TREE_BBA ? n_end * n_end : 0);   /*      1 / a_q */ \
+  double* g0 = gia + (TREE == TREE_BBA ? n_end * n_end : 0);   /*      p_0 = 1 / sqrt(h_0(l)) */ \
+  /* caa: the Jacobi recurrence p_{m+1} = (jA x + jB) p_m - jC p_{m-1} of cbar_single and its norm, at [(a * n_end + b) * K2 + m] */ \
+  const int K2 = (n_end + 1) / 2, ncaa = TREE == TREE_CAA ? n_end * n_end * K2 : 0; \
+  double* jA = g0 + (TREE == TREE_BBA ? ((n_end + 1) & ~1) : 0); \
+  double* jB = jA + ncaa; \
+  double* jC = jB + ncaa; \
+  double* jN = jC + ncaa; \
+  cplx* sC = (cplx*)(jN + ncaa); \
+  const int ms = 2 * n_end - 1; \
+  const int nC = TREE == TREE_BA ? n_end * n_end : TREE == TREE_BBA ? n_end * n_end * ms : TREE == TREE_CAA ? n_end * ms * ms : ms;
+#define BIEM_FAST_TABLES() \
+  if (LEG) { \
+    for (int e = tid; e < n_end * n_end; e += T) { \
+      const int q = e / n_end, m = e - q * n_end; \
+      double a = 0.0, b = 0.0; \
+      if (q > m) { \
+        a = sqrt((double)(4 * q * q - 1) / (double)(q * q - m * m)); \
+        b = sqrt((double)((q - 1) * (q - 1) - m * m) / (double)(4 * (q - 1) * (q - 1) - 1)); \
+      } \
+      ra[e] = a; rb[e] = b; \
+    } \
+    for (int m = tid; m < n_end; m += T) cmm[m] = m == 0 ? 0.0 : sqrt((double)(2 * m + 1) / (double)(2 * m)); \
+  } \
+  if (TREE == TREE_CAA) { \
+    for (int e = tid; e < ncaa; e += T) { \
+      const int a = e / (n_end * K2), b = (e / K2) % n_end, m = e % K2; \
+      const double al = (double)b, be = (double)a;   /* Jacobi P^{(alpha = b, beta = a)} */ \
+      double A, Bc, C; \
+      if (m == 0) { A = 0.5 * (al + be + 2.0); Bc = (al + 1.0) - A; C = 0.0; } \
+      else { \
+        const double t = 2.0 * m + al + be, den = 2.0 * (m + 1.0) * (m + al + be + 1.0) * t; \
+        A = (t + 1.0) * (t + 2.0) * t / den; Bc = (t + 1.0) * (al * al - be * be) / den; C = 2.0 * (m + al) * (m + be) * (t + 2.0) / den; \
+      } \
+      double nr = 2.0 * (2.0 * m + a + b + 1.0); \
+      for (int i = 1; i <= a; ++i) nr *= (double)(m + b + i) / (double)(m + i); \
+      jA[e] = A; jB[e] = Bc; jC[e] = C; jN[e] = sqrt(nr); \
+    } \
+  } \
+  if (TREE == TREE_BBA) {   /* the coefficients of gbar_single */ \
+    for (int e = tid; e < n_end * n_end; e += T) { \
+      const int l = e / n_end, q = e - l * n_end; \
+      const double lam = (double)(l + 1); \
+      const double aq = q == 0 ? 1.0 : 0.5 * sqrt((double)q * ((double)q + 2.0 * lam - 1.0) / (((double)q + lam - 1.0) * ((double)q + lam))); \
+      ga[e] = q == 0 ? 0.0 : aq; gia[e] = 1.0 / aq; \
+    } \
+    for (int l = tid; l < n_end; l += T) { \
+      double h0 = 0.5 * kPi; \
+      for (int i = 1; i <= l; ++i) h0 *= ((double)i + 0.5) / ((double)i + 1.0); \
+      g0[l] = 1.0 / sqrt(h0); \
+    } \
+  }
+#define BIEM_FAST_STAGE() \
+  for (int h = tid; h < H; h += T) { \
+    int pos; \
+    if (TREE == TREE_BA) { const int n = labels[3 * h], m = labels[3 * h + 1]; pos = n * n + n + m; } \
+    else if (TREE == TREE_BBA) pos = (labels[3 * h] * n_end + labels[3 * h + 1]) * (2 * n_end - 1) + labels[3 * h + 2] + n_end - 1; \
+    else if (TREE == TREE_CAA) pos = (labels[3 * h] * ms + labels[3 * h + 1] + n_end - 1) * ms + labels[3 * h + 2] + n_end - 1; \
+    else pos = labels[3 * h] + n_end - 1; \
+    sC[pos] = cs[h]; \
+  }
 template <int TREE, bool FAR, bool INNER>
 __global__ void __launch_bounds__(256) k_uscat_fast(int d, int H, int n_end, const int* __restrict__ labels, int nb, int B, int P,
                                                      const cplx* __restrict__ k, const double* __restrict__ centers,
                                                      const double* __restrict__ radii, int geom_batched, const cplx* __restrict__ c,
                                                      const double* __restrict__ pts, int flags, cplx* __restrict__ out) {
-  extern __shared__ double sfast[];
-  // 3-D: ra[q * n_end + m], rb[q * n_end + m] (q > m), cm[m]; then the ball's coefficients sC[pos]
-  constexpr bool LEG = TREE == TREE_BA || TREE == TREE_BBA;       // a Legendre factor Pbar_l^m
-  double* ra = sfast;
-  double* rb = ra + (LEG ? n_end * n_end : 0);
-  double* cmm = rb + (LEG ? n_end * n_end : 0);
-  double* ga = cmm + (LEG ? ((n_end + 1) & ~1) : 0);              // bba: Gegenbauer a_q of order lam = l + 1 at [l * n_end + q]
-  double* gia = ga + (TREE == TREE_BBA ? n_end * n_end : 0);       //      1 / a_q
-  double* g0 = gia + (TREE == TREE_BBA ? n_end * n_end : 0);       //      p_0 = 1 / sqrt(h_0(l))
-  // caa: the Jacobi recurrence p_{m+1} = (jA x + jB) p_m - jC p_{m-1} of cbar_single and its norm, at [(a * n_end + b) * K2 + m]
-  const int K2 = (n_end + 1) / 2, ncaa = TREE == TREE_CAA ? n_end * n_end * K2 : 0;
-  double* jA = g0 + (TREE == TREE_BBA ? ((n_end + 1) & ~1) : 0);
-  double* jB = jA + ncaa;
-  double* jC = jB + ncaa;
-  double* jN = jC + ncaa;
-  cplx* sC = (cplx*)(jN + ncaa);
-  const int ms = 2 * n_end - 1;
-  const int nC = TREE == TREE_BA ? n_end * n_end : TREE == TREE_BBA ? n_end * n_end * ms : TREE == TREE_CAA ? n_end * ms * ms : ms;
+  BIEM_FAST_LAYOUT()
   const int js = (n_end + 2) | 1;           // INNER: row stride of the per-lane j_n store (radial_jh wants n_end + 1 slots at d = 4)
   const int s = blockIdx.y, tid = threadIdx.x, T = blockDim.x;
   cplx* sJl = sC + nC + (size_t)tid * js;
   const int p = blockIdx.x * T + tid, pc = p < P ? p : P - 1;
   const bool per_ball = (flags & BIEM_USCAT_PER_BALL) != 0, pb = (flags & BIEM_USCAT_POINTS_BATCHED) != 0;
-  if (LEG) {
-    for (int e = tid; e < n_end * n_end; e += T) {
-      const int q = e / n_end, m = e - q * n_end;
-      double a = 0.0, b = 0.0;
-      if (q > m) {
-        a = sqrt((double)(4 * q * q - 1) / (double)(q * q - m * m));
-        b = sqrt((double)((q - 1) * (q - 1) - m * m) / (double)(4 * (q - 1) * (q - 1) - 1));
-      }
-      ra[e] = a; rb[e] = b;
-    }
-    for (int m = tid; m < n_end; m += T) cmm[m] = m == 0 ? 0.0 : sqrt((double)(2 * m + 1) / (double)(2 * m));
-  }
-  if (TREE == TREE_CAA) {
-    for (int e = tid; e < ncaa; e += T) {
-      const int a = e / (n_end * K2), b = (e / K2) % n_end, m = e % K2;
-      const double al = (double)b, be = (double)a;            // Jacobi P^{(alpha = b, beta = a)}
-      double A, Bc, C;
-      if (m == 0) { A = 0.5 * (al + be + 2.0); Bc = (al + 1.0) - A; C = 0.0; }
-      else {
-        const double t = 2.0 * m + al + be, den = 2.0 * (m + 1.0) * (m + al + be + 1.0) * t;
-        A = (t + 1.0) * (t + 2.0) * t / den; Bc = (t + 1.0) * (al * al - be * be) / den; C = 2.0 * (m + al) * (m + be) * (t + 2.0) / den;
-      }
-      double nr = 2.0 * (2.0 * m + a + b + 1.0);
-      for (int i = 1; i <= a; ++i) nr *= (double)(m + b + i) / (double)(m + i);
-      jA[e] = A; jB[e] = Bc; jC[e] = C; jN[e] = sqrt(nr);
-    }
-  }
-  if (TREE == TREE_BBA) {                   // the coefficients of gbar_single
-    for (int e = tid; e < n_end * n_end; e += T) {
-      const int l = e / n_end, q = e - l * n_end;
-      const double lam = (double)(l + 1);
-      const double aq = q == 0 ? 1.0 : 0.5 * sqrt((double)q * ((double)q + 2.0 * lam - 1.0) / (((double)q + lam - 1.0) * ((double)q + lam)));
-      ga[e] = q == 0 ? 0.0 : aq; gia[e] = 1.0 / aq;
-    }
-    for (int l = tid; l < n_end; l += T) {
-      double h0 = 0.5 * kPi;
-      for (int i = 1; i <= l; ++i) h0 *= ((double)i + 0.5) / ((double)i + 1.0);
-      g0[l] = 1.0 / sqrt(h0);
-    }
-  }
+  BIEM_FAST_TABLES()
   double x[4];
   for (int i = 0; i < d; ++i) x[i] = pb ? pts[((size_t)i * P + pc) * nb + s] : pts[(size_t)i * P + pc];
   const cplx kk = k[s];
@@ -233,14 +251,7 @@ __global__ void __launch_bounds__(256) k_uscat_fast(int d, int H, int n_end, con
   for (int b = 0; b < B; ++b) {
     __syncthreads();                       // the previous ball's coefficients are no longer read (and the tables are written)
     const cplx* cs = c + ((size_t)s * B + b) * H;
-    for (int h = tid; h < H; h += T) {
-      int pos;
-      if (TREE == TREE_BA) { const int n = labels[3 * h], m = labels[3 * h + 1]; pos = n * n + n + m; }
-      else if (TREE == TREE_BBA) pos = (labels[3 * h] * n_end + labels[3 * h + 1]) * (2 * n_end - 1) + labels[3 * h + 2] + n_end - 1;
-      else if (TREE == TREE_CAA) pos = (labels[3 * h] * ms + labels[3 * h + 1] + n_end - 1) * ms + labels[3 * h + 2] + n_end - 1;
-      else pos = labels[3 * h] + n_end - 1;
-      sC[pos] = cs[h];
-    }
+    BIEM_FAST_STAGE()
     __syncthreads();
     const double* cb = centers + ((geom_batched ? (size_t)s * B : 0) + b) * d;
     const double rho = radii[(geom_batched ? (size_t)s * B : 0) + b];
@@ -449,6 +460,336 @@ __global__ void __launch_bounds__(256) k_uscat_fast(int d, int H, int n_end, con
 }
 
 // ---------------------------------------------------------------------------------------------
+// Gradient of the near field, trees a, ba, bba, caa (bpa / bpbpa in permuted axes), both kinds: ONE POINT PER LANE, the loops of
+// k_uscat_fast with the derivative of every factor carried along its recurrence and d complex sums instead of one.
+//   Write a term as z_n(k r) Y_h(u / r) = [z_n(k r) / r^n] S_h(u) with the solid harmonic S_h(u) = r^n Y_h(u / r), a homogeneous
+//   polynomial of degree n in the Cartesian components.  With z_n'(x) = (n / x) z_n - z_{n+1}:
+//       grad (z_n Y_h) = -k z_{n+1}(k r) Y_h(e) e + (z_n(k r) / r) (grad S_h)(e),      e = u / r,
+//   and both S_h and grad S_h are evaluated ON THE UNIT SPHERE by recurrences in the components of e that never divide:
+//     e^{i m phi} sin^m      -> w^m, w = e_a + i e_b (the last two components), gradient m w^{m-1} (1, i);
+//     Pbar_l^m(c) / sin^m    -> Q_l^m(c), the same three-term recurrence (tables ra, rb) started from the constant Q_m^m; below the
+//                               root (bba) in the homogeneous form L_l = t^{l-m} Q_l^m(e_1 / t), t^2 = e_1^2 + e_2^2 + e_3^2,
+//                               L_l = ra (e_1 L_{l-1} - rb t^2 L_{l-2}) with gradient a_l (0,1,0,0) + b_l (0, e_1, e_2, e_3);
+//     Gegenbauer / Jacobi    -> polynomials in e_0 (bba) or in xx = e_0^2 + e_1^2 - e_2^2 - e_3^2 (caa): value and derivative.
+//   So a point whose offset lies on a coordinate axis of the tree (sin theta = 0 at any node) is an ordinary point: no branch, no
+//   guard, the same instructions.  At the centre of a ball (inner kind) only z_1 / r -> k z_0(0) / d survives; e is then arbitrary
+//   (grad S_1 is constant).
+//   Per innermost step three radial weights (alpha_n = -k z_{n+1}, beta_n = z_n / r): W1 = P (alpha + (n - n0) beta),
+//   W2 = beta P', W3 = beta P, each times the coefficients of the sign combinations that share them.
+// out[i][p][s] (or [i][p][s][b]): component i in the plan's (canonical) axes.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void cacc(cplx& acc, const cplx& a, const cplx& b) {           // acc += a b
+  acc.x += a.x * b.x - a.y * b.y; acc.y += a.x * b.y + a.y * b.x;
+}
+__device__ __forceinline__ void cacc_conj(cplx& acc, const cplx& a, const cplx& b) {          // acc += a conj(b)
+  acc.x += a.x * b.x + a.y * b.y; acc.y += a.y * b.x - a.x * b.y;
+}
+__device__ __forceinline__ void cacc_real(cplx& acc, const cplx& a, double s) { acc.x += a.x * s; acc.y += a.y * s; }
+__device__ __forceinline__ cplx cmulc(const cplx& a, const cplx& b) {                     // a conj(b)
+  return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
+}
+
+template <int TREE, bool INNER>
+__global__ void __launch_bounds__(256) k_uscat_grad_fast(int d, int H, int n_end, const int* __restrict__ labels, int nb, int B, int P,
+                                                          const cplx* __restrict__ k, const double* __restrict__ centers,
+                                                          const double* __restrict__ radii, int geom_batched,
+                                                          const cplx* __restrict__ c, const double* __restrict__ pts, int flags,
+                                                          cplx* __restrict__ out) {
+  constexpr int D = TREE == TREE_A ? 2 : TREE == TREE_BA ? 3 : 4;   // = d (a compile-time extent keeps x, e, g in registers)
+  BIEM_FAST_LAYOUT()
+  const int js = (n_end + 3) | 1;           // INNER: j_0 .. j_{n_end} per lane (radial_jh wants n_end + 2 slots at d = 4)
+  const int s = blockIdx.y, tid = threadIdx.x, T = blockDim.x;
+  cplx* sJl = sC + nC + (size_t)tid * js;
+  const int p = blockIdx.x * T + tid, pc = p < P ? p : P - 1;
+  const bool per_ball = (flags & BIEM_USCAT_PER_BALL) != 0, pb = (flags & BIEM_USCAT_POINTS_BATCHED) != 0;
+  const size_t cstride = (size_t)P * nb * (per_ball ? B : 1);      // between the components of the output
+  (void)ra; (void)rb; (void)cmm; (void)ga; (void)gia; (void)g0; (void)jA; (void)jB; (void)jC; (void)jN; (void)K2; (void)ms;
+  BIEM_FAST_TABLES()
+  double x[4];
+  for (int i = 0; i < D; ++i) x[i] = pb ? pts[((size_t)i * P + pc) * nb + s] : pts[(size_t)i * P + pc];
+  const cplx kk = k[s];
+  bool bad = false;
+  cplx tot[4];
+  for (int i = 0; i < 4; ++i) tot[i] = make_double2(0.0, 0.0);
+  const double dd2 = (double)(d - 2);
+  const cplx zero = make_double2(0.0, 0.0);
+  for (int b = 0; b < B; ++b) {
+    __syncthreads();                       // the previous ball's coefficients are no longer read (and the tables are written)
+    const cplx* cs = c + ((size_t)s * B + b) * H;
+    BIEM_FAST_STAGE()
+    __syncthreads();
+    const double* cb = centers + ((geom_batched ? (size_t)s * B : 0) + b) * D;
+    const double rho = radii[(geom_batched ? (size_t)s * B : 0) + b];
+    double u[4] = {0.0, 0.0, 0.0, 0.0}, r2 = 0.0;
+    for (int i = 0; i < D; ++i) { u[i] = x[i] - cb[i]; r2 += u[i] * u[i]; }
+    const double r = sqrt(r2);
+    if (INNER ? r > rho : r < rho) bad = true;
+    // e = u / r; at r = 0 (a masked point of the outer kind, the centre of the inner kind) any unit vector does
+    double invr = r > 0.0 ? 1.0 / r : 1.0;
+    double e[4] = {1.0, 0.0, 0.0, 0.0};
+    if (r > 0.0) for (int i = 0; i < 4; ++i) e[i] = u[i] / r;
+    cplx kneg = make_double2(-kk.x, -kk.y);                       // alpha_n = kneg z_{n+1}
+    cplx h0 = zero, h1 = zero, ix = zero;
+    if (INNER) {
+      if (r > 0.0) radial_jh(d, n_end, cscale(kk, r), (zc*)sJl, nullptr);
+      else {                                // centre: z_{n+1}(0) = 0 and z_n / r -> delta_{n1} k z_0(0) / d, kept in place of z_1 (invr = 1)
+        const double z0 = radial_z0_at_zero(d) / (double)d;
+        for (int n = 0; n <= n_end; ++n) sJl[n] = n == 1 ? cscale(kk, z0) : zero;
+        kneg = zero;
+      }
+    } else {
+      const double ra0 = r > 0.0 ? r : rho;                       // (r = 0 only inside a ball: the value is discarded)
+      zc J2[4], H2[4];
+      radial_jh(d, 1, cscale(kk, ra0), J2, H2);
+      h0 = H2[0]; h1 = H2[1];
+      ix = crecip(cscale(kk, ra0));
+    }
+    // next of (h_{q-1}, h_q): h_{q+1} = ((2 q + d - 2) / x) h_q - h_{q-1}
+    auto advance = [&](const cplx& hprev, const cplx& hcur, double two_q) -> cplx {
+      return csub(cmul(cscale(ix, two_q + dd2), hcur), hprev);
+    };
+    // (alpha_n, beta_n) = (-k z_{n+1}, z_n / r) from the pair (h_n, h_{n+1}) of the upward recurrence, or from the lane's j_n row
+    auto radial2 = [&](int n, const cplx& hn, const cplx& hn1, cplx& al, cplx& be) {
+      if (INNER) { al = cmul(kneg, sJl[n + 1]); be = cscale(sJl[n], invr); }
+      else { al = cmul(kneg, hn1); be = cscale(hn, invr); }
+    };
+    cplx g[4] = {zero, zero, zero, zero};
+    if (TREE == TREE_A) {
+      // S_{+-n} = (e0 +- i e1)^n / sqrt(2 pi)
+      const cplx w = make_double2(e[0], e[1]);
+      cplx wn = make_double2(1.0, 0.0), wn1 = zero;       // w^n, w^{n-1}
+      cplx hp = h0, hc = h1;
+      cplx R = zero;                                      // coefficient of e
+      for (int n = 0; n < n_end; ++n) {
+        cplx al, be;
+        radial2(n, hp, hc, al, be);
+        const cplx cp = sC[n_end - 1 + n];
+        cplx t = cmul(cp, wn);
+        if (n > 0) {
+          const cplx cn = sC[n_end - 1 - n];
+          cacc_conj(t, cn, wn);
+          const cplx tp = cmul(cp, wn1), tm = cmulc(cn, wn1);
+          const cplx bn = cscale(be, (double)n);
+          cacc(g[0], bn, cadd(tp, tm));
+          const cplx df = csub(tp, tm);
+          cacc(g[1], bn, make_double2(-df.y, df.x));
+        }
+        cacc(R, al, t);
+        const cplx hn = advance(hp, hc, 2.0 * n + 2.0);
+        hp = hc; hc = hn;
+        wn1 = wn; wn = cmul(wn, w);
+      }
+      for (int i = 0; i < 2; ++i) cacc_real(g[i], R, e[i]);
+    } else if (TREE == TREE_BA) {
+      // S_{n, +-m} = r^{n-m} Q_n^m(u0 / r) (u1 +- i u2)^m / sqrt(2 pi)
+      const double c0 = e[0];
+      const cplx w = make_double2(e[1], e[2]);
+      cplx wm = make_double2(1.0, 0.0), wm1 = zero;
+      double qmm = 0.70710678118654752440;
+      cplx hm = h0, hm1 = h1;
+      cplx R = zero;                                      // coefficient of e
+      for (int m = 0; m < n_end; ++m) {
+        if (m > 0) {
+          qmm *= cmm[m];
+          const cplx hn = advance(hm, hm1, 2.0 * m);
+          hm = hm1; hm1 = hn;
+          wm1 = wm; wm = cmul(wm, w);
+        }
+        cplx hp = hm, hc = hm1;
+        double q0 = 0.0, q1 = qmm, d0 = 0.0, d1 = 0.0;    // Q_n^m and its derivative
+        cplx A = zero, Bq = zero, C = zero, An = zero, Bn = zero, Cn = zero;
+        for (int n = m; n < n_end; ++n) {
+          cplx al, be;
+          radial2(n, hp, hc, al, be);
+          const cplx W3 = cscale(be, q1), W2 = cscale(be, d1);
+          const double nm = (double)(n - m);
+          const cplx W1 = make_double2(al.x * q1 + nm * W3.x, al.y * q1 + nm * W3.y);
+          const cplx cp = sC[n * n + n + m];
+          cacc(A, W1, cp); cacc(Bq, W2, cp); cacc(C, W3, cp);
+          if (m > 0) { const cplx cn = sC[n * n + n - m]; cacc(An, W1, cn); cacc(Bn, W2, cn); cacc(Cn, W3, cn); }
+          const int q = n + 1;
+          if (q < n_end) {
+            const double a = ra[q * n_end + m], bb = rb[q * n_end + m];
+            const double q2 = a * (c0 * q1 - bb * q0), d2 = a * (q1 + c0 * d1 - bb * d0);
+            q0 = q1; q1 = q2; d0 = d1; d1 = d2;
+            const cplx hn = advance(hp, hc, 2.0 * q);
+            hp = hc; hc = hn;
+          }
+        }
+        cplx T1 = cmul(A, wm), T2 = cmul(Bq, wm);
+        cacc_conj(T1, An, wm); cacc_conj(T2, Bn, wm);
+        R.x += T1.x - c0 * T2.x; R.y += T1.y - c0 * T2.y;
+        g[0].x += T2.x; g[0].y += T2.y;
+        if (m > 0) {
+          const cplx tp = cmul(C, wm1), tm = cmulc(Cn, wm1);
+          const double fm = (double)m;
+          g[1].x += fm * (tp.x + tm.x); g[1].y += fm * (tp.y + tm.y);
+          g[2].x -= fm * (tp.y - tm.y); g[2].y += fm * (tp.x - tm.x);
+        }
+      }
+      for (int i = 0; i < 3; ++i) cacc_real(g[i], R, e[i]);
+    } else if (TREE == TREE_BBA) {
+      // S_{n l +-m} = r^{n-l} g_{n-l}^{(l+1)}(u0 / r) L_l(u1, u2, u3) (u2 +- i u3)^m / sqrt(2 pi)
+      const double c0 = e[0], u1 = e[1], tau = e[1] * e[1] + e[2] * e[2] + e[3] * e[3];
+      const cplx w = make_double2(e[2], e[3]);
+      const int mstride = 2 * n_end - 1;
+      cplx wm = make_double2(1.0, 0.0), wm1 = zero;
+      double qmm = 0.70710678118654752440;
+      cplx hm = h0, hm1 = h1;
+      cplx R = zero, V = zero;                            // coefficients of e and of (0, e1, e2, e3)
+      for (int m = 0; m < n_end; ++m) {
+        if (m > 0) {
+          qmm *= cmm[m];
+          const cplx hn = advance(hm, hm1, 2.0 * m);
+          hm = hm1; hm1 = hn;
+          wm1 = wm; wm = cmul(wm, w);
+        }
+        double L0 = 0.0, L1 = qmm, a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;   // L_l and grad L_l = a_l (0,1,0,0) + b_l (0, e1, e2, e3)
+        cplx hl = hm, hl1 = hm1;
+        cplx XU = zero, XE = zero, XA = zero, XV = zero, XM = zero, YU = zero, YE = zero, YA = zero, YV = zero, YM = zero;   // +m, -m
+        for (int l = m; l < n_end; ++l) {
+          double gp0 = 0.0, gp1 = g0[l], gd0 = 0.0, gd1 = 0.0;   // the Gegenbauer factor and its derivative
+          cplx hp = hl, hc = hl1;
+          cplx S1 = zero, S2 = zero, S3 = zero, N1 = zero, N2 = zero, N3 = zero;
+          for (int n = l; n < n_end; ++n) {
+            cplx al, be;
+            radial2(n, hp, hc, al, be);
+            const cplx W3 = cscale(be, gp1), W2 = cscale(be, gd1);
+            const double nl = (double)(n - l);
+            const cplx W1 = make_double2(al.x * gp1 + nl * W3.x, al.y * gp1 + nl * W3.y);
+            const cplx* cc = sC + (n * n_end + l) * mstride + n_end - 1;
+            const cplx cp = cc[m];
+            cacc(S1, W1, cp); cacc(S2, W2, cp); cacc(S3, W3, cp);
+            if (m > 0) { const cplx cn = cc[-m]; cacc(N1, W1, cn); cacc(N2, W2, cn); cacc(N3, W3, cn); }
+            const int q = n - l + 1;
+            if (n + 1 < n_end) {
+              const double gq = ga[l * n_end + q - 1], gi = gia[l * n_end + q];
+              const double gp2 = (c0 * gp1 - gq * gp0) * gi, gd2 = (gp1 + c0 * gd1 - gq * gd0) * gi;
+              gp0 = gp1; gp1 = gp2; gd0 = gd1; gd1 = gd2;
+              const cplx hn = advance(hp, hc, 2.0 * (n + 1));
+              hp = hc; hc = hn;
+            }
+          }
+          cacc_real(XU, S1, L1); cacc_real(XE, S2, L1); cacc_real(XA, S3, a1); cacc_real(XV, S3, b1); cacc_real(XM, S3, L1);
+          if (m > 0) { cacc_real(YU, N1, L1); cacc_real(YE, N2, L1); cacc_real(YA, N3, a1); cacc_real(YV, N3, b1); cacc_real(YM, N3, L1); }
+          const int ql = l + 1;
+          if (ql < n_end) {
+            const double a = ra[ql * n_end + m], bb = rb[ql * n_end + m];
+            const double L2 = a * (u1 * L1 - bb * tau * L0);
+            const double a2 = a * (L1 + u1 * a1 - bb * tau * a0);
+            const double b2 = a * (u1 * b1 - bb * (2.0 * L0 + tau * b0));
+            L0 = L1; L1 = L2; a0 = a1; a1 = a2; b0 = b1; b1 = b2;
+            const cplx hn = advance(hl, hl1, 2.0 * ql);
+            hl = hl1; hl1 = hn;
+          }
+        }
+        cplx TU = cmul(XU, wm), TE = cmul(XE, wm), TA = cmul(XA, wm), TV = cmul(XV, wm);
+        cacc_conj(TU, YU, wm); cacc_conj(TE, YE, wm); cacc_conj(TA, YA, wm); cacc_conj(TV, YV, wm);
+        R.x += TU.x - c0 * TE.x; R.y += TU.y - c0 * TE.y;
+        g[0].x += TE.x; g[0].y += TE.y;
+        g[1].x += TA.x; g[1].y += TA.y;
+        V.x += TV.x; V.y += TV.y;
+        if (m > 0) {
+          const cplx tp = cmul(XM, wm1), tm = cmulc(YM, wm1);
+          const double fm = (double)m;
+          g[2].x += fm * (tp.x + tm.x); g[2].y += fm * (tp.y + tm.y);
+          g[3].x -= fm * (tp.y - tm.y); g[3].y += fm * (tp.x - tm.x);
+        }
+      }
+      for (int i = 0; i < 4; ++i) cacc_real(g[i], R, e[i]);
+      for (int i = 1; i < 4; ++i) cacc_real(g[i], V, e[i]);
+    } else {
+      // caa: S_{n, +-a, +-b} = r^{2 k} Pbar_k^{(b,a)}(xx) (u0 +- i u1)^a (u2 +- i u3)^b / (2 pi), xx = (u0^2 + u1^2 - u2^2 - u3^2) / r^2,
+      // n = a + b + 2 k; grad xx on the unit sphere = 2 (e0, e1, -e2, -e3) - 2 xx e
+      const double xx = (e[0] * e[0] + e[1] * e[1]) - (e[2] * e[2] + e[3] * e[3]);
+      const cplx w1 = make_double2(e[0], e[1]), w2 = make_double2(e[2], e[3]);
+      cplx wa = make_double2(1.0, 0.0), wa1 = zero;
+      cplx ha = h0, ha1 = h1;
+      cplx U = zero, V = zero;                            // coefficients of e and of 2 (e0, e1, -e2, -e3) - 2 xx e
+      for (int a = 0; a < n_end; ++a) {
+        if (a > 0) {
+          const cplx hn = advance(ha, ha1, 2.0 * a);
+          ha = ha1; ha1 = hn;
+          wa1 = wa; wa = cmul(wa, w1);
+        }
+        cplx wb = make_double2(1.0, 0.0), wb1 = zero;
+        cplx hb = ha, hb1 = ha1;
+        for (int b2 = 0; a + b2 < n_end; ++b2) {
+          if (b2 > 0) {
+            const cplx hn = advance(hb, hb1, 2.0 * (a + b2));
+            hb = hb1; hb1 = hn;
+            wb1 = wb; wb = cmul(wb, w2);
+          }
+          const int tb = (a * n_end + b2) * K2;
+          double p0 = 0.0, p1 = 1.0, d0 = 0.0, d1 = 0.0;
+          cplx hp = hb, hc = hb1;
+          // sums of the (+-a, +-b) coefficients under the three weights: pp, mp (-a, +b), pm (+a, -b), mm
+          cplx pp1 = zero, pp2 = zero, pp3 = zero, mp1 = zero, mp2 = zero, mp3 = zero, pm1 = zero, pm2 = zero, pm3 = zero, mm1 = zero,
+               mm2 = zero, mm3 = zero;
+          for (int kq = 0, n = a + b2; n < n_end; ++kq, n += 2) {
+            cplx al, be;
+            radial2(n, hp, hc, al, be);
+            const double nr = jN[tb + kq], pv = nr * p1, dv = nr * d1;
+            const cplx W3 = cscale(be, pv), W2 = cscale(be, dv);
+            const double k2 = (double)(2 * kq);
+            const cplx W1 = make_double2(al.x * pv + k2 * W3.x, al.y * pv + k2 * W3.y);
+            const cplx* cc = sC + (n * ms + n_end - 1) * ms + n_end - 1;
+            { const cplx cv = cc[a * ms + b2]; cacc(pp1, W1, cv); cacc(pp2, W2, cv); cacc(pp3, W3, cv); }
+            if (a > 0) { const cplx cv = cc[-a * ms + b2]; cacc(mp1, W1, cv); cacc(mp2, W2, cv); cacc(mp3, W3, cv); }
+            if (b2 > 0) { const cplx cv = cc[a * ms - b2]; cacc(pm1, W1, cv); cacc(pm2, W2, cv); cacc(pm3, W3, cv); }
+            if (a > 0 && b2 > 0) { const cplx cv = cc[-a * ms - b2]; cacc(mm1, W1, cv); cacc(mm2, W2, cv); cacc(mm3, W3, cv); }
+            if (n + 2 < n_end) {
+              const double lin = jA[tb + kq] * xx + jB[tb + kq];
+              const double p2 = lin * p1 - jC[tb + kq] * p0, d2 = jA[tb + kq] * p1 + lin * d1 - jC[tb + kq] * d0;
+              p0 = p1; p1 = p2; d0 = d1; d1 = d2;
+              cplx hn = advance(hp, hc, 2.0 * (n + 1));
+              hp = hc; hc = hn;
+              hn = advance(hp, hc, 2.0 * (n + 2));
+              hp = hc; hc = hn;
+            }
+          }
+          // w1^{+-a} w2^{+-b} (a negative power is the conjugate's)
+          const cplx Epp = cmul(wa, wb), Emp = cmulc(wb, wa);
+          cacc(U, pp1, Epp); cacc_conj(U, mm1, Epp); cacc(U, mp1, Emp); cacc_conj(U, pm1, Emp);
+          cacc(V, pp2, Epp); cacc_conj(V, mm2, Epp); cacc(V, mp2, Emp); cacc_conj(V, pm2, Emp);
+          if (a > 0) {                       // a w1^{+-(a-1)} (1, +-i, 0, 0)
+            const cplx Fpp = cmul(wa1, wb), Fmp = cmulc(wb, wa1);
+            cplx tp = cmul(pp3, Fpp), tm = cmul(mp3, Fmp);
+            cacc_conj(tp, pm3, Fmp); cacc_conj(tm, mm3, Fpp);
+            const double fa = (double)a;
+            g[0].x += fa * (tp.x + tm.x); g[0].y += fa * (tp.y + tm.y);
+            g[1].x -= fa * (tp.y - tm.y); g[1].y += fa * (tp.x - tm.x);
+          }
+          if (b2 > 0) {                      // b w2^{+-(b-1)} (0, 0, 1, +-i)
+            const cplx Hpp = cmul(wa, wb1), Hmp = cmulc(wb1, wa);
+            cplx tp = cmul(pp3, Hpp), tm = cmulc(pm3, Hmp);
+            cacc(tp, mp3, Hmp); cacc_conj(tm, mm3, Hpp);
+            const double fb = (double)b2;
+            g[2].x += fb * (tp.x + tm.x); g[2].y += fb * (tp.y + tm.y);
+            g[3].x -= fb * (tp.y - tm.y); g[3].y += fb * (tp.x - tm.x);
+          }
+        }
+      }
+      const cplx R = make_double2(U.x - 2.0 * xx * V.x, U.y - 2.0 * xx * V.y);
+      for (int i = 0; i < 4; ++i) { cacc_real(g[i], R, e[i]); cacc_real(g[i], V, i < 2 ? 2.0 * e[i] : -2.0 * e[i]); }
+      for (int i = 0; i < 4; ++i) g[i] = cscale(g[i], kInvSqrt2Pi);   // (the second 1 / sqrt(2 pi) below)
+    }
+    for (int i = 0; i < D; ++i) {
+      g[i] = cscale(g[i], kInvSqrt2Pi);
+      if (per_ball) { if (p < P) out[i * cstride + ((size_t)p * nb + s) * B + b] = g[i]; }
+      else { tot[i].x += g[i].x; tot[i].y += g[i].y; }
+    }
+  }
+  const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+  if (p >= P) return;
+  for (int i = 0; i < D; ++i) {
+    if (per_ball) {
+      if (bad) for (int b = 0; b < B; ++b) out[i * cstride + ((size_t)p * nb + s) * B + b] = make_double2(qnan, 0.0);
+    } else out[i * cstride + (size_t)p * nb + s] = bad ? make_double2(qnan, 0.0) : tot[i];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Chain trees (any depth): one workgroup of 4 waves per (point, system), a wave per ball as in k_uscat, but the harmonics come from
 // node tables: lane 0 runs the radial functions and the angles, the lanes fill F_j[L][L1] (one lane per (node j, L1): the Gegenbauer
 // degree recurrence once) and the phases e^{i m phi}, then every harmonic is d - 2 LDS lookups and one phase.
@@ -636,6 +977,61 @@ int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, co
   }
   hipLaunchKernelGGL(k_uscat, dim3(P, nb), dim3(256), (size_t)B * sizeof(cplx), st, p->tree, p->d, p->H, p->n_end, p->d_labels,
                      p->d_deg, nb, B, P, (const cplx*)d_k, d_centers, d_radii, geom_batched, (const cplx*)c, d_points, flags, (cplx*)d_out);
+  BIEM_LAUNCHCHK();
+  return BIEM_OK;
+}
+
+// Gradient of the near field: the per-lane kernels only.  Whatever they do not cover (chain trees, orders above the per-lane
+// ceilings, a workgroup's tables beyond the LDS) is BIEM_ERR_UNSUPPORTED - there is no generic gradient kernel to fall through to.
+int launch_uscat_grad(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                      const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
+                      double* d_out, void* d_work, size_t work_bytes, hipStream_t st) {
+  if (flags & BIEM_USCAT_FAR_FIELD) { set_error("biem_uscat_grad: the far-field pattern has no gradient in space (BIEM_USCAT_FAR_FIELD)"); return BIEM_ERR_ARG; }
+  const int ne = p->n_end, ms = 2 * ne - 1;
+  const int cap = p->tree == TREE_A ? kFastNendMax2 : p->tree == TREE_BA ? kFastNendMax3 : p->tree == TREE_BBA ? kFastNendMax4 :
+                  p->tree == TREE_CAA ? kFastNendMaxCaa : 0;
+  if (cap == 0) {
+    set_error("biem_uscat_grad: built for the trees a, ba (bpa), bba (bpbpa) and caa; chain trees (d=%d) are not covered", p->d);
+    return BIEM_ERR_UNSUPPORTED;
+  }
+  if (ne > cap) {
+    set_error("biem_uscat_grad: n_end=%d above the per-lane ceiling %d of this tree (a %d, ba %d, bba %d, caa %d)", ne, cap,
+              kFastNendMax2, kFastNendMax3, kFastNendMax4, kFastNendMaxCaa);
+    return BIEM_ERR_UNSUPPORTED;
+  }
+  if (nb > 65535) { set_error("biem_uscat_grad: more than 65535 systems in one call (%d)", nb); return BIEM_ERR_UNSUPPORTED; }
+  if (nb <= 0 || B <= 0 || P <= 0) return BIEM_OK;
+  const bool inner = (flags & BIEM_USCAT_KIND_INNER) != 0;
+  const int T = inner ? 64 : 256;
+  size_t tab = 0, nC = 0;                 // doubles of tables, complex of coefficients (BIEM_FAST_LAYOUT)
+  if (p->tree == TREE_BA) { tab = (size_t)2 * ne * ne + ((ne + 1) & ~1); nC = (size_t)ne * ne; }
+  else if (p->tree == TREE_BBA) { tab = (size_t)4 * ne * ne + 2 * ((ne + 1) & ~1); nC = (size_t)ne * ne * ms; }
+  else if (p->tree == TREE_CAA) { tab = (size_t)4 * ne * ne * ((ne + 1) / 2); nC = (size_t)ne * ms * ms; }
+  else nC = (size_t)ms;
+  const size_t shm = tab * sizeof(double) + (nC + (inner ? (size_t)T * ((ne + 3) | 1) : 0)) * sizeof(cplx);
+  if (shm > 160 * 1024) {
+    set_error("biem_uscat_grad: n_end=%d needs %zu bytes of LDS per workgroup (limit %d)", ne, shm, 160 * 1024);
+    return BIEM_ERR_UNSUPPORTED;
+  }
+  size_t need = (size_t)nb * B * p->H * sizeof(cplx);
+  if (work_bytes < need) { set_error("biem_uscat_grad: workspace too small"); return BIEM_ERR_ARG; }
+  cplx* c = (cplx*)d_work;
+  hipLaunchKernelGGL(k_uscat_coef, dim3(B, nb), dim3(64), 0, st, p->d, p->H, ne, p->d_deg, B, inner ? 1 : 0, (const cplx*)d_k, d_eta,
+                     d_radii, geom_batched, (const cplx*)d_density, c, (cplx*)nullptr);
+  BIEM_LAUNCHCHK();
+#define BIEM_USCAT_GRAD(TREE, INNERF)                                                                                            \
+  {                                                                                                                              \
+    BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_uscat_grad_fast<TREE, INNERF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
+    hipLaunchKernelGGL((k_uscat_grad_fast<TREE, INNERF>), dim3((P + T - 1) / T, nb), dim3(T), shm, st, p->d, p->H, ne, p->d_labels, nb, \
+                       B, P, (const cplx*)d_k, d_centers, d_radii, geom_batched, (const cplx*)c, d_points, flags, (cplx*)d_out); \
+  }
+#define BIEM_USCAT_GRAD_TREE(TREE) { if (inner) BIEM_USCAT_GRAD(TREE, true) else BIEM_USCAT_GRAD(TREE, false) }
+  if (p->tree == TREE_BA) BIEM_USCAT_GRAD_TREE(TREE_BA)
+  else if (p->tree == TREE_BBA) BIEM_USCAT_GRAD_TREE(TREE_BBA)
+  else if (p->tree == TREE_CAA) BIEM_USCAT_GRAD_TREE(TREE_CAA)
+  else BIEM_USCAT_GRAD_TREE(TREE_A)
+#undef BIEM_USCAT_GRAD_TREE
+#undef BIEM_USCAT_GRAD
   BIEM_LAUNCHCHK();
   return BIEM_OK;
 }

@@ -211,6 +211,15 @@ int biem_uscat(const biem_plan* plan, int nb, int B, int P, const double* d_k /*
                const double* d_centers, const double* d_radii, int geom_batched, const double* d_density,
                const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes, void* stream);
 
+/* Cartesian gradient of the near field at the same points: out[d][P][nb] or [d][P][nb][B] (per ball), complex128, component i
+ * along axis i of the plan's tree; NaN in every component where biem_uscat gives NaN.  Arguments, flags and workspace
+ * (biem_uscat_workspace_bytes) as biem_uscat.  BIEM_USCAT_FAR_FIELD is BIEM_ERR_ARG (the far-field pattern is no field in
+ * space).  Covered: trees a, ba, bba, caa up to the per-lane orders (n_end <= 320, 48, 14, 12; kind inner on tree a further while
+ * a workgroup's 64 rows of n_end + 3 radial values fit the LDS); chain trees and larger orders are BIEM_ERR_UNSUPPORTED. */
+int biem_uscat_grad(const biem_plan* plan, int nb, int B, int P, const double* d_k /*c128*/, const double* d_eta,
+                    const double* d_centers, const double* d_radii, int geom_batched, const double* d_density,
+                    const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- one call for the whole path: ball tables + fill (equilibrated) + LU + density, systems processed in
  *      chunks of `chunk` resident matrices (0 = choose); every system is factored once for its nrhs right-hand sides.
  *      d_g [nb][nrhs][B][Q] as in biem_rhs_project, d_density [nb][nrhs][B][H]. ---- */
