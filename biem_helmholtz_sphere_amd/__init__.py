@@ -16,6 +16,7 @@ from ._biem import (
     biem_factorize,
     biem_u,
     biem_u_grad,
+    fluid_inclusion_bc,
     max_memory,
     max_n_end,
     plane_wave,
@@ -33,6 +34,7 @@ __all__ = [
     "biem_factorize",
     "biem_u",
     "biem_u_grad",
+    "fluid_inclusion_bc",
     "max_memory",
     "max_n_end",
     "plane_wave",

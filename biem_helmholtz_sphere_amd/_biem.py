@@ -37,7 +37,7 @@ Array = Any
 
 __all__ = [
     "BIEMFactorization", "BIEMKwargs", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
-    "biem_factorize", "biem_u", "max_memory", "max_n_end", "plane_wave", "point_source",
+    "biem_factorize", "biem_u", "fluid_inclusion_bc", "max_memory", "max_n_end", "plane_wave", "point_source",
 ]
 
 
@@ -358,6 +358,55 @@ def point_source(*, k: Array, source: Array, n: int) -> Tuple[Callable[[Array], 
     return inner, inner_grad
 
 
+def fluid_inclusion_bc(*, c_ndim: int, n_end: int, radii: Array, k_interior: Array, density_ratio: Array,
+                       k: Array | None = None) -> Tuple[Array, Array]:
+    r"""Degree-dependent boundary coefficients ``(alpha_n, beta_n)`` of penetrable fluid spheres, for ``biem(alpha_n=, beta_n=)``.
+
+    Ball b holds a fluid of wavenumber ``k_interior`` (complex: absorbing) and density ``density_ratio`` times the exterior's.  The
+    interior field :math:`\sum c_h j_n(k_b r) Y_h` with u and (1/density) d_n u continuous across the sphere leaves, with the interior
+    eliminated and nothing divided,
+
+        alpha_{b,n} = -k_b j_n'(k_b rho_b),      beta_{b,n} = delta_b j_n(k_b rho_b)
+
+    (j_n the c_ndim-dimensional spherical Bessel function of ``biem_radial_complex``).  ``k_b = k, delta = 1`` is a transparent sphere
+    (gj_n = 0), ``delta -> 0`` the sound-soft and ``delta -> infinity`` the sound-hard one.  A boundary condition may be scaled freely
+    per degree: with the exterior wavenumber ``k`` (shape ``(...)``, as :func:`biem` takes it) every pair is returned scaled to
+    ``max(|alpha_n|, |k beta_n|) = 1``, so no row underflows at high n; without it the interior wavenumber sets the scale,
+    ``max(|alpha_n|, |k_b beta_n|) = 1`` (the same up to the contrast; the solution does not depend on it).
+
+    ``radii``, ``k_interior`` and ``density_ratio`` broadcast to ``(..., B)``; the results have shape ``(..., B, n_end)``, complex128,
+    in the namespace (and on the device) of the inputs.  ``k_interior * radii == 0`` is a ``ValueError`` (no interior field).
+    """
+    n_end = int(n_end)
+    if n_end < 1:
+        raise ValueError(f"n_end must be positive, got {n_end}")
+    tens = [a for a in (radii, k_interior, density_ratio, k) if isinstance(a, torch.Tensor)]
+    dev = _compute_device(tens[0].device if tens else None)
+    rho, kb, delta = (_to_dev(a, dev, torch.complex128) for a in (radii, k_interior, density_ratio))
+    ks = kb if k is None else _to_dev(k, dev, torch.complex128)[..., None]          # the wavenumber of the scale, along (..., B)
+    shape = tuple(torch.broadcast_shapes(tuple(rho.shape), tuple(kb.shape), tuple(delta.shape), tuple(ks.shape)))
+    z = (kb * rho).expand(shape).contiguous().reshape(-1)
+    if bool(torch.any(z == 0)):
+        raise ValueError("k_interior * radii must not be zero")
+    out = torch.empty((z.numel(), 2, n_end + 1), dtype=torch.complex128, device=dev)
+    if z.numel() > 0:
+        with torch.cuda.device(dev):
+            L.check(L.load().biem_radial_complex(int(c_ndim), n_end, z.numel(), _ptr(z), _ptr(out), _stream_ptr(dev)), "biem_radial_complex")
+    j = out[:, 0, :].reshape(shape + (n_end + 1,))
+    n = torch.arange(n_end, dtype=torch.float64, device=dev)
+    zz = (kb * rho).expand(shape)[..., None]
+    jp = n / zz * j[..., :n_end] - j[..., 1:]                        # j_n' = (n / z) j_n - j_{n+1}
+    kbx = kb.expand(shape)[..., None]
+    alpha_n = -kbx * jp
+    beta_n = delta.expand(shape)[..., None] * j[..., :n_end]
+    scale = torch.maximum(alpha_n.abs(), (ks.expand(shape)[..., None] * beta_n).abs())
+    scale = torch.where(scale > 0, scale, torch.ones_like(scale))
+    alpha_n, beta_n = alpha_n / scale, beta_n / scale
+    if tens:
+        return alpha_n.to(tens[0].device), beta_n.to(tens[0].device)
+    return alpha_n.cpu().numpy(), beta_n.cpu().numpy()
+
+
 # --------------------------------------------------------------------------------------
 # result object (reference :196-237)
 # --------------------------------------------------------------------------------------
@@ -451,6 +500,36 @@ def _validate_biem_inputs(c, centers, radii, k, eta, alpha, beta) -> Tuple[int, 
     return tuple(batch)
 
 
+def _is_default(v: Any, default: float) -> bool:
+    return isinstance(v, (int, float, complex)) and not isinstance(v, bool) and v == default
+
+
+def _validate_degree_bc(batch, ks, B: int, n_end: int, alpha, beta, alpha_n, beta_n) -> Tuple[int, ...]:
+    """Checks of the degree-dependent pair alpha_n / beta_n of shape (..., B, n_end) on metadata only; returns the batch shape
+    with their leading axes broadcast in."""
+    if (alpha_n is None) != (beta_n is None):
+        raise ValueError("alpha_n and beta_n must be given together")
+    if not (_is_default(alpha, 1.0) and _is_default(beta, 0.0)):
+        raise ValueError("alpha_n / beta_n replace alpha / beta: leave alpha and beta at their defaults when alpha_n and beta_n are given")
+    ans, bns = _shape(alpha_n), _shape(beta_n)
+    for nm, sh in (("alpha_n", ans), ("beta_n", bns)):
+        if len(sh) != len(ks) + 2:
+            raise ValueError(f"{nm} must be an array of shape (..., B, n_end) with {len(ks) + 2} axes, got shape {sh}")
+        if sh[-1] != n_end:
+            raise ValueError(f"The last dimension of {nm} must be n_end={n_end}, but got {sh[-1]}")
+    try:
+        np.broadcast_shapes(ans[-2:-1], bns[-2:-1], (B,))
+        if np.broadcast_shapes(ans[-2:-1], (B,)) != (B,) or np.broadcast_shapes(bns[-2:-1], (B,)) != (B,):
+            raise ValueError
+        return tuple(np.broadcast_shapes(tuple(batch), ans[:-2], bns[:-2]))
+    except ValueError as e:
+        raise ValueError(
+            "Shapes of alpha_n, beta_n and the batch shape + (B, n_end) "
+            "are not broadcastable\n"
+            f"tuple(alpha_n.shape)={ans}\ntuple(beta_n.shape)={bns}\nbatch shape={tuple(batch)}, B={B}, n_end={n_end}"
+        ) from e
+
+
 def _host_array(a: Any) -> np.ndarray:
     """Any accepted input (torch tensor on any device, NumPy array, list, scalar) as a NumPy array on the host."""
     if isinstance(a, torch.Tensor):
@@ -512,11 +591,16 @@ class _Operator:
     beta: Any
     alpha_t: torch.Tensor
     beta_t: torch.Tensor
+    per_degree: bool = False # alpha / beta are the degree-dependent alpha_n / beta_n of shape (..., B, n_end); fl.alpha / fl.beta likewise
 
 
-def _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind) -> _Operator:
+def _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n=None, beta_n=None) -> _Operator:
     """Input checks of reference :240-326, the operands on the device and the plan."""
     batch = _validate_biem_inputs(c, centers, radii, k, eta, alpha, beta)
+    per_degree = alpha_n is not None or beta_n is not None
+    if per_degree:
+        batch = _validate_degree_bc(batch, _shape(k), _shape(radii)[-1], int(n_end), alpha, beta, alpha_n, beta_n)
+        alpha, beta = alpha_n, beta_n                  # from here on the pair is (alpha_n, beta_n), one more trailing axis
     _warn_biem_inputs(k, eta)
     origin, dev = _origin_of(centers, radii, k, eta, alpha, beta)
     f64 = torch.float64
@@ -537,9 +621,9 @@ def _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind) -> _Operator:
     tree, perm = canonical_tree(c.branching_types_expression_str)
     plan = _plan(tree, n_end, dev)
     fl = _flatten(batch, centers_t if list(perm) == list(range(len(perm))) else centers_t[..., list(perm)], radii_t, k_t, eta_t,
-                  alpha_t, beta_t)
+                  alpha_t, beta_t, int(n_end) if per_degree else 0)
     return _Operator(c, n_end, kind, origin, dev, tuple(batch), perm, plan, fl, centers_t, radii_t, k_t, eta_t, _is_complex(k),
-                     alpha, beta, alpha_t, beta_t)
+                     alpha, beta, alpha_t, beta_t, per_degree)
 
 
 # --------------------------------------------------------------------------------------
@@ -556,12 +640,12 @@ class _Flat:
     centers: torch.Tensor    # [nb or 1, B, d]
     radii: torch.Tensor      # [nb or 1, B]
     geom_batched: int
-    alpha: Optional[torch.Tensor] = None     # [nb or 1, B] complex128
+    alpha: Optional[torch.Tensor] = None     # [nb or 1, B] complex128; degree-dependent: [nb or 1, B, n_end]
     beta: Optional[torch.Tensor] = None
     ab_batched: int = 0
 
 
-def _flatten(batch, centers_t, radii_t, k_t, eta_t, alpha_t=None, beta_t=None) -> _Flat:
+def _flatten(batch, centers_t, radii_t, k_t, eta_t, alpha_t=None, beta_t=None, degree_axis: int = 0) -> _Flat:
     nb = int(np.prod(batch)) if len(batch) else 1
     B, d = int(radii_t.shape[-1]), centers_t.shape[-1]
     kf = k_t.expand(batch).reshape(nb).contiguous()
@@ -575,6 +659,11 @@ def _flatten(batch, centers_t, radii_t, k_t, eta_t, alpha_t=None, beta_t=None) -
         rf = radii_t.reshape(1, B).contiguous()
     if alpha_t is None:
         return _Flat(nb, B, kf, ef, cf, rf, int(geom_b))
+    if degree_axis:
+        ab_b = any(s != 1 for s in tuple(alpha_t.shape[:-2]) + tuple(beta_t.shape[:-2]))
+        lead = (tuple(batch), nb) if ab_b else ((1,) * len(batch), 1)
+        af, bf = (t.expand(lead[0] + (B, degree_axis)).reshape(lead[1], B, degree_axis).contiguous() for t in (alpha_t, beta_t))
+        return _Flat(nb, B, kf, ef, cf, rf, int(geom_b), af, bf, int(ab_b))
     ab_b = any(s != 1 for s in tuple(alpha_t.shape[:-1]) + tuple(beta_t.shape[:-1]))
     if ab_b:
         af = alpha_t.expand(tuple(batch) + (B,)).reshape(nb, B).contiguous()
@@ -614,17 +703,43 @@ def _ball_tables(op: _Operator, sp: int, fill: bool = True) -> torch.Tensor:
     fl, plan = op.fl, op.plan
     tab = torch.empty((fl.nb, fl.B, 3, op.n_end), dtype=torch.complex128, device=op.dev)
     if fill:
-        L.check(L.load().biem_ball_tables(plan.handle, fl.nb, fl.B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
-                                          _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), sp), "biem_ball_tables")
+        entry, what = (L.load().biem_ball_tables_n, "biem_ball_tables_n") if op.per_degree else (L.load().biem_ball_tables, "biem_ball_tables")
+        L.check(entry(plan.handle, fl.nb, fl.B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
+                      _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), sp), what)
     return tab
+
+
+def _nrhs(g) -> int:
+    """Right-hand sides per system of the samples of _boundary_samples (a tensor, or the unmixed pair of the degree-dependent case)."""
+    return int((g if isinstance(g, torch.Tensor) else next(t for t in g if t is not None)).shape[1])
+
+
+def _sample_ptrs(g, s0: int = 0):
+    """The sample arguments of an entry point from system s0 on: (d_g,) or (d_gu, d_gdn), a missing set as the null pointer."""
+    if isinstance(g, torch.Tensor):
+        return (_ptr(g[s0:]),)
+    return tuple(_ptr(None if t is None else t[s0:]) for t in g)
+
+
+def _rhs_project(op: _Operator, n: int, g, s0: int, f: torch.Tensor, sys_stride: int, elem_stride: int, rhs_stride: int, sp: int) -> None:
+    """biem_rhs_project / biem_rhs_project_n of the n systems from s0 on into f (natural order)."""
+    lib, plan, fl = L.load(), op.plan, op.fl
+    nrhs = _nrhs(g)
+    if op.per_degree:
+        a0 = s0 if fl.ab_batched else 0
+        L.check(lib.biem_rhs_project_n(plan.handle, n, fl.B, nrhs, *_sample_ptrs(g, s0), _ptr(fl.alpha[a0:]), _ptr(fl.beta[a0:]), fl.ab_batched,
+                                       _ptr(f), sys_stride, elem_stride, rhs_stride, sp), "biem_rhs_project_n")
+    else:
+        L.check(lib.biem_rhs_project(plan.handle, n, fl.B, nrhs, *_sample_ptrs(g, s0), _ptr(f), sys_stride, elem_stride, rhs_stride, sp),
+                "biem_rhs_project")
 
 
 def _single_ball_density(op: _Operator, g: torch.Tensor, tab: torch.Tensor, density_t: torch.Tensor, sp: int) -> None:
     """Single ball: density = f / (blc (alpha h + beta k h'))    (reference :648-691)."""
     lib, plan, nb, B = L.load(), op.plan, op.fl.nb, op.fl.B
-    H, nrhs = plan.H, int(g.shape[1])
+    H, nrhs = plan.H, _nrhs(g)
     f = torch.empty((nb, nrhs, B * H), dtype=torch.complex128, device=op.dev)
-    L.check(lib.biem_rhs_project(plan.handle, nb, B, nrhs, _ptr(g), _ptr(f), nrhs * B * H, 1, B * H, sp), "biem_rhs_project")
+    _rhs_project(op, nb, g, 0, f, nrhs * B * H, 1, B * H, sp)
     L.check(lib.biem_density(plan.handle, nb, B, nrhs, _ptr(f), nrhs * B * H, 1, B * H, _ptr(tab), _ptr(density_t), sp), "biem_density")
 
 
@@ -672,8 +787,10 @@ def _result(op: _Operator, uin, density_t: Optional[torch.Tensor], axes, with_ma
     )
 
 
-def _boundary_samples(op: _Operator, uin, uin_grad) -> torch.Tensor:
-    """g[nb, B, Q] = (-alpha u_in - beta d_n u_in)(c_b + rho_b y_q): the closure `f` of reference :611-624.
+def _boundary_samples(op: _Operator, uin, uin_grad):
+    """g[nb, nrhs, B, Q] = (-alpha u_in - beta d_n u_in)(c_b + rho_b y_q): the closure `f` of reference :611-624.  With degree-dependent
+    coefficients the two parts stay apart and unweighted, g = (gu, gdn) = (u_in, d_n u_in) at those points (a missing callable: None):
+    the degree is known only after the projection (biem_rhs_project_n).
 
     fl.centers are in the plan's canonical axes; the user's callables see ORIGINAL axes (x_orig[perm[i]] = x_canon[i])."""
     plan, origin, fl, batch, perm = op.plan, op.origin, op.fl, op.batch, op.perm
@@ -710,20 +827,28 @@ def _boundary_samples(op: _Operator, uin, uin_grad) -> torch.Tensor:
         t = t.reshape((tuple(batch) if fl.ab_batched else (1,) * nbt) + (B,))
         return torch.movedim(t, -1, 0)[(None,) * len(qshape)]       # (1.., B, ...batch)
     g = None
-    if uin is not None:
-        u = _to_dev(uin(xu), dev, torch.complex128)
-        g = (ab(fl.alpha) * u).neg_()                                  # (a fresh tensor: negated in place)
-    if uin_grad is not None:
-        gu = _to_dev(uin_grad(xu), dev, torch.complex128)
-        t = ab(fl.beta) * torch.sum(gu * x_rel.to(torch.complex128), dim=0)
-        g = t.neg_() if g is None else g - t
     lead = qshape + (B,) + tuple(batch)
-    if g is None:
-        g = torch.zeros(lead, dtype=torch.complex128, device=dev)
+    if op.per_degree:
+        parts = [None if uin is None else _to_dev(uin(xu), dev, torch.complex128),
+                 None if uin_grad is None else torch.sum(_to_dev(uin_grad(xu), dev, torch.complex128) * x_rel.to(torch.complex128), dim=0)]
+        tgt = tuple(torch.broadcast_shapes(lead, *(tuple(t.shape) for t in parts if t is not None)))
+        parts = [None if t is None else t.expand(tgt) for t in parts]
+        g = next(t for t in parts if t is not None)
     else:
-        tgt = tuple(torch.broadcast_shapes(tuple(g.shape), lead))       # (a callable that returned fewer / shorter axes than it was given)
-        if tuple(g.shape) != tgt:
-            g = g.expand(tgt)
+        if uin is not None:
+            u = _to_dev(uin(xu), dev, torch.complex128)
+            g = (ab(fl.alpha) * u).neg_()                                  # (a fresh tensor: negated in place)
+        if uin_grad is not None:
+            gu = _to_dev(uin_grad(xu), dev, torch.complex128)
+            t = ab(fl.beta) * torch.sum(gu * x_rel.to(torch.complex128), dim=0)
+            g = t.neg_() if g is None else g - t
+        if g is None:
+            g = torch.zeros(lead, dtype=torch.complex128, device=dev)
+        else:
+            tgt = tuple(torch.broadcast_shapes(tuple(g.shape), lead))       # (a callable that returned fewer / shorter axes than it was given)
+            if tuple(g.shape) != tgt:
+                g = g.expand(tgt)
+        parts = [g]
     # The incident field may vary along batch axes on which the operator (k, eta, geometry, alpha, beta) has size 1
     # (e.g. many incidence directions for one wavenumber): those axes become right-hand sides of ONE factorisation.
     # The reference broadcasts the matrix over them in btensorsolve (_biem.py:797), i.e. factors it again per incidence.
@@ -734,9 +859,12 @@ def _boundary_samples(op: _Operator, uin, uin_grad) -> torch.Tensor:
     op_axes = [i for i in range(nbt) if batch[i] == full[i]]
     rhs_axes = [i for i in range(nbt) if batch[i] != full[i]]
     nrhs = int(np.prod([full[i] for i in rhs_axes])) if rhs_axes else 1
-    g = g.reshape((Q, B) + full)
-    g = g.permute([2 + i for i in op_axes] + [2 + i for i in rhs_axes] + [1, 0])      # (*op, *rhs, B, Q)
-    return g.reshape(nb, nrhs, B, Q).contiguous(), full, op_axes, rhs_axes
+    def laid_out(t):
+        t = t.reshape((Q, B) + full)
+        t = t.permute([2 + i for i in op_axes] + [2 + i for i in rhs_axes] + [1, 0])      # (*op, *rhs, B, Q)
+        return t.reshape(nb, nrhs, B, Q).contiguous()
+    parts = [None if t is None else laid_out(t) for t in parts]
+    return (tuple(parts) if op.per_degree else parts[0]), full, op_axes, rhs_axes
 
 
 def _restore_batch(t: torch.Tensor, full, op_axes, rhs_axes) -> torch.Tensor:
@@ -765,6 +893,8 @@ def biem(
     force_matrix: bool = False,
     translational_coefficients_method: Literal["gumerov", "plane_wave", "triplet"] | None = None,
     chunk: int = 0,
+    alpha_n: Array | None = None,
+    beta_n: Array | None = None,
 ) -> BIEMResultCalculator:
     r"""Boundary Integral Equation Method (BIEM) for the Helmholtz equation on MI355X.
 
@@ -778,6 +908,12 @@ def biem(
     exact closed form of SURVEY A.5 (the reference's "triplet" implementation is itself inexact).
     ``chunk`` (extension) bounds how many system matrices are resident at once (0 = choose).
 
+    ``alpha_n`` / ``beta_n`` (extension, given together, shape ``(..., B, n_end)``, leading axes broadcasting like those of alpha and
+    beta): boundary coefficients that depend on the harmonic degree, ``alpha_{b,n} u + beta_{b,n} d_n u = 0`` on ball b.  They take the
+    place of alpha and beta (which then stay at their defaults) in gj, gh and f above, with n the degree of the row.  A radially
+    symmetric inclusion the wave enters is such a condition: :func:`fluid_inclusion_bc`.  A ball that does not scatter some degree
+    (gj_n = 0, e.g. a transparent sphere) has no symmetric form; its systems are solved by the pivoted LU.
+
     Solver: the reference passes every system to a general dense solve (``_biem.py:797``).  Here the system is first brought
     to its complex-symmetric form (real harmonics, symmetric scaling) and factored as U^T U (Cholesky-type, no conjugation)
     without interchanges - half the flops; a system in which a multiplier would exceed 100, or whose factor grew by more than
@@ -786,7 +922,7 @@ def biem(
     """
     if translational_coefficients_method not in (None, "gumerov", "plane_wave", "triplet"):
         raise ValueError(f"Invalid translational_coefficients_method: {translational_coefficients_method}")
-    op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind)
+    op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n, beta_n)
     lib = L.load()
     plan, fl, dev = op.plan, op.fl, op.dev
     B, nb, H = fl.B, fl.nb, plan.H
@@ -810,7 +946,7 @@ def biem(
     if has_rhs:
         _check_incident(op, uin, uin_grad)
         g, *axes = _boundary_samples(op, uin, uin_grad)
-        nrhs = int(g.shape[1])
+        nrhs = _nrhs(g)
 
     use_matrix = (not has_rhs) or B > 1 or force_matrix          # reference :643-645
     density_t = None
@@ -857,9 +993,11 @@ def biem(
             # (info < 0: close to a resonance of a sphere, or strongly coupled spheres) are solved again with the pivoted LU,
             # which is what the reference's linalg.solve does for every system (_biem.py:797).  BIEM_SOLVER=lu: LU only.
             solver = _solver()
-            entry = lib.biem_solve_ldlt if solver == "ldlt" else lib.biem_solve
+            # (degree-dependent coefficients: the *_n entries, alpha_n / beta_n for alpha / beta and the unmixed samples for g)
+            e_sym, e_lu = (lib.biem_solve_ldlt_n, lib.biem_solve_n) if op.per_degree else (lib.biem_solve_ldlt, lib.biem_solve)
+            entry = e_sym if solver == "ldlt" else e_lu
             L.check(entry(plan.handle, nb, B, nrhs, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
-                          _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(g), _ptr(density_t), _ptr(info), chunk,
+                          _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, *_sample_ptrs(g), _ptr(density_t), _ptr(info), chunk,
                           _ptr(work), wbytes, sp), "biem_solve")
             if solver == "ldlt":
                 # (the codes come to the host in ONE copy and the rejected systems are picked there: torch.nonzero on the device is five
@@ -870,14 +1008,15 @@ def biem(
                 if redo.numel() > 0:
                     nr = int(redo.numel())
                     pick = lambda t, batched: t[redo].contiguous() if batched else t
-                    k_r, eta_r, g_r = fl.k[redo].contiguous(), fl.eta[redo].contiguous(), g[redo].contiguous()
+                    k_r, eta_r = fl.k[redo].contiguous(), fl.eta[redo].contiguous()
+                    g_r = g[redo].contiguous() if isinstance(g, torch.Tensor) else tuple(None if t is None else t[redo].contiguous() for t in g)
                     cen_r, rad_r = pick(fl.centers, fl.geom_batched), pick(fl.radii, fl.geom_batched)
                     al_r, be_r = pick(fl.alpha, fl.ab_batched), pick(fl.beta, fl.ab_batched)
                     dens_r = torch.empty((nr, nrhs, B, H), dtype=torch.complex128, device=dev)
                     info_r = torch.zeros(nr, dtype=torch.int32, device=dev)
-                    L.check(lib.biem_solve(plan.handle, nr, B, nrhs, _ptr(k_r), _ptr(eta_r), _ptr(cen_r), _ptr(rad_r), fl.geom_batched,
-                                           _ptr(al_r), _ptr(be_r), fl.ab_batched, _ptr(g_r), _ptr(dens_r), _ptr(info_r), min(chunk, nr),
-                                           _ptr(work), wbytes, sp), "biem_solve")
+                    L.check(e_lu(plan.handle, nr, B, nrhs, _ptr(k_r), _ptr(eta_r), _ptr(cen_r), _ptr(rad_r), fl.geom_batched,
+                                 _ptr(al_r), _ptr(be_r), fl.ab_batched, *_sample_ptrs(g_r), _ptr(dens_r), _ptr(info_r), min(chunk, nr),
+                                 _ptr(work), wbytes, sp), "biem_solve")
                     density_t[redo] = dens_r
             _last_solve_stats["ldlt_systems"] = nb if solver == "ldlt" else 0
             _last_solve_stats["lu_systems"] = (int(redo.numel()) if solver == "ldlt" else nb)
@@ -1046,7 +1185,7 @@ class BIEMFactorization:
         if has_rhs:
             _check_incident(op, uin, uin_grad)
             g, *axes = _boundary_samples(op, uin, uin_grad)
-            nrhs = int(g.shape[1])
+            nrhs = _nrhs(g)
             density_t = torch.empty((nb, nrhs, B, H), dtype=torch.complex128, device=dev)
             sp = _stream_ptr(dev)
             with torch.cuda.device(dev):
@@ -1058,8 +1197,13 @@ class BIEMFactorization:
                     if self.n_symmetric > 0:
                         wb = int(lib.biem_solve_factored_workspace_bytes(plan.handle, nb, B, nrhs))
                         work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
-                        L.check(lib.biem_solve_factored(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab), _ptr(g),
-                                                        _ptr(density_t), _ptr(work), wb, sp), "biem_solve_factored")
+                        if op.per_degree:
+                            L.check(lib.biem_solve_factored_n(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab),
+                                                              _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, *_sample_ptrs(g),
+                                                              _ptr(density_t), _ptr(work), wb, sp), "biem_solve_factored_n")
+                        else:
+                            L.check(lib.biem_solve_factored(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab), _ptr(g),
+                                                            _ptr(density_t), _ptr(work), wb, sp), "biem_solve_factored")
                         del work
                     # LU-form systems (runs of consecutive systems): equilibrated right-hand sides in natural order, stored LU, density
                     ldx = nrhs
@@ -1067,7 +1211,7 @@ class BIEMFactorization:
                         n = s1 - s0
                         x = torch.zeros((n, n_pad, ldx), dtype=torch.complex128, device=dev)
                         xs = n_pad * ldx
-                        L.check(lib.biem_rhs_project(plan.handle, n, B, nrhs, _ptr(g[s0:s1]), _ptr(x), xs, ldx, 1, sp), "biem_rhs_project")
+                        _rhs_project(op, n, g, s0, x, xs, ldx, 1, sp)
                         L.check(lib.biem_lu_solve(n, n_pad, nrhs, _ptr(self._factors[s0]), n_pad, sst, _ptr(self._ipiv[s0]), _ptr(x), ldx, xs, sp),
                                 "biem_lu_solve")
                         L.check(lib.biem_density(plan.handle, n, B, nrhs, _ptr(x), xs, ldx, 1, _ptr(self._tab[s0]), _ptr(density_t[s0]), sp),
@@ -1088,17 +1232,20 @@ def biem_factorize(
     eta: Array | None = None,
     kind: Literal["inner", "outer"] = "outer",
     chunk: int = 0,
+    alpha_n: Array | None = None,
+    beta_n: Array | None = None,
 ) -> BIEMFactorization:
     r"""Factor the BIEM operator of :func:`biem` once; solve incident fields against it later with ``.solve(uin=, uin_grad=)``.
 
-    Arguments and their checks are those of :func:`biem` without the incident field; alpha and beta belong to the operator.
+    Arguments and their checks are those of :func:`biem` without the incident field; alpha and beta (or the degree-dependent pair
+    alpha_n, beta_n) belong to the operator.
     The factors of all systems of the batch are kept on the device, ``nb x n_pad^2 x 16`` bytes (n_pad = B H rounded up to
     64); if they do not fit, ``torch.OutOfMemoryError`` states the bytes needed - the batch is never split silently, since
     factors that are not kept cannot be reused.  ``chunk`` bounds how many systems are filled and factored at once (0 =
     choose); it sizes the workspace on top of the factors, not the factors.  A single ball keeps only its tables (the
     shortcut of :func:`biem`).
     """
-    op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind)
+    op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n, beta_n)
     lib = L.load()
     plan, fl, dev = op.plan, op.fl, op.dev
     B, nb, H = fl.B, fl.nb, plan.H
@@ -1125,9 +1272,10 @@ def biem_factorize(
                 raise torch.OutOfMemoryError(f"biem_factorize: the factors of {nb} systems need {fbytes} bytes: {e}") from e
             info = torch.zeros(nb, dtype=torch.int32, device=dev)
             work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
-            L.check(lib.biem_factor_ldlt(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
-                                         _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(factors), n_pad, n_pad * n_pad, _ptr(tab),
-                                         _ptr(info), chunk, _ptr(work), wb, sp), "biem_factor_ldlt")
+            factor = lib.biem_factor_ldlt_n if op.per_degree else lib.biem_factor_ldlt
+            L.check(factor(plan.handle, nb, B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
+                           _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(factors), n_pad, n_pad * n_pad, _ptr(tab),
+                           _ptr(info), chunk, _ptr(work), wb, sp), "biem_factor_ldlt")
             del work
             # systems the symmetric factorisation rejected (or all of them with BIEM_SOLVER=lu): pivoted LU of the equilibrated
             # system in the same slot, as biem() re-solves them

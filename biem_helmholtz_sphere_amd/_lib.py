@@ -68,6 +68,13 @@ SIGNATURES = {
     "biem_factor_ldlt": (_i, [_vp, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _ll, _ll, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_factored_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "biem_solve_factored": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _vp, _sz, _vp]),
+    "biem_ball_tables_n": (_i, [_vp, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _vp]),
+    "biem_rhs_project_n": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _ll, _ll, _ll, _vp]),
+    "biem_solve_n": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_solve_ldlt_n": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_factor_ldlt_n": (_i, [_vp, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _ll, _ll, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_solve_factored_n": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _i, _dp, _dp, _dp, _vp, _sz, _vp]),
+    "biem_flag_unscalable": (_i, [_vp, _i, _i, _dp, _ip, _i, _vp]),
     "biem_profile_begin": (_i, []),
     "biem_profile_end": (_i, [_vp, _vp, _vp]),
     "biem_bench_mfma_f64": (_i, [_i, C.POINTER(C.c_double), _vp]),

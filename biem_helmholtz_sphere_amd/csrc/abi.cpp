@@ -16,8 +16,11 @@ hipEvent_t Profiler::get() {
 }
 }  // namespace biem
 
-#define NEED(p, what) do { if (!(p)) { set_error("%s: null %s", __func__, what); return BIEM_ERR_ARG; } } while (0)
-#define NEED_DEV(pl) do { NEED(pl, "plan"); if ((pl)->device < 0) { set_error("%s: plan not uploaded to a device (biem_plan_upload)", __func__); return BIEM_ERR_ARG; } } while (0)
+// (the *_AS forms: a body shared by two entry points reports under the name of the one that was called)
+#define NEED_AS(who, p, what) do { if (!(p)) { set_error("%s: null %s", who, what); return BIEM_ERR_ARG; } } while (0)
+#define NEED_DEV_AS(who, pl) do { NEED_AS(who, pl, "plan"); if ((pl)->device < 0) { set_error("%s: plan not uploaded to a device (biem_plan_upload)", who); return BIEM_ERR_ARG; } } while (0)
+#define NEED(p, what) NEED_AS(__func__, p, what)
+#define NEED_DEV(pl) NEED_DEV_AS(__func__, pl)
 
 extern "C" {
 
@@ -197,6 +200,25 @@ int biem_rhs_project(const biem_plan* plan, int nb, int B, int nrhs, const doubl
   return launch_rhs_project(plan, nb, B, nrhs, d_g, d_f, sys_stride, elem_stride, rhs_stride, (hipStream_t)stream);
 }
 
+int biem_ball_tables_n(const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
+                       int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched, double* d_tab, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_eta, "d_eta"); NEED(d_radii, "d_radii"); NEED(d_alpha_n, "d_alpha_n"); NEED(d_beta_n, "d_beta_n"); NEED(d_tab, "d_tab");
+  return launch_ball_tables_n(plan, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha_n, d_beta_n, ab_batched, d_tab, (hipStream_t)stream);
+}
+
+int biem_rhs_project_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_gu, const double* d_gdn, const double* d_alpha_n,
+                       const double* d_beta_n, int ab_batched, double* d_f, long long sys_stride, long long elem_stride,
+                       long long rhs_stride, void* stream) {
+  NEED_DEV(plan); NEED(d_alpha_n, "d_alpha_n"); NEED(d_beta_n, "d_beta_n"); NEED(d_f, "d_f");
+  return launch_rhs_project_n(plan, nb, B, nrhs, d_gu, d_gdn, d_alpha_n, d_beta_n, ab_batched, d_f, sys_stride, elem_stride, rhs_stride,
+                              (hipStream_t)stream);
+}
+
+int biem_flag_unscalable(const biem_plan* plan, int nb, int B, const double* d_tab, int* d_info, int code, void* stream) {
+  NEED_DEV(plan); NEED(d_tab, "d_tab"); NEED(d_info, "d_info");
+  return launch_flag_unscalable(plan, nb, B, d_tab, d_info, code, (hipStream_t)stream);
+}
+
 size_t biem_fill_workspace_bytes(const biem_plan* plan, int nb, int B) { return plan ? fill_workspace_bytes(plan, nb, B) : 0; }
 
 int biem_fill(const biem_plan* plan, int nb, int B, const double* d_k, const double* d_centers, int geom_batched,
@@ -297,6 +319,9 @@ struct SolveLayout {
   size_t off_tab, off_A, off_T, off_P, off_ipiv, total;
 };
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// degree-dependent boundary coefficients of the *_n entries: alpha_n / beta_n [nb or 1][B][n_end] in place of alpha / beta [nb or 1][B],
+// the unmixed samples gu / gdn [nb][nrhs][B][Q] (either may be null: zero) in place of g
+struct DegreeBc { const double* alpha_n; const double* beta_n; const double* gu; const double* gdn; };
 SolveLayout make_layout(const biem_plan* p, int nb, int B, int nrhs, int chunk) {
   SolveLayout L;
   L.N = B * p->H;
@@ -331,9 +356,11 @@ size_t biem_solve_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs
 static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
                const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched,
                const double* d_g, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes, void* stream,
-               bool symmetric) {
+               bool symmetric, const DegreeBc* bcn = nullptr) {
   NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_eta, "d_eta"); NEED(d_centers, "d_centers"); NEED(d_radii, "d_radii");
-  NEED(d_alpha, "d_alpha"); NEED(d_beta, "d_beta"); NEED(d_g, "d_g"); NEED(d_density, "d_density"); NEED(d_info, "d_info"); NEED(d_work, "d_work");
+  if (bcn) { NEED(bcn->alpha_n, "d_alpha_n"); NEED(bcn->beta_n, "d_beta_n"); }
+  else { NEED(d_alpha, "d_alpha"); NEED(d_beta, "d_beta"); NEED(d_g, "d_g"); }
+  NEED(d_density, "d_density"); NEED(d_info, "d_info"); NEED(d_work, "d_work");
   if (nb <= 0 || B <= 0) return BIEM_OK;
   if (nrhs < 1) { set_error("biem_solve: nrhs < 1"); return BIEM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
@@ -346,7 +373,8 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
   void* Pw = w + L.off_P;
   int* ipiv = (int*)(w + L.off_ipiv);
   const int H = plan->H, d = plan->d, Q = plan->Q;
-  int rc = launch_ball_tables(plan, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, tab, st);
+  int rc = bcn ? launch_ball_tables_n(plan, nb, B, d_k, d_eta, d_radii, geom_batched, bcn->alpha_n, bcn->beta_n, ab_batched, tab, st)
+               : launch_ball_tables(plan, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, tab, st);
   if (rc) return rc;
   for (int s0 = 0; s0 < nb; s0 += L.chunk) {
     const int c = (nb - s0 < L.chunk) ? nb - s0 : L.chunk;
@@ -359,8 +387,9 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
     // blocks of ball pairs with the same displacement and the same (radius, alpha, beta) on either side are contracted once
     const FillDedupe dd = {d_radii, d_alpha, d_beta};
     if (symmetric)
+      // (degree-dependent coefficients: every pair on its own - the classes are keyed on one (alpha, beta) per ball)
       rc = launch_fill_sym(plan, c, B, ks, cen, geom_batched, tb, A, L.lda, L.sys_stride, L.n_pad, T, fill_workspace_bytes(plan, c, B), st, small,
-                           (!geom_batched && !ab_batched) ? &dd : nullptr);
+                           (!geom_batched && !ab_batched && !bcn) ? &dd : nullptr);
     else
       rc = launch_fill(plan, c, B, ks, cen, geom_batched, tb, BIEM_FILL_EQUILIBRATED, A, L.lda, L.sys_stride, L.n_pad, T,
                        fill_workspace_bytes(plan, c, B), st);
@@ -368,7 +397,14 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
     if (!small)
       BIEM_HIPCHK(hipMemset2DAsync(A + (size_t)L.n_pad * 2, (size_t)L.lda * 16, 0, (size_t)(L.lda - L.n_pad) * 16,
                                    (size_t)L.n_pad * c, st));
-    rc = launch_rhs_project(plan, c, B, nrhs, d_g + (size_t)s0 * nrhs * B * Q * 2, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, st, symmetric);
+    const size_t g0 = (size_t)s0 * nrhs * B * Q * 2;
+    if (bcn) {
+      const size_t ab0 = ab_batched ? (size_t)s0 * B * plan->n_end * 2 : 0;
+      rc = launch_rhs_project_n(plan, c, B, nrhs, bcn->gu ? bcn->gu + g0 : nullptr, bcn->gdn ? bcn->gdn + g0 : nullptr, bcn->alpha_n + ab0,
+                                bcn->beta_n + ab0, ab_batched, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, st, symmetric);
+    } else {
+      rc = launch_rhs_project(plan, c, B, nrhs, d_g + g0, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, st, symmetric);
+    }
     if (rc) return rc;
     bool amax_ready = false;
     if (symmetric) {
@@ -386,6 +422,11 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
       rc = launch_lu_factor_solve(c, L.n_pad, nrhs, A, L.lda, L.sys_stride, ipiv, d_info + s0, Pw, lu_workspace_bytes(c, L.n_pad, nrhs), st,
                                   /*keep_multipliers=*/false, false, false);   // the fused path only needs the solution
     if (rc) return rc;
+    if (symmetric && bcn) {
+      // a degree with gj = 0 (a ball that does not scatter it) has no symmetric scaling: rejected here whatever the factorisation reported
+      rc = launch_flag_unscalable(plan, c, B, tb, d_info + s0, -(L.n_pad + 2), st);
+      if (rc) return rc;
+    }
     if (symmetric) {
       rc = launch_sym_rhs(plan, c, B, nrhs, L.n_pad, tb, A, L.lda, L.sys_stride, true, st);
       if (rc) return rc;
@@ -408,6 +449,24 @@ int biem_solve_ldlt(const biem_plan* plan, int nb, int B, int nrhs, const double
                     const double* d_g, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes, void* stream) {
   return solve_impl(plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_g, d_density, d_info,
                     chunk, d_work, work_bytes, stream, true);
+}
+
+int biem_solve_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                 const double* d_radii, int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched,
+                 const double* d_gu, const double* d_gdn, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                 void* stream) {
+  const DegreeBc bcn = {d_alpha_n, d_beta_n, d_gu, d_gdn};
+  return solve_impl(plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, nullptr, nullptr, ab_batched, nullptr, d_density, d_info,
+                    chunk, d_work, work_bytes, stream, false, &bcn);
+}
+
+int biem_solve_ldlt_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                      const double* d_radii, int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched,
+                      const double* d_gu, const double* d_gdn, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                      void* stream) {
+  const DegreeBc bcn = {d_alpha_n, d_beta_n, d_gu, d_gdn};
+  return solve_impl(plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, nullptr, nullptr, ab_batched, nullptr, d_density, d_info,
+                    chunk, d_work, work_bytes, stream, true, &bcn);
 }
 
 // ---- factor now, solve later: the symmetric path split at the factorisation -------------------------------------------------
@@ -455,26 +514,27 @@ size_t biem_factor_workspace_bytes(const biem_plan* plan, int nb, int B, int chu
   return make_factor_layout(plan, nb, B, chunk).total;
 }
 
-int biem_factor_ldlt(const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_centers,
-                     const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, double* d_F,
-                     long long lda, long long sys_stride, double* d_tab, int* d_info, int chunk, void* d_work, size_t work_bytes,
-                     void* stream) {
-  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_eta, "d_eta"); NEED(d_centers, "d_centers"); NEED(d_radii, "d_radii");
-  NEED(d_alpha, "d_alpha"); NEED(d_beta, "d_beta"); NEED(d_F, "d_F"); NEED(d_tab, "d_tab"); NEED(d_info, "d_info"); NEED(d_work, "d_work");
-  if (nb < 0 || nb > 65535 || B < 0) { set_error("%s: 0 .. 65535 systems per call and B >= 0 (got nb=%d, B=%d)", __func__, nb, B); return BIEM_ERR_ARG; }
+static int factor_impl(const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_centers,
+                       const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, double* d_F,
+                       long long lda, long long sys_stride, double* d_tab, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                       void* stream, bool per_degree, const char* who) {
+  NEED_DEV_AS(who, plan); NEED_AS(who, d_k, "d_k"); NEED_AS(who, d_eta, "d_eta"); NEED_AS(who, d_centers, "d_centers"); NEED_AS(who, d_radii, "d_radii");
+  NEED_AS(who, d_alpha, "d_alpha"); NEED_AS(who, d_beta, "d_beta"); NEED_AS(who, d_F, "d_F"); NEED_AS(who, d_tab, "d_tab"); NEED_AS(who, d_info, "d_info"); NEED_AS(who, d_work, "d_work");
+  if (nb < 0 || nb > 65535 || B < 0) { set_error("%s: 0 .. 65535 systems per call and B >= 0 (got nb=%d, B=%d)", who, nb, B); return BIEM_ERR_ARG; }
   if (nb == 0 || B == 0) return BIEM_OK;
   const FactorLayout L = make_factor_layout(plan, nb, B, chunk);
   if (lda < L.n_pad || sys_stride < (long long)L.n_pad * lda) {
-    set_error("%s: lda=%lld < n_pad=%d or sys_stride=%lld < n_pad * lda", __func__, lda, L.n_pad, sys_stride);
+    set_error("%s: lda=%lld < n_pad=%d or sys_stride=%lld < n_pad * lda", who, lda, L.n_pad, sys_stride);
     return BIEM_ERR_ARG;
   }
-  if (work_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, L.total); return BIEM_ERR_ARG; }
+  if (work_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, work_bytes, L.total); return BIEM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   char* w = (char*)d_work;
   void* T = w + L.off_T;
   void* Pw = w + L.off_P;
   const int d = plan->d;
-  int rc = launch_ball_tables(plan, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_tab, st);
+  int rc = per_degree ? launch_ball_tables_n(plan, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_tab, st)
+                      : launch_ball_tables(plan, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_tab, st);
   if (rc) return rc;
   const FillDedupe dd = {d_radii, d_alpha, d_beta};
   for (int s0 = 0; s0 < nb; s0 += L.chunk) {
@@ -486,14 +546,34 @@ int biem_factor_ldlt(const biem_plan* plan, int nb, int B, const double* d_k, co
     // identity padding written (no_padding = false) even where the one-launch path factors the active rows only: the solve runs
     // over all n_pad rows and finds U = I there
     rc = launch_fill_sym(plan, c, B, ks, cen, geom_batched, tb, A, lda, sys_stride, L.n_pad, T, fill_workspace_bytes(plan, c, B), st, false,
-                         (!geom_batched && !ab_batched) ? &dd : nullptr);
+                         (!geom_batched && !ab_batched && !per_degree) ? &dd : nullptr);
     if (rc) return rc;
     rc = lu_growth_init(Pw, c, L.n_pad, 1.0, st);     // max |A~| >= 1 (unit diagonal), as in biem_solve_ldlt
     if (rc) return rc;
     rc = launch_sym_factor_solve(c, L.n_pad, 0, A, lda, sys_stride, d_info + s0, Pw, lu_workspace_bytes(c, L.n_pad, 0), st, true, L.N);
     if (rc) return rc;
+    if (per_degree) {     // a degree with gj = 0 has no symmetric scaling (biem_solve_ldlt_n)
+      rc = launch_flag_unscalable(plan, c, B, tb, d_info + s0, -(L.n_pad + 2), st);
+      if (rc) return rc;
+    }
   }
   return BIEM_OK;
+}
+
+int biem_factor_ldlt(const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_centers,
+                     const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, double* d_F,
+                     long long lda, long long sys_stride, double* d_tab, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                     void* stream) {
+  return factor_impl(plan, nb, B, d_k, d_eta, d_centers, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_F, lda, sys_stride, d_tab,
+                     d_info, chunk, d_work, work_bytes, stream, false, "biem_factor_ldlt");
+}
+
+int biem_factor_ldlt_n(const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_centers,
+                       const double* d_radii, int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched,
+                       double* d_F, long long lda, long long sys_stride, double* d_tab, int* d_info, int chunk, void* d_work,
+                       size_t work_bytes, void* stream) {
+  return factor_impl(plan, nb, B, d_k, d_eta, d_centers, d_radii, geom_batched, d_alpha_n, d_beta_n, ab_batched, d_F, lda, sys_stride, d_tab,
+                     d_info, chunk, d_work, work_bytes, stream, true, "biem_factor_ldlt_n");
 }
 
 size_t biem_solve_factored_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs) {
@@ -501,28 +581,32 @@ size_t biem_solve_factored_workspace_bytes(const biem_plan* plan, int nb, int B,
   return (size_t)nb * lu_npad(B * plan->H) * solve_ldx(nrhs) * sizeof(cplx);
 }
 
-int biem_solve_factored(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
-                        const double* d_tab, const double* d_g, double* d_density, void* d_work, size_t work_bytes, void* stream) {
-  NEED_DEV(plan); NEED(d_F, "d_F"); NEED(d_tab, "d_tab"); NEED(d_g, "d_g"); NEED(d_density, "d_density"); NEED(d_work, "d_work");
+static int solve_factored_impl(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                               const double* d_tab, const double* d_g, double* d_density, void* d_work, size_t work_bytes, void* stream,
+                               const DegreeBc* bcn, int ab_batched, const char* who) {
+  NEED_DEV_AS(who, plan); NEED_AS(who, d_F, "d_F"); NEED_AS(who, d_tab, "d_tab"); NEED_AS(who, d_density, "d_density"); NEED_AS(who, d_work, "d_work");
+  if (bcn) { NEED_AS(who, bcn->alpha_n, "d_alpha_n"); NEED_AS(who, bcn->beta_n, "d_beta_n"); }
+  else NEED_AS(who, d_g, "d_g");
   if (nb < 0 || nb > 65535 || nrhs < 0 || nrhs > 65535 || B < 0) {
-    set_error("%s: 0 .. 65535 systems / right-hand sides per call and B >= 0 (got nb=%d, nrhs=%d, B=%d)", __func__, nb, nrhs, B);
+    set_error("%s: 0 .. 65535 systems / right-hand sides per call and B >= 0 (got nb=%d, nrhs=%d, B=%d)", who, nb, nrhs, B);
     return BIEM_ERR_ARG;
   }
   if (nb == 0 || nrhs == 0 || B == 0) return BIEM_OK;
   const int n_pad = lu_npad(B * plan->H);
   if (lda < n_pad || sys_stride < (long long)n_pad * lda) {
-    set_error("%s: lda=%lld < n_pad=%d or sys_stride=%lld < n_pad * lda", __func__, lda, n_pad, sys_stride);
+    set_error("%s: lda=%lld < n_pad=%d or sys_stride=%lld < n_pad * lda", who, lda, n_pad, sys_stride);
     return BIEM_ERR_ARG;
   }
   const size_t need = biem_solve_factored_workspace_bytes(plan, nb, B, nrhs);
-  if (work_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, need); return BIEM_ERR_ARG; }
+  if (work_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", who, work_bytes, need); return BIEM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   // right-hand sides X[s][row][q] (row-major, ldx columns), rows in the slot order of the symmetric form; padding rows zero
   double* X = (double*)d_work;
   const long long ldx = solve_ldx(nrhs), xs = (long long)n_pad * ldx;
   double* Xaug = X - 2 * (size_t)n_pad;      // X seen as the augmented columns n_pad .. of a matrix with leading dimension ldx
   BIEM_HIPCHK(hipMemsetAsync(X, 0, need, st));
-  int rc = launch_rhs_project(plan, nb, B, nrhs, d_g, X, xs, ldx, 1, st, true);
+  int rc = bcn ? launch_rhs_project_n(plan, nb, B, nrhs, bcn->gu, bcn->gdn, bcn->alpha_n, bcn->beta_n, ab_batched, X, xs, ldx, 1, st, true)
+               : launch_rhs_project(plan, nb, B, nrhs, d_g, X, xs, ldx, 1, st, true);
   if (rc) return rc;
   rc = launch_sym_rhs(plan, nb, B, nrhs, n_pad, d_tab, Xaug, ldx, xs, false, st);
   if (rc) return rc;
@@ -531,6 +615,20 @@ int biem_solve_factored(const biem_plan* plan, int nb, int B, int nrhs, const do
   rc = launch_sym_rhs(plan, nb, B, nrhs, n_pad, d_tab, Xaug, ldx, xs, true, st);
   if (rc) return rc;
   return launch_density(plan, nb, B, nrhs, X, xs, ldx, 1, d_tab, d_density, st, true);
+}
+
+int biem_solve_factored(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                        const double* d_tab, const double* d_g, double* d_density, void* d_work, size_t work_bytes, void* stream) {
+  return solve_factored_impl(plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, d_g, d_density, d_work, work_bytes, stream, nullptr, 0,
+                             "biem_solve_factored");
+}
+
+int biem_solve_factored_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                          const double* d_tab, const double* d_alpha_n, const double* d_beta_n, int ab_batched, const double* d_gu,
+                          const double* d_gdn, double* d_density, void* d_work, size_t work_bytes, void* stream) {
+  const DegreeBc bcn = {d_alpha_n, d_beta_n, d_gu, d_gdn};
+  return solve_factored_impl(plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, nullptr, d_density, d_work, work_bytes, stream, &bcn, ab_batched,
+                             "biem_solve_factored_n");
 }
 
 int biem_profile_begin(void) {

@@ -9,6 +9,8 @@ namespace biem {
 
 typedef double2 cplx;  // .x = re, .y = im
 
+constexpr int kMaxRad = 320;   // max table order handled per thread-local/LDS radial array (every translation unit: one value)
+
 __host__ __device__ inline cplx cmul(cplx a, cplx b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __host__ __device__ inline cplx cadd(cplx a, cplx b) { return make_double2(a.x + b.x, a.y + b.y); }
 __host__ __device__ inline cplx csub(cplx a, cplx b) { return make_double2(a.x - b.x, a.y - b.y); }
@@ -75,6 +77,17 @@ int launch_ball_tables(const biem_plan* p, int nb, int B, const double* d_k, con
 // slot_order: harmonic h of a ball goes to / comes from the plan's internal slot hpos[h] (symmetric path) instead of position h
 int launch_rhs_project(const biem_plan* p, int nb, int B, int nrhs, const double* d_g, double* d_f, long long sys_stride,
                        long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order = false);
+// degree-dependent boundary coefficients (kernels_degree_bc.hip): alpha_n / beta_n [nb or 1][B][n_end] complex; the tables are laid out
+// as launch_ball_tables' and feed the same fill / solve / density launches
+int launch_ball_tables_n(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
+                         int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched, double* d_tab, hipStream_t st);
+// f = -(alpha_n P[gu] + beta_n P[gdn]); a null sample set is zero; strides and slot order as launch_rhs_project
+int launch_rhs_project_n(const biem_plan* p, int nb, int B, int nrhs, const double* d_gu, const double* d_gdn, const double* d_alpha_n,
+                         const double* d_beta_n, int ab_batched, double* d_f, long long sys_stride, long long elem_stride,
+                         long long rhs_stride, hipStream_t st, bool slot_order = false);
+// d_info[s] = code for every system with a (ball, degree) whose symmetric scaling 1 / sqrt(gj gh) is not finite (gj = 0); others untouched
+// (biem_flag_unscalable exposes it for tests)
+int launch_flag_unscalable(const biem_plan* p, int nb, int B, const double* d_tab, int* d_info, int code, hipStream_t st);
 size_t fill_workspace_bytes(const biem_plan* p, int nb, int B);
 int launch_fill(const biem_plan* p, int nb, int B, const double* d_k, const double* d_centers, int geom_batched,
                 const double* d_tab, int scaling, double* d_A, long long lda, long long sys_stride, int n_pad,

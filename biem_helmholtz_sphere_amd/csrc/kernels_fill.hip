@@ -7,8 +7,6 @@
 
 namespace biem {
 
-constexpr int kMaxRad = 320;   // max table order handled per thread-local/LDS radial array
-
 // ---------------------------------------------------------------------------------------------
 // test entry: radial functions at arbitrary arguments
 // ---------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 namespace biem {
 
 constexpr int kMaxRadU = 320;
+static_assert(kMaxRadU == kMaxRad, "one table order for every translation unit (common.hpp)");
 
 // c[s][b][h] = density * blc_{n(h)}(rho_b) (inner: the interior coefficient with h_n, h_n' at k rho): one wave per (system, ball)
 __global__ void __launch_bounds__(64) k_uscat_coef(int d, int H, int n_end, const int* __restrict__ deg, int B, int inner,

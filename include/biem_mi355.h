@@ -275,6 +275,53 @@ size_t biem_solve_factored_workspace_bytes(const biem_plan* plan, int nb, int B,
 int biem_solve_factored(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
                         const double* d_tab, const double* d_g, double* d_density, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- boundary coefficients that depend on the harmonic degree:  alpha_{b,n} u + beta_{b,n} d_n u = 0 on ball b (a sphere the wave
+ *      enters acts on the exterior field through one scalar per degree).  Every entry below mirrors its namesake
+ *      without _n; only what differs is described.  d_alpha_n / d_beta_n are [nb][B][n_end] complex128 when ab_batched != 0, else
+ *      [B][n_end] shared by all systems.  The tables have biem_ball_tables' layout, so biem_fill, biem_density, biem_lu_*,
+ *      biem_sym_*, biem_uscat and biem_uscat_grad take them and their results as they are. ----
+ * biem_ball_tables_n: [0] gj_n = alpha_n j_n + beta_n k j_n', [1] gh_n = alpha_n h_n + beta_n k h_n', [2] blc_n; per degree the
+ * arithmetic of biem_ball_tables, so coefficients that do not vary with n give its table.  Same trees and orders. */
+int biem_ball_tables_n(const biem_plan* plan, int nb, int B, const double* d_k /*c128*/, const double* d_eta, const double* d_radii,
+                       int geom_batched, const double* d_alpha_n /*c128*/, const double* d_beta_n /*c128*/, int ab_batched,
+                       double* d_tab, void* stream);
+/* biem_rhs_project_n: the degree of a harmonic is known only after the projection, so the two parts of the boundary data cross the
+ * ABI apart and unweighted: d_gu[s][r][b][q] = u_in(c_b + rho_b y_q), d_gdn[s][r][b][q] = (y_q . grad u_in)(c_b + rho_b y_q), each
+ * [nb][nrhs][B][Q] complex128; a null pointer is a set of zeros (and costs nothing).  Writes
+ *   f(s, r, b, h) = -( alpha_{b,n(h)} sum_q W[q][h] gu[s][r][b][q] + beta_{b,n(h)} sum_q W[q][h] gdn[s][r][b][q] )
+ * to d_f[s*sys_stride + (b*H + h)*elem_stride + r*rhs_stride] as biem_rhs_project does (one read of W serves both sums). */
+int biem_rhs_project_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_gu, const double* d_gdn,
+                       const double* d_alpha_n, const double* d_beta_n, int ab_batched, double* d_f, long long sys_stride,
+                       long long elem_stride, long long rhs_stride, void* stream);
+/* biem_solve_n / biem_solve_ldlt_n: biem_solve / biem_solve_ldlt with (d_alpha_n, d_beta_n) for (d_alpha, d_beta) and (d_gu, d_gdn)
+ * for d_g; workspace biem_solve_workspace_bytes.  The symmetric fill takes every ball pair on its own (no pair classes: they are keyed
+ * on one (alpha, beta) per ball).  One more d_info code of biem_solve_ldlt_n: -(Npad+2) marks a system with a (ball, degree) whose
+ * gj_n gh_n is zero or whose scaling 1/sqrt(gj_n gh_n) is not finite - a degree the ball does not scatter, e.g. a transparent sphere
+ * (k_b = k, density ratio 1) - for which the symmetric form does not exist; like every d_info < 0 the caller re-solves it with
+ * biem_solve_n, whose equilibrated form divides by gh only. */
+int biem_solve_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_centers,
+                 const double* d_radii, int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched,
+                 const double* d_gu, const double* d_gdn, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                 void* stream);
+int biem_solve_ldlt_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta,
+                      const double* d_centers, const double* d_radii, int geom_batched, const double* d_alpha_n, const double* d_beta_n,
+                      int ab_batched, const double* d_gu, const double* d_gdn, double* d_density, int* d_info, int chunk, void* d_work,
+                      size_t work_bytes, void* stream);
+/* biem_factor_ldlt_n: biem_factor_ldlt with the tables of biem_ball_tables_n (workspace biem_factor_workspace_bytes; no pair classes;
+ * d_info as biem_solve_ldlt_n).  biem_solve_factored_n: biem_solve_factored with the right-hand sides of biem_rhs_project_n - the
+ * coefficients are passed again because the stored tables hold only their combinations gj, gh (workspace
+ * biem_solve_factored_workspace_bytes). */
+/* the check behind that d_info code, on its own (tests): d_info[s] = code for every system s of d_tab [nb][B][3][n_end] with a
+ * (ball, degree) whose 1/sqrt(gj gh) or gj/sqrt(gj gh) is not finite; the entries of the other systems are left as they are. */
+int biem_flag_unscalable(const biem_plan* plan, int nb, int B, const double* d_tab, int* d_info, int code, void* stream);
+int biem_factor_ldlt_n(const biem_plan* plan, int nb, int B, const double* d_k /*c128*/, const double* d_eta, const double* d_centers,
+                       const double* d_radii, int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched,
+                       double* d_F, long long lda, long long sys_stride, double* d_tab, int* d_info, int chunk, void* d_work,
+                       size_t work_bytes, void* stream);
+int biem_solve_factored_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                          const double* d_tab, const double* d_alpha_n, const double* d_beta_n, int ab_batched, const double* d_gu,
+                          const double* d_gdn, double* d_density, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- per-kernel-class timing with HIP events on the launch stream (thread-local; used by bench.py for the
  *      live `roofline` figures).  Between begin and end every launch of the calling thread is bracketed by two
  *      events; end synchronises on them and returns, per class, elapsed ms, algorithmic work and launch count.
