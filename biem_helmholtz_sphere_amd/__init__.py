@@ -16,6 +16,8 @@ from ._biem import (
     biem_factorize,
     biem_u,
     biem_u_grad,
+    biem_u_interior,
+    biem_u_total,
     fluid_inclusion_bc,
     max_memory,
     max_n_end,
@@ -34,6 +36,8 @@ __all__ = [
     "biem_factorize",
     "biem_u",
     "biem_u_grad",
+    "biem_u_interior",
+    "biem_u_total",
     "fluid_inclusion_bc",
     "max_memory",
     "max_n_end",

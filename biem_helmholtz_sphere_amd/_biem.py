@@ -37,7 +37,7 @@ Array = Any
 
 __all__ = [
     "BIEMFactorization", "BIEMKwargs", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
-    "biem_factorize", "biem_u", "fluid_inclusion_bc", "max_memory", "max_n_end", "plane_wave", "point_source",
+    "biem_factorize", "biem_u", "biem_u_interior", "biem_u_total", "fluid_inclusion_bc", "max_memory", "max_n_end", "plane_wave", "point_source",
 ]
 
 
@@ -451,6 +451,14 @@ class BIEMResultCalculator:
     def uscat_grad(self, x: Array, /, per_ball: bool = False, expand_x: bool = True) -> Array:
         """Cartesian gradient of the scattered field, component axis first (see :func:`biem_u_grad`)."""
         return biem_u_grad(self, x, per_ball=per_ball, expand_x=expand_x)
+
+    def uinterior(self, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
+        """Total field inside penetrable fluid balls, NaN outside them (see :func:`biem_u_interior`)."""
+        return biem_u_interior(self, x, k_interior=k_interior, density_ratio=density_ratio, expand_x=expand_x)
+
+    def utotal(self, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
+        """Total field inside and outside penetrable fluid balls (see :func:`biem_u_total`)."""
+        return biem_u_total(self, x, k_interior=k_interior, density_ratio=density_ratio, expand_x=expand_x)
 
 
 # --------------------------------------------------------------------------------------
@@ -1053,26 +1061,29 @@ def biem_u_grad(res: Any, x: Array, /, per_ball: bool = False, expand_x: bool = 
     return _field(res, x, far_field=False, per_ball=per_ball, expand_x=expand_x, grad=True)
 
 
-def _field(res: Any, x: Array, *, far_field: bool, per_ball: bool, expand_x: bool, grad: bool) -> Array:
-    if res.density is None:
-        raise ValueError("The BIEMResult does not have density.")
-    if res.kind not in ("outer", "inner"):
-        raise ValueError(f"Invalid kind: {res.kind}")
+@dataclass
+class _FieldOperands:
+    """The flattened device operands of one field evaluation (biem_u, biem_u_grad, biem_u_interior)."""
+
+    origin: _Origin
+    dev: torch.device
+    fl: _Flat
+    plan: _Plan
+    pts: torch.Tensor         # [d, P] or [d, P, nb] (flags: USCAT_POINTS_BATCHED), canonical axes
+    density: torch.Tensor     # [nb, B, H]
+    flags: int
+    xshape: Tuple[int, ...]
+    batch: Tuple[int, ...]
+
+
+def _field_operands(res: Any, x: Array, tree: str, perm, expand_x: bool, extra_batch=()) -> _FieldOperands:
+    """extra_batch: leading shapes of further per-system operands, broadcast into the batch shape."""
     c = res.c
-    tree, perm = canonical_tree(c.branching_types_expression_str)
-    if grad:
-        ne = n_end_from_harm(tree, int(res.density.shape[-1]))
-        if ne > USCAT_GRAD_N_END_MAX.get(tree, 0):
-            cov = ", ".join(f"{t} (n_end <= {n})" for t, n in USCAT_GRAD_N_END_MAX.items())
-            raise NotImplementedError(
-                f"uscat_grad is not built for tree {c.branching_types_expression_str!r} at n_end={ne}; covered: {cov}, "
-                "bpa and bpbpa as ba and bba; the chain trees d >= 5 and larger orders have uscat() only")
     origin, dev = _origin_of(res.centers, res.radii, res.k, res.density, x)
     if isinstance(res.density, torch.Tensor) and res.density.dtype == torch.complex64:
         origin.real_dtype = torch.float32
     elif isinstance(res.density, np.ndarray) and res.density.dtype == np.complex64:
         origin.real_dtype = torch.float32
-    lib = L.load()
     f64 = torch.float64
     k_t = _to_dev(res.k, dev, torch.complex128)
     eta_t = _to_dev(res.eta, dev, f64)
@@ -1084,7 +1095,7 @@ def _field(res: Any, x: Array, *, far_field: bool, per_ball: bool, expand_x: boo
     n_end = n_end_from_harm(tree, H)
     ndim_first = k_t.ndim
     batch = tuple(np.broadcast_shapes(tuple(k_t.shape), tuple(eta_t.shape), tuple(cen_t.shape[1:-1]), tuple(rad_t.shape[:-1]),
-                                      tuple(dens_t.shape[:-2])))
+                                      tuple(dens_t.shape[:-2]), *extra_batch))
     fl = _flatten(batch, torch.movedim(cen_t, 0, -1), rad_t, k_t, eta_t)
     nb, B = fl.nb, fl.B
     plan = _plan(tree, n_end, dev)
@@ -1106,7 +1117,28 @@ def _field(res: Any, x: Array, *, far_field: bool, per_ball: bool, expand_x: boo
         xshape = tuple(x_t.shape[1:1 + nx])
         pts = x_t.expand((d,) + xshape + batch).reshape(d, -1, nb).contiguous()
         flags = L.USCAT_POINTS_BATCHED
-    P = int(pts.shape[1])
+    df = dens_t.expand(batch + (B, H)).reshape(nb, B, H).contiguous()
+    return _FieldOperands(origin, dev, fl, plan, pts, df, flags, xshape, batch)
+
+
+def _field(res: Any, x: Array, *, far_field: bool, per_ball: bool, expand_x: bool, grad: bool) -> Array:
+    if res.density is None:
+        raise ValueError("The BIEMResult does not have density.")
+    if res.kind not in ("outer", "inner"):
+        raise ValueError(f"Invalid kind: {res.kind}")
+    c = res.c
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    if grad:
+        ne = n_end_from_harm(tree, int(res.density.shape[-1]))
+        if ne > USCAT_GRAD_N_END_MAX.get(tree, 0):
+            cov = ", ".join(f"{t} (n_end <= {n})" for t, n in USCAT_GRAD_N_END_MAX.items())
+            raise NotImplementedError(
+                f"uscat_grad is not built for tree {c.branching_types_expression_str!r} at n_end={ne}; covered: {cov}, "
+                "bpa and bpbpa as ba and bba; the chain trees d >= 5 and larger orders have uscat() only")
+    lib = L.load()
+    f = _field_operands(res, x, tree, perm, expand_x)
+    origin, dev, fl, plan, pts, df, flags, xshape, batch = f.origin, f.dev, f.fl, f.plan, f.pts, f.density, f.flags, f.xshape, f.batch
+    nb, B, d, P = fl.nb, fl.B, c.c_ndim, int(pts.shape[1])
     if far_field:
         flags |= L.USCAT_FAR_FIELD
     if per_ball:
@@ -1114,7 +1146,6 @@ def _field(res: Any, x: Array, *, far_field: bool, per_ball: bool, expand_x: boo
     if res.kind == "inner":
         flags |= L.USCAT_KIND_INNER
 
-    df = dens_t.expand(batch + (B, H)).reshape(nb, B, H).contiguous()
     out = torch.empty(((d,) if grad else ()) + ((P, nb, B) if per_ball else (P, nb)), dtype=torch.complex128, device=dev)
     fn, what = (lib.biem_uscat_grad, "biem_uscat_grad") if grad else (lib.biem_uscat, "biem_uscat")
     with torch.cuda.device(dev):
@@ -1135,6 +1166,97 @@ def _field(res: Any, x: Array, *, far_field: bool, per_ball: bool, expand_x: boo
         out = out[inv]
     out = out.reshape(((d,) if grad else ()) + xshape + batch + ((B,) if per_ball else ()))
     return origin.give(out)
+
+
+# --------------------------------------------------------------------------------------
+# the total field inside penetrable fluid balls (an extension)
+# --------------------------------------------------------------------------------------
+def biem_u_interior(res: Any, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
+    r"""Total field inside the penetrable fluid balls of a :func:`biem` result solved with :func:`fluid_inclusion_bc`.
+
+    ``x`` as :func:`biem_u` takes it; ``k_interior`` and ``density_ratio`` as :func:`fluid_inclusion_bc` takes them (they broadcast
+    to ``(..., B)``, real or complex).  The result has the shape and namespace of ``biem_u(res, x, expand_x=expand_x)``.  A point with
+    ``|x - c_b| < rho_b`` gets :math:`u_b(x) = \sum_h a_{b,h} j_n(k_b |x - c_b|) Y_h`, every other point NaN: exactly the complement of
+    where :func:`biem_u` is valid (a point at ``r == rho`` belongs to the exterior).  The coefficients follow algebraically from the
+    density, :math:`a = -s\,\delta_b k W / gj_n` with :math:`s` = density x blc_n and :math:`W = i / (k\rho_b)^{d-1}`: no second solve.
+
+    A ball whose ``k_interior`` is NaN is impenetrable: NaN inside it.  ``density_ratio = 0`` (the sound-soft limit) gives 0 inside.
+    A degree the ball does not scatter (``gj_n = 0``: the transparent sphere ``k_b = k, delta = 1``) leaves no trace in the density, so
+    the field inside that ball cannot be recovered from it: NaN inside, no error.
+
+    ``ValueError`` for ``kind != "outer"``, a result without density, ``k_interior * radii == 0`` and shapes that do not broadcast.
+    Built for the trees a, ba, bpa, bba, bpbpa, caa up to n_end 320 / 48 / 14 / 12 (2-D / 3-D / bba / caa) while the per-lane
+    rows fit the LDS (2-D: n_end <= 153); ``NotImplementedError`` beyond that and for the chain trees d >= 5.
+    """
+    if res.density is None:
+        raise ValueError("The BIEMResult does not have density.")
+    if res.kind != "outer":
+        raise ValueError(f"Invalid kind: {res.kind} (the interior field belongs to an exterior problem, kind='outer')")
+    c = res.c
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    ne = n_end_from_harm(tree, int(res.density.shape[-1]))
+    if ne > USCAT_GRAD_N_END_MAX.get(tree, 0):
+        cov = ", ".join(f"{t} (n_end <= {n})" for t, n in USCAT_GRAD_N_END_MAX.items())
+        raise NotImplementedError(
+            f"uinterior is not built for tree {c.branching_types_expression_str!r} at n_end={ne}; covered: {cov}, "
+            "bpa and bpbpa as ba and bba; the chain trees d >= 5 and larger orders have no interior field")
+    rs, ks, kis, dls = _shape(res.radii), _shape(res.k), _shape(k_interior), _shape(density_ratio)
+    B = rs[-1]
+    try:
+        full = np.broadcast_shapes(kis, dls, rs)
+        if full[-1] != B or len(kis) > len(ks) + 1 or len(dls) > len(ks) + 1:
+            raise ValueError
+        np.broadcast_shapes(full[:-1], ks)
+    except ValueError as e:
+        raise ValueError(
+            "Shapes of k_interior, density_ratio and the batch shape + (B,) are not broadcastable\n"
+            f"tuple(k_interior.shape)={kis}\ntuple(density_ratio.shape)={dls}\ntuple(radii.shape)={rs}\ntuple(k.shape)={ks}") from e
+    if np.any(_host_array(k_interior) * _host_array(res.radii) == 0):
+        raise ValueError("k_interior * radii must not be zero")
+
+    lib = L.load()
+    f = _field_operands(res, x, tree, perm, expand_x, extra_batch=(kis[:-1], dls[:-1]))
+    dev, fl, batch = f.dev, f.fl, f.batch
+    nb, P = fl.nb, int(f.pts.shape[1])
+    kb_t, dl_t = (_to_dev(a, dev, torch.complex128) for a in (k_interior, density_ratio))
+    fluid_b = any(s != 1 for s in tuple(kb_t.shape[:-1]) + tuple(dl_t.shape[:-1]))
+
+    def per_ball(t):                                       # [nb, B], or [1, B] shared by all systems
+        t = t.expand(tuple(torch.broadcast_shapes(tuple(t.shape), (B,))))
+        return (t.expand(batch + (B,)).reshape(nb, B) if fluid_b else t.reshape(1, B)).contiguous()
+
+    kb_f, dl_f = per_ball(kb_t), per_ball(dl_t)
+    out = torch.empty((P, nb), dtype=torch.complex128, device=dev)
+    with torch.cuda.device(dev):
+        wb = int(lib.biem_uinterior_workspace_bytes(f.plan.handle, nb, B))
+        work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+        if P > 0 and nb > 0:
+            rc = lib.biem_uinterior(f.plan.handle, nb, B, P, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
+                                    _ptr(kb_f), _ptr(dl_f), int(fluid_b), _ptr(f.density), _ptr(f.pts), f.flags, _ptr(out), _ptr(work), wb,
+                                    _stream_ptr(dev))
+            if rc == L.BIEM_ERR_UNSUPPORTED:               # a limit the table above does not know (the LDS of the per-lane rows in 2-D)
+                msg = lib.biem_last_error()
+                raise NotImplementedError(msg.decode() if msg else "biem_uinterior: not built for this size")
+            L.check(rc, "biem_uinterior")
+    return f.origin.give(out.reshape(f.xshape + batch))
+
+
+def biem_u_total(res: Any, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
+    """Total field everywhere: ``res.uin(x) + uscat(x)`` outside all balls, :func:`biem_u_interior` inside them.
+
+    Arguments, shape and namespace as :func:`biem_u_interior`.  NaN remains only inside an impenetrable ball (``k_interior`` NaN) or
+    one whose interior field cannot be recovered from the density.  ``ValueError`` if the result carries no ``uin``.
+    """
+    if res.uin is None:
+        raise ValueError("The BIEMResult does not have uin.")
+    inside = biem_u_interior(res, x, k_interior=k_interior, density_ratio=density_ratio, expand_x=expand_x)
+    outside = biem_u(res, x, expand_x=expand_x)
+    uin = res.uin(x, expand_x=expand_x)
+    if isinstance(inside, torch.Tensor):
+        uin = uin.to(inside.device) if isinstance(uin, torch.Tensor) else torch.as_tensor(np.asarray(uin), device=inside.device)
+        return torch.where(torch.isnan(inside.real), (uin + outside).to(inside.dtype), inside)
+    uin = uin.detach().cpu().numpy() if isinstance(uin, torch.Tensor) else np.asarray(uin)
+    return np.where(np.isnan(inside.real), (uin + outside).astype(inside.dtype), inside)
 
 
 # --------------------------------------------------------------------------------------

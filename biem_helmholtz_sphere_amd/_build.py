@@ -18,8 +18,8 @@ from collections import Counter
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbiem_mi355.so")
-SOURCES = ["abi.cpp", "plan.cpp", "kernels_fill.hip", "kernels_degree_bc.hip", "kernels_uscat.hip", "kernels_lu.hip"]
-HEADERS = ["common.hpp", "plan.hpp", "special.hpp", os.path.join("..", "..", "include", "biem_mi355.h")]
+SOURCES = ["abi.cpp", "plan.cpp", "kernels_fill.hip", "kernels_degree_bc.hip", "kernels_uscat.hip", "kernels_uinterior.hip", "kernels_lu.hip"]
+HEADERS = ["common.hpp", "plan.hpp", "special.hpp", "fast_layout.hpp", os.path.join("..", "..", "include", "biem_mi355.h")]
 _MARK = b"BIEM_SRC_HASH="
 
 

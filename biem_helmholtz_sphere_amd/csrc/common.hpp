@@ -111,6 +111,17 @@ int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, co
 int launch_uscat_grad(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
                       const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
                       double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
+// per-lane order ceiling of a tree (kernels_uscat.hip: kFastNendMax*; 0 for the chain trees)
+int uscat_fast_nend_max(int tree);
+// total field inside penetrable fluid balls (kernels_uinterior.hip).  d_kint / d_delta [nb or 1][B] complex; the coefficient step
+// a[s][b][h] on its own, and the field at points (out[P][nb], NaN outside every ball); workspace: the coefficients, nb B H complex
+int launch_interior_coef(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
+                         int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched, const double* d_density,
+                         double* d_a, hipStream_t st);
+int launch_uinterior(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                     const double* d_radii, int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched,
+                     const double* d_density, const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes,
+                     hipStream_t st);
 int lu_npad(int N);
 size_t lu_workspace_bytes(int nb, int n_pad, int nrhs);
 int launch_lu_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long lda, long long sys_stride, int* d_ipiv,

@@ -1,0 +1,337 @@
+// kernels_uinterior.hip -- the total field INSIDE penetrable fluid balls, gfx950.
+//   u_b(y) = sum_h a_{b,h} j_n(k_b |y - c_b|) Y_h(dir(y - c_b)),      |y - c_b| < rho_b
+// The coefficients follow algebraically from the solved density.  Row (b, h) of the system says that the regular local coefficient
+// of the exterior total field at ball b is I = -s gh_n / gj_n with s = density blc_n(rho_b) (what k_uscat_coef forms); continuity of u
+// and of (1 / density) d_n u across the sphere, with the unscaled pair alpha^_n = -k_b j_n'(k_b rho), beta^_n = delta j_n(k_b rho), gives
+//   a_{b,h} = -s delta k W(x) / gj_n,    W(x) = j_n h_n' - j_n' h_n = i / x^{d-1},    gj_n = alpha^_n j_n(x) + beta^_n k j_n'(x),    x = k rho
+// with nothing divided by j_n(k_b rho).  No second solve, no matrix, no matvec.
+#include "fast_layout.hpp"
+
+namespace biem {
+
+namespace {
+__device__ inline bool cfinite(cplx a) { return isfinite(a.x) && isfinite(a.y); }
+__device__ inline cplx cnan() { const double q = __longlong_as_double(0x7ff8000000000000LL); return make_double2(q, q); }
+constexpr double kInteriorCancel = 64.0 * 2.220446049250313e-16;   // |gj| below this fraction of its two terms: no correct digit left
+}  // namespace
+
+// a[s][b][h] = density[s][b][h] F_n,  F_n = -blc_n delta k W / gj_n: one wave per (system, ball), like k_uscat_coef.
+// The pair (alpha^_n, beta^_n) is scaled by 1 / sigma_n, sigma_n = max(|alpha^_n|, |k beta^_n|) (the scale of fluid_inclusion_bc), in gj and
+// in the numerator alike, so the quotient neither under- nor overflows while j_n(k rho) and j_n(k_b rho) are normal numbers each.
+// Not finite (k_b NaN: an impenetrable ball; gj_n = 0: a degree the ball does not scatter, whose interior field the density does not
+// determine) is written as NaN: the field kernel's sums then give NaN inside that ball.  gj_n counts as 0 when its two terms cancel to
+// rounding (kInteriorCancel): the transparent sphere k_b = k, delta = 1 leaves rounding noise there, not a value.
+__global__ void __launch_bounds__(64) k_interior_coef(int d, int H, int n_end, const int* __restrict__ deg, int B,
+                                                       const cplx* __restrict__ k, const double* __restrict__ eta,
+                                                       const double* __restrict__ radii, int geom_batched,
+                                                       const cplx* __restrict__ kint, const cplx* __restrict__ delta, int fluid_batched,
+                                                       const cplx* __restrict__ dens, cplx* __restrict__ a) {
+  __shared__ cplx sJ[kMaxRad + 3], sH[kMaxRad + 3], sJz[kMaxRad + 3];
+  __shared__ cplx sF[kMaxRad];
+  const int b = blockIdx.x, s = blockIdx.y;
+  const cplx kk = k[s];
+  const double et = eta[s];
+  const double rho = radii[(geom_batched ? (size_t)s * B : 0) + b];
+  const cplx kb = kint[(fluid_batched ? (size_t)s * B : 0) + b];
+  const cplx dl = delta[(fluid_batched ? (size_t)s * B : 0) + b];
+  if (threadIdx.x == 0) {
+    const cplx x = cscale(kk, rho), z = cscale(kb, rho);
+    const bool fluid = cfinite(z) && cfinite(dl) && (z.x != 0.0 || z.y != 0.0);
+    if (!fluid) {
+      for (int n = 0; n < n_end; ++n) sF[n] = cnan();
+    } else {
+      radial_jh(d, n_end, x, sJ, sH);          // orders 0 .. n_end (one extra for the derivative)
+      radial_jh(d, n_end, z, sJz, nullptr);
+      const cplx ix = crecip(x), iz = crecip(z);
+      double rp = 1.0; for (int q = 0; q < d - 1; ++q) rp *= rho;
+      cplx kd2 = make_double2(1.0, 0.0); for (int q = 0; q < d - 2; ++q) kd2 = cmul(kd2, kk);
+      cplx xw = make_double2(1.0, 0.0); for (int q = 0; q < d - 1; ++q) xw = cmul(xw, x);
+      const cplx ixw = crecip(xw);
+      const cplx dkw = cmul(cmul(dl, kk), make_double2(-ixw.y, ixw.x));     // delta k W,  W = i / x^{d-1}
+      for (int n = 0; n < n_end; ++n) {
+        const cplx j = sJ[n];
+        const cplx kjp = cmul(kk, csub(cscale(cmul(ix, j), (double)n), sJ[n + 1]));
+        const cplx blc = cscale(cmul(kd2, make_double2(et * j.x - kjp.y, et * j.y + kjp.x)), rp);   // as k_uscat_coef
+        const cplx jz = sJz[n];
+        const cplx kjpz = cmul(kb, csub(cscale(cmul(iz, jz), (double)n), sJz[n + 1]));              // k_b j_n'(k_b rho) = -alpha^_n
+        const cplx bj = cmul(dl, jz);                                                               // beta^_n
+        const double sg = fmax(zabs1(kjpz), zabs1(cmul(kk, bj)));
+        const double is = 1.0 / sg;
+        const cplx t1 = cmul(j, cscale(kjpz, is)), t2 = cmul(cscale(bj, is), kjp);
+        const cplx gj = csub(t2, t1);                                                               // gj_n / sigma_n
+        cplx f = cmul(cmul(blc, crecip(gj)), cscale(dkw, -is));
+        if (!(zabs1(gj) > kInteriorCancel * (zabs1(t1) + zabs1(t2))) || !cfinite(f)) f = cnan();
+        sF[n] = f;
+      }
+    }
+  }
+  __syncthreads();
+  const size_t base = ((size_t)s * B + b) * H;
+  for (int h = threadIdx.x; h < H; h += 64) {
+    cplx v = cmul(dens[base + h], sF[deg[h]]);
+    if (!cfinite(v)) v = cnan();
+    a[base + h] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The field, ONE POINT PER LANE: the skeleton of k_uscat_fast<TREE, false, true> (workgroup-uniform loop over the balls, the ball's
+// coefficients staged in LDS, j_n by radial_jh's backward recurrence into the lane's own LDS row, the harmonic recurrences of that
+// kernel), with three differences:
+//   - the argument of j_n is k_b r with the ball's own complex wavenumber;
+//   - a lane contributes only for the ball that contains its point (r < rho: exactly where k_uscat_fast masks);
+//   - a ball that holds no point of the workgroup is not staged, and a wave none of whose lanes lies in it skips its radial and
+//     harmonic loops.  Both barriers of a ball are reached by every wave or by none (the vote is workgroup-wide).
+// out[p][s]; NaN where no ball contains the point, and inside a ball with a NaN coefficient (the sums carry it) or a NaN k_b.
+// ---------------------------------------------------------------------------------------------
+template <int TREE>
+__global__ void __launch_bounds__(64) k_uinterior_fast(int d, int H, int n_end, const int* __restrict__ labels, int nb, int B, int P,
+                                                        const double* __restrict__ centers, const double* __restrict__ radii,
+                                                        int geom_batched, const cplx* __restrict__ kint, int fluid_batched,
+                                                        const cplx* __restrict__ a, const double* __restrict__ pts, int flags,
+                                                        cplx* __restrict__ out) {
+  BIEM_FAST_LAYOUT()
+  const int js = (n_end + 2) | 1;           // row stride of the per-lane j_n store (radial_jh wants n_end + 1 slots at d = 4); odd: conflict-free
+  const int s = blockIdx.y, tid = threadIdx.x, T = blockDim.x;
+  cplx* sJl = sC + nC + (size_t)tid * js;
+  const int p = blockIdx.x * T + tid, pc = p < P ? p : P - 1;
+  const bool pb = (flags & BIEM_USCAT_POINTS_BATCHED) != 0;
+  (void)ra; (void)rb; (void)cmm; (void)ga; (void)gia; (void)g0; (void)jA; (void)jB; (void)jC; (void)jN; (void)K2; (void)ms;
+  BIEM_FAST_TABLES()
+  double x[4];
+  for (int i = 0; i < d; ++i) x[i] = pb ? pts[((size_t)i * P + pc) * nb + s] : pts[(size_t)i * P + pc];
+  const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+  double tr = qnan, ti = 0.0;               // no ball contains the point
+  for (int b = 0; b < B; ++b) {
+    const double* cb = centers + ((geom_batched ? (size_t)s * B : 0) + b) * d;
+    const double rho = radii[(geom_batched ? (size_t)s * B : 0) + b];
+    double u[4] = {0.0, 0.0, 0.0, 0.0}, r2 = 0.0;
+    for (int i = 0; i < d; ++i) { u[i] = x[i] - cb[i]; r2 += u[i] * u[i]; }
+    const double r = sqrt(r2);
+    const bool in = p < P && r < rho;
+    // (a barrier: the previous ball's coefficients are no longer read, and the tables are written)
+    if (!__syncthreads_or(in ? 1 : 0)) continue;
+    const cplx* cs = a + ((size_t)s * B + b) * H;
+    BIEM_FAST_STAGE()
+    __syncthreads();
+    if (__ballot(in) == 0ull) continue;     // (after both barriers)
+    if (in) {
+      const cplx kb = kint[(fluid_batched ? (size_t)s * B : 0) + b];
+      double ar = qnan, ai = 0.0;
+      if (isfinite(kb.x) && isfinite(kb.y)) {
+        if (r > 0.0) radial_jh(d, n_end - 1, cscale(kb, r), (zc*)sJl, nullptr);
+        else {                                // centre of the ball: z_n(0) = delta_{n0} sqrt(pi/2) 2^{1-d/2} / Gamma(d/2)
+          const double z0 = radial_z0_at_zero(d);
+          for (int n = 0; n < n_end; ++n) sJl[n] = make_double2(n == 0 ? z0 : 0.0, 0.0);
+        }
+        ar = 0.0;
+        if (TREE == TREE_A) {
+          // Y_m = e^{i m theta} / sqrt(2 pi); degree n = |m|
+          const double e1x = r > 0.0 ? u[0] / r : 1.0, e1y = r > 0.0 ? u[1] / r : 0.0;
+          double ex = 1.0, ey = 0.0;
+          for (int n = 0; n < n_end; ++n) {
+            const cplx cp = sC[n_end - 1 + n];
+            cplx t = make_double2(cp.x * ex - cp.y * ey, cp.x * ey + cp.y * ex);
+            if (n > 0) { const cplx cn = sC[n_end - 1 - n]; t.x += cn.x * ex + cn.y * ey; t.y += cn.y * ex - cn.x * ey; }
+            const cplx hv = sJl[n];
+            ar += hv.x * t.x - hv.y * t.y; ai += hv.x * t.y + hv.y * t.x;
+            const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx;
+          }
+        } else if (TREE == TREE_BBA) {
+          // Y_{n l m} = s0^l g_{n-l}^{(l+1)}(c0) Pbar_l^{|m|}(c1) e^{i m phi} / sqrt(2 pi)
+          const double rho2 = sqrt(u[2] * u[2] + u[3] * u[3]), rho1 = sqrt(u[1] * u[1] + rho2 * rho2);
+          const double c0 = r > 0.0 ? u[0] / r : 1.0, s0 = r > 0.0 ? rho1 / r : 0.0;
+          const double c1 = rho1 > 0.0 ? u[1] / rho1 : 1.0, s1 = rho1 > 0.0 ? rho2 / rho1 : 0.0;
+          const double e1x = rho2 > 0.0 ? u[2] / rho2 : 1.0, e1y = rho2 > 0.0 ? u[3] / rho2 : 0.0;
+          const int mstride = 2 * n_end - 1;
+          double ex = 1.0, ey = 0.0, pmm = 0.70710678118654752440, s0m = 1.0;
+          for (int m = 0; m < n_end; ++m) {
+            if (m > 0) {
+              pmm *= cmm[m] * s1; s0m *= s0;
+              const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx;
+            }
+            double p0 = 0.0, p1 = pmm, sl = s0m;
+            double sr = 0.0, si = 0.0, qr = 0.0, qi = 0.0;
+            for (int l = m; l < n_end; ++l) {
+              double gp0 = 0.0, gp1 = g0[l];
+              const double alm = sl * p1;
+              for (int n = l; n < n_end; ++n) {
+                const double amp = alm * gp1;
+                const cplx hv = sJl[n];
+                const double wr = hv.x * amp, wi = hv.y * amp;
+                const cplx* cc = sC + (n * n_end + l) * mstride + n_end - 1;
+                const cplx cp = cc[m];
+                sr += wr * cp.x - wi * cp.y; si += wr * cp.y + wi * cp.x;
+                if (m > 0) { const cplx cn = cc[-m]; qr += wr * cn.x - wi * cn.y; qi += wr * cn.y + wi * cn.x; }
+                const int q = n - l + 1;
+                if (n + 1 < n_end) {
+                  const double gp2 = (c0 * gp1 - ga[l * n_end + q - 1] * gp0) * gia[l * n_end + q];
+                  gp0 = gp1; gp1 = gp2;
+                }
+              }
+              const int ql = l + 1;
+              if (ql < n_end) {
+                const double p2 = ra[ql * n_end + m] * (c1 * p1 - rb[ql * n_end + m] * p0);
+                p0 = p1; p1 = p2;
+                sl *= s0;
+              }
+            }
+            ar += sr * ex - si * ey + qr * ex + qi * ey;
+            ai += sr * ey + si * ex + qi * ex - qr * ey;
+          }
+        } else if (TREE == TREE_CAA) {
+          // Y_{n m1 m2} = cos^a sin^b Pbar_k^{(b,a)}(cos 2 t0) e^{i (m1 t1 + m2 t2)} / (2 pi), a = |m1|, b = |m2|, n = a + b + 2 k
+          const double r01 = sqrt(u[0] * u[0] + u[1] * u[1]), r23 = sqrt(u[2] * u[2] + u[3] * u[3]);
+          const double c0 = r > 0.0 ? r01 / r : 1.0, s0 = r > 0.0 ? r23 / r : 0.0, xx = c0 * c0 - s0 * s0;
+          const double e1x = r01 > 0.0 ? u[0] / r01 : 1.0, e1y = r01 > 0.0 ? u[1] / r01 : 0.0;
+          const double e2x = r23 > 0.0 ? u[2] / r23 : 1.0, e2y = r23 > 0.0 ? u[3] / r23 : 0.0;
+          double ca = 1.0, eax = 1.0, eay = 0.0;
+          for (int aa = 0; aa < n_end; ++aa) {
+            if (aa > 0) {
+              ca *= c0;
+              const double nx = eax * e1x - eay * e1y; eay = eax * e1y + eay * e1x; eax = nx;
+            }
+            double sb = 1.0, ebx = 1.0, eby = 0.0;
+            for (int bq = 0; aa + bq < n_end; ++bq) {
+              if (bq > 0) {
+                sb *= s0;
+                const double nx = ebx * e2x - eby * e2y; eby = ebx * e2y + eby * e2x; ebx = nx;
+              }
+              const int tb = (aa * n_end + bq) * K2;
+              const double amp0 = ca * sb;
+              double p0 = 0.0, p1 = 1.0;
+              double ppr = 0.0, ppi = 0.0, mpr = 0.0, mpi = 0.0, pmr = 0.0, pmi = 0.0, mmr = 0.0, mmi = 0.0;   // sums of the (+-a, +-b) coefficients
+              for (int kq = 0, n = aa + bq; n < n_end; ++kq, n += 2) {
+                const cplx hv = sJl[n];
+                const double amp = amp0 * jN[tb + kq] * p1;
+                const double wr = hv.x * amp, wi = hv.y * amp;
+                const cplx* cc = sC + (n * ms + n_end - 1) * ms + n_end - 1;
+                { const cplx cv = cc[aa * ms + bq]; ppr += wr * cv.x - wi * cv.y; ppi += wr * cv.y + wi * cv.x; }
+                if (aa > 0) { const cplx cv = cc[-aa * ms + bq]; mpr += wr * cv.x - wi * cv.y; mpi += wr * cv.y + wi * cv.x; }
+                if (bq > 0) { const cplx cv = cc[aa * ms - bq]; pmr += wr * cv.x - wi * cv.y; pmi += wr * cv.y + wi * cv.x; }
+                if (aa > 0 && bq > 0) { const cplx cv = cc[-aa * ms - bq]; mmr += wr * cv.x - wi * cv.y; mmi += wr * cv.y + wi * cv.x; }
+                if (n + 2 < n_end) {
+                  const double p2 = (jA[tb + kq] * xx + jB[tb + kq]) * p1 - jC[tb + kq] * p0;
+                  p0 = p1; p1 = p2;
+                }
+              }
+              const double fx = eax * ebx - eay * eby, fy = eax * eby + eay * ebx;     // e^{i (a t1 + b t2)}
+              const double gx = eax * ebx + eay * eby, gy = eax * eby - eay * ebx;     // e^{i (-a t1 + b t2)}
+              ar += ppr * fx - ppi * fy + mmr * fx + mmi * fy + mpr * gx - mpi * gy + pmr * gx + pmi * gy;
+              ai += ppr * fy + ppi * fx + mmi * fx - mmr * fy + mpr * gy + mpi * gx + pmi * gx - pmr * gy;
+            }
+          }
+          ar *= kInvSqrt2Pi; ai *= kInvSqrt2Pi;   // (the second 1 / sqrt(2 pi) below)
+        } else {
+          // ba: Y_{n m} = Pbar_n^{|m|}(c0) e^{i m phi} / sqrt(2 pi)
+          const double rxy = sqrt(u[1] * u[1] + u[2] * u[2]);
+          const double c0 = r > 0.0 ? u[0] / r : 1.0, s0 = r > 0.0 ? rxy / r : 0.0;
+          const double e1x = rxy > 0.0 ? u[1] / rxy : 1.0, e1y = rxy > 0.0 ? u[2] / rxy : 0.0;
+          double ex = 1.0, ey = 0.0, pmm = 0.70710678118654752440;
+          for (int m = 0; m < n_end; ++m) {
+            if (m > 0) {
+              pmm *= cmm[m] * s0;
+              const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx;
+            }
+            double p0 = 0.0, p1 = pmm;
+            double sr = 0.0, si = 0.0;         // sum over n of j_n Pbar_n^m a_{n, +-m} (the e^{+- i m phi} factors applied once per m)
+            double qr = 0.0, qi = 0.0;
+            for (int n = m; n < n_end; ++n) {
+              const cplx cp = sC[n * n + n + m];
+              const cplx hv = sJl[n];
+              const double wr = hv.x * p1, wi = hv.y * p1;
+              sr += wr * cp.x - wi * cp.y; si += wr * cp.y + wi * cp.x;
+              if (m > 0) { const cplx cn = sC[n * n + n - m]; qr += wr * cn.x - wi * cn.y; qi += wr * cn.y + wi * cn.x; }
+              const int q = n + 1;
+              if (q < n_end) {
+                const double p2 = ra[q * n_end + m] * (c0 * p1 - rb[q * n_end + m] * p0);
+                p0 = p1; p1 = p2;
+              }
+            }
+            ar += sr * ex - si * ey + qr * ex + qi * ey;
+            ai += sr * ey + si * ex + qi * ex - qr * ey;
+          }
+        }
+        ar *= kInvSqrt2Pi; ai *= kInvSqrt2Pi;
+        if (!(isfinite(ar) && isfinite(ai))) { ar = qnan; ai = 0.0; }
+      }
+      tr = ar; ti = ai;
+    }
+  }
+  if (p < P) out[(size_t)p * nb + s] = make_double2(tr, ti);
+}
+
+namespace {
+// what the per-lane kernel covers: 0 and a message otherwise
+int interior_cap(const biem_plan* p, const char* who) {
+  const int cap = uscat_fast_nend_max(p->tree);
+  if (cap == 0) {
+    set_error("%s: built for the trees a, ba (bpa), bba (bpbpa) and caa; chain trees (d=%d) are not covered", who, p->d);
+    return 0;
+  }
+  if (p->n_end > cap) {
+    set_error("%s: n_end=%d above the per-lane ceiling %d of this tree (a %d, ba %d, bba %d, caa %d)", who, p->n_end, cap,
+              uscat_fast_nend_max(TREE_A), uscat_fast_nend_max(TREE_BA), uscat_fast_nend_max(TREE_BBA), uscat_fast_nend_max(TREE_CAA));
+    return 0;
+  }
+  return cap;
+}
+}  // namespace
+
+int launch_interior_coef(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
+                         int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched, const double* d_density,
+                         double* d_a, hipStream_t st) {
+  static_assert(kMaxRad >= 320, "the coefficient kernel's LDS tables hold every per-lane order");
+  if (!interior_cap(p, "biem_interior_coef")) return BIEM_ERR_UNSUPPORTED;
+  if (nb > 65535) { set_error("biem_interior_coef: more than 65535 systems in one call (%d)", nb); return BIEM_ERR_UNSUPPORTED; }
+  if (nb <= 0 || B <= 0) return BIEM_OK;
+  hipLaunchKernelGGL(k_interior_coef, dim3(B, nb), dim3(64), 0, st, p->d, p->H, p->n_end, p->d_deg, B, (const cplx*)d_k, d_eta, d_radii,
+                     geom_batched, (const cplx*)d_kint, (const cplx*)d_delta, fluid_batched, (const cplx*)d_density, (cplx*)d_a);
+  BIEM_LAUNCHCHK();
+  return BIEM_OK;
+}
+
+int launch_uinterior(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                     const double* d_radii, int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched,
+                     const double* d_density, const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes,
+                     hipStream_t st) {
+  if (flags & ~BIEM_USCAT_POINTS_BATCHED) {
+    set_error("biem_uinterior: flags=%d; only BIEM_USCAT_POINTS_BATCHED applies to the interior field", flags); return BIEM_ERR_ARG;
+  }
+  if (!interior_cap(p, "biem_uinterior")) return BIEM_ERR_UNSUPPORTED;
+  if (nb > 65535) { set_error("biem_uinterior: more than 65535 systems in one call (%d)", nb); return BIEM_ERR_UNSUPPORTED; }
+  const int ne = p->n_end, ms = 2 * ne - 1, T = 64;
+  size_t tab = 0, nC = 0;                 // doubles of tables, complex of coefficients (BIEM_FAST_LAYOUT)
+  if (p->tree == TREE_BA) { tab = (size_t)2 * ne * ne + ((ne + 1) & ~1); nC = (size_t)ne * ne; }
+  else if (p->tree == TREE_BBA) { tab = (size_t)4 * ne * ne + 2 * ((ne + 1) & ~1); nC = (size_t)ne * ne * ms; }
+  else if (p->tree == TREE_CAA) { tab = (size_t)4 * ne * ne * ((ne + 1) / 2); nC = (size_t)ne * ms * ms; }
+  else nC = (size_t)ms;
+  const size_t shm = tab * sizeof(double) + (nC + (size_t)T * ((ne + 2) | 1)) * sizeof(cplx);
+  if (shm > 160 * 1024) {
+    set_error("biem_uinterior: n_end=%d needs %zu bytes of LDS per workgroup (limit %d)", ne, shm, 160 * 1024);
+    return BIEM_ERR_UNSUPPORTED;
+  }
+  if (nb <= 0 || B <= 0 || P <= 0) return BIEM_OK;
+  const size_t need = (size_t)nb * B * p->H * sizeof(cplx);
+  if (work_bytes < need) { set_error("biem_uinterior: workspace too small"); return BIEM_ERR_ARG; }
+  cplx* a = (cplx*)d_work;
+  const int rc = launch_interior_coef(p, nb, B, d_k, d_eta, d_radii, geom_batched, d_kint, d_delta, fluid_batched, d_density,
+                                      (double*)a, st);
+  if (rc != BIEM_OK) return rc;
+#define BIEM_UINTERIOR(TREE)                                                                                                     \
+  {                                                                                                                              \
+    BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_uinterior_fast<TREE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
+    hipLaunchKernelGGL((k_uinterior_fast<TREE>), dim3((P + T - 1) / T, nb), dim3(T), shm, st, p->d, p->H, ne, p->d_labels, nb, B, P, \
+                       d_centers, d_radii, geom_batched, (const cplx*)d_kint, fluid_batched, (const cplx*)a, d_points, flags,    \
+                       (cplx*)d_out);                                                                                            \
+  }
+  if (p->tree == TREE_BA) BIEM_UINTERIOR(TREE_BA)
+  else if (p->tree == TREE_BBA) BIEM_UINTERIOR(TREE_BBA)
+  else if (p->tree == TREE_CAA) BIEM_UINTERIOR(TREE_CAA)
+  else BIEM_UINTERIOR(TREE_A)
+#undef BIEM_UINTERIOR
+  BIEM_LAUNCHCHK();
+  return BIEM_OK;
+}
+
+}  // namespace biem

@@ -220,6 +220,27 @@ int biem_uscat_grad(const biem_plan* plan, int nb, int B, int P, const double* d
                     const double* d_centers, const double* d_radii, int geom_batched, const double* d_density,
                     const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- total field inside penetrable fluid balls ----
+ * Ball b holds a fluid of wavenumber d_kint[b] and density d_delta[b] times the exterior's (what fluid_inclusion_bc takes; both
+ * complex128, [nb][B] when fluid_batched != 0, else [B] shared by all systems).  With s = density blc_n the interior field is
+ *   u_b(y) = sum_h a[b][h] j_n(k_b |y - c_b|) Y_h,   a = -s delta k W / gj_n,   W = i / (k rho)^{d-1},
+ *   gj_n = alpha_n j_n(k rho) + beta_n k j_n'(k rho),   alpha_n = -k_b j_n'(k_b rho),   beta_n = delta j_n(k_b rho):
+ * algebra on the solved density, no second solve.  biem_interior_coef writes the coefficients alone.  An entry that is not finite
+ * (k_b NaN: an impenetrable ball; gj_n = 0 to rounding: a degree the ball does not scatter) is written as NaN.
+ * biem_uinterior: d_points as biem_uscat; out[P][nb] complex128 = u_b where |y - c_b| < rho_b (the points biem_uscat masks), NaN at
+ * every other point and inside a ball with a NaN coefficient.  flags: BIEM_USCAT_POINTS_BATCHED only, any other is BIEM_ERR_ARG.
+ * Workspace: biem_uinterior_workspace_bytes (holds a).  Covered: trees a, ba, bba, caa up to the per-lane orders (n_end <= 320, 48,
+ * 14, 12) while a workgroup's 64 rows of n_end + 2 radial values fit the LDS (tree a: n_end <= 153); chain trees, larger orders
+ * and more than 65535 systems are BIEM_ERR_UNSUPPORTED with a message. */
+int biem_interior_coef(const biem_plan* plan, int nb, int B, const double* d_k /*c128*/, const double* d_eta, const double* d_radii,
+                       int geom_batched, const double* d_kint /*[nb or 1][B] c128*/, const double* d_delta /*c128*/,
+                       int fluid_batched, const double* d_density, double* d_a /*[nb][B][H] c128*/, void* stream);
+size_t biem_uinterior_workspace_bytes(const biem_plan* plan, int nb, int B);
+int biem_uinterior(const biem_plan* plan, int nb, int B, int P, const double* d_k /*c128*/, const double* d_eta,
+                   const double* d_centers, const double* d_radii, int geom_batched, const double* d_kint /*[nb or 1][B] c128*/,
+                   const double* d_delta /*c128*/, int fluid_batched, const double* d_density, const double* d_points, int flags,
+                   double* d_out /*[P][nb]*/, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- one call for the whole path: ball tables + fill (equilibrated) + LU + density, systems processed in
  *      chunks of `chunk` resident matrices (0 = choose); every system is factored once for its nrhs right-hand sides.
  *      d_g [nb][nrhs][B][Q] as in biem_rhs_project, d_density [nb][nrhs][B][H]. ---- */
