@@ -17,7 +17,9 @@ from ._biem import (
     biem_u,
     biem_u_grad,
     biem_u_interior,
+    biem_u_interior_grad,
     biem_u_total,
+    biem_u_total_grad,
     fluid_inclusion_bc,
     max_memory,
     max_n_end,
@@ -37,7 +39,9 @@ __all__ = [
     "biem_u",
     "biem_u_grad",
     "biem_u_interior",
+    "biem_u_interior_grad",
     "biem_u_total",
+    "biem_u_total_grad",
     "fluid_inclusion_bc",
     "max_memory",
     "max_n_end",

@@ -37,7 +37,8 @@ Array = Any
 
 __all__ = [
     "BIEMFactorization", "BIEMKwargs", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
-    "biem_factorize", "biem_u", "biem_u_interior", "biem_u_total", "fluid_inclusion_bc", "max_memory", "max_n_end", "plane_wave", "point_source",
+    "biem_factorize", "biem_u", "biem_u_interior", "biem_u_interior_grad", "biem_u_total", "biem_u_total_grad", "fluid_inclusion_bc",
+    "max_memory", "max_n_end", "plane_wave", "point_source",
 ]
 
 
@@ -459,6 +460,15 @@ class BIEMResultCalculator:
     def utotal(self, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
         """Total field inside and outside penetrable fluid balls (see :func:`biem_u_total`)."""
         return biem_u_total(self, x, k_interior=k_interior, density_ratio=density_ratio, expand_x=expand_x)
+
+    def uinterior_grad(self, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
+        """Gradient of the field inside penetrable fluid balls, component axis first (see :func:`biem_u_interior_grad`)."""
+        return biem_u_interior_grad(self, x, k_interior=k_interior, density_ratio=density_ratio, expand_x=expand_x)
+
+    def utotal_grad(self, x: Array, /, *, k_interior: Array, density_ratio: Array, uin_grad: Callable[[Array], Array],
+                    expand_x: bool = True) -> Array:
+        """Gradient of the total field inside and outside penetrable fluid balls (see :func:`biem_u_total_grad`)."""
+        return biem_u_total_grad(self, x, k_interior=k_interior, density_ratio=density_ratio, uin_grad=uin_grad, expand_x=expand_x)
 
 
 # --------------------------------------------------------------------------------------
@@ -1063,7 +1073,7 @@ def biem_u_grad(res: Any, x: Array, /, per_ball: bool = False, expand_x: bool = 
 
 @dataclass
 class _FieldOperands:
-    """The flattened device operands of one field evaluation (biem_u, biem_u_grad, biem_u_interior)."""
+    """The flattened device operands of one field evaluation (biem_u, biem_u_grad, biem_u_interior, biem_u_interior_grad)."""
 
     origin: _Origin
     dev: torch.device
@@ -1188,6 +1198,12 @@ def biem_u_interior(res: Any, x: Array, /, *, k_interior: Array, density_ratio: 
     Built for the trees a, ba, bpa, bba, bpbpa, caa up to n_end 320 / 48 / 14 / 12 (2-D / 3-D / bba / caa) while the per-lane
     rows fit the LDS (2-D: n_end <= 153); ``NotImplementedError`` beyond that and for the chain trees d >= 5.
     """
+    return _interior(res, x, k_interior, density_ratio, expand_x, grad=False)
+
+
+def _interior(res: Any, x: Array, k_interior: Array, density_ratio: Array, expand_x: bool, *, grad: bool) -> Array:
+    """biem_u_interior (grad=False) and biem_u_interior_grad (grad=True): one set of checks and operands, two library entries."""
+    what = "uinterior_grad" if grad else "uinterior"
     if res.density is None:
         raise ValueError("The BIEMResult does not have density.")
     if res.kind != "outer":
@@ -1198,7 +1214,7 @@ def biem_u_interior(res: Any, x: Array, /, *, k_interior: Array, density_ratio: 
     if ne > USCAT_GRAD_N_END_MAX.get(tree, 0):
         cov = ", ".join(f"{t} (n_end <= {n})" for t, n in USCAT_GRAD_N_END_MAX.items())
         raise NotImplementedError(
-            f"uinterior is not built for tree {c.branching_types_expression_str!r} at n_end={ne}; covered: {cov}, "
+            f"{what} is not built for tree {c.branching_types_expression_str!r} at n_end={ne}; covered: {cov}, "
             "bpa and bpbpa as ba and bba; the chain trees d >= 5 and larger orders have no interior field")
     rs, ks, kis, dls = _shape(res.radii), _shape(res.k), _shape(k_interior), _shape(density_ratio)
     B = rs[-1]
@@ -1226,19 +1242,43 @@ def biem_u_interior(res: Any, x: Array, /, *, k_interior: Array, density_ratio: 
         return (t.expand(batch + (B,)).reshape(nb, B) if fluid_b else t.reshape(1, B)).contiguous()
 
     kb_f, dl_f = per_ball(kb_t), per_ball(dl_t)
-    out = torch.empty((P, nb), dtype=torch.complex128, device=dev)
+    d = c.c_ndim
+    out = torch.empty(((d,) if grad else ()) + (P, nb), dtype=torch.complex128, device=dev)
+    fn, entry = (lib.biem_uinterior_grad, "biem_uinterior_grad") if grad else (lib.biem_uinterior, "biem_uinterior")
     with torch.cuda.device(dev):
         wb = int(lib.biem_uinterior_workspace_bytes(f.plan.handle, nb, B))
         work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
         if P > 0 and nb > 0:
-            rc = lib.biem_uinterior(f.plan.handle, nb, B, P, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
-                                    _ptr(kb_f), _ptr(dl_f), int(fluid_b), _ptr(f.density), _ptr(f.pts), f.flags, _ptr(out), _ptr(work), wb,
-                                    _stream_ptr(dev))
+            rc = fn(f.plan.handle, nb, B, P, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
+                    _ptr(kb_f), _ptr(dl_f), int(fluid_b), _ptr(f.density), _ptr(f.pts), f.flags, _ptr(out), _ptr(work), wb,
+                    _stream_ptr(dev))
             if rc == L.BIEM_ERR_UNSUPPORTED:               # a limit the table above does not know (the LDS of the per-lane rows in 2-D)
                 msg = lib.biem_last_error()
-                raise NotImplementedError(msg.decode() if msg else "biem_uinterior: not built for this size")
-            L.check(rc, "biem_uinterior")
-    return f.origin.give(out.reshape(f.xshape + batch))
+                raise NotImplementedError(msg.decode() if msg else f"{entry}: not built for this size")
+            L.check(rc, entry)
+    if grad and list(perm) != list(range(d)):
+        # the kernel's components are along the canonical axes y_i = x_{perm[i]}: hand them back along the caller's (as _field does)
+        inv = [0] * d
+        for i, q in enumerate(perm):
+            inv[q] = i
+        out = out[inv]
+    return f.origin.give(out.reshape(((d,) if grad else ()) + f.xshape + batch))
+
+
+def biem_u_interior_grad(res: Any, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
+    r"""Cartesian gradient of the field inside the penetrable fluid balls, component axis first.
+
+    Arguments, checks, broadcasting and namespace as :func:`biem_u_interior`; shape ``(c_ndim, ...(x), ...(first))`` like
+    :func:`biem_u_grad`, components in the caller's axis order for every tree.  Inside ball ``b`` it is the term-by-term gradient of
+    the series of :func:`biem_u_interior`, :math:`\nabla (j_n Y_h) = -k_b j_{n+1}(k_b r) Y_h e + (j_n(k_b r) / r) (\nabla S_h)(e)`
+    with the solid harmonic :math:`S_h`, a form that never divides by a sine: the centre of a ball and points on the axes of the
+    coordinate tree are ordinary points.  NaN in every component exactly where :func:`biem_u_interior` is NaN (a point in no ball,
+    an impenetrable ball, a ball whose interior field the density does not determine); ``density_ratio = 0`` gives exactly 0.
+
+    Built for the trees a, ba, bpa, bba, bpbpa, caa up to n_end 320 / 48 / 14 / 12 (2-D / 3-D / bba / caa) while the per-lane
+    rows fit the LDS (2-D: n_end <= 152); ``NotImplementedError`` beyond that and for the chain trees d >= 5.
+    """
+    return _interior(res, x, k_interior, density_ratio, expand_x, grad=True)
 
 
 def biem_u_total(res: Any, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
@@ -1252,6 +1292,33 @@ def biem_u_total(res: Any, x: Array, /, *, k_interior: Array, density_ratio: Arr
     inside = biem_u_interior(res, x, k_interior=k_interior, density_ratio=density_ratio, expand_x=expand_x)
     outside = biem_u(res, x, expand_x=expand_x)
     uin = res.uin(x, expand_x=expand_x)
+    if isinstance(inside, torch.Tensor):
+        uin = uin.to(inside.device) if isinstance(uin, torch.Tensor) else torch.as_tensor(np.asarray(uin), device=inside.device)
+        return torch.where(torch.isnan(inside.real), (uin + outside).to(inside.dtype), inside)
+    uin = uin.detach().cpu().numpy() if isinstance(uin, torch.Tensor) else np.asarray(uin)
+    return np.where(np.isnan(inside.real), (uin + outside).astype(inside.dtype), inside)
+
+
+def biem_u_total_grad(res: Any, x: Array, /, *, k_interior: Array, density_ratio: Array, uin_grad: Callable[[Array], Array],
+                      expand_x: bool = True) -> Array:
+    """Gradient of the total field everywhere: ``uin_grad(x) + uscat_grad(x)`` outside all balls, :func:`biem_u_interior_grad` inside.
+
+    Arguments, shape and namespace as :func:`biem_u_interior_grad`.  The result record keeps no gradient of the incident field, so
+    ``uin_grad`` - the callable :func:`biem` took - is a required keyword; for ``expand_x=True`` it is called with ``x`` extended by
+    the trailing singleton batch axes that ``res.uin`` adds.  NaN remains only inside an impenetrable ball (``k_interior`` NaN) or
+    one whose interior field cannot be recovered from the density.
+
+    Across a surface the tangential components are continuous, while the normal component jumps by the factor ``density_ratio``:
+    the transmission condition is continuity of ``(1 / density) d_n u``, so ``d_n u_interior = density_ratio * d_n u_exterior``.
+    That is physics, not an error of the evaluation.
+    """
+    inside = biem_u_interior_grad(res, x, k_interior=k_interior, density_ratio=density_ratio, expand_x=expand_x)
+    outside = biem_u_grad(res, x, expand_x=expand_x)
+    if expand_x:
+        if isinstance(x, (list, tuple)):
+            x = np.stack([np.asarray(v) for v in x], 0) if not isinstance(x[0], torch.Tensor) else torch.stack(list(x), 0)
+        x = x[(...,) + (None,) * len(_shape(res.k))]
+    uin = uin_grad(x)
     if isinstance(inside, torch.Tensor):
         uin = uin.to(inside.device) if isinstance(uin, torch.Tensor) else torch.as_tensor(np.asarray(uin), device=inside.device)
         return torch.where(torch.isnan(inside.real), (uin + outside).to(inside.dtype), inside)

@@ -59,6 +59,7 @@ SIGNATURES = {
     "biem_interior_coef": (_i, [_vp, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _vp]),
     "biem_uinterior_workspace_bytes": (_sz, [_vp, _i, _i]),
     "biem_uinterior": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _i, _dp, _vp, _sz, _vp]),
+    "biem_uinterior_grad": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _i, _dp, _vp, _sz, _vp]),
     "biem_solve_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "biem_solve": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_ldlt": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _ip, _i, _vp, _sz, _vp]),

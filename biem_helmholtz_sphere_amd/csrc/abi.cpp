@@ -336,6 +336,17 @@ int biem_uinterior(const biem_plan* plan, int nb, int B, int P, const double* d_
                           d_points, flags, d_out, d_work, work_bytes, (hipStream_t)stream);
 }
 
+int biem_uinterior_grad(const biem_plan* plan, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                        const double* d_radii, int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched,
+                        const double* d_density, const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes,
+                        void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_eta, "d_eta"); NEED(d_centers, "d_centers"); NEED(d_radii, "d_radii");
+  NEED(d_kint, "d_kint"); NEED(d_delta, "d_delta"); NEED(d_density, "d_density"); NEED(d_points, "d_points"); NEED(d_out, "d_out");
+  NEED(d_work, "d_work");
+  return launch_uinterior_grad(plan, nb, B, P, d_k, d_eta, d_centers, d_radii, geom_batched, d_kint, d_delta, fluid_batched, d_density,
+                               d_points, flags, d_out, d_work, work_bytes, (hipStream_t)stream);
+}
+
 // ---- whole path -----------------------------------------------------------------------------
 namespace {
 struct SolveLayout {

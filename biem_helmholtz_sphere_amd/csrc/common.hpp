@@ -34,6 +34,17 @@ __host__ __device__ inline cplx crecip(cplx a) {
   }
 }
 __host__ __device__ inline cplx cdiv(cplx a, cplx b) { return cmul(a, crecip(b)); }
+// accumulating forms of the gradient kernels (BIEM_GRAD_HARMONICS, fast_layout.hpp)
+__device__ __forceinline__ void cacc(cplx& acc, const cplx& a, const cplx& b) {           // acc += a b
+  acc.x += a.x * b.x - a.y * b.y; acc.y += a.x * b.y + a.y * b.x;
+}
+__device__ __forceinline__ void cacc_conj(cplx& acc, const cplx& a, const cplx& b) {          // acc += a conj(b)
+  acc.x += a.x * b.x + a.y * b.y; acc.y += a.y * b.x - a.x * b.y;
+}
+__device__ __forceinline__ void cacc_real(cplx& acc, const cplx& a, double s) { acc.x += a.x * s; acc.y += a.y * s; }
+__device__ __forceinline__ cplx cmulc(const cplx& a, const cplx& b) {                     // a conj(b)
+  return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
+}
 
 #define BIEM_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { biem::set_error("%s failed: %s", #x, hipGetErrorString(e_)); return BIEM_ERR_HIP; } } while (0)
 #define BIEM_LAUNCHCHK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { biem::set_error("kernel launch failed at %s:%d: %s", __FILE__, __LINE__, hipGetErrorString(e_)); return BIEM_ERR_HIP; } } while (0)
@@ -122,6 +133,11 @@ int launch_uinterior(const biem_plan* p, int nb, int B, int P, const double* d_k
                      const double* d_radii, int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched,
                      const double* d_density, const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes,
                      hipStream_t st);
+// its Cartesian gradient, out[d][P][nb] in the plan's axes: the arguments and the workspace of launch_uinterior
+int launch_uinterior_grad(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                          const double* d_radii, int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched,
+                          const double* d_density, const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes,
+                          hipStream_t st);
 int lu_npad(int N);
 size_t lu_workspace_bytes(int nb, int n_pad, int nrhs);
 int launch_lu_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long lda, long long sys_stride, int* d_ipiv,

@@ -1,4 +1,4 @@
-// kernels_uinterior.hip -- the total field INSIDE penetrable fluid balls, gfx950.
+// kernels_uinterior.hip -- the total field INSIDE penetrable fluid balls and its gradient (5e), gfx950.
 //   u_b(y) = sum_h a_{b,h} j_n(k_b |y - c_b|) Y_h(dir(y - c_b)),      |y - c_b| < rho_b
 // The coefficients follow algebraically from the solved density.  Row (b, h) of the system says that the regular local coefficient
 // of the exterior total field at ball b is I = -s gh_n / gj_n with s = density blc_n(rho_b) (what k_uscat_coef forms); continuity of u
@@ -261,6 +261,80 @@ __global__ void __launch_bounds__(64) k_uinterior_fast(int d, int H, int n_end, 
   if (p < P) out[(size_t)p * nb + s] = make_double2(tr, ti);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The gradient of that field, ONE POINT PER LANE: the skeleton of k_uinterior_fast (containment vote, staging only the
+// balls that hold a point of the workgroup, both barriers reached by every wave or by none) around the harmonic loops of
+// k_uscat_grad_fast<TREE, true> (BIEM_GRAD_HARMONICS: the solid-harmonic form, which never divides by a sine, so the centre of a ball
+// and the axes of the tree are ordinary points).  The radial weights carry the ball's own complex wavenumber,
+//   alpha_n = -k_b j_{n+1}(k_b r),   beta_n = j_n(k_b r) / r,
+// from j_0 .. j_{n_end} in the lane's LDS row; at r = 0 only j_1 / r -> k_b z_0(0) / d survives and alpha = 0.
+// out[i][p][s], component i in the plan's (canonical) axes; NaN in every component wherever k_uinterior_fast writes NaN: a NaN
+// coefficient enters at least one of the d sums, and one sum that is not finite poisons all components of that ball.
+// ---------------------------------------------------------------------------------------------
+template <int TREE>
+__global__ void __launch_bounds__(64) k_uinterior_grad_fast(int d, int H, int n_end, const int* __restrict__ labels, int nb, int B, int P,
+                                                             const double* __restrict__ centers, const double* __restrict__ radii,
+                                                             int geom_batched, const cplx* __restrict__ kint, int fluid_batched,
+                                                             const cplx* __restrict__ a, const double* __restrict__ pts, int flags,
+                                                             cplx* __restrict__ out) {
+  constexpr int D = TREE == TREE_A ? 2 : TREE == TREE_BA ? 3 : 4;   // = d (a compile-time extent keeps x, e, g in registers)
+  BIEM_FAST_LAYOUT()
+  const int js = (n_end + 3) | 1;           // j_0 .. j_{n_end} per lane (radial_jh wants n_end + 2 slots at d = 4); odd: conflict-free
+  const int s = blockIdx.y, tid = threadIdx.x, T = blockDim.x;
+  cplx* sJl = sC + nC + (size_t)tid * js;
+  const int p = blockIdx.x * T + tid, pc = p < P ? p : P - 1;
+  const bool pb = (flags & BIEM_USCAT_POINTS_BATCHED) != 0;
+  const size_t cstride = (size_t)P * nb;    // between the components of the output
+  (void)d; (void)ra; (void)rb; (void)cmm; (void)ga; (void)gia; (void)g0; (void)jA; (void)jB; (void)jC; (void)jN; (void)K2; (void)ms;
+  BIEM_FAST_TABLES()
+  double x[4];
+  for (int i = 0; i < D; ++i) x[i] = pb ? pts[((size_t)i * P + pc) * nb + s] : pts[(size_t)i * P + pc];
+  const cplx zero = make_double2(0.0, 0.0), qnan = cnan();
+  cplx tot[4] = {qnan, qnan, qnan, qnan};   // no ball contains the point
+  for (int b = 0; b < B; ++b) {
+    const double* cb = centers + ((geom_batched ? (size_t)s * B : 0) + b) * D;
+    const double rho = radii[(geom_batched ? (size_t)s * B : 0) + b];
+    double u[4] = {0.0, 0.0, 0.0, 0.0}, r2 = 0.0;
+    for (int i = 0; i < D; ++i) { u[i] = x[i] - cb[i]; r2 += u[i] * u[i]; }
+    const double r = sqrt(r2);
+    const bool in = p < P && r < rho;
+    // (a barrier: the previous ball's coefficients are no longer read, and the tables are written)
+    if (!__syncthreads_or(in ? 1 : 0)) continue;
+    const cplx* cs = a + ((size_t)s * B + b) * H;
+    BIEM_FAST_STAGE()
+    __syncthreads();
+    if (__ballot(in) == 0ull) continue;     // (after both barriers)
+    if (in) {
+      const cplx kb = kint[(fluid_batched ? (size_t)s * B : 0) + b];
+      for (int i = 0; i < D; ++i) tot[i] = qnan;
+      if (cfinite(kb)) {
+        // e = u / r; at the centre any unit vector does (grad S_1 is constant)
+        const double invr = r > 0.0 ? 1.0 / r : 1.0;
+        double e[4] = {1.0, 0.0, 0.0, 0.0};
+        if (r > 0.0) for (int i = 0; i < 4; ++i) e[i] = u[i] / r;
+        cplx kneg = make_double2(-kb.x, -kb.y);                     // alpha_n = kneg j_{n+1}
+        if (r > 0.0) radial_jh(D, n_end, cscale(kb, r), (zc*)sJl, nullptr);
+        else {                                // centre: j_{n+1}(0) = 0 and j_n / r -> delta_{n1} k_b z_0(0) / d, kept in place of j_1 (invr = 1)
+          const double z0 = radial_z0_at_zero(D) / (double)D;
+          for (int n = 0; n <= n_end; ++n) sJl[n] = n == 1 ? cscale(kb, z0) : zero;
+          kneg = zero;
+        }
+        // the radial part BIEM_GRAD_HARMONICS asks for: no upward recurrence here, the weights come from the lane's j_n row
+        const cplx h0 = zero, h1 = zero;
+        auto advance = [&](const cplx&, const cplx&, double) -> cplx { return zero; };
+        auto radial2 = [&](int n, const cplx&, const cplx&, cplx& al, cplx& be) {
+          al = cmul(kneg, sJl[n + 1]); be = cscale(sJl[n], invr);
+        };
+        BIEM_GRAD_HARMONICS()
+        bool fin = true;
+        for (int i = 0; i < D; ++i) { g[i] = cscale(g[i], kInvSqrt2Pi); fin = fin && cfinite(g[i]); }
+        if (fin) for (int i = 0; i < D; ++i) tot[i] = g[i];
+      }
+    }
+  }
+  if (p < P) for (int i = 0; i < D; ++i) out[i * cstride + (size_t)p * nb + s] = tot[i];
+}
+
 namespace {
 // what the per-lane kernel covers: 0 and a message otherwise
 int interior_cap(const biem_plan* p, const char* who) {
@@ -291,47 +365,70 @@ int launch_interior_coef(const biem_plan* p, int nb, int B, const double* d_k, c
   return BIEM_OK;
 }
 
-int launch_uinterior(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
-                     const double* d_radii, int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched,
-                     const double* d_density, const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes,
-                     hipStream_t st) {
+namespace {
+// the field (grad = false: out[P][nb]) or its gradient (out[d][P][nb]) at points, after the coefficients
+int interior_field(bool grad, const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                   const double* d_radii, int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched,
+                   const double* d_density, const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes,
+                   hipStream_t st) {
+  const char* who = grad ? "biem_uinterior_grad" : "biem_uinterior";
   if (flags & ~BIEM_USCAT_POINTS_BATCHED) {
-    set_error("biem_uinterior: flags=%d; only BIEM_USCAT_POINTS_BATCHED applies to the interior field", flags); return BIEM_ERR_ARG;
+    set_error("%s: flags=%d; only BIEM_USCAT_POINTS_BATCHED applies to the interior field", who, flags); return BIEM_ERR_ARG;
   }
-  if (!interior_cap(p, "biem_uinterior")) return BIEM_ERR_UNSUPPORTED;
-  if (nb > 65535) { set_error("biem_uinterior: more than 65535 systems in one call (%d)", nb); return BIEM_ERR_UNSUPPORTED; }
+  if (!interior_cap(p, who)) return BIEM_ERR_UNSUPPORTED;
+  if (nb > 65535) { set_error("%s: more than 65535 systems in one call (%d)", who, nb); return BIEM_ERR_UNSUPPORTED; }
   const int ne = p->n_end, ms = 2 * ne - 1, T = 64;
   size_t tab = 0, nC = 0;                 // doubles of tables, complex of coefficients (BIEM_FAST_LAYOUT)
   if (p->tree == TREE_BA) { tab = (size_t)2 * ne * ne + ((ne + 1) & ~1); nC = (size_t)ne * ne; }
   else if (p->tree == TREE_BBA) { tab = (size_t)4 * ne * ne + 2 * ((ne + 1) & ~1); nC = (size_t)ne * ne * ms; }
   else if (p->tree == TREE_CAA) { tab = (size_t)4 * ne * ne * ((ne + 1) / 2); nC = (size_t)ne * ms * ms; }
   else nC = (size_t)ms;
-  const size_t shm = tab * sizeof(double) + (nC + (size_t)T * ((ne + 2) | 1)) * sizeof(cplx);
+  const size_t row = grad ? (ne + 3) | 1 : (ne + 2) | 1;           // the kernels' js: the gradient reads j_{n_end} too
+  const size_t shm = tab * sizeof(double) + (nC + (size_t)T * row) * sizeof(cplx);
   if (shm > 160 * 1024) {
-    set_error("biem_uinterior: n_end=%d needs %zu bytes of LDS per workgroup (limit %d)", ne, shm, 160 * 1024);
+    set_error("%s: n_end=%d needs %zu bytes of LDS per workgroup (limit %d)", who, ne, shm, 160 * 1024);
     return BIEM_ERR_UNSUPPORTED;
   }
   if (nb <= 0 || B <= 0 || P <= 0) return BIEM_OK;
   const size_t need = (size_t)nb * B * p->H * sizeof(cplx);
-  if (work_bytes < need) { set_error("biem_uinterior: workspace too small"); return BIEM_ERR_ARG; }
+  if (work_bytes < need) { set_error("%s: workspace too small", who); return BIEM_ERR_ARG; }
   cplx* a = (cplx*)d_work;
   const int rc = launch_interior_coef(p, nb, B, d_k, d_eta, d_radii, geom_batched, d_kint, d_delta, fluid_batched, d_density,
                                       (double*)a, st);
   if (rc != BIEM_OK) return rc;
-#define BIEM_UINTERIOR(TREE)                                                                                                     \
+#define BIEM_UINTERIOR(KERNEL, TREE)                                                                                             \
   {                                                                                                                              \
-    BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_uinterior_fast<TREE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
-    hipLaunchKernelGGL((k_uinterior_fast<TREE>), dim3((P + T - 1) / T, nb), dim3(T), shm, st, p->d, p->H, ne, p->d_labels, nb, B, P, \
+    BIEM_HIPCHK(hipFuncSetAttribute((const void*)KERNEL<TREE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));           \
+    hipLaunchKernelGGL((KERNEL<TREE>), dim3((P + T - 1) / T, nb), dim3(T), shm, st, p->d, p->H, ne, p->d_labels, nb, B, P,       \
                        d_centers, d_radii, geom_batched, (const cplx*)d_kint, fluid_batched, (const cplx*)a, d_points, flags,    \
                        (cplx*)d_out);                                                                                            \
   }
-  if (p->tree == TREE_BA) BIEM_UINTERIOR(TREE_BA)
-  else if (p->tree == TREE_BBA) BIEM_UINTERIOR(TREE_BBA)
-  else if (p->tree == TREE_CAA) BIEM_UINTERIOR(TREE_CAA)
-  else BIEM_UINTERIOR(TREE_A)
+#define BIEM_UINTERIOR_TREE(TREE) { if (grad) BIEM_UINTERIOR(k_uinterior_grad_fast, TREE) else BIEM_UINTERIOR(k_uinterior_fast, TREE) }
+  if (p->tree == TREE_BA) BIEM_UINTERIOR_TREE(TREE_BA)
+  else if (p->tree == TREE_BBA) BIEM_UINTERIOR_TREE(TREE_BBA)
+  else if (p->tree == TREE_CAA) BIEM_UINTERIOR_TREE(TREE_CAA)
+  else BIEM_UINTERIOR_TREE(TREE_A)
+#undef BIEM_UINTERIOR_TREE
 #undef BIEM_UINTERIOR
   BIEM_LAUNCHCHK();
   return BIEM_OK;
+}
+}  // namespace
+
+int launch_uinterior(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                     const double* d_radii, int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched,
+                     const double* d_density, const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes,
+                     hipStream_t st) {
+  return interior_field(false, p, nb, B, P, d_k, d_eta, d_centers, d_radii, geom_batched, d_kint, d_delta, fluid_batched, d_density,
+                        d_points, flags, d_out, d_work, work_bytes, st);
+}
+
+int launch_uinterior_grad(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                          const double* d_radii, int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched,
+                          const double* d_density, const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes,
+                          hipStream_t st) {
+  return interior_field(true, p, nb, B, P, d_k, d_eta, d_centers, d_radii, geom_batched, d_kint, d_delta, fluid_batched, d_density,
+                        d_points, flags, d_out, d_work, work_bytes, st);
 }
 
 }  // namespace biem

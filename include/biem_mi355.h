@@ -241,6 +241,16 @@ int biem_uinterior(const biem_plan* plan, int nb, int B, int P, const double* d_
                    const double* d_delta /*c128*/, int fluid_batched, const double* d_density, const double* d_points, int flags,
                    double* d_out /*[P][nb]*/, void* d_work, size_t work_bytes, void* stream);
 
+/* Cartesian gradient of that field at the same points: out[d][P][nb] complex128, component i along axis i of the plan's tree; NaN
+ * in every component exactly where biem_uinterior gives NaN (a NaN coefficient poisons all components of its ball).  The centre of
+ * a ball and points on the axes of the tree are ordinary points.  Arguments, flags, errors and workspace
+ * (biem_uinterior_workspace_bytes) as biem_uinterior.  Covered as biem_uinterior, with per-lane rows of n_end + 3 radial values
+ * (tree a: n_end <= 152). */
+int biem_uinterior_grad(const biem_plan* plan, int nb, int B, int P, const double* d_k /*c128*/, const double* d_eta,
+                        const double* d_centers, const double* d_radii, int geom_batched, const double* d_kint /*[nb or 1][B] c128*/,
+                        const double* d_delta /*c128*/, int fluid_batched, const double* d_density, const double* d_points, int flags,
+                        double* d_out /*[d][P][nb]*/, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- one call for the whole path: ball tables + fill (equilibrated) + LU + density, systems processed in
  *      chunks of `chunk` resident matrices (0 = choose); every system is factored once for its nrhs right-hand sides.
  *      d_g [nb][nrhs][B][Q] as in biem_rhs_project, d_density [nb][nrhs][B][H]. ---- */
