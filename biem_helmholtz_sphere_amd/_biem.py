@@ -1051,7 +1051,12 @@ def biem(
 # field evaluation (reference biem_u :822-977)
 # --------------------------------------------------------------------------------------
 def biem_u(res: Any, x: Array, /, far_field: bool = False, per_ball: bool = False, expand_x: bool = True) -> Array:
-    """Scattered field at cartesian x of shape (c_ndim, ...(x)) [expand_x] or (c_ndim, ...(x), ...(first))."""
+    """Scattered field at cartesian x of shape (c_ndim, ...(x)) [expand_x] or (c_ndim, ...(x), ...(first)).
+
+    The near field is NaN (for every ball of ``per_ball=True``) where its series is not valid: ``kind="outer"`` inside any ball,
+    ``kind="inner"`` outside any ball.  So ``kind="inner"`` with B >= 2 marks every point NaN unless it lies inside ALL balls -
+    for disjoint balls, every point; the oracle's mask and the kernels' alike.  The far field has no mask.
+    """
     return _field(res, x, far_field=far_field, per_ball=per_ball, expand_x=expand_x, grad=False)
 
 
@@ -1196,7 +1201,7 @@ def biem_u_interior(res: Any, x: Array, /, *, k_interior: Array, density_ratio: 
 
     ``ValueError`` for ``kind != "outer"``, a result without density, ``k_interior * radii == 0`` and shapes that do not broadcast.
     Built for the trees a, ba, bpa, bba, bpbpa, caa up to n_end 320 / 48 / 14 / 12 (2-D / 3-D / bba / caa) while the per-lane
-    rows fit the LDS (2-D: n_end <= 153); ``NotImplementedError`` beyond that and for the chain trees d >= 5.
+    rows fit the LDS (2-D: n_end <= 152); ``NotImplementedError`` beyond that and for the chain trees d >= 5.
     """
     return _interior(res, x, k_interior, density_ratio, expand_x, grad=False)
 

@@ -5,6 +5,7 @@
 // and of (1 / density) d_n u across the sphere, with the unscaled pair alpha^_n = -k_b j_n'(k_b rho), beta^_n = delta j_n(k_b rho), gives
 //   a_{b,h} = -s delta k W(x) / gj_n,    W(x) = j_n h_n' - j_n' h_n = i / x^{d-1},    gj_n = alpha^_n j_n(x) + beta^_n k j_n'(x),    x = k rho
 // with nothing divided by j_n(k_b rho).  No second solve, no matrix, no matvec.
+#include <atomic>
 #include "fast_layout.hpp"
 
 namespace biem {
@@ -385,8 +386,24 @@ int interior_field(bool grad, const biem_plan* p, int nb, int B, int P, const do
   else nC = (size_t)ms;
   const size_t row = grad ? (ne + 3) | 1 : (ne + 2) | 1;           // the kernels' js: the gradient reads j_{n_end} too
   const size_t shm = tab * sizeof(double) + (nC + (size_t)T * row) * sizeof(cplx);
-  if (shm > 160 * 1024) {
-    set_error("%s: n_end=%d needs %zu bytes of LDS per workgroup (limit %d)", who, ne, shm, 160 * 1024);
+  // The kernel's own LDS (what the compiler reserves beside the dynamic part) counts against the same 160 KiB per workgroup.  Without
+  // it 2-D n_end = 153 passed this check with 163600 bytes and failed later in hipFuncSetAttribute.  Read once per kernel.
+  const void* kern = nullptr;
+#define BIEM_UINTERIOR_PICK(TREE) kern = grad ? (const void*)k_uinterior_grad_fast<TREE> : (const void*)k_uinterior_fast<TREE>;
+  if (p->tree == TREE_BA) BIEM_UINTERIOR_PICK(TREE_BA)
+  else if (p->tree == TREE_BBA) BIEM_UINTERIOR_PICK(TREE_BBA)
+  else if (p->tree == TREE_CAA) BIEM_UINTERIOR_PICK(TREE_CAA)
+  else BIEM_UINTERIOR_PICK(TREE_A)
+#undef BIEM_UINTERIOR_PICK
+  static std::atomic<long> own_lds[2][4] = {{{-1}, {-1}, {-1}, {-1}}, {{-1}, {-1}, {-1}, {-1}}};
+  std::atomic<long>& own = own_lds[grad ? 1 : 0][p->tree];
+  if (own.load() < 0) {
+    hipFuncAttributes fa;
+    BIEM_HIPCHK(hipFuncGetAttributes(&fa, kern));
+    own.store((long)fa.sharedSizeBytes);
+  }
+  if (shm + (size_t)own.load() > 160 * 1024) {
+    set_error("%s: n_end=%d needs %zu bytes of LDS per workgroup (limit %d)", who, ne, shm + (size_t)own.load(), 160 * 1024);
     return BIEM_ERR_UNSUPPORTED;
   }
   if (nb <= 0 || B <= 0 || P <= 0) return BIEM_OK;

@@ -230,7 +230,7 @@ int biem_uscat_grad(const biem_plan* plan, int nb, int B, int P, const double* d
  * biem_uinterior: d_points as biem_uscat; out[P][nb] complex128 = u_b where |y - c_b| < rho_b (the points biem_uscat masks), NaN at
  * every other point and inside a ball with a NaN coefficient.  flags: BIEM_USCAT_POINTS_BATCHED only, any other is BIEM_ERR_ARG.
  * Workspace: biem_uinterior_workspace_bytes (holds a).  Covered: trees a, ba, bba, caa up to the per-lane orders (n_end <= 320, 48,
- * 14, 12) while a workgroup's 64 rows of n_end + 2 radial values fit the LDS (tree a: n_end <= 153); chain trees, larger orders
+ * 14, 12) while a workgroup's 64 rows of n_end + 2 radial values fit the LDS beside the kernel's own (tree a: n_end <= 152); chain trees, larger orders
  * and more than 65535 systems are BIEM_ERR_UNSUPPORTED with a message. */
 int biem_interior_coef(const biem_plan* plan, int nb, int B, const double* d_k /*c128*/, const double* d_eta, const double* d_radii,
                        int geom_batched, const double* d_kint /*[nb or 1][B] c128*/, const double* d_delta /*c128*/,
