@@ -815,9 +815,7 @@ def _boundary_samples(op: _Operator, uin, uin_grad):
     dev, d, Q, B, nb = plan.dev, plan.d, plan.Q, fl.B, fl.nb
     qshape = plan.quad_shape()
     nbt = len(batch)
-    inv = [0] * d
-    for i, pi_ in enumerate(perm):
-        inv[pi_] = i
+    inv = _inverse_perm(perm)
     ident = inv == list(range(d))                                      # (no primed nodes: no gather kernels for the axis order)
     ykey = tuple(inv)
     y = plan.y_by_axes.get(ykey)
@@ -1076,6 +1074,39 @@ def biem_u_grad(res: Any, x: Array, /, per_ball: bool = False, expand_x: bool = 
     return _field(res, x, far_field=False, per_ball=per_ball, expand_x=expand_x, grad=True)
 
 
+def _inverse_perm(perm) -> list:
+    """inv with inv[perm[i]] = i.  The kernels' gradient components lie along the plan's canonical axes y_i = x_{perm[i]}: out[inv] hands
+    them back along the caller's."""
+    inv = [0] * len(perm)
+    for i, q in enumerate(perm):
+        inv[q] = i
+    return inv
+
+
+def _check_built(lib, rc: int, entry: str) -> None:
+    """L.check, with BIEM_ERR_UNSUPPORTED (a limit only the library knows: the LDS of the per-lane rows in 2-D) as NotImplementedError."""
+    if rc == L.BIEM_ERR_UNSUPPORTED:
+        msg = lib.biem_last_error()
+        raise NotImplementedError(msg.decode() if msg else f"{entry}: not built for this size")
+    L.check(rc, entry)
+
+
+def _check_covered(what: str, c: Any, tree: str, n_end: int, beyond: str) -> None:
+    """NotImplementedError unless the per-lane kernels cover (tree, n_end); `beyond`: what the trees and orders outside them are left with."""
+    if n_end > USCAT_GRAD_N_END_MAX.get(tree, 0):
+        cov = ", ".join(f"{t} (n_end <= {n})" for t, n in USCAT_GRAD_N_END_MAX.items())
+        raise NotImplementedError(
+            f"{what} is not built for tree {c.branching_types_expression_str!r} at n_end={n_end}; covered: {cov}, "
+            f"bpa and bpbpa as ba and bba; the chain trees d >= 5 and larger orders have {beyond}")
+
+
+def _stacked(x: Array) -> Array:
+    """A list / tuple of coordinate arrays as one array, component axis first."""
+    if isinstance(x, (list, tuple)):
+        return np.stack([np.asarray(v) for v in x], 0) if not isinstance(x[0], torch.Tensor) else torch.stack(list(x), 0)
+    return x
+
+
 @dataclass
 class _FieldOperands:
     """The flattened device operands of one field evaluation (biem_u, biem_u_grad, biem_u_interior, biem_u_interior_grad)."""
@@ -1115,9 +1146,7 @@ def _field_operands(res: Any, x: Array, tree: str, perm, expand_x: bool, extra_b
     nb, B = fl.nb, fl.B
     plan = _plan(tree, n_end, dev)
 
-    if isinstance(x, (list, tuple)):
-        x = np.stack([np.asarray(v) for v in x], 0) if not isinstance(x[0], torch.Tensor) else torch.stack(list(x), 0)
-    x_t = _to_dev(x, dev, f64)
+    x_t = _to_dev(_stacked(x), dev, f64)
     if x_t.shape[0] != d:
         raise ValueError(f"x must have shape ({d}, ...), got {tuple(x_t.shape)}")
     x_t = x_t[list(perm)]
@@ -1144,12 +1173,7 @@ def _field(res: Any, x: Array, *, far_field: bool, per_ball: bool, expand_x: boo
     c = res.c
     tree, perm = canonical_tree(c.branching_types_expression_str)
     if grad:
-        ne = n_end_from_harm(tree, int(res.density.shape[-1]))
-        if ne > USCAT_GRAD_N_END_MAX.get(tree, 0):
-            cov = ", ".join(f"{t} (n_end <= {n})" for t, n in USCAT_GRAD_N_END_MAX.items())
-            raise NotImplementedError(
-                f"uscat_grad is not built for tree {c.branching_types_expression_str!r} at n_end={ne}; covered: {cov}, "
-                "bpa and bpbpa as ba and bba; the chain trees d >= 5 and larger orders have uscat() only")
+        _check_covered("uscat_grad", c, tree, n_end_from_harm(tree, int(res.density.shape[-1])), "uscat() only")
     lib = L.load()
     f = _field_operands(res, x, tree, perm, expand_x)
     origin, dev, fl, plan, pts, df, flags, xshape, batch = f.origin, f.dev, f.fl, f.plan, f.pts, f.density, f.flags, f.xshape, f.batch
@@ -1169,16 +1193,12 @@ def _field(res: Any, x: Array, *, far_field: bool, per_ball: bool, expand_x: boo
         if P > 0 and nb > 0:
             rc = fn(plan.handle, nb, B, P, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
                     _ptr(df), _ptr(pts), flags, _ptr(out), _ptr(work), wb, _stream_ptr(dev))
-            if grad and rc == L.BIEM_ERR_UNSUPPORTED:      # a limit the table above does not know (the LDS of kind inner in 2-D)
-                msg = lib.biem_last_error()
-                raise NotImplementedError(msg.decode() if msg else "biem_uscat_grad: not built for this size")
-            L.check(rc, what)
+            if grad:
+                _check_built(lib, rc, what)
+            else:
+                L.check(rc, what)
     if grad and list(perm) != list(range(d)):
-        # the kernel's components are along the canonical axes y_i = x_{perm[i]}: hand them back along the caller's
-        inv = [0] * d
-        for i, q in enumerate(perm):
-            inv[q] = i
-        out = out[inv]
+        out = out[_inverse_perm(perm)]
     out = out.reshape(((d,) if grad else ()) + xshape + batch + ((B,) if per_ball else ()))
     return origin.give(out)
 
@@ -1215,12 +1235,7 @@ def _interior(res: Any, x: Array, k_interior: Array, density_ratio: Array, expan
         raise ValueError(f"Invalid kind: {res.kind} (the interior field belongs to an exterior problem, kind='outer')")
     c = res.c
     tree, perm = canonical_tree(c.branching_types_expression_str)
-    ne = n_end_from_harm(tree, int(res.density.shape[-1]))
-    if ne > USCAT_GRAD_N_END_MAX.get(tree, 0):
-        cov = ", ".join(f"{t} (n_end <= {n})" for t, n in USCAT_GRAD_N_END_MAX.items())
-        raise NotImplementedError(
-            f"{what} is not built for tree {c.branching_types_expression_str!r} at n_end={ne}; covered: {cov}, "
-            "bpa and bpbpa as ba and bba; the chain trees d >= 5 and larger orders have no interior field")
+    _check_covered(what, c, tree, n_end_from_harm(tree, int(res.density.shape[-1])), "no interior field")
     rs, ks, kis, dls = _shape(res.radii), _shape(res.k), _shape(k_interior), _shape(density_ratio)
     B = rs[-1]
     try:
@@ -1257,16 +1272,9 @@ def _interior(res: Any, x: Array, k_interior: Array, density_ratio: Array, expan
             rc = fn(f.plan.handle, nb, B, P, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
                     _ptr(kb_f), _ptr(dl_f), int(fluid_b), _ptr(f.density), _ptr(f.pts), f.flags, _ptr(out), _ptr(work), wb,
                     _stream_ptr(dev))
-            if rc == L.BIEM_ERR_UNSUPPORTED:               # a limit the table above does not know (the LDS of the per-lane rows in 2-D)
-                msg = lib.biem_last_error()
-                raise NotImplementedError(msg.decode() if msg else f"{entry}: not built for this size")
-            L.check(rc, entry)
+            _check_built(lib, rc, entry)
     if grad and list(perm) != list(range(d)):
-        # the kernel's components are along the canonical axes y_i = x_{perm[i]}: hand them back along the caller's (as _field does)
-        inv = [0] * d
-        for i, q in enumerate(perm):
-            inv[q] = i
-        out = out[inv]
+        out = out[_inverse_perm(perm)]
     return f.origin.give(out.reshape(((d,) if grad else ()) + f.xshape + batch))
 
 
@@ -1286,6 +1294,15 @@ def biem_u_interior_grad(res: Any, x: Array, /, *, k_interior: Array, density_ra
     return _interior(res, x, k_interior, density_ratio, expand_x, grad=True)
 
 
+def _inside_or(inside: Array, outside: Array, uin: Array) -> Array:
+    """`inside` where it has a value, `uin + outside` where it is NaN, in the namespace, dtype and on the device of `inside`."""
+    if isinstance(inside, torch.Tensor):
+        uin = uin.to(inside.device) if isinstance(uin, torch.Tensor) else torch.as_tensor(np.asarray(uin), device=inside.device)
+        return torch.where(torch.isnan(inside.real), (uin + outside).to(inside.dtype), inside)
+    uin = uin.detach().cpu().numpy() if isinstance(uin, torch.Tensor) else np.asarray(uin)
+    return np.where(np.isnan(inside.real), (uin + outside).astype(inside.dtype), inside)
+
+
 def biem_u_total(res: Any, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
     """Total field everywhere: ``res.uin(x) + uscat(x)`` outside all balls, :func:`biem_u_interior` inside them.
 
@@ -1297,11 +1314,7 @@ def biem_u_total(res: Any, x: Array, /, *, k_interior: Array, density_ratio: Arr
     inside = biem_u_interior(res, x, k_interior=k_interior, density_ratio=density_ratio, expand_x=expand_x)
     outside = biem_u(res, x, expand_x=expand_x)
     uin = res.uin(x, expand_x=expand_x)
-    if isinstance(inside, torch.Tensor):
-        uin = uin.to(inside.device) if isinstance(uin, torch.Tensor) else torch.as_tensor(np.asarray(uin), device=inside.device)
-        return torch.where(torch.isnan(inside.real), (uin + outside).to(inside.dtype), inside)
-    uin = uin.detach().cpu().numpy() if isinstance(uin, torch.Tensor) else np.asarray(uin)
-    return np.where(np.isnan(inside.real), (uin + outside).astype(inside.dtype), inside)
+    return _inside_or(inside, outside, uin)
 
 
 def biem_u_total_grad(res: Any, x: Array, /, *, k_interior: Array, density_ratio: Array, uin_grad: Callable[[Array], Array],
@@ -1320,15 +1333,9 @@ def biem_u_total_grad(res: Any, x: Array, /, *, k_interior: Array, density_ratio
     inside = biem_u_interior_grad(res, x, k_interior=k_interior, density_ratio=density_ratio, expand_x=expand_x)
     outside = biem_u_grad(res, x, expand_x=expand_x)
     if expand_x:
-        if isinstance(x, (list, tuple)):
-            x = np.stack([np.asarray(v) for v in x], 0) if not isinstance(x[0], torch.Tensor) else torch.stack(list(x), 0)
-        x = x[(...,) + (None,) * len(_shape(res.k))]
+        x = _stacked(x)[(...,) + (None,) * len(_shape(res.k))]
     uin = uin_grad(x)
-    if isinstance(inside, torch.Tensor):
-        uin = uin.to(inside.device) if isinstance(uin, torch.Tensor) else torch.as_tensor(np.asarray(uin), device=inside.device)
-        return torch.where(torch.isnan(inside.real), (uin + outside).to(inside.dtype), inside)
-    uin = uin.detach().cpu().numpy() if isinstance(uin, torch.Tensor) else np.asarray(uin)
-    return np.where(np.isnan(inside.real), (uin + outside).astype(inside.dtype), inside)
+    return _inside_or(inside, outside, uin)
 
 
 # --------------------------------------------------------------------------------------

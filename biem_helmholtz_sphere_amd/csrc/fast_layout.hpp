@@ -1,5 +1,5 @@
-// fast_layout.hpp -- the LDS layout of the per-lane field kernels and the harmonic loops of the gradient kernels (kernels_uscat.hip,
-// kernels_uinterior.hip).
+// fast_layout.hpp -- the LDS layout of the per-lane field kernels (with its size and the tree dispatch for their launchers) and the
+// harmonic loops of the value and of the gradient kernels (kernels_uscat.hip, kernels_uinterior.hip).
 #pragma once
 #include "common.hpp"
 
@@ -76,6 +76,191 @@
     else if (TREE == TREE_CAA) pos = (labels[3 * h] * ms + labels[3 * h + 1] + n_end - 1) * ms + labels[3 * h + 2] + n_end - 1; \
     else pos = labels[3 * h] + n_end - 1; \
     sC[pos] = cs[h]; \
+  }
+
+namespace biem {
+// The dynamic LDS bytes of BIEM_FAST_LAYOUT for a workgroup of `threads` lanes: the tables, one ball's coefficients and, behind them, a
+// row of `row` complex radial values per lane (the kernels' js; 0: no rows).  The launchers' one copy of what the macro lays out.
+inline size_t fast_layout_lds_bytes(int tree, int n_end, int threads, size_t row) {
+  const size_t ne = (size_t)n_end, ms = 2 * ne - 1, ne1 = (ne + 1) & ~(size_t)1;
+  size_t tab = 0, nC = ms;                 // doubles of tables, complex of coefficients
+  if (tree == TREE_BA) { tab = 2 * ne * ne + ne1; nC = ne * ne; }
+  else if (tree == TREE_BBA) { tab = 4 * ne * ne + 2 * ne1; nC = ne * ne * ms; }
+  else if (tree == TREE_CAA) { tab = 4 * ne * ne * ((ne + 1) / 2); nC = ne * ms * ms; }
+  return tab * sizeof(double) + (nC + (size_t)threads * row) * sizeof(cplx);
+}
+}  // namespace biem
+// STMT(TREE) for the per-lane tree of a plan (a, ba, bba or caa: the caller has excluded the chains), TREE a compile-time constant
+#define BIEM_FAST_TREE_DISPATCH(tree, STMT) \
+  if ((tree) == TREE_BA) { STMT(TREE_BA) } \
+  else if ((tree) == TREE_BBA) { STMT(TREE_BBA) } \
+  else if ((tree) == TREE_CAA) { STMT(TREE_CAA) } \
+  else { STMT(TREE_A) }
+
+// The harmonic loops of the value kernels: one text for k_uscat_fast (kernels_uscat.hip) and k_uinterior_fast (kernels_uinterior.hip),
+// moved here token for token from the former.  Expects BIEM_FAST_LAYOUT's names, n_end, the offset u[4] from the ball's centre and its
+// length r, and the caller's radial part: h0, h1 (the pair (h_0, h_1) of an upward recurrence, or zero), advance(hprev, hcur, two_q)
+// (its next member) and radial(n, hup) giving the radial factor of degree n - hup, the recurrence's h_n, or the entry of a per-lane
+// row.  Defines ar, ai: one ball's sum, without the common factor 1 / sqrt(2 pi).
+#define BIEM_FIELD_HARMONICS() \
+  double ar = 0.0, ai = 0.0; \
+  if (TREE == TREE_A) { \
+    /* Y_m = e^{i m theta} / sqrt(2 pi); degree n = |m| */ \
+    const double e1x = r > 0.0 ? u[0] / r : 1.0, e1y = r > 0.0 ? u[1] / r : 0.0; \
+    double ex = 1.0, ey = 0.0; \
+    cplx hp = h0, hc = h1;               /* h_n, h_{n+1} */ \
+    for (int n = 0; n < n_end; ++n) { \
+      const cplx cp = sC[n_end - 1 + n]; \
+      cplx t = make_double2(cp.x * ex - cp.y * ey, cp.x * ey + cp.y * ex); \
+      if (n > 0) { const cplx cn = sC[n_end - 1 - n]; t.x += cn.x * ex + cn.y * ey; t.y += cn.y * ex - cn.x * ey; } \
+      const cplx hv = radial(n, hp); \
+      ar += hv.x * t.x - hv.y * t.y; ai += hv.x * t.y + hv.y * t.x; \
+      const cplx hn = advance(hp, hc, 2.0 * n + 2.0); \
+      hp = hc; hc = hn; \
+      const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx; \
+    } \
+  } else if (TREE == TREE_BBA) { \
+    /* Y_{n l m} = s0^l g_{n-l}^{(l+1)}(c0) Pbar_l^{|m|}(c1) e^{i m phi} / sqrt(2 pi): three nested recurrences; (h_m, h_{m+1}) */ \
+    /* runs along m, (h_l, h_{l+1}) along l from it, (h_n, h_{n+1}) along n from that - no restart from h_0 */ \
+    const double rho2 = sqrt(u[2] * u[2] + u[3] * u[3]), rho1 = sqrt(u[1] * u[1] + rho2 * rho2); \
+    const double c0 = r > 0.0 ? u[0] / r : 1.0, s0 = r > 0.0 ? rho1 / r : 0.0; \
+    const double c1 = rho1 > 0.0 ? u[1] / rho1 : 1.0, s1 = rho1 > 0.0 ? rho2 / rho1 : 0.0; \
+    const double e1x = rho2 > 0.0 ? u[2] / rho2 : 1.0, e1y = rho2 > 0.0 ? u[3] / rho2 : 0.0; \
+    const int mstride = 2 * n_end - 1; \
+    double ex = 1.0, ey = 0.0, pmm = 0.70710678118654752440, s0m = 1.0; \
+    cplx hm = h0, hm1 = h1; \
+    for (int m = 0; m < n_end; ++m) { \
+      if (m > 0) { \
+        pmm *= cmm[m] * s1; s0m *= s0; \
+        const cplx hn = advance(hm, hm1, 2.0 * m); \
+        hm = hm1; hm1 = hn; \
+        const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx; \
+      } \
+      double p0 = 0.0, p1 = pmm, sl = s0m; \
+      cplx hl = hm, hl1 = hm1; \
+      double sr = 0.0, si = 0.0, qr = 0.0, qi = 0.0; \
+      for (int l = m; l < n_end; ++l) { \
+        double gp0 = 0.0, gp1 = g0[l]; \
+        cplx hp = hl, hc = hl1; \
+        const double alm = sl * p1; \
+        for (int n = l; n < n_end; ++n) { \
+          const double amp = alm * gp1; \
+          const cplx hv = radial(n, hp); \
+          const double wr = hv.x * amp, wi = hv.y * amp; \
+          const cplx* cc = sC + (n * n_end + l) * mstride + n_end - 1; \
+          const cplx cp = cc[m]; \
+          sr += wr * cp.x - wi * cp.y; si += wr * cp.y + wi * cp.x; \
+          if (m > 0) { const cplx cn = cc[-m]; qr += wr * cn.x - wi * cn.y; qi += wr * cn.y + wi * cn.x; } \
+          const int q = n - l + 1; \
+          if (n + 1 < n_end) { \
+            const double gp2 = (c0 * gp1 - ga[l * n_end + q - 1] * gp0) * gia[l * n_end + q]; \
+            gp0 = gp1; gp1 = gp2; \
+            const cplx hn = advance(hp, hc, 2.0 * (n + 1)); \
+            hp = hc; hc = hn; \
+          } \
+        } \
+        const int ql = l + 1; \
+        if (ql < n_end) { \
+          const double p2 = ra[ql * n_end + m] * (c1 * p1 - rb[ql * n_end + m] * p0); \
+          p0 = p1; p1 = p2; \
+          sl *= s0; \
+          const cplx hn = advance(hl, hl1, 2.0 * ql); \
+          hl = hl1; hl1 = hn; \
+        } \
+      } \
+      ar += sr * ex - si * ey + qr * ex + qi * ey; \
+      ai += sr * ey + si * ex + qi * ex - qr * ey; \
+    } \
+  } else if (TREE == TREE_CAA) { \
+    /* Y_{n m1 m2} = cos^a sin^b Pbar_k^{(b,a)}(cos 2 t0) e^{i (m1 t1 + m2 t2)} / (2 pi), a = |m1|, b = |m2|, n = a + b + 2 k: the */ \
+    /* Jacobi recurrence runs along k inside (a, b); the four sign combinations share it and the radial factor */ \
+    const double r01 = sqrt(u[0] * u[0] + u[1] * u[1]), r23 = sqrt(u[2] * u[2] + u[3] * u[3]); \
+    const double c0 = r > 0.0 ? r01 / r : 1.0, s0 = r > 0.0 ? r23 / r : 0.0, xx = c0 * c0 - s0 * s0; \
+    const double e1x = r01 > 0.0 ? u[0] / r01 : 1.0, e1y = r01 > 0.0 ? u[1] / r01 : 0.0; \
+    const double e2x = r23 > 0.0 ? u[2] / r23 : 1.0, e2y = r23 > 0.0 ? u[3] / r23 : 0.0; \
+    double ca = 1.0, eax = 1.0, eay = 0.0; \
+    cplx ha = h0, ha1 = h1;              /* h_a, h_{a+1} */ \
+    for (int a = 0; a < n_end; ++a) { \
+      if (a > 0) { \
+        ca *= c0; \
+        const cplx hn = advance(ha, ha1, 2.0 * a); \
+        ha = ha1; ha1 = hn; \
+        const double nx = eax * e1x - eay * e1y; eay = eax * e1y + eay * e1x; eax = nx; \
+      } \
+      double sb = 1.0, ebx = 1.0, eby = 0.0; \
+      cplx hb = ha, hb1 = ha1;           /* h_{a+b}, h_{a+b+1} */ \
+      for (int b = 0; a + b < n_end; ++b) { \
+        if (b > 0) { \
+          sb *= s0; \
+          const cplx hn = advance(hb, hb1, 2.0 * (a + b)); \
+          hb = hb1; hb1 = hn; \
+          const double nx = ebx * e2x - eby * e2y; eby = ebx * e2y + eby * e2x; ebx = nx; \
+        } \
+        const int tb = (a * n_end + b) * K2; \
+        const double amp0 = ca * sb; \
+        double p0 = 0.0, p1 = 1.0; \
+        cplx hp = hb, hc = hb1; \
+        double ppr = 0.0, ppi = 0.0, mpr = 0.0, mpi = 0.0, pmr = 0.0, pmi = 0.0, mmr = 0.0, mmi = 0.0;   /* sums of the (+-a, +-b) coefficients */ \
+        for (int kq = 0, n = a + b; n < n_end; ++kq, n += 2) { \
+          const cplx hv = radial(n, hp); \
+          const double amp = amp0 * jN[tb + kq] * p1; \
+          const double wr = hv.x * amp, wi = hv.y * amp; \
+          const cplx* cc = sC + (n * ms + n_end - 1) * ms + n_end - 1; \
+          { const cplx cv = cc[a * ms + b]; ppr += wr * cv.x - wi * cv.y; ppi += wr * cv.y + wi * cv.x; } \
+          if (a > 0) { const cplx cv = cc[-a * ms + b]; mpr += wr * cv.x - wi * cv.y; mpi += wr * cv.y + wi * cv.x; } \
+          if (b > 0) { const cplx cv = cc[a * ms - b]; pmr += wr * cv.x - wi * cv.y; pmi += wr * cv.y + wi * cv.x; } \
+          if (a > 0 && b > 0) { const cplx cv = cc[-a * ms - b]; mmr += wr * cv.x - wi * cv.y; mmi += wr * cv.y + wi * cv.x; } \
+          if (n + 2 < n_end) { \
+            const double p2 = (jA[tb + kq] * xx + jB[tb + kq]) * p1 - jC[tb + kq] * p0; \
+            p0 = p1; p1 = p2; \
+            cplx hn = advance(hp, hc, 2.0 * (n + 1)); \
+            hp = hc; hc = hn; \
+            hn = advance(hp, hc, 2.0 * (n + 2)); \
+            hp = hc; hc = hn; \
+          } \
+        } \
+        /* e^{i (+-a t1 +- b t2)} */ \
+        const double fx = eax * ebx - eay * eby, fy = eax * eby + eay * ebx;     /* e^{i (a t1 + b t2)} */ \
+        const double gx = eax * ebx + eay * eby, gy = eax * eby - eay * ebx;     /* e^{i (-a t1 + b t2)} */ \
+        ar += ppr * fx - ppi * fy + mmr * fx + mmi * fy + mpr * gx - mpi * gy + pmr * gx + pmi * gy; \
+        ai += ppr * fy + ppi * fx + mmi * fx - mmr * fy + mpr * gy + mpi * gx + pmi * gx - pmr * gy; \
+      } \
+    } \
+    ar *= kInvSqrt2Pi; ai *= kInvSqrt2Pi;   /* (the second 1 / sqrt(2 pi) below) */ \
+  } else { \
+    const double rxy = sqrt(u[1] * u[1] + u[2] * u[2]); \
+    const double c0 = r > 0.0 ? u[0] / r : 1.0, s0 = r > 0.0 ? rxy / r : 0.0; \
+    const double e1x = rxy > 0.0 ? u[1] / rxy : 1.0, e1y = rxy > 0.0 ? u[2] / rxy : 0.0; \
+    double ex = 1.0, ey = 0.0, pmm = 0.70710678118654752440; \
+    cplx hm = h0, hm1 = h1;              /* h_m, h_{m+1}: advanced by one per order m */ \
+    for (int m = 0; m < n_end; ++m) { \
+      if (m > 0) { \
+        pmm *= cmm[m] * s0; \
+        const cplx hn = advance(hm, hm1, 2.0 * m); \
+        hm = hm1; hm1 = hn; \
+        const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx; \
+      } \
+      cplx hp = hm, hc = hm1;            /* h_n, h_{n+1} for n = m .. */ \
+      double p0 = 0.0, p1 = pmm; \
+      double sr = 0.0, si = 0.0;         /* sum over n of h_n Pbar_n^m c_{n, +-m} (the e^{+- i m phi} factors applied once per m) */ \
+      double qr = 0.0, qi = 0.0; \
+      for (int n = m; n < n_end; ++n) { \
+        const cplx cp = sC[n * n + n + m]; \
+        const cplx hv = radial(n, hp); \
+        const double wr = hv.x * p1, wi = hv.y * p1; \
+        sr += wr * cp.x - wi * cp.y; si += wr * cp.y + wi * cp.x; \
+        if (m > 0) { const cplx cn = sC[n * n + n - m]; qr += wr * cn.x - wi * cn.y; qi += wr * cn.y + wi * cn.x; } \
+        const int q = n + 1; \
+        if (q < n_end) { \
+          const double p2 = ra[q * n_end + m] * (c0 * p1 - rb[q * n_end + m] * p0); \
+          p0 = p1; p1 = p2; \
+          const cplx hn = advance(hp, hc, 2.0 * q); \
+          hp = hc; hc = hn; \
+        } \
+      } \
+      ar += sr * ex - si * ey + qr * ex + qi * ey; \
+      ai += sr * ey + si * ex + qi * ex - qr * ey; \
+    } \
   }
 
 // The harmonic loops of the gradient kernels: the solid-harmonic form of kernels_uscat.hip's header (grad (z_n Y_h) = alpha_n Y_h e +

@@ -77,8 +77,9 @@ __global__ void __launch_bounds__(64) k_interior_coef(int d, int H, int n_end, c
 
 // ---------------------------------------------------------------------------------------------
 // The field, ONE POINT PER LANE: the skeleton of k_uscat_fast<TREE, false, true> (workgroup-uniform loop over the balls, the ball's
-// coefficients staged in LDS, j_n by radial_jh's backward recurrence into the lane's own LDS row, the harmonic recurrences of that
-// kernel), with three differences:
+// coefficients staged in LDS, j_n by radial_jh's backward recurrence into the lane's own LDS row) around that kernel's harmonic loops
+// (BIEM_FIELD_HARMONICS, fast_layout.hpp: one text for both; the upward recurrence of the exterior kind is a constant zero here and
+// folds away), with three differences:
 //   - the argument of j_n is k_b r with the ball's own complex wavenumber;
 //   - a lane contributes only for the ball that contains its point (r < rho: exactly where k_uscat_fast masks);
 //   - a ball that holds no point of the workgroup is not staged, and a wave none of whose lanes lies in it skips its radial and
@@ -118,145 +119,23 @@ __global__ void __launch_bounds__(64) k_uinterior_fast(int d, int H, int n_end, 
     if (__ballot(in) == 0ull) continue;     // (after both barriers)
     if (in) {
       const cplx kb = kint[(fluid_batched ? (size_t)s * B : 0) + b];
-      double ar = qnan, ai = 0.0;
+      double br = qnan, bi = 0.0;           // (a NaN k_b)
       if (isfinite(kb.x) && isfinite(kb.y)) {
         if (r > 0.0) radial_jh(d, n_end - 1, cscale(kb, r), (zc*)sJl, nullptr);
         else {                                // centre of the ball: z_n(0) = delta_{n0} sqrt(pi/2) 2^{1-d/2} / Gamma(d/2)
           const double z0 = radial_z0_at_zero(d);
           for (int n = 0; n < n_end; ++n) sJl[n] = make_double2(n == 0 ? z0 : 0.0, 0.0);
         }
-        ar = 0.0;
-        if (TREE == TREE_A) {
-          // Y_m = e^{i m theta} / sqrt(2 pi); degree n = |m|
-          const double e1x = r > 0.0 ? u[0] / r : 1.0, e1y = r > 0.0 ? u[1] / r : 0.0;
-          double ex = 1.0, ey = 0.0;
-          for (int n = 0; n < n_end; ++n) {
-            const cplx cp = sC[n_end - 1 + n];
-            cplx t = make_double2(cp.x * ex - cp.y * ey, cp.x * ey + cp.y * ex);
-            if (n > 0) { const cplx cn = sC[n_end - 1 - n]; t.x += cn.x * ex + cn.y * ey; t.y += cn.y * ex - cn.x * ey; }
-            const cplx hv = sJl[n];
-            ar += hv.x * t.x - hv.y * t.y; ai += hv.x * t.y + hv.y * t.x;
-            const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx;
-          }
-        } else if (TREE == TREE_BBA) {
-          // Y_{n l m} = s0^l g_{n-l}^{(l+1)}(c0) Pbar_l^{|m|}(c1) e^{i m phi} / sqrt(2 pi)
-          const double rho2 = sqrt(u[2] * u[2] + u[3] * u[3]), rho1 = sqrt(u[1] * u[1] + rho2 * rho2);
-          const double c0 = r > 0.0 ? u[0] / r : 1.0, s0 = r > 0.0 ? rho1 / r : 0.0;
-          const double c1 = rho1 > 0.0 ? u[1] / rho1 : 1.0, s1 = rho1 > 0.0 ? rho2 / rho1 : 0.0;
-          const double e1x = rho2 > 0.0 ? u[2] / rho2 : 1.0, e1y = rho2 > 0.0 ? u[3] / rho2 : 0.0;
-          const int mstride = 2 * n_end - 1;
-          double ex = 1.0, ey = 0.0, pmm = 0.70710678118654752440, s0m = 1.0;
-          for (int m = 0; m < n_end; ++m) {
-            if (m > 0) {
-              pmm *= cmm[m] * s1; s0m *= s0;
-              const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx;
-            }
-            double p0 = 0.0, p1 = pmm, sl = s0m;
-            double sr = 0.0, si = 0.0, qr = 0.0, qi = 0.0;
-            for (int l = m; l < n_end; ++l) {
-              double gp0 = 0.0, gp1 = g0[l];
-              const double alm = sl * p1;
-              for (int n = l; n < n_end; ++n) {
-                const double amp = alm * gp1;
-                const cplx hv = sJl[n];
-                const double wr = hv.x * amp, wi = hv.y * amp;
-                const cplx* cc = sC + (n * n_end + l) * mstride + n_end - 1;
-                const cplx cp = cc[m];
-                sr += wr * cp.x - wi * cp.y; si += wr * cp.y + wi * cp.x;
-                if (m > 0) { const cplx cn = cc[-m]; qr += wr * cn.x - wi * cn.y; qi += wr * cn.y + wi * cn.x; }
-                const int q = n - l + 1;
-                if (n + 1 < n_end) {
-                  const double gp2 = (c0 * gp1 - ga[l * n_end + q - 1] * gp0) * gia[l * n_end + q];
-                  gp0 = gp1; gp1 = gp2;
-                }
-              }
-              const int ql = l + 1;
-              if (ql < n_end) {
-                const double p2 = ra[ql * n_end + m] * (c1 * p1 - rb[ql * n_end + m] * p0);
-                p0 = p1; p1 = p2;
-                sl *= s0;
-              }
-            }
-            ar += sr * ex - si * ey + qr * ex + qi * ey;
-            ai += sr * ey + si * ex + qi * ex - qr * ey;
-          }
-        } else if (TREE == TREE_CAA) {
-          // Y_{n m1 m2} = cos^a sin^b Pbar_k^{(b,a)}(cos 2 t0) e^{i (m1 t1 + m2 t2)} / (2 pi), a = |m1|, b = |m2|, n = a + b + 2 k
-          const double r01 = sqrt(u[0] * u[0] + u[1] * u[1]), r23 = sqrt(u[2] * u[2] + u[3] * u[3]);
-          const double c0 = r > 0.0 ? r01 / r : 1.0, s0 = r > 0.0 ? r23 / r : 0.0, xx = c0 * c0 - s0 * s0;
-          const double e1x = r01 > 0.0 ? u[0] / r01 : 1.0, e1y = r01 > 0.0 ? u[1] / r01 : 0.0;
-          const double e2x = r23 > 0.0 ? u[2] / r23 : 1.0, e2y = r23 > 0.0 ? u[3] / r23 : 0.0;
-          double ca = 1.0, eax = 1.0, eay = 0.0;
-          for (int aa = 0; aa < n_end; ++aa) {
-            if (aa > 0) {
-              ca *= c0;
-              const double nx = eax * e1x - eay * e1y; eay = eax * e1y + eay * e1x; eax = nx;
-            }
-            double sb = 1.0, ebx = 1.0, eby = 0.0;
-            for (int bq = 0; aa + bq < n_end; ++bq) {
-              if (bq > 0) {
-                sb *= s0;
-                const double nx = ebx * e2x - eby * e2y; eby = ebx * e2y + eby * e2x; ebx = nx;
-              }
-              const int tb = (aa * n_end + bq) * K2;
-              const double amp0 = ca * sb;
-              double p0 = 0.0, p1 = 1.0;
-              double ppr = 0.0, ppi = 0.0, mpr = 0.0, mpi = 0.0, pmr = 0.0, pmi = 0.0, mmr = 0.0, mmi = 0.0;   // sums of the (+-a, +-b) coefficients
-              for (int kq = 0, n = aa + bq; n < n_end; ++kq, n += 2) {
-                const cplx hv = sJl[n];
-                const double amp = amp0 * jN[tb + kq] * p1;
-                const double wr = hv.x * amp, wi = hv.y * amp;
-                const cplx* cc = sC + (n * ms + n_end - 1) * ms + n_end - 1;
-                { const cplx cv = cc[aa * ms + bq]; ppr += wr * cv.x - wi * cv.y; ppi += wr * cv.y + wi * cv.x; }
-                if (aa > 0) { const cplx cv = cc[-aa * ms + bq]; mpr += wr * cv.x - wi * cv.y; mpi += wr * cv.y + wi * cv.x; }
-                if (bq > 0) { const cplx cv = cc[aa * ms - bq]; pmr += wr * cv.x - wi * cv.y; pmi += wr * cv.y + wi * cv.x; }
-                if (aa > 0 && bq > 0) { const cplx cv = cc[-aa * ms - bq]; mmr += wr * cv.x - wi * cv.y; mmi += wr * cv.y + wi * cv.x; }
-                if (n + 2 < n_end) {
-                  const double p2 = (jA[tb + kq] * xx + jB[tb + kq]) * p1 - jC[tb + kq] * p0;
-                  p0 = p1; p1 = p2;
-                }
-              }
-              const double fx = eax * ebx - eay * eby, fy = eax * eby + eay * ebx;     // e^{i (a t1 + b t2)}
-              const double gx = eax * ebx + eay * eby, gy = eax * eby - eay * ebx;     // e^{i (-a t1 + b t2)}
-              ar += ppr * fx - ppi * fy + mmr * fx + mmi * fy + mpr * gx - mpi * gy + pmr * gx + pmi * gy;
-              ai += ppr * fy + ppi * fx + mmi * fx - mmr * fy + mpr * gy + mpi * gx + pmi * gx - pmr * gy;
-            }
-          }
-          ar *= kInvSqrt2Pi; ai *= kInvSqrt2Pi;   // (the second 1 / sqrt(2 pi) below)
-        } else {
-          // ba: Y_{n m} = Pbar_n^{|m|}(c0) e^{i m phi} / sqrt(2 pi)
-          const double rxy = sqrt(u[1] * u[1] + u[2] * u[2]);
-          const double c0 = r > 0.0 ? u[0] / r : 1.0, s0 = r > 0.0 ? rxy / r : 0.0;
-          const double e1x = rxy > 0.0 ? u[1] / rxy : 1.0, e1y = rxy > 0.0 ? u[2] / rxy : 0.0;
-          double ex = 1.0, ey = 0.0, pmm = 0.70710678118654752440;
-          for (int m = 0; m < n_end; ++m) {
-            if (m > 0) {
-              pmm *= cmm[m] * s0;
-              const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx;
-            }
-            double p0 = 0.0, p1 = pmm;
-            double sr = 0.0, si = 0.0;         // sum over n of j_n Pbar_n^m a_{n, +-m} (the e^{+- i m phi} factors applied once per m)
-            double qr = 0.0, qi = 0.0;
-            for (int n = m; n < n_end; ++n) {
-              const cplx cp = sC[n * n + n + m];
-              const cplx hv = sJl[n];
-              const double wr = hv.x * p1, wi = hv.y * p1;
-              sr += wr * cp.x - wi * cp.y; si += wr * cp.y + wi * cp.x;
-              if (m > 0) { const cplx cn = sC[n * n + n - m]; qr += wr * cn.x - wi * cn.y; qi += wr * cn.y + wi * cn.x; }
-              const int q = n + 1;
-              if (q < n_end) {
-                const double p2 = ra[q * n_end + m] * (c0 * p1 - rb[q * n_end + m] * p0);
-                p0 = p1; p1 = p2;
-              }
-            }
-            ar += sr * ex - si * ey + qr * ex + qi * ey;
-            ai += sr * ey + si * ex + qi * ex - qr * ey;
-          }
-        }
+        // the radial part BIEM_FIELD_HARMONICS asks for: no upward recurrence here, the factor comes from the lane's j_n row
+        const cplx zero = make_double2(0.0, 0.0), h0 = zero, h1 = zero;
+        auto advance = [&](const cplx&, const cplx&, double) -> cplx { return zero; };
+        auto radial = [&](int n, const cplx&) -> cplx { return sJl[n]; };
+        BIEM_FIELD_HARMONICS()
         ar *= kInvSqrt2Pi; ai *= kInvSqrt2Pi;
         if (!(isfinite(ar) && isfinite(ai))) { ar = qnan; ai = 0.0; }
+        br = ar; bi = ai;
       }
-      tr = ar; ti = ai;
+      tr = br; ti = bi;
     }
   }
   if (p < P) out[(size_t)p * nb + s] = make_double2(tr, ti);
@@ -378,22 +257,13 @@ int interior_field(bool grad, const biem_plan* p, int nb, int B, int P, const do
   }
   if (!interior_cap(p, who)) return BIEM_ERR_UNSUPPORTED;
   if (nb > 65535) { set_error("%s: more than 65535 systems in one call (%d)", who, nb); return BIEM_ERR_UNSUPPORTED; }
-  const int ne = p->n_end, ms = 2 * ne - 1, T = 64;
-  size_t tab = 0, nC = 0;                 // doubles of tables, complex of coefficients (BIEM_FAST_LAYOUT)
-  if (p->tree == TREE_BA) { tab = (size_t)2 * ne * ne + ((ne + 1) & ~1); nC = (size_t)ne * ne; }
-  else if (p->tree == TREE_BBA) { tab = (size_t)4 * ne * ne + 2 * ((ne + 1) & ~1); nC = (size_t)ne * ne * ms; }
-  else if (p->tree == TREE_CAA) { tab = (size_t)4 * ne * ne * ((ne + 1) / 2); nC = (size_t)ne * ms * ms; }
-  else nC = (size_t)ms;
-  const size_t row = grad ? (ne + 3) | 1 : (ne + 2) | 1;           // the kernels' js: the gradient reads j_{n_end} too
-  const size_t shm = tab * sizeof(double) + (nC + (size_t)T * row) * sizeof(cplx);
+  const int ne = p->n_end, T = 64;
+  const size_t shm = fast_layout_lds_bytes(p->tree, ne, T, grad ? (ne + 3) | 1 : (ne + 2) | 1);   // (the kernels' js: the gradient reads j_{n_end} too)
   // The kernel's own LDS (what the compiler reserves beside the dynamic part) counts against the same 160 KiB per workgroup.  Without
   // it 2-D n_end = 153 passed this check with 163600 bytes and failed later in hipFuncSetAttribute.  Read once per kernel.
   const void* kern = nullptr;
 #define BIEM_UINTERIOR_PICK(TREE) kern = grad ? (const void*)k_uinterior_grad_fast<TREE> : (const void*)k_uinterior_fast<TREE>;
-  if (p->tree == TREE_BA) BIEM_UINTERIOR_PICK(TREE_BA)
-  else if (p->tree == TREE_BBA) BIEM_UINTERIOR_PICK(TREE_BBA)
-  else if (p->tree == TREE_CAA) BIEM_UINTERIOR_PICK(TREE_CAA)
-  else BIEM_UINTERIOR_PICK(TREE_A)
+  BIEM_FAST_TREE_DISPATCH(p->tree, BIEM_UINTERIOR_PICK)
 #undef BIEM_UINTERIOR_PICK
   static std::atomic<long> own_lds[2][4] = {{{-1}, {-1}, {-1}, {-1}}, {{-1}, {-1}, {-1}, {-1}}};
   std::atomic<long>& own = own_lds[grad ? 1 : 0][p->tree];
@@ -421,10 +291,7 @@ int interior_field(bool grad, const biem_plan* p, int nb, int B, int P, const do
                        (cplx*)d_out);                                                                                            \
   }
 #define BIEM_UINTERIOR_TREE(TREE) { if (grad) BIEM_UINTERIOR(k_uinterior_grad_fast, TREE) else BIEM_UINTERIOR(k_uinterior_fast, TREE) }
-  if (p->tree == TREE_BA) BIEM_UINTERIOR_TREE(TREE_BA)
-  else if (p->tree == TREE_BBA) BIEM_UINTERIOR_TREE(TREE_BBA)
-  else if (p->tree == TREE_CAA) BIEM_UINTERIOR_TREE(TREE_CAA)
-  else BIEM_UINTERIOR_TREE(TREE_A)
+  BIEM_FAST_TREE_DISPATCH(p->tree, BIEM_UINTERIOR_TREE)
 #undef BIEM_UINTERIOR_TREE
 #undef BIEM_UINTERIOR
   BIEM_LAUNCHCHK();

@@ -9,7 +9,7 @@
 //   ultrasphere presumably selects it - parity unpinned, no reference fixture has kind = "inner").  The exterior form is
 //   singular at r -> 0 and is not the potential there.  tests: jump relation u(rho+) - u(rho-) = density . Y, regularity at
 //   r = 0, Helmholtz residual inside the ball.
-#include "common.hpp"
+#include "fast_layout.hpp"   // BIEM_FAST_LAYOUT / TABLES / STAGE, BIEM_FIELD_HARMONICS, BIEM_GRAD_HARMONICS, the launchers' LDS size and dispatch
 
 namespace biem {
 
@@ -157,7 +157,6 @@ constexpr int kFastNendMaxCaa = 12;        // 4-D (caa): c in a dense [n][m1][m2
 // INNER (kind = "inner", near field): the radial factor is the regular function j_n(k r), whose upward recurrence is unstable
 // for n > |k r|: each lane computes j_0 .. j_{n_end-1} once per ball by the backward recurrence of radial_jh into its own LDS row
 // (64-thread workgroups; odd row stride: conflict-free 16-byte reads) and the harmonic loops read it by degree.
-#include "fast_layout.hpp"   // BIEM_FAST_LAYOUT, BIEM_FAST_TABLES, BIEM_FAST_STAGE
 template <int TREE, bool FAR, bool INNER>
 __global__ void __launch_bounds__(256) k_uscat_fast(int d, int H, int n_end, const int* __restrict__ labels, int nb, int B, int P,
                                                      const cplx* __restrict__ k, const double* __restrict__ centers,
@@ -208,165 +207,7 @@ __global__ void __launch_bounds__(256) k_uscat_fast(int d, int H, int n_end, con
       return csub(cmul(cscale(ix, two_q + dd2), hcur), hprev);
     };
     auto radial = [&](int n, const cplx& hup) -> cplx { if (INNER) return sJl[n]; return hup; };   // the radial factor of degree n
-    double ar = 0.0, ai = 0.0;
-    if (TREE == TREE_A) {
-      // Y_m = e^{i m theta} / sqrt(2 pi); degree n = |m|
-      const double e1x = r > 0.0 ? u[0] / r : 1.0, e1y = r > 0.0 ? u[1] / r : 0.0;
-      double ex = 1.0, ey = 0.0;
-      cplx hp = h0, hc = h1;               // h_n, h_{n+1}
-      for (int n = 0; n < n_end; ++n) {
-        const cplx cp = sC[n_end - 1 + n];
-        cplx t = make_double2(cp.x * ex - cp.y * ey, cp.x * ey + cp.y * ex);
-        if (n > 0) { const cplx cn = sC[n_end - 1 - n]; t.x += cn.x * ex + cn.y * ey; t.y += cn.y * ex - cn.x * ey; }
-        const cplx hv = radial(n, hp);
-        ar += hv.x * t.x - hv.y * t.y; ai += hv.x * t.y + hv.y * t.x;
-        const cplx hn = advance(hp, hc, 2.0 * n + 2.0);
-        hp = hc; hc = hn;
-        const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx;
-      }
-    } else if (TREE == TREE_BBA) {
-      // Y_{n l m} = s0^l g_{n-l}^{(l+1)}(c0) Pbar_l^{|m|}(c1) e^{i m phi} / sqrt(2 pi): three nested recurrences; (h_m, h_{m+1})
-      // runs along m, (h_l, h_{l+1}) along l from it, (h_n, h_{n+1}) along n from that - no restart from h_0
-      const double rho2 = sqrt(u[2] * u[2] + u[3] * u[3]), rho1 = sqrt(u[1] * u[1] + rho2 * rho2);
-      const double c0 = r > 0.0 ? u[0] / r : 1.0, s0 = r > 0.0 ? rho1 / r : 0.0;
-      const double c1 = rho1 > 0.0 ? u[1] / rho1 : 1.0, s1 = rho1 > 0.0 ? rho2 / rho1 : 0.0;
-      const double e1x = rho2 > 0.0 ? u[2] / rho2 : 1.0, e1y = rho2 > 0.0 ? u[3] / rho2 : 0.0;
-      const int mstride = 2 * n_end - 1;
-      double ex = 1.0, ey = 0.0, pmm = 0.70710678118654752440, s0m = 1.0;
-      cplx hm = h0, hm1 = h1;
-      for (int m = 0; m < n_end; ++m) {
-        if (m > 0) {
-          pmm *= cmm[m] * s1; s0m *= s0;
-          const cplx hn = advance(hm, hm1, 2.0 * m);
-          hm = hm1; hm1 = hn;
-          const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx;
-        }
-        double p0 = 0.0, p1 = pmm, sl = s0m;
-        cplx hl = hm, hl1 = hm1;
-        double sr = 0.0, si = 0.0, qr = 0.0, qi = 0.0;
-        for (int l = m; l < n_end; ++l) {
-          double gp0 = 0.0, gp1 = g0[l];
-          cplx hp = hl, hc = hl1;
-          const double alm = sl * p1;
-          for (int n = l; n < n_end; ++n) {
-            const double amp = alm * gp1;
-            const cplx hv = radial(n, hp);
-            const double wr = hv.x * amp, wi = hv.y * amp;
-            const cplx* cc = sC + (n * n_end + l) * mstride + n_end - 1;
-            const cplx cp = cc[m];
-            sr += wr * cp.x - wi * cp.y; si += wr * cp.y + wi * cp.x;
-            if (m > 0) { const cplx cn = cc[-m]; qr += wr * cn.x - wi * cn.y; qi += wr * cn.y + wi * cn.x; }
-            const int q = n - l + 1;
-            if (n + 1 < n_end) {
-              const double gp2 = (c0 * gp1 - ga[l * n_end + q - 1] * gp0) * gia[l * n_end + q];
-              gp0 = gp1; gp1 = gp2;
-              const cplx hn = advance(hp, hc, 2.0 * (n + 1));
-              hp = hc; hc = hn;
-            }
-          }
-          const int ql = l + 1;
-          if (ql < n_end) {
-            const double p2 = ra[ql * n_end + m] * (c1 * p1 - rb[ql * n_end + m] * p0);
-            p0 = p1; p1 = p2;
-            sl *= s0;
-            const cplx hn = advance(hl, hl1, 2.0 * ql);
-            hl = hl1; hl1 = hn;
-          }
-        }
-        ar += sr * ex - si * ey + qr * ex + qi * ey;
-        ai += sr * ey + si * ex + qi * ex - qr * ey;
-      }
-    } else if (TREE == TREE_CAA) {
-      // Y_{n m1 m2} = cos^a sin^b Pbar_k^{(b,a)}(cos 2 t0) e^{i (m1 t1 + m2 t2)} / (2 pi), a = |m1|, b = |m2|, n = a + b + 2 k: the
-      // Jacobi recurrence runs along k inside (a, b); the four sign combinations share it and the radial factor
-      const double r01 = sqrt(u[0] * u[0] + u[1] * u[1]), r23 = sqrt(u[2] * u[2] + u[3] * u[3]);
-      const double c0 = r > 0.0 ? r01 / r : 1.0, s0 = r > 0.0 ? r23 / r : 0.0, xx = c0 * c0 - s0 * s0;
-      const double e1x = r01 > 0.0 ? u[0] / r01 : 1.0, e1y = r01 > 0.0 ? u[1] / r01 : 0.0;
-      const double e2x = r23 > 0.0 ? u[2] / r23 : 1.0, e2y = r23 > 0.0 ? u[3] / r23 : 0.0;
-      double ca = 1.0, eax = 1.0, eay = 0.0;
-      cplx ha = h0, ha1 = h1;              // h_a, h_{a+1}
-      for (int a = 0; a < n_end; ++a) {
-        if (a > 0) {
-          ca *= c0;
-          const cplx hn = advance(ha, ha1, 2.0 * a);
-          ha = ha1; ha1 = hn;
-          const double nx = eax * e1x - eay * e1y; eay = eax * e1y + eay * e1x; eax = nx;
-        }
-        double sb = 1.0, ebx = 1.0, eby = 0.0;
-        cplx hb = ha, hb1 = ha1;           // h_{a+b}, h_{a+b+1}
-        for (int b = 0; a + b < n_end; ++b) {
-          if (b > 0) {
-            sb *= s0;
-            const cplx hn = advance(hb, hb1, 2.0 * (a + b));
-            hb = hb1; hb1 = hn;
-            const double nx = ebx * e2x - eby * e2y; eby = ebx * e2y + eby * e2x; ebx = nx;
-          }
-          const int tb = (a * n_end + b) * K2;
-          const double amp0 = ca * sb;
-          double p0 = 0.0, p1 = 1.0;
-          cplx hp = hb, hc = hb1;
-          double ppr = 0.0, ppi = 0.0, mpr = 0.0, mpi = 0.0, pmr = 0.0, pmi = 0.0, mmr = 0.0, mmi = 0.0;   // sums of the (+-a, +-b) coefficients
-          for (int kq = 0, n = a + b; n < n_end; ++kq, n += 2) {
-            const cplx hv = radial(n, hp);
-            const double amp = amp0 * jN[tb + kq] * p1;
-            const double wr = hv.x * amp, wi = hv.y * amp;
-            const cplx* cc = sC + (n * ms + n_end - 1) * ms + n_end - 1;
-            { const cplx cv = cc[a * ms + b]; ppr += wr * cv.x - wi * cv.y; ppi += wr * cv.y + wi * cv.x; }
-            if (a > 0) { const cplx cv = cc[-a * ms + b]; mpr += wr * cv.x - wi * cv.y; mpi += wr * cv.y + wi * cv.x; }
-            if (b > 0) { const cplx cv = cc[a * ms - b]; pmr += wr * cv.x - wi * cv.y; pmi += wr * cv.y + wi * cv.x; }
-            if (a > 0 && b > 0) { const cplx cv = cc[-a * ms - b]; mmr += wr * cv.x - wi * cv.y; mmi += wr * cv.y + wi * cv.x; }
-            if (n + 2 < n_end) {
-              const double p2 = (jA[tb + kq] * xx + jB[tb + kq]) * p1 - jC[tb + kq] * p0;
-              p0 = p1; p1 = p2;
-              cplx hn = advance(hp, hc, 2.0 * (n + 1));
-              hp = hc; hc = hn;
-              hn = advance(hp, hc, 2.0 * (n + 2));
-              hp = hc; hc = hn;
-            }
-          }
-          // e^{i (+-a t1 +- b t2)}
-          const double fx = eax * ebx - eay * eby, fy = eax * eby + eay * ebx;     // e^{i (a t1 + b t2)}
-          const double gx = eax * ebx + eay * eby, gy = eax * eby - eay * ebx;     // e^{i (-a t1 + b t2)}
-          ar += ppr * fx - ppi * fy + mmr * fx + mmi * fy + mpr * gx - mpi * gy + pmr * gx + pmi * gy;
-          ai += ppr * fy + ppi * fx + mmi * fx - mmr * fy + mpr * gy + mpi * gx + pmi * gx - pmr * gy;
-        }
-      }
-      ar *= kInvSqrt2Pi; ai *= kInvSqrt2Pi;   // (the second 1 / sqrt(2 pi) below)
-    } else {
-      const double rxy = sqrt(u[1] * u[1] + u[2] * u[2]);
-      const double c0 = r > 0.0 ? u[0] / r : 1.0, s0 = r > 0.0 ? rxy / r : 0.0;
-      const double e1x = rxy > 0.0 ? u[1] / rxy : 1.0, e1y = rxy > 0.0 ? u[2] / rxy : 0.0;
-      double ex = 1.0, ey = 0.0, pmm = 0.70710678118654752440;
-      cplx hm = h0, hm1 = h1;              // h_m, h_{m+1}: advanced by one per order m
-      for (int m = 0; m < n_end; ++m) {
-        if (m > 0) {
-          pmm *= cmm[m] * s0;
-          const cplx hn = advance(hm, hm1, 2.0 * m);
-          hm = hm1; hm1 = hn;
-          const double nx = ex * e1x - ey * e1y; ey = ex * e1y + ey * e1x; ex = nx;
-        }
-        cplx hp = hm, hc = hm1;            // h_n, h_{n+1} for n = m ..
-        double p0 = 0.0, p1 = pmm;
-        double sr = 0.0, si = 0.0;         // sum over n of h_n Pbar_n^m c_{n, +-m} (the e^{+- i m phi} factors applied once per m)
-        double qr = 0.0, qi = 0.0;
-        for (int n = m; n < n_end; ++n) {
-          const cplx cp = sC[n * n + n + m];
-          const cplx hv = radial(n, hp);
-          const double wr = hv.x * p1, wi = hv.y * p1;
-          sr += wr * cp.x - wi * cp.y; si += wr * cp.y + wi * cp.x;
-          if (m > 0) { const cplx cn = sC[n * n + n - m]; qr += wr * cn.x - wi * cn.y; qi += wr * cn.y + wi * cn.x; }
-          const int q = n + 1;
-          if (q < n_end) {
-            const double p2 = ra[q * n_end + m] * (c0 * p1 - rb[q * n_end + m] * p0);
-            p0 = p1; p1 = p2;
-            const cplx hn = advance(hp, hc, 2.0 * q);
-            hp = hc; hc = hn;
-          }
-        }
-        ar += sr * ex - si * ey + qr * ex + qi * ey;
-        ai += sr * ey + si * ex + qi * ex - qr * ey;
-      }
-    }
+    BIEM_FIELD_HARMONICS()                 // the harmonic loops (fast_layout.hpp, shared with k_uinterior_fast): defines ar, ai
     ar *= kInvSqrt2Pi; ai *= kInvSqrt2Pi;
     if (FAR) {
       // e^{-i k x.c_b} / (i k)^{(d-1)/2}, as in the generic kernel
@@ -642,17 +483,12 @@ int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, co
   // the far field does not depend on the kind; the near field of kind inner reads j_n from a per-lane LDS row (INNER)
   const bool far = (flags & BIEM_USCAT_FAR_FIELD) != 0;
   const bool inner = !far && (flags & BIEM_USCAT_KIND_INNER);
-  const int ne = p->n_end, ms = 2 * ne - 1;
+  const int ne = p->n_end;
   const bool fast_tree = (p->tree == TREE_BA && ne <= kFastNendMax3) || (p->tree == TREE_A && (big || ne <= kFastNendMax2)) ||
                          (p->tree == TREE_BBA && ne <= kFastNendMax4) || (p->tree == TREE_CAA && ne <= kFastNendMaxCaa);
   if (fast_tree && !getenv("BIEM_USCAT_GENERIC") && nb <= 65535) {
     const int T = inner ? 64 : 256;
-    size_t tab = 0, nC = 0;               // doubles of tables, complex of coefficients (the layout at the head of k_uscat_fast)
-    if (p->tree == TREE_BA) { tab = (size_t)2 * ne * ne + ((ne + 1) & ~1); nC = (size_t)ne * ne; }
-    else if (p->tree == TREE_BBA) { tab = (size_t)4 * ne * ne + 2 * ((ne + 1) & ~1); nC = (size_t)ne * ne * ms; }
-    else if (p->tree == TREE_CAA) { tab = (size_t)4 * ne * ne * ((ne + 1) / 2); nC = (size_t)ne * ms * ms; }
-    else nC = (size_t)ms;
-    const size_t shm = tab * sizeof(double) + (nC + (inner ? (size_t)T * ((ne + 2) | 1) : 0)) * sizeof(cplx);
+    const size_t shm = fast_layout_lds_bytes(p->tree, ne, T, inner ? (ne + 2) | 1 : 0);   // (the kernel's js)
     if (shm <= 160 * 1024) {
 #define BIEM_USCAT_FAST(TREE, FARF, INNERF)                                                                                      \
   {                                                                                                                              \
@@ -662,10 +498,7 @@ int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, co
   }
 #define BIEM_USCAT_FAST_TREE(TREE)                                                                                               \
   { if (far) BIEM_USCAT_FAST(TREE, true, false) else if (inner) BIEM_USCAT_FAST(TREE, false, true) else BIEM_USCAT_FAST(TREE, false, false) }
-      if (p->tree == TREE_BA) BIEM_USCAT_FAST_TREE(TREE_BA)
-      else if (p->tree == TREE_BBA) BIEM_USCAT_FAST_TREE(TREE_BBA)
-      else if (p->tree == TREE_CAA) BIEM_USCAT_FAST_TREE(TREE_CAA)
-      else BIEM_USCAT_FAST_TREE(TREE_A)
+      BIEM_FAST_TREE_DISPATCH(p->tree, BIEM_USCAT_FAST_TREE)
 #undef BIEM_USCAT_FAST_TREE
 #undef BIEM_USCAT_FAST
       BIEM_LAUNCHCHK();
@@ -684,9 +517,7 @@ int launch_uscat_grad(const biem_plan* p, int nb, int B, int P, const double* d_
                       const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
                       double* d_out, void* d_work, size_t work_bytes, hipStream_t st) {
   if (flags & BIEM_USCAT_FAR_FIELD) { set_error("biem_uscat_grad: the far-field pattern has no gradient in space (BIEM_USCAT_FAR_FIELD)"); return BIEM_ERR_ARG; }
-  const int ne = p->n_end, ms = 2 * ne - 1;
-  const int cap = p->tree == TREE_A ? kFastNendMax2 : p->tree == TREE_BA ? kFastNendMax3 : p->tree == TREE_BBA ? kFastNendMax4 :
-                  p->tree == TREE_CAA ? kFastNendMaxCaa : 0;
+  const int ne = p->n_end, cap = uscat_fast_nend_max(p->tree);
   if (cap == 0) {
     set_error("biem_uscat_grad: built for the trees a, ba (bpa), bba (bpbpa) and caa; chain trees (d=%d) are not covered", p->d);
     return BIEM_ERR_UNSUPPORTED;
@@ -700,12 +531,7 @@ int launch_uscat_grad(const biem_plan* p, int nb, int B, int P, const double* d_
   if (nb <= 0 || B <= 0 || P <= 0) return BIEM_OK;
   const bool inner = (flags & BIEM_USCAT_KIND_INNER) != 0;
   const int T = inner ? 64 : 256;
-  size_t tab = 0, nC = 0;                 // doubles of tables, complex of coefficients (BIEM_FAST_LAYOUT)
-  if (p->tree == TREE_BA) { tab = (size_t)2 * ne * ne + ((ne + 1) & ~1); nC = (size_t)ne * ne; }
-  else if (p->tree == TREE_BBA) { tab = (size_t)4 * ne * ne + 2 * ((ne + 1) & ~1); nC = (size_t)ne * ne * ms; }
-  else if (p->tree == TREE_CAA) { tab = (size_t)4 * ne * ne * ((ne + 1) / 2); nC = (size_t)ne * ms * ms; }
-  else nC = (size_t)ms;
-  const size_t shm = tab * sizeof(double) + (nC + (inner ? (size_t)T * ((ne + 3) | 1) : 0)) * sizeof(cplx);
+  const size_t shm = fast_layout_lds_bytes(p->tree, ne, T, inner ? (ne + 3) | 1 : 0);   // (the kernel's js)
   if (shm > 160 * 1024) {
     set_error("biem_uscat_grad: n_end=%d needs %zu bytes of LDS per workgroup (limit %d)", ne, shm, 160 * 1024);
     return BIEM_ERR_UNSUPPORTED;
@@ -723,10 +549,7 @@ int launch_uscat_grad(const biem_plan* p, int nb, int B, int P, const double* d_
                        B, P, (const cplx*)d_k, d_centers, d_radii, geom_batched, (const cplx*)c, d_points, flags, (cplx*)d_out); \
   }
 #define BIEM_USCAT_GRAD_TREE(TREE) { if (inner) BIEM_USCAT_GRAD(TREE, true) else BIEM_USCAT_GRAD(TREE, false) }
-  if (p->tree == TREE_BA) BIEM_USCAT_GRAD_TREE(TREE_BA)
-  else if (p->tree == TREE_BBA) BIEM_USCAT_GRAD_TREE(TREE_BBA)
-  else if (p->tree == TREE_CAA) BIEM_USCAT_GRAD_TREE(TREE_CAA)
-  else BIEM_USCAT_GRAD_TREE(TREE_A)
+  BIEM_FAST_TREE_DISPATCH(p->tree, BIEM_USCAT_GRAD_TREE)
 #undef BIEM_USCAT_GRAD_TREE
 #undef BIEM_USCAT_GRAD
   BIEM_LAUNCHCHK();
