@@ -156,7 +156,8 @@ BIEM_HD void radial_d(int d, int nmax, double x, double* J, double* Y) {
 // OUTGOING ones h_n = j_n + i y_n directly: for Im z > 0 both j and y grow like e^{Im z} while h decays, so h is never
 // formed as a sum.  (zc = double2: .x real, .y imaginary.)
 //   d = 3 : j_n by Miller's backward recurrence normalised with the larger of j_0 = sin z / z, j_1;  h_0 = -i e^{iz}/z,
-//           h_1 = -(z + i) e^{iz}/z^2, h_n by forward recurrence (h is the dominant solution in n).
+//           h_1 = -(z + i) e^{iz}/z^2, h_n by forward recurrence (h is the dominant solution in n); Im z < 0 through
+//           h(z) = 2 j(z) - conj(h(conj z)), as the integer orders below.
 //   d = 2,4: J_n by Miller's recurrence normalised with e^{-+iz} = J_0 + 2 sum_k (-+i)^k J_k (the sign that makes the
 //           right-hand side the large exponential); H_0, H_1 from the modified functions K_0, K_1 at w = -iz:
 //           H_0 = (2/(pi i)) K_0(w), H_1 = -(2/pi) K_1(w), with K by power series for |w| <= 2 and Steed's continued
@@ -220,16 +221,23 @@ BIEM_HD void bessel_jh_sph_c(int nmax, zc z, zc* J, zc* H) {
   zc scale = (zabs1(j0) >= zabs1(j1)) ? zdiv(j0, jc) : zdiv(j1, jp1);
   for (int q = 0; q <= nmax; ++q) J[q] = zmul(J[q], scale);
   if (H == nullptr) return;                     // regular functions only
-  // h_0 = -i e^{iz} / z,  h_1 = -(z + i) e^{iz} / z^2
-  zc e = zexp(zmk(-z.y, z.x));
-  zc h0 = zmul(zmk(e.y, -e.x), iz);                         // -i e
-  zc h1 = zmul(zmul(zmk(-(z.x), -(z.y + 1.0)), e), zmul(iz, iz));
+  // h_0 = -i e^{iz} / z,  h_1 = -(z + i) e^{iz} / z^2 at zz = z (Im z >= 0) or conj z: for Im z < 0 |h_n(z)| FALLS with n up to
+  // the turning point, so the forward recurrence there would amplify rounding by e^{2 |Im z|}
+  const bool up = z.y >= 0.0;
+  const zc zz = up ? z : zmk(z.x, -z.y);
+  const zc izz = up ? iz : zmk(iz.x, -iz.y);
+  zc e = zexp(zmk(-zz.y, zz.x));
+  zc h0 = zmul(zmk(e.y, -e.x), izz);                        // -i e
+  zc h1 = zmul(zmul(zmk(-(zz.x), -(zz.y + 1.0)), e), zmul(izz, izz));
   H[0] = h0;
   if (nmax >= 1) H[1] = h1;
   for (int n = 1; n < nmax; ++n) {
-    zc h2 = zsub(zscl(zmul(iz, h1), (double)(2 * n + 1)), h0);
+    zc h2 = zsub(zscl(zmul(izz, h1), (double)(2 * n + 1)), h0);
     H[n + 1] = h2;
     h0 = h1; h1 = h2;
+  }
+  if (!up) {                                               // h(z) = 2 j(z) - conj(h(conj z))
+    for (int n = 0; n <= nmax; ++n) H[n] = zsub(zscl(J[n], 2.0), zmk(H[n].x, -H[n].y));
   }
 }
 
