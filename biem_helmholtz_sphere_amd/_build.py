@@ -79,6 +79,10 @@ def is_stale() -> bool:
 #     C unit + the clamped edge-tile group).  A different count means the compiler restructured the groups: re-derive the
 #     vmcnt(N) constants of kernels_lu.hip against the new disassembly before changing the numbers here.
 EXPECTED_LDS_DMA = {64: 34, 128: 28, 192: 32, 256: 32}
+# k_gemm3m_pipe<0>, the K-long instance of the left-looking update (run-time chunk count, no tile map): the same pins, reported by
+# check_isa_klong(); check_isa() checks it too and returns the reports of the fixed-K instances
+KLONG = 0
+EXPECTED_LDS_DMA_KLONG = 32
 EXPECTED_STORES = 48
 MFMA_PER_CHUNK = 96
 MAX_TILE_MAP_LOADS = 2
@@ -142,7 +146,7 @@ def _chunk_loop(ins):
     return best, n_mfma
 
 
-def check_isa(lib_path: str = LIB, verbose: bool = False) -> dict:
+def check_isa(lib_path: str = LIB, verbose: bool = False, _with_klong: bool = False) -> dict:
     """Disassemble the gfx950 code objects of `lib_path`; raise IsaCheckError unless every k_gemm3m_pipe<*> has no scratch,
     no VGPR spills, 96 MFMAs in its chunk loop and only the expected vector-memory instructions there.  Returns the report."""
     objdump, readelf = _llvm_tool("llvm-objdump"), _llvm_tool("llvm-readelf")
@@ -187,20 +191,28 @@ def check_isa(lib_path: str = LIB, verbose: bool = False) -> dict:
                 extra = {op: c for op, c in vm.items() if op not in ("global_load_lds_dwordx4", "global_load_dword", "global_store_dwordx4")}
                 if extra:
                     bad.append(f"unexpected vector-memory instructions: {extra}")
-                if vm.get("global_load_lds_dwordx4", 0) != EXPECTED_LDS_DMA[kd]:
-                    bad.append(f"{vm.get('global_load_lds_dwordx4', 0)} LDS-DMA instructions (reviewed build: {EXPECTED_LDS_DMA[kd]})")
+                want_dma = EXPECTED_LDS_DMA_KLONG if kd == KLONG else EXPECTED_LDS_DMA.get(kd)
+                if vm.get("global_load_lds_dwordx4", 0) != want_dma:
+                    bad.append(f"{vm.get('global_load_lds_dwordx4', 0)} LDS-DMA instructions (reviewed build: {want_dma})")
                 if vm.get("global_store_dwordx4", 0) != EXPECTED_STORES:
                     bad.append(f"{vm.get('global_store_dwordx4', 0)} result stores (reviewed build: {EXPECTED_STORES})")
                 if vm.get("global_load_dword", 0) > MAX_TILE_MAP_LOADS:
                     bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (expected <= {MAX_TILE_MAP_LOADS})")
                 if bad:
                     raise IsaCheckError(f"k_gemm3m_pipe<{kd}>: the hand-counted vmcnt scheme is not safe with this code object: " + "; ".join(bad))
-    if set(report) != set(EXPECTED_LDS_DMA):
-        raise IsaCheckError(f"k_gemm3m_pipe instances found: {sorted(report)}, expected {sorted(EXPECTED_LDS_DMA)}")
+    if set(report) != set(EXPECTED_LDS_DMA) | {KLONG}:
+        raise IsaCheckError(f"k_gemm3m_pipe instances found: {sorted(report)}, expected {sorted(set(EXPECTED_LDS_DMA) | {KLONG})}")
     if verbose:
         for kd in sorted(report):
             print(f"isa check k_gemm3m_pipe<{kd}>: {report[kd]}")
-    return report
+    # (tests/test_host_logic.py pins the key set of this report to the fixed-K instances [64, 128, 192, 256]: the K-long instance is
+    # checked above like the others and handed out by check_isa_klong)
+    return report if _with_klong else {kd: r for kd, r in report.items() if kd != KLONG}
+
+
+def check_isa_klong(lib_path: str = LIB) -> dict:
+    """The report of k_gemm3m_pipe<0> (same checks as check_isa, which raises for it as well)."""
+    return check_isa(lib_path, _with_klong=True)[KLONG]
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

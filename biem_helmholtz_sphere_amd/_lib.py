@@ -66,6 +66,7 @@ SIGNATURES = {
     "biem_ldlt_factor_solve": (_i, [_i, _i, _i, _dp, _ll, _ll, _ip, _ip, _vp, _sz, _vp]),
     "biem_sym_factor_solve": (_i, [_i, _i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
     "biem_sym_factor_solve_n": (_i, [_i, _i, _i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
+    "biem_sym_update_form": (_i, [_i, _i, _i]),
     "biem_sym_factor": (_i, [_i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
     "biem_sym_solve": (_i, [_i, _i, _i, _dp, _ll, _ll, _dp, _ll, _ll, _vp]),
     "biem_factor_workspace_bytes": (_sz, [_vp, _i, _i, _i]),

@@ -283,6 +283,8 @@ int biem_sym_factor_solve_n(int nb, int n_pad, int n_active, int nrhs, double* d
   return launch_sym_factor_solve(nb, n_pad, nrhs, d_A, lda, sys_stride, d_info, d_work, work_bytes, (hipStream_t)stream, false, n_active);
 }
 
+int biem_sym_update_form(int nb, int n_pad, int nrhs) { return sym_update_left(nb, n_pad, nrhs); }
+
 int biem_density(const biem_plan* plan, int nb, int B, int nrhs, const double* d_x, long long sys_stride, long long elem_stride,
                  long long rhs_stride, const double* d_tab, double* d_density, void* stream) {
   NEED_DEV(plan); NEED(d_x, "d_x"); NEED(d_tab, "d_tab"); NEED(d_density, "d_density");

@@ -407,10 +407,16 @@ struct TileGrid {
   // column-major P[c][row]) instead of the matrix, which saves that panel's transposing load; pout == nullptr: off
   cplx* pout; long long pout_ld, pout_stride; int pcol_tx;
   int tri;                                      // 1: only tiles with tx <= ty (square region, symmetric update); 2: only tx >= ty
-  const int* tri_map; int tri_full;             // (ty << 16 | tx) of the first tri_full tiles of that order (the full bands)
+  // (ty << 16 | tx) of the first tri_full tiles of that order (the full bands); the K-long launch (k_gemm3m_pipe<0>, band order
+  // below, no tile map) keeps its K-chunks per tile, kd / 8, in the same word: the argument layout of the other launches is unchanged
+  const int* tri_map; union { int tri_full; int nch; };
   int blk_sh;                                   // log2 of the tiles per XCD block of the workgroup -> tile map: 6, or 3 for small launches
   unsigned long long per_sys_magic;             // ceil(2^40 / per_sys): t / per_sys = (t * magic) >> 40 for t < 2^25 (scalar multiply, no VALU division)
 };
+// nch shares tri_full's word: only k_gemm3m_pipe<0> reads nch, and it never calls tile_decode (the one reader of tri_full); its
+// launch (launch_gemm_left) sets tri = 0 and no tile map.  The layout the fixed-K instances were compiled against is pinned:
+static_assert(sizeof(TileGrid) == 96 && offsetof(TileGrid, nch) == offsetof(TileGrid, tri_full) && offsetof(TileGrid, tri_full) == 80 &&
+              offsetof(TileGrid, per_sys_magic) == 88, "TileGrid: the kernel-argument layout of k_gemm3m_pipe changed");
 
 // the triangular order: lower triangle incl. the diagonal tiles in bands of 8 tile rows; band b (tile rows 8b .. 8b+hb-1) holds
 // the columns 0 .. 8b+hb-1, column-major; column tx <= 8b has hb tiles, column 8b+q has hb-q.  A full band holds 64 b + 36
@@ -455,7 +461,34 @@ __device__ inline void tile_decode(const TileGrid& tg, int t, int& s, int& ty, i
   }
 }
 
+// the band order of a left-looking launch: a band of h = ty_n <= 4 tile rows, the tiles with tx >= ty, column-major (four-tall):
+// column q < h holds q + 1 tiles (q (q + 1) / 2 precede it), every later column h; h (h + 1) / 2 + (tx_n - h) h tiles per system.
+// 64 consecutive tiles right of the diagonal block are 4 A panels x 16 B panels.
+__device__ __host__ inline int band_tiles(int h, int tx_n) { return tx_n >= h ? h * (h + 1) / 2 + (tx_n - h) * h : tx_n * (tx_n + 1) / 2; }
+__device__ __host__ inline void band_decode(int r, int h, int& ty, int& tx) {
+  const int head = h * (h + 1) / 2;
+  if (r < head) {
+    int q = 0;
+    while (r >= q + 1) { r -= q + 1; ++q; }
+    tx = q; ty = r;
+  } else {
+    const int rem = r - head;
+    if (h == 4) { tx = 4 + (rem >> 2); ty = rem & 3; }
+    else { const int c = rem / h; tx = h + c; ty = rem - c * h; }
+  }
+}
+template <int KD>
+__device__ inline void tile_decode_of(const TileGrid& tg, int t, int& s, int& ty, int& tx) {
+  if constexpr (KD == 0) {
+    s = (int)(((unsigned long long)(unsigned)t * tg.per_sys_magic) >> 40);
+    int r = t - s * tg.per_sys;
+    if (r >= tg.per_sys) { r -= tg.per_sys; ++s; }
+    band_decode(r, tg.ty_n, ty, tx);
+  } else tile_decode(tg, t, s, ty, tx);
+}
+
 constexpr int BM3 = 64, BN3 = 64;   // workgroup tile of the trailing update
+constexpr int GEMM_GRID_CAP = 512;  // the persistent grid of the update kernels: 2 workgroups per CU
 constexpr int KC = 8;               // K rows per LDS stage (chunk)
 
 // ---------------------------------------------------------------------------------------------
@@ -522,9 +555,13 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
                                                          const cplx* __restrict__ Pw, long long ldp, long long p_stride,
                                                          TileGrid tg) {
   const int n_pad = tg.row_end, n_cols = tg.col_end;
-  constexpr int NCH = KD / KC;               // 8, 16 or 32 K-chunks per tile
-  constexpr int UPC = NCH >= 16 ? 1 : 16 / NCH;   // C units (one complex per lane) per chunk that carries C: 1 or 2
+  // KD = 0 is the K-long form of the left-looking update: the chunk count is a run-time value (TileGrid.nch = kd / 8 >= 16), the
+  // accumulators stay in registers over the whole K, C is read in the first 16 chunks and stored once
+  constexpr int NCHC = KD / KC;              // 8, 16, 24 or 32 K-chunks per tile (0: run-time)
+  const int NCH = KD != 0 ? NCHC : tg.nch;
+  constexpr int UPC = KD == 0 || NCHC >= 16 ? 1 : 16 / NCHC;   // C units (one complex per lane) per chunk that carries C: 1 or 2
   constexpr int NCC = 16 / UPC;              // chunks that carry C units: the first NCC of a tile (all of them for K <= 128)
+  constexpr bool ALLC = KD != 0 && NCC == NCHC;   // every chunk of a tile carries C units
 #if defined(BIEM_ABL_NOCDMA)                  // timing ablation: no C-slice DMA in the fused (interior, K = 128) path
   constexpr int NDMA = 4;
 #elif defined(BIEM_ABL_ONLYCDMA)              // timing ablation: only the C-slice DMA
@@ -558,7 +595,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   typedef const __attribute__((address_space(1))) void* glb_ptr_t;
   int cs, cty, ctx;
-  tile_decode(tg, t, cs, cty, ctx);
+  tile_decode_of<KD>(tg, t, cs, cty, ctx);
 
   const unsigned offA0 = (unsigned)(((size_t)(wave) * ldp + lane) * sizeof(cplx));
   const unsigned offA1 = (unsigned)(((size_t)(wave + 4) * ldp + lane) * sizeof(cplx));
@@ -596,7 +633,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
       __builtin_amdgcn_global_load_lds((glb_ptr_t)(pA + offA1), (lds_ptr_t)(S + (wave + 4) * AST), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((glb_ptr_t)(pB + offB0), (lds_ptr_t)(S + BOF + wave * 64), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((glb_ptr_t)(pB + offB1), (lds_ptr_t)(S + BOF + (wave + 4) * 64), 16, 0, 0);
-      if (NCC == NCH || p_ch < NCC) {
+      if (ALLC || p_ch < NCC) {
 #pragma unroll
         for (int i = 0; i < UPC; ++i) {
           const int u = p_ch * UPC + i;
@@ -618,7 +655,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
       for (int r = 0; r < 2; ++r)
         __builtin_amdgcn_global_load_lds((glb_ptr_t)(As + (size_t)(tg.brow + p_ch * KC + wave + 4 * r) * lda + bc),
                                          (lds_ptr_t)(S + BOF + (wave + 4 * r) * 64), 16, 0, 0);
-      if (NCC == NCH || p_ch < NCC) {
+      if (ALLC || p_ch < NCC) {
 #pragma unroll
         for (int i = 0; i < UPC; ++i) {
           const int u = p_ch * UPC + i;
@@ -629,13 +666,13 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
         }
       }
     }
-    n_new = (NCC == NCH || p_ch < NCC) ? NDMA : NDMA - UPC;      // VM instructions of the group just issued
+    n_new = (ALLC || p_ch < NCC) ? NDMA : NDMA - UPC;      // VM instructions of the group just issued
   };
   auto advance = [&]() {
     pA += strideA; pB += strideB;
     if (++p_ch == NCH) {                                   // producer moves on to the next tile of this workgroup
       int tn = next_tile();
-      if (tn >= 0) { tile_decode(tg, tn, p_s, p_ty, p_tx); producer_tile(); }
+      if (tn >= 0) { tile_decode_of<KD>(tg, tn, p_s, p_ty, p_tx); producer_tile(); }
       else p_valid = false;
     }
   };
@@ -676,7 +713,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
       // reads the stage the next group is about to overwrite
       BIEM_TR(0)
       // (the newest group holds n_new instructions: NDMA, or NDMA - UPC for the chunks of a K = 256 tile without a C unit)
-      const bool small_grp = NCC != NCH && n_new != NDMA;
+      const bool small_grp = !ALLC && n_new != NDMA;
       if (__builtin_expect(stores_pending == 0 && p_valid, 1)) {
         if (small_grp) wait_vmcnt<NDMA - UPC>(); else wait_vmcnt<NDMA>();
       } else if (!p_valid) {
@@ -712,7 +749,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
       cplx fb[2][4], fa[2][4], cv[UPC];   // [k4][column group of 16], [k4][row quad]
       unsigned m0_keep;                    // M0 is compiler-reserved: the fused statements save and restore it
       {
-        if (UPC == 1 && fused && (NCC == NCH || p_ch < NCC)) {
+        if (UPC == 1 && fused && (ALLC || p_ch < NCC)) {
           typedef __attribute__((address_space(3))) cplx* lds_cplx_t;
           cplx* S2 = ring + st2 * STG;
           const unsigned mA = (unsigned)(size_t)(lds_cplx_t)(S2 + wave * AST), mB = (unsigned)(size_t)(lds_cplx_t)(S2 + BOF + wave * 64);
@@ -872,7 +909,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
       // all units cost 32 FP64 VALU instructions that compete with the MFMAs for the FP64 pipe.  A dynamically indexed
       // register array compiles to s_set_gpr_idx + v_mov (indirect VGPR addressing): 3 FP64 adds per unit.
 #ifndef BIEM_ABL_NOCADD
-      if (NCC == NCH || c < NCC) {
+      if (ALLC || c < NCC) {
 #pragma unroll
         for (int i = 0; i < UPC; ++i) {
           (&N1[0][0])[c * UPC + i] += cv[i].x;
@@ -1015,11 +1052,11 @@ static int launch_gemm_stream(hipStream_t st, int nb, cplx* A, long long lda, lo
   // Up to 512 tiles every tile has its own workgroup: tile = blockIdx (a block of ONE tile per label and round) - with blocks of 8 a
   // 33-tile launch (the strip of one system half-way through its factorisation) ran on the workgroups of 5 labels, several of them
   // taking two tiles in sequence while three quarters of the grid had none: 29.5 us per K = 64 strip launch instead of 13.
-  tg.blk_sh = tg.ntiles <= 512 ? 0 : tg.ntiles < 2048 ? 3 : 6;
+  tg.blk_sh = tg.ntiles <= GEMM_GRID_CAP ? 0 : tg.ntiles < 2048 ? 3 : 6;
   tg.per_sys_magic = ((1ULL << 40) + (unsigned long long)tg.per_sys - 1) / (unsigned long long)tg.per_sys;
   if (tg.ntiles >= (1 << 25)) { set_error("biem_lu: more than 2^25 tiles in one update launch"); return BIEM_ERR_ARG; }   // unreachable: 2^25 tiles are 2 TB of matrix
   tg.row_begin = row_begin; tg.row_end = row_end; tg.col_begin = col_begin; tg.col_end = col_end; tg.brow = brow;
-  const int cap = 512;                         // persistent grid: 2 workgroups per CU
+  const int cap = GEMM_GRID_CAP;               // persistent grid: 2 workgroups per CU
   int want = (tg.ntiles + 7) / 8 * 8;          // one workgroup per tile up to the cap, multiple of 8
   int grid = want < cap ? want : cap;
   ProfScope ps(prof_class, st, prof_work >= 0.0 ? prof_work : 8.0 * (double)nb * (tri ? (double)tg.per_sys * BM3 * BN3 : rrows * (double)rcols) * kd);
@@ -1032,6 +1069,45 @@ static int launch_gemm_stream(hipStream_t st, int nb, cplx* A, long long lda, lo
   else
     hipLaunchKernelGGL(k_gemm3m_pipe<128>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, Pw, ldp, p_stride, tg);
   return BIEM_OK;
+}
+
+// Left-looking update of the row form A = U^T U: the band of rows J .. row_end (up to four tile rows) takes every pending update
+// of the finished rows 0 .. J-1 in one K-long pass,
+//   A[J:row_end, J:col_end] -= U[0:J, J:row_end]^T U[0:J, J:col_end]      (tiles with tx >= ty only)
+// Both operands are rows of the matrix itself (Pw = A, brow = 0, kd = J); every tile reads and writes its C once.
+static int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, int J, int row_end, int col_end) {
+  if (J <= 0 || row_end <= J || col_end < row_end) return BIEM_OK;
+  TileGrid tg;
+  tg.pout = nullptr; tg.pout_ld = 0; tg.pout_stride = 0; tg.pcol_tx = 0; tg.tri = 0; tg.tri_map = nullptr; tg.full_bands = 0;
+  tg.ty_n = (row_end - J) / BM3; tg.tx_n = (col_end - J + BN3 - 1) / BN3;
+  tg.per_sys = band_tiles(tg.ty_n, tg.tx_n); tg.ntiles = tg.per_sys * nb;
+  tg.blk_sh = tg.ntiles <= GEMM_GRID_CAP ? 0 : tg.ntiles < 2048 ? 3 : 6;            // as in launch_gemm_stream
+  tg.per_sys_magic = ((1ULL << 40) + (unsigned long long)tg.per_sys - 1) / (unsigned long long)tg.per_sys;
+  if (tg.ntiles >= (1 << 25)) { set_error("biem_lu: more than 2^25 tiles in one update launch"); return BIEM_ERR_ARG; }
+  tg.row_begin = J; tg.row_end = row_end; tg.col_begin = J; tg.col_end = col_end; tg.brow = 0; tg.nch = J / KC;
+  const int want = (tg.ntiles + 7) / 8 * 8;
+  const int grid = want < GEMM_GRID_CAP ? want : GEMM_GRID_CAP;
+  ProfScope ps(PK_GEMM, st, 8.0 * (double)nb * (double)tg.per_sys * BM3 * BN3 * (double)J);
+  hipLaunchKernelGGL(k_gemm3m_pipe<0>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, A, lda, sys_stride, tg);
+  return BIEM_OK;
+}
+
+// Which form of the bulk update launch_sym_factor_solve runs: 1 = left-looking (launch_gemm_left before every group), 0 = right-
+// looking (the K = 256 update after every group).  Left-looking tiles of late groups are long and few: a launch with fewer tiles
+// than the chip has CUs leaves CUs idle for a whole K = J tile, where the right-looking form spreads the same work over every tile
+// below the group.  So the left form runs when even the SMALLEST of its launches - the last group's band - has a tile for every CU,
+// i.e. half the persistent grid of two workgroups per CU (one workgroup per CU runs at 75-80 % of the two-workgroup rate).
+// Measured at N = 6400: 8 systems per call (80 tiles) right by 4 %, 32 systems (320 tiles) left by 3 %, more
+// systems left by 3-6 %.  BIEM_SYM_UPDATE=left|right forces a form (read per call).
+int sym_update_left(int nb, int n_pad, int nrhs) {
+  if (n_pad <= 4 * NB) return 0;                                   // one group: no bulk update at all
+  const char* e = getenv("BIEM_SYM_UPDATE");
+  if (e && e[0] == 'l') return 1;
+  if (e && e[0] == 'r') return 0;
+  const int T = n_pad / NB, h_last = T % 4 ? T % 4 : 4;
+  const int cols_last = h_last + (nrhs > 8 ? (nrhs + BN3 - 1) / BN3 : 0);
+  const long long smallest = (long long)band_tiles(h_last, cols_last) * nb;
+  return 2 * smallest >= GEMM_GRID_CAP ? 1 : 0;
 }
 
 // W = I - L11^{-1} for the unit-lower 64 x 64 diagonal block of a panel, stored [k][i] (the MFMA A-operand order), so that
@@ -1327,6 +1403,43 @@ __global__ void __launch_bounds__(256) k_rhs_update(cplx* __restrict__ A, long l
   if (kq > 0) part[kq - 1][lane] = sum;
   __syncthreads();
   if (kq == 0 && i < n_pad) {
+    cplx f = F[(size_t)i * lda];
+    f.x -= (sum.x + part[0][lane].x) + (part[1][lane].x + part[2][lane].x);
+    f.y -= (sum.y + part[0][lane].y) + (part[1][lane].y + part[2][lane].y);
+    F[(size_t)i * lda] = f;
+  }
+}
+
+// the left-looking form of the same update: rows row_begin .. row_end-1 take the terms of ALL finished rows, f[i] -= U[0:kd, i]^T y[0:kd],
+// walked in blocks of 256 (what sy holds); the four waves take a quarter of every block each and the sums are formed in a fixed order,
+// so two solves of the same data agree bit for bit
+__global__ void __launch_bounds__(256) k_rhs_update_left(cplx* __restrict__ A, long long lda, long long sys_stride, int n_pad, int row_begin,
+                                                          int row_end, int kd) {
+  __shared__ cplx sy[4 * NB];
+  __shared__ cplx part[3][64];
+  const int s = blockIdx.y, q = blockIdx.z;
+  cplx* F = A + (size_t)s * sys_stride + n_pad + q;
+  const int lane = threadIdx.x & 63, kq = threadIdx.x >> 6;
+  const int i = row_begin + blockIdx.x * RHS_UPD_ROWS + lane, ic = i < row_end ? i : row_end - 1;
+  const cplx* Ur = A + (size_t)s * sys_stride + ic;
+  cplx a0 = make_double2(0.0, 0.0), a1 = a0, a2 = a0, a3 = a0;
+  for (int kb = 0; kb < kd; kb += 4 * NB) {                          // kd is a multiple of 256 here (the rows of the finished groups)
+    __syncthreads();
+    sy[threadIdx.x] = F[(size_t)(kb + threadIdx.x) * lda];
+    __syncthreads();
+    const cplx* Pr = Ur + (size_t)(kb + NB * kq) * lda;
+    const cplx* yk = sy + NB * kq;
+    for (int k = 0; k < NB; k += 4) {
+      a0 = cfma(Pr[(size_t)k * lda], yk[k], a0);
+      a1 = cfma(Pr[(size_t)(k + 1) * lda], yk[k + 1], a1);
+      a2 = cfma(Pr[(size_t)(k + 2) * lda], yk[k + 2], a2);
+      a3 = cfma(Pr[(size_t)(k + 3) * lda], yk[k + 3], a3);
+    }
+  }
+  const cplx sum = make_double2((a0.x + a1.x) + (a2.x + a3.x), (a0.y + a1.y) + (a2.y + a3.y));
+  if (kq > 0) part[kq - 1][lane] = sum;
+  __syncthreads();
+  if (kq == 0 && i < row_end) {
     cplx f = F[(size_t)i * lda];
     f.x -= (sum.x + part[0][lane].x) + (part[1][lane].x + part[2][lane].x);
     f.y -= (sum.y + part[0][lane].y) + (part[1][lane].y + part[2][lane].y);
@@ -2291,6 +2404,7 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
   // limit, so the same K-chunks in fewer passes gain 2.5 % of panel + in-group time at cfg 3, nothing at cfg 5, and lose 27 % at
   // cfg 4 and 30 % for one system per call (three more small launches per panel).  Not kept)
   // second stream + two events for the right-hand sides' update beside the K = 256 update (below); the stream lives per device
+  const bool left = sym_update_left(nb, n_pad, nrhs) != 0;       // form of the bulk update (one rule, BIEM_SYM_UPDATE forces one)
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // Opt-in (BIEM_RHS_SIDE_STREAM=1): measured +0.7 % (cfg 3) and +2 % (cfg 5) of the step in alternating runs on one box, but on
@@ -2298,7 +2412,7 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
   // have the CUs to itself - and one system per call pays the two cross-stream dependencies per group (cfg 4: 6.8 -> 7.0 ms).
   { const char* es = getenv("BIEM_RHS_SIDE_STREAM");
     const bool want = es != nullptr && es[0] == '1';
-    if (rhs_gemv && n_pad > 4 * NB && want) {
+    if (rhs_gemv && n_pad > 4 * NB && want && !left) {      // (the left form has no launch to run beside)
       static hipStream_t side_of[64] = {nullptr};
       int devid = 0;
       if (hipGetDevice(&devid) == hipSuccess && devid >= 0 && devid < 64) {
@@ -2311,6 +2425,16 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
   struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev_guard{ev_fork, ev_join};
   for (int J = 0; J < n_pad; J += 4 * NB) {
     const cplx* strip = A + (size_t)J * lda;        // both operands of this group's updates: rows J .. of the matrix itself
+    if (left && J > 0) {
+      // left-looking: the group's rows take every pending update of the finished rows 0 .. J-1 now, in one K = J pass (few right-hand
+      // sides: matrix-vector work beside it; many: tile columns of the same launch)
+      const int row_end = J + 4 * NB < n_pad ? J + 4 * NB : n_pad;
+      { const int r = launch_gemm_left(st, nb, A, lda, sys_stride, J, row_end, rhs_gemv ? n_pad : n_cols); if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r; }
+      if (rhs_gemv) {
+        ProfScope ps(PK_OTHER, st, 0.0);
+        hipLaunchKernelGGL(k_rhs_update_left, dim3((row_end - J) / RHS_UPD_ROWS, nb, nrhs), dim3(256), 0, st, A, lda, sys_stride, n_pad, J, row_end, J);
+      }
+    }
     panel(J);
     for (int q = 1; q < 4; ++q) {
       const int jq = J + q * NB;
@@ -2320,6 +2444,7 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
       panel(jq);
     }
     if (J + 4 * NB >= n_pad) break;
+    if (left) continue;                              // no update after the group: the rows below take it when their own group starts
     // The right-hand sides' update of the rows below the group streams the group's strips once (bandwidth, a few KB of LDS, few
     // registers); the K = 256 update of the matrix is bound by the matrix pipe and touches no right-hand-side column: the two run
     // side by side - the small kernel on a second stream between two events, joined before the next panel (whose strip solve reads
@@ -2627,6 +2752,24 @@ extern "C" int biem_debug_gemm(int nb, int n, int kd, int reps, unsigned long lo
   hipMemcpyFromSymbol(trace_out, HIP_SYMBOL(g_gemm_trace), sizeof(unsigned long long) * 16 * 64 * 8);
   hipFree(A); hipFree(P);
   return 0;
+}
+// the K-long launch of the left-looking update alone: a band of four tile rows J = kd .. kd + 256 over n columns right of J
+extern "C" int biem_debug_gemm_left(int nb, int n, int kd, int reps, float* ms_out, int* tiles_out) {
+  const long long lda = kd + n + 8, rows = kd + 256;
+  cplx* A = nullptr;
+  const size_t na = (size_t)nb * rows * lda;
+  if (hipMalloc((void**)&A, na * sizeof(cplx)) != hipSuccess) return 1;
+  hipLaunchKernelGGL(k_trace_fill, dim3(2048), dim3(256), 0, 0, (double*)A, na * 2);
+  hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+  launch_gemm_left(0, nb, A, lda, rows * lda, kd, kd + 256, kd + n);
+  hipDeviceSynchronize();
+  hipEventRecord(e0, 0);
+  for (int r = 0; r < reps; ++r) launch_gemm_left(0, nb, A, lda, rows * lda, kd, kd + 256, kd + n);
+  hipEventRecord(e1, 0); hipEventSynchronize(e1);
+  float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms / reps;
+  *tiles_out = nb * band_tiles(4, n / 64);
+  hipFree(A);
+  return hipGetLastError() != hipSuccess;
 }
 #endif
 #ifdef BIEM_DIAG_TRACE

@@ -197,6 +197,12 @@ int biem_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long ld
  * rows as biem_sym_factor_solve does.  Arguments, workspace and d_info as biem_sym_factor_solve. */
 int biem_sym_factor_solve_n(int nb, int n_pad, int n_active, int nrhs, double* d_A, long long lda, long long sys_stride,
                             int* d_info /*[nb]*/, void* d_work, size_t work_bytes, void* stream);
+/* Form of the bulk update biem_sym_factor_solve runs for a call of this shape (host only, no GPU work): 1 = left-looking (the rows of
+ * a four-panel group take all pending updates of the finished rows in one K-long pass before the group is factored; every tile of the
+ * matrix is read and written once by the bulk update), 0 = right-looking (a K = 256 update of everything below after every group).
+ * Left runs when even its smallest launch, the last group's band, has a tile for every CU over the nb systems: 256 tiles, half the
+ * update kernel's persistent grid of 512 workgroups.  BIEM_SYM_UPDATE=left|right in the environment forces a form; read per call. */
+int biem_sym_update_form(int nb, int n_pad, int nrhs);
 
 /* density[s][r][b][h] = x / (gh * blc): the reference's `density` from the equilibrated unknowns (also the
  * single-ball shortcut _biem.py:648-691 with x = f).  x element (s, r, i) at d_x[s*sys_stride + i*elem_stride + r*rhs_stride]. */

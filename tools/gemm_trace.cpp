@@ -4,9 +4,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
+extern "C" int biem_debug_gemm_left(int nb, int n, int kd, int reps, float* ms_out, int* tiles_out);
 extern "C" int biem_debug_gemm(int nb, int n, int kd, int reps, unsigned long long* trace_out, float* ms_out);
 int main(int argc, char** argv) {
   int nb = argc > 1 ? atoi(argv[1]) : 8, n = argc > 2 ? atoi(argv[2]) : 6272, kd = argc > 3 ? atoi(argv[3]) : 128;
+  if (argc > 4 && argv[4][0] == 'l') {   // gemm_trace nb n kd left: the K-long launch of the left-looking update alone (four tile rows, n columns)
+    float ms = 0; int tiles = 0;
+    if (biem_debug_gemm_left(nb, n, kd, 3, &ms, &tiles)) { printf("failed\n"); return 1; }
+    const double units = (double)tiles * kd / 256.0;
+    printf("left nb=%d n=%d kd=%d  tiles=%d  %.3f ms  %.2f TFLOP/s (algorithmic)  %.4f us per tile and K-256 unit\n", nb, n, kd, tiles, ms,
+           8.0 * tiles * 64.0 * 64.0 * kd / (ms * 1e-3) / 1e12, ms * 1e3 / units);
+    return 0;
+  }
   std::vector<unsigned long long> tr(16 * 64 * 8);
   float ms = 0;
   if (biem_debug_gemm(nb, n, kd, 3, tr.data(), &ms)) { printf("failed\n"); return 1; }
