@@ -18,8 +18,9 @@ from collections import Counter
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbiem_mi355.so")
-SOURCES = ["abi.cpp", "plan.cpp", "kernels_fill.hip", "kernels_degree_bc.hip", "kernels_uscat.hip", "kernels_uinterior.hip", "kernels_lu.hip"]
-HEADERS = ["common.hpp", "plan.hpp", "special.hpp", "fast_layout.hpp", os.path.join("..", "..", "include", "biem_mi355.h")]
+SOURCES = ["abi.cpp", "plan.cpp", "kernels_fill.hip", "kernels_degree_bc.hip", "kernels_uscat.hip", "kernels_uinterior.hip",
+           "kernels_gemm3m.hip", "kernels_lu.hip", "kernels_sym.hip", "kernels_trisolve.hip"]
+HEADERS = ["common.hpp", "plan.hpp", "special.hpp", "fast_layout.hpp", "dense.hpp", os.path.join("..", "..", "include", "biem_mi355.h")]
 _MARK = b"BIEM_SRC_HASH="
 
 
@@ -77,7 +78,7 @@ def is_stale() -> bool:
 #     producer moves to its next tile; hipcc waits vmcnt(0) for it, which only drains the ring early);
 #   * the static number of LDS-DMA instructions equals the count of the reviewed build (prologue + fused groups with / without a
 #     C unit + the clamped edge-tile group).  A different count means the compiler restructured the groups: re-derive the
-#     vmcnt(N) constants of kernels_lu.hip against the new disassembly before changing the numbers here.
+#     vmcnt(N) constants of kernels_gemm3m.hip against the new disassembly before changing the numbers here.
 EXPECTED_LDS_DMA = {64: 34, 128: 28, 192: 32, 256: 32}
 # k_gemm3m_pipe<0>, the K-long instance of the left-looking update (run-time chunk count, no tile map): the same pins, reported by
 # check_isa_klong(); check_isa() checks it too and returns the reports of the fixed-K instances

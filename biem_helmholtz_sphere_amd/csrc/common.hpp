@@ -143,7 +143,7 @@ size_t lu_workspace_bytes(int nb, int n_pad, int nrhs);
 int launch_lu_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long lda, long long sys_stride, int* d_ipiv,
                            int* d_info, void* d_work, size_t work_bytes, hipStream_t st, bool keep_multipliers = true,
                            bool symmetric = false, bool amax_ready = false);
-// complex-symmetric A = U^T U in row form on the upper triangle (kernels_lu.hip), fused with the solve of the augmented columns
+// complex-symmetric A = U^T U in row form on the upper triangle (kernels_sym.hip), fused with the solve of the augmented columns
 int sym_update_left(int nb, int n_pad, int nrhs);  // form of the bulk update launch_sym_factor_solve runs for this call: 1 left-looking, 0 right-looking
 bool sym_small_path(int n_active, int nrhs);      // whether launch_sym_factor_solve takes its one-launch LDS-resident path
 // (n_active: rows n_active .. n_pad-1 are identity padding; systems of at most 128 active rows run in one LDS-resident launch)

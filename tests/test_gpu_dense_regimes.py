@@ -5,7 +5,7 @@ the persistent path of launch_gemm_stream (a workgroup walking several tiles in 
 across tile boundaries), and no call spans 2^31 elements.  The headline step runs almost only there.  This module
 
   * models the update schedule of the factorisations (which gemm launches, with how many tiles, in which regime) after
-    biem_helmholtz_sphere_amd/csrc/kernels_lu.hip, and checks on the CPU that the case lists below reach every regime;
+    biem_helmholtz_sphere_amd/csrc/kernels_{gemm3m,sym,lu}.hip, and checks on the CPU that the case lists below reach every regime;
   * runs those cases on the GPU with entry-wise checks: backward residual and info of every system, U^T U = A of every system
     (row-form symmetric path), exact zeros in the padding rows of the solution, and numpy.linalg.solve on a few systems;
   * drives the one-launch small-system kernel (k_small_utu) through biem_sym_factor_solve_n with NaN in the padding it promises
@@ -26,37 +26,37 @@ except ImportError:  # the schedule model and its coverage test need no torch
 
 gpu = pytest.mark.gpu
 
-# ---------------------------------------------------------------------------- schedule model (kernels_lu.hip)
-NB = 64                  # panel width, tile edge BM3 = BN3 (kernels_lu.hip:458)
-SMALL_N_MAX, SMALL_RHS_MAX, SMALL_THREADS = 128, 8, 512     # kernels_lu.hip:1814-1816
+# ---------------------------------------------------------------------------- schedule model (csrc/kernels_gemm3m.hip, kernels_sym.hip, kernels_lu.hip)
+NB = 64                  # panel width, tile edge BM3 = BN3 (dense.hpp; kernels_gemm3m.hip)
+SMALL_N_MAX, SMALL_RHS_MAX, SMALL_THREADS = 128, 8, 512     # kernels_sym.hip, at k_small_utu
 
 
 def npad_of(N):
-    return -(-N // NB) * NB                                          # lu_npad, kernels_lu.hip:27
+    return -(-N // NB) * NB                                          # lu_npad, kernels_lu.hip
 
 
 def gemm_launch(kind, nb, row_begin, row_end, col_begin, col_end, kd, tri=0):
-    """One launch_gemm_stream call (kernels_lu.hip:999-1036): its tile grid and persistent-block regime, or None if empty."""
+    """One launch_gemm_stream call (kernels_gemm3m.hip, with finish_tile_grid): its tile grid and persistent-block regime, or None if empty."""
     rrows, rcols = row_end - row_begin, col_end - col_begin
     if rrows <= 0 or rcols <= 0:
         return None
-    ty_n, tx_n = -(-rrows // NB), -(-rcols // NB)                   # :1008
-    per_sys = ty_n * (ty_n + 1) // 2 if tri else ty_n * tx_n         # :1009
+    ty_n, tx_n = -(-rrows // NB), -(-rcols // NB)
+    per_sys = ty_n * (ty_n + 1) // 2 if tri else ty_n * tx_n
     ntiles = per_sys * nb
-    blk_sh = 0 if ntiles <= 512 else 3 if ntiles < 2048 else 6      # :1018
+    blk_sh = 0 if ntiles <= 512 else 3 if ntiles < 2048 else 6      # finish_tile_grid
     return dict(kind=kind, kd=kd, tri=tri, ty_n=ty_n, tx_n=tx_n, per_sys=per_sys, ntiles=ntiles, blk_sh=blk_sh,
-                full_bands=ty_n // 8, grid=min((ntiles + 7) // 8 * 8, 512), col_end=col_end, rcols=rcols)   # :1009, :1021-1024
+                full_bands=ty_n // 8, grid=min((ntiles + 7) // 8 * 8, 512), col_end=col_end, rcols=rcols)   # finish_tile_grid
 
 
 def sym_small_path(n_active, nrhs, no_small=False):
-    """kernels_lu.hip:2204-2207 (BIEM_NO_SMALL_PATH switches it off)."""
-    lds = (n_active * (n_active + 1) // 2 + n_active * nrhs + 4 * n_active) * 16          # small_utu_lds, :1819
+    """sym_small_path, kernels_sym.hip (BIEM_NO_SMALL_PATH switches it off)."""
+    lds = (n_active * (n_active + 1) // 2 + n_active * nrhs + 4 * n_active) * 16          # small_utu_lds
     return (0 < n_active <= SMALL_N_MAX and nrhs <= SMALL_RHS_MAX and n_active + nrhs <= 128 and lds <= 160 * 1024 - 2048
             and not no_small)
 
 
 def small_instance(n_active, nrhs):
-    """The k_small_utu<KR, TWO> instantiation launch_sym_factor_solve picks (kernels_lu.hip:2231-2243)."""
+    """The k_small_utu<KR, TWO> instantiation launch_sym_factor_solve picks (kernels_sym.hip, at BIEM_SMALL)."""
     two = n_active + nrhs > 64
     kr = -(-n_active // (SMALL_THREADS // 64))
     if not two:
@@ -68,15 +68,15 @@ def small_instance(n_active, nrhs):
 
 
 def sym_schedule(nb, n_pad, nrhs, n_active=None, no_small=False):
-    """launch_sym_factor_solve (row form A = U^T U, kernels_lu.hip:2209-2402) with the default environment."""
+    """launch_sym_factor_solve (row form A = U^T U, kernels_sym.hip) with the default environment."""
     n_active = n_pad if n_active is None else n_active
     if sym_small_path(n_active, nrhs, no_small):
         return dict(small=small_instance(n_active, nrhs), launches=[], back=None)
     n_cols = n_pad + nrhs
-    rhs_gemv = 0 < nrhs <= 8                                                       # :2260
-    col_form = nb <= 64                                                            # :2265
-    keep_w = col_form and 0 < nrhs <= 3 * NB and nb <= 8                           # :2268
-    back = "keep_w" if keep_w else "col" if (nrhs > 4 * NB or (col_form and nrhs > 0)) else "row"   # :2361-2384
+    rhs_gemv = 0 < nrhs <= 8
+    col_form = nb <= 64
+    keep_w = col_form and 0 < nrhs <= 3 * NB and nb <= 8
+    back = "keep_w" if keep_w else "col" if (nrhs > 4 * NB or (col_form and nrhs > 0)) else "row"
     out = []
 
     def add(*a, **k):
@@ -84,28 +84,28 @@ def sym_schedule(nb, n_pad, nrhs, n_active=None, no_small=False):
         if g:
             out.append(g)
 
-    def panel(j):                                                                  # :2276-2287
+    def panel(j):                                                                  # its `panel` lambda
         if n_cols > j + NB:
             add("panel", nb, j, j + NB, j + NB, n_cols, NB)
 
-    for J in range(0, n_pad, 4 * NB):                                              # :2312
+    for J in range(0, n_pad, 4 * NB):
         panel(J)
         for q in range(1, 4):
             jq = J + q * NB
             if jq >= n_pad:
                 break
-            add("in_group", nb, jq, jq + NB, jq, n_cols, q * NB)                   # :2319
+            add("in_group", nb, jq, jq + NB, jq, n_cols, q * NB)
             panel(jq)
         if J + 4 * NB >= n_pad:
             break
-        add("k256", nb, J + 4 * NB, n_pad, J + 4 * NB, n_pad, 4 * NB, tri=2)       # :2336 (upper triangle of tiles)
+        add("k256", nb, J + 4 * NB, n_pad, J + 4 * NB, n_pad, 4 * NB, tri=2)       # (upper triangle of tiles)
         if not rhs_gemv and nrhs > 0:
-            add("rhs", nb, J + 4 * NB, n_pad, n_pad, n_cols, 4 * NB)               # :2345
+            add("rhs", nb, J + 4 * NB, n_pad, n_pad, n_cols, 4 * NB)
     return dict(small=None, launches=out, back=back)
 
 
 def lu_schedule(nb, n_pad, nrhs, symmetric=False):
-    """launch_lu_factor_solve (kernels_lu.hip:1463-1663): the pivoted LU, or its column form L D L^T (symmetric=True)."""
+    """launch_lu_factor_solve (kernels_lu.hip): the pivoted LU, or its column form L D L^T (symmetric=True)."""
     n_cols = n_pad + nrhs
     out = []
 
@@ -114,20 +114,20 @@ def lu_schedule(nb, n_pad, nrhs, symmetric=False):
         if g:
             out.append(g)
 
-    def trsm(j, col_begin=None):                                                   # :1537-1548
+    def trsm(j, col_begin=None):                                                   # its `trsm` lambda
         col_begin = j + NB if col_begin is None else col_begin
         add("trsm", nb, j, j + NB, col_begin, n_cols, NB)
 
     if symmetric:
-        rhs_gemv = 0 < nrhs <= 8                                                   # :1550
+        rhs_gemv = 0 < nrhs <= 8
 
-        def u_rows_sym(j, pc):                                                     # :1551-1563
+        def u_rows_sym(j, pc):                                                     # its `u_rows_sym` lambda
             if not rhs_gemv and nrhs > 0:
                 if pc > 0:
                     add("rhs", nb, j, j + NB, n_pad, n_cols, pc)
                 trsm(j, n_pad)
 
-        for J in range(0, n_pad, 4 * NB):                                          # :1585
+        for J in range(0, n_pad, 4 * NB):
             u_rows_sym(J, 0)
             for q in range(1, 4):
                 jq = J + q * NB
@@ -142,7 +142,7 @@ def lu_schedule(nb, n_pad, nrhs, symmetric=False):
                 add("rhs", nb, J + 4 * NB, n_pad, n_pad, n_cols, 4 * NB)
         return dict(small=None, launches=out, back="col" if nrhs > 0 else None)
 
-    for J in range(0, n_pad, 4 * NB):                                              # :1622-1653
+    for J in range(0, n_pad, 4 * NB):
         trsm(J)
         if J + NB >= n_pad:
             break

@@ -5,7 +5,7 @@ triangle below.  Left-looking: immediately before group J is factored its (up to
 
     A[J:J+256, J:n_cols] -= U[0:J, J:J+256]^T U[0:J, J:n_cols]          (K = J, tiles with tx >= ty only)
 
-by k_gemm3m_pipe<0> (launch_gemm_left, kernels_lu.hip), whose chunk count is a run-time value; the right-hand sides take the same
+by k_gemm3m_pipe<0> (launch_gemm_left, kernels_gemm3m.hip), whose chunk count is a run-time value; the right-hand sides take the same
 terms in k_rhs_update_left (nrhs <= 8, K walked in blocks of 256) or as tile columns of the same launch (nrhs > 8).
 
 This module
@@ -38,7 +38,7 @@ def npad_of(N):
     return -(-N // NB) * NB
 
 
-# ---------------------------------------------------------------------------- model of the left form (kernels_lu.hip)
+# ---------------------------------------------------------------------------- model of the left form (kernels_gemm3m.hip: sym_update_left, launch_gemm_left; kernels_sym.hip: launch_sym_factor_solve)
 def band_tiles(h, tx_n):
     """Tiles of a band of h <= 4 tile rows and tx_n >= h tile columns with tx >= ty."""
     return h * (h + 1) // 2 + (tx_n - h) * h if tx_n >= h else tx_n * (tx_n + 1) // 2

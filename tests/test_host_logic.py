@@ -133,6 +133,16 @@ def test_isa_check_of_the_built_library():
         assert set(r["vm"]) <= {"global_load_lds_dwordx4", "global_load_dword", "global_store_dwordx4"}, (kd, r)
 
 
+def test_build_lists_every_file_of_csrc():
+    """The files in csrc/ are exactly the translation units and the csrc headers of the build: one missing from the lists would be
+    missing from the library, or (a header) from the hash that tells a stale library from a current one."""
+    from biem_helmholtz_sphere_amd import _build
+
+    listed = _build.SOURCES + [h for h in _build.HEADERS if os.path.dirname(h) == ""]
+    assert len(set(listed)) == len(listed)
+    assert sorted(listed) == sorted(os.listdir(_build.CSRC))
+
+
 def test_plane_wave_contract():
     u, g = amd.plane_wave(k=np.asarray(2.0), direction=np.asarray((0.0, 3.0, 0.0)))
     x = np.zeros((3, 4, 2))

@@ -1,6 +1,6 @@
 // gemm_trace.cpp -- timeline of the trailing-update kernel's chunk loop (diagnostic; built with -DBIEM_GEMM_TRACE together
 // with the library sources):  hipcc -O3 -std=c++17 --offload-arch=gfx950 -DBIEM_GEMM_TRACE tools/gemm_trace.cpp \
-//     biem_helmholtz_sphere_amd/csrc/{abi.cpp,plan.cpp,kernels_fill.hip,kernels_uscat.hip,kernels_lu.hip} -o tools/gemm_trace
+//     biem_helmholtz_sphere_amd/csrc/*.cpp biem_helmholtz_sphere_amd/csrc/*.hip -o tools/gemm_trace   (tools/build_trace.sh)
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
