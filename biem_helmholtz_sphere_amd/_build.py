@@ -84,6 +84,20 @@ EXPECTED_LDS_DMA = {64: 34, 128: 28, 192: 32, 256: 32}
 # check_isa_klong(); check_isa() checks it too and returns the reports of the fixed-K instances
 KLONG = 0
 EXPECTED_LDS_DMA_KLONG = 32
+# The reviewed K-long build keeps every scalar of its chunk loop in SGPRs: no v_readlane / v_writelane (scalars spilled to VGPR lanes and
+# read back in front of the MFMA block) inside the loop.  The build before it had 15 and ran the bulk update measurably slower
+# (DESIGN.md section 5), so a compiler that brings them back is reported, not taken silently.
+MAX_LANE_SPILL_OPS_KLONG = 0
+# k_gemm3m_strip, the product form of the K = 64 kernel (symmetric strip pass: no C slots, four DMAs per group): the same pins, under
+# the key STRIP, handed out by check_isa_strip().  In its chunk loop the vector-memory instructions are the ring's LDS-DMA alone: the
+# product form adds none.  24 = six groups of four (prologue, fused, unfused interior and clamped edge
+# forms), every wait is vmcnt(4), vmcnt(4 + 16) behind a full tile's stores, or vmcnt(0).
+# The epilogue that carries the right-hand sides adds, outside the chunk loop, exactly 5 global_load_dwordx4 (z_j of the lane's four
+# rows, the 64 entries of Y) and 17 stores (a fourth form of the 16 result stores, Y); tiles that run it end with vmcnt(0).
+STRIP = "strip"
+EXPECTED_LDS_DMA_STRIP = 24
+EXPECTED_STORES_STRIP = 65
+EXPECTED_LOADS_STRIP = 5
 EXPECTED_STORES = 48
 MFMA_PER_CHUNK = 96
 MAX_TILE_MAP_LOADS = 2
@@ -147,7 +161,7 @@ def _chunk_loop(ins):
     return best, n_mfma
 
 
-def check_isa(lib_path: str = LIB, verbose: bool = False, _with_klong: bool = False) -> dict:
+def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = False) -> dict:
     """Disassemble the gfx950 code objects of `lib_path`; raise IsaCheckError unless every k_gemm3m_pipe<*> has no scratch,
     no VGPR spills, 96 MFMAs in its chunk loop and only the expected vector-memory instructions there.  Returns the report."""
     objdump, readelf = _llvm_tool("llvm-objdump"), _llvm_tool("llvm-readelf")
@@ -164,16 +178,17 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _with_klong: bool = Fa
         for o in objs:
             path = os.path.join(tmp, o)
             metas = _kernel_meta(readelf, path)
-            gemm = [n for n in metas if "k_gemm3m_pipe" in n]
+            gemm = [n for n in metas if "k_gemm3m_pipe" in n or "k_gemm3m_strip" in n]
             if not gemm:
                 continue
             dis = _disassemble(objdump, path)
             for name in gemm:
-                kd = int(re.search(r"k_gemm3m_pipeILi(\d+)E", name).group(1))
+                kd = STRIP if "k_gemm3m_strip" in name else int(re.search(r"k_gemm3m_pipeILi(\d+)E", name).group(1))
+                label = "k_gemm3m_strip" if kd == STRIP else f"k_gemm3m_pipe<{kd}>"
                 meta, ins = metas[name], dis[name]
                 loop, n_mfma = _chunk_loop(ins)
                 if loop is None:
-                    raise IsaCheckError(f"k_gemm3m_pipe<{kd}>: no loop holds the kernel's MFMAs")
+                    raise IsaCheckError(f"{label}: no loop holds the kernel's MFMAs")
                 ops = Counter(op for _, op, _ in ins)
                 lops = Counter(op for _, op, _ in loop)
                 vm = {op: c for op, c in ops.items() if op.startswith(("global_", "buffer_", "flat_", "scratch_"))}
@@ -190,30 +205,41 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _with_klong: bool = Fa
                 if rep["mfma_in_chunk_loop"] != MFMA_PER_CHUNK or n_mfma != MFMA_PER_CHUNK:
                     bad.append(f"{rep['mfma_in_chunk_loop']} MFMAs in the chunk loop, {n_mfma} in the kernel (expected {MFMA_PER_CHUNK})")
                 extra = {op: c for op, c in vm.items() if op not in ("global_load_lds_dwordx4", "global_load_dword", "global_store_dwordx4")}
+                if kd == STRIP and extra.get("global_load_dwordx4") == EXPECTED_LOADS_STRIP and \
+                        not any(op == "global_load_dwordx4" for _, op, _ in loop):
+                    del extra["global_load_dwordx4"]
                 if extra:
                     bad.append(f"unexpected vector-memory instructions: {extra}")
-                want_dma = EXPECTED_LDS_DMA_KLONG if kd == KLONG else EXPECTED_LDS_DMA.get(kd)
+                want_dma = EXPECTED_LDS_DMA_STRIP if kd == STRIP else EXPECTED_LDS_DMA_KLONG if kd == KLONG else EXPECTED_LDS_DMA.get(kd)
                 if vm.get("global_load_lds_dwordx4", 0) != want_dma:
                     bad.append(f"{vm.get('global_load_lds_dwordx4', 0)} LDS-DMA instructions (reviewed build: {want_dma})")
-                if vm.get("global_store_dwordx4", 0) != EXPECTED_STORES:
-                    bad.append(f"{vm.get('global_store_dwordx4', 0)} result stores (reviewed build: {EXPECTED_STORES})")
+                want_stores = EXPECTED_STORES_STRIP if kd == STRIP else EXPECTED_STORES
+                if vm.get("global_store_dwordx4", 0) != want_stores:
+                    bad.append(f"{vm.get('global_store_dwordx4', 0)} result stores (reviewed build: {want_stores})")
+                if kd == KLONG and rep["lane_spill_ops_in_chunk_loop"] > MAX_LANE_SPILL_OPS_KLONG:
+                    bad.append(f"{rep['lane_spill_ops_in_chunk_loop']} lane-spill instructions in the chunk loop (reviewed build: {MAX_LANE_SPILL_OPS_KLONG})")
                 if vm.get("global_load_dword", 0) > MAX_TILE_MAP_LOADS:
                     bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (expected <= {MAX_TILE_MAP_LOADS})")
                 if bad:
-                    raise IsaCheckError(f"k_gemm3m_pipe<{kd}>: the hand-counted vmcnt scheme is not safe with this code object: " + "; ".join(bad))
-    if set(report) != set(EXPECTED_LDS_DMA) | {KLONG}:
-        raise IsaCheckError(f"k_gemm3m_pipe instances found: {sorted(report)}, expected {sorted(set(EXPECTED_LDS_DMA) | {KLONG})}")
+                    raise IsaCheckError(f"{label}: the hand-counted vmcnt scheme is not safe with this code object: " + "; ".join(bad))
+    if set(report) != set(EXPECTED_LDS_DMA) | {KLONG, STRIP}:
+        raise IsaCheckError(f"update kernels found: {sorted(report, key=str)}, expected {sorted(set(EXPECTED_LDS_DMA) | {KLONG, STRIP}, key=str)}")
     if verbose:
-        for kd in sorted(report):
-            print(f"isa check k_gemm3m_pipe<{kd}>: {report[kd]}")
-    # (tests/test_host_logic.py pins the key set of this report to the fixed-K instances [64, 128, 192, 256]: the K-long instance is
-    # checked above like the others and handed out by check_isa_klong)
-    return report if _with_klong else {kd: r for kd, r in report.items() if kd != KLONG}
+        for kd in sorted(report, key=str):
+            print(f"isa check {'k_gemm3m_strip' if kd == STRIP else f'k_gemm3m_pipe<{kd}>'}: {report[kd]}")
+    # (tests/test_host_logic.py pins the key set of this report to the fixed-K instances [64, 128, 192, 256]: the K-long instance and the
+    # strip kernel are checked above like the others and handed out by check_isa_klong / check_isa_strip)
+    return report if _all_kernels else {kd: r for kd, r in report.items() if kd not in (KLONG, STRIP)}
 
 
 def check_isa_klong(lib_path: str = LIB) -> dict:
     """The report of k_gemm3m_pipe<0> (same checks as check_isa, which raises for it as well)."""
-    return check_isa(lib_path, _with_klong=True)[KLONG]
+    return check_isa(lib_path, _all_kernels=True)[KLONG]
+
+
+def check_isa_strip(lib_path: str = LIB) -> dict:
+    """The report of k_gemm3m_strip (same checks as check_isa, which raises for it as well)."""
+    return check_isa(lib_path, _all_kernels=True)[STRIP]
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

@@ -54,7 +54,7 @@ __device__ inline double lane_bcast(double v, int i) {
   return __hiloint2double(hi, lo);
 }
 constexpr int BACK_ROWS = 16;   // rows per workgroup (4 per wave)
-constexpr int RHS_UPD_ROWS = 64;  // rows per workgroup of k_rhs_update / k_rhs_update_left
+constexpr int RHS_UPD_ROWS = 64;  // rows per workgroup of k_rhs_update
 
 #pragma GCC visibility push(hidden)   // between the units of one library: none of these is exported
 // ---- kernels_gemm3m.hip
@@ -65,6 +65,10 @@ int launch_gemm_stream(hipStream_t st, int nb, cplx* A, long long lda, long long
                        long long pout_stride = 0, int pcol_tx = 0, const int* tri_map = nullptr, bool upper = false);
 // the K-long left-looking update of the row form: A[J:row_end, J:col_end] -= U[0:J, J:row_end]^T U[0:J, J:col_end]
 int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, int J, int row_end, int col_end);
+// the strip of panel j of the symmetric factorisation as a pure product: A[j:j+64, j+64:col_end] = -V^T A[j:j+64, j+64:col_end] (pass V - j);
+// with Y (compact Y[s][q][row], y_ld rows per right-hand side, nrhs <= 8) also Y[.., c] -= U[j:j+64, c]^T Y[.., j:j+64] for the strip's columns
+int launch_gemm_strip(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, const cplx* V, long long v_stride, int j, int col_end,
+                      cplx* Y = nullptr, int nrhs = 0, int y_ld = 0);
 void launch_tri_map(hipStream_t st, int* tri_map, int n_pad);   // tile map of the triangular updates of an n_pad system
 // ---- kernels_trisolve.hip
 void launch_zero_int(hipStream_t st, int* p, int n);

@@ -175,10 +175,39 @@ __device__ unsigned long long g_gemm_trace[16][64][8];
 #define BIEM_TR(i)
 #define BIEM_TR_NEXT()
 #endif
-template <int KD>
-__global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, long long lda, long long sys_stride,
-                                                         const cplx* __restrict__ Pw, long long ldp, long long p_stride,
-                                                         TileGrid tg) {
+// the 16 fragment reads of a chunk and the four operand DMAs of a fused group, as the statements below spell them out: the text of
+// the product form's groups, which carry no C unit
+#define BIEM_FRAG_READS16                                                                                                                  \
+  "ds_read_b128 %[b0], %[aB]\n\tds_read_b128 %[b1], %[aB] offset:256\n\tds_read_b128 %[b2], %[aB] offset:512\n\tds_read_b128 %[b3], %[aB] offset:768\n\t" \
+  "ds_read_b128 %[b4], %[aB] offset:4096\n\tds_read_b128 %[b5], %[aB] offset:4352\n\tds_read_b128 %[b6], %[aB] offset:4608\n\tds_read_b128 %[b7], %[aB] offset:4864\n\t" \
+  "ds_read_b128 %[a0], %[aA]\n\tds_read_b128 %[a1], %[aA] offset:64\n\tds_read_b128 %[a2], %[aA] offset:128\n\tds_read_b128 %[a3], %[aA] offset:192\n\t" \
+  "ds_read_b128 %[a4], %[aA] offset:4352\n\tds_read_b128 %[a5], %[aA] offset:4416\n\tds_read_b128 %[a6], %[aA] offset:4480\n\tds_read_b128 %[a7], %[aA] offset:4544\n\t"
+#define BIEM_OPERAND_DMA4                                                                     \
+  "s_mov_b32 %[keep], m0\n\t"                                                                 \
+  "s_mov_b32 m0, %[mA]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA0], %[pA]\n\t"               \
+  "s_add_u32 m0, %[mA], 4352\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA1], %[pA]\n\t"         \
+  "s_mov_b32 m0, %[mB]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB0], %[pB]\n\t"               \
+  "s_add_u32 m0, %[mB], 4096\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB1], %[pB]\n\t"         \
+  "s_mov_b32 m0, %[keep]\n\t"
+#define BIEM_FRAG_OUTS                                                                                                                     \
+  [a0] "=&v"(fa[0][0]), [a1] "=&v"(fa[0][1]), [a2] "=&v"(fa[0][2]), [a3] "=&v"(fa[0][3]), [a4] "=&v"(fa[1][0]), [a5] "=&v"(fa[1][1]),       \
+  [a6] "=&v"(fa[1][2]), [a7] "=&v"(fa[1][3]), [b0] "=&v"(fb[0][0]), [b1] "=&v"(fb[0][1]), [b2] "=&v"(fb[0][2]), [b3] "=&v"(fb[0][3]),       \
+  [b4] "=&v"(fb[1][0]), [b5] "=&v"(fb[1][1]), [b6] "=&v"(fb[1][2]), [b7] "=&v"(fb[1][3])
+
+// One text of the tile loop for two kernels (as fast_layout.hpp does for the field kernels): k_gemm3m_pipe<KD> is the body with
+// PROD = false.  PROD = true is the pure product of the symmetric strip pass (k_gemm3m_strip, K = 64): no C slots in the stage, four
+// DMAs and 16 fragment reads per chunk, no C additions; the accumulators start at zero, so the tile stored is -A^T B.
+//
+// The product form also carries the forward substitution of up to 8 right-hand sides (StripRhs, Y[s][q][row] compact): the strip of
+// panel j holds the finished rows U[j .. j+63, :], and y[c] -= sum_r U[j + r, c] z_j[r] for the 64 columns c of a tile is taken from the
+// tile in registers - in a fixed order: in-lane over the four row quads, across lane >> 4, then across the four waves through LDS.
+// Exactly one workgroup per (panel, tile column, system) touches those 64 entries: no atomics, two solves agree bit for bit.  Its
+// loads and stores are unknown to the ring's vmcnt counts: such a tile ends with stores_pending = 2 (vmcnt(0) at the next first chunk).
+struct StripRhs { cplx* Y; int nrhs; int ld; };   // Y == nullptr: none; ld = rows per right-hand side (n_pad)
+template <int KD, bool PROD>
+__device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda, long long sys_stride, const cplx* __restrict__ Pw,
+                                            long long ldp, long long p_stride, const TileGrid& tg, const StripRhs& yr) {
+  static_assert(!PROD || KD == 64, "the product form exists for the K = 64 strip only");
   const int n_pad = tg.row_end, n_cols = tg.col_end;
   // KD = 0 is the K-long form of the left-looking update: the chunk count is a run-time value (TileGrid.nch = kd / 8 >= 16), the
   // accumulators stay in registers over the whole K, C is read in the first 16 chunks and stored once
@@ -192,13 +221,16 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
 #elif defined(BIEM_ABL_ONLYCDMA)              // timing ablation: only the C-slice DMA
   constexpr int NDMA = 1;
 #else
-  constexpr int NDMA = 4 + UPC;              // LDS-DMA instructions per wave per chunk
+  constexpr int NDMA = PROD ? 4 : 4 + UPC;   // LDS-DMA instructions per wave per chunk
 #endif
   constexpr int AST = 68;                    // A row stride in LDS: +4 elements (64 B) so the broadcast A-fragment reads of
                                              // two k-rows in one ds_read_b128 lane group hit different banks
   constexpr int BOF = KC * AST;              // B block offset inside a stage
   constexpr int COF = BOF + KC * 64;         // C-slice offset
-  constexpr int STG = COF + UPC * 256;       // complex elements per stage
+  constexpr int STG = COF + (PROD ? 0 : UPC * 256);   // complex elements per stage
+  // (A fused group of its own for the K-long steady state - consumer and producer both past the NCC chunks that carry C, so 16 reads
+  // and no read of the C slot - was built and measured against this text in one A/B: the bulk update ran 11 ms per cfg 3 step SLOWER
+  // with it, 972.2 against 961.0 ms.  Not kept)
   __shared__ cplx ring[3 * STG];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: LDS-DMA bases (M0) and tile offsets stay on the SALU
@@ -258,7 +290,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
       __builtin_amdgcn_global_load_lds((glb_ptr_t)(pA + offA1), (lds_ptr_t)(S + (wave + 4) * AST), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((glb_ptr_t)(pB + offB0), (lds_ptr_t)(S + BOF + wave * 64), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((glb_ptr_t)(pB + offB1), (lds_ptr_t)(S + BOF + (wave + 4) * 64), 16, 0, 0);
-      if (ALLC || p_ch < NCC) {
+      if (!PROD && (ALLC || p_ch < NCC)) {
 #pragma unroll
         for (int i = 0; i < UPC; ++i) {
           const int u = p_ch * UPC + i;
@@ -280,7 +312,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
       for (int r = 0; r < 2; ++r)
         __builtin_amdgcn_global_load_lds((glb_ptr_t)(As + (size_t)(tg.brow + p_ch * KC + wave + 4 * r) * lda + bc),
                                          (lds_ptr_t)(S + BOF + (wave + 4 * r) * 64), 16, 0, 0);
-      if (ALLC || p_ch < NCC) {
+      if (!PROD && (ALLC || p_ch < NCC)) {
 #pragma unroll
         for (int i = 0; i < UPC; ++i) {
           const int u = p_ch * UPC + i;
@@ -291,7 +323,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
         }
       }
     }
-    n_new = (ALLC || p_ch < NCC) ? NDMA : NDMA - UPC;      // VM instructions of the group just issued
+    n_new = (PROD || ALLC || p_ch < NCC) ? NDMA : NDMA - UPC;      // VM instructions of the group just issued
   };
   auto advance = [&]() {
     pA += strideA; pB += strideB;
@@ -374,7 +406,22 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
       cplx fb[2][4], fa[2][4], cv[UPC];   // [k4][column group of 16], [k4][row quad]
       unsigned m0_keep;                    // M0 is compiler-reserved: the fused statements save and restore it
       {
-        if (UPC == 1 && fused && (ALLC || p_ch < NCC)) {
+        if (PROD && fused) {
+          // the product form: 16 fragment reads, the four operand DMAs
+          typedef __attribute__((address_space(3))) cplx* lds_cplx_t;
+          cplx* S2 = ring + st2 * STG;
+          const unsigned mA = (unsigned)(size_t)(lds_cplx_t)(S2 + wave * AST), mB = (unsigned)(size_t)(lds_cplx_t)(S2 + BOF + wave * 64);
+          asm volatile(BIEM_FRAG_READS16 BIEM_OPERAND_DMA4 "s_waitcnt lgkmcnt(0)"
+                       : [keep] "=&s"(m0_keep), BIEM_FRAG_OUTS
+                       : [aA] "v"(aA), [aB] "v"(aB), [mA] "s"(mA), [mB] "s"(mB), [oA0] "v"(offA0), [oA1] "v"(offA1), [oB0] "v"(offB0),
+                         [oB1] "v"(offB1), [pA] "s"(pA), [pB] "s"(pB)
+                       : "memory", "scc");
+          __builtin_amdgcn_sched_barrier(0);
+          n_new = NDMA;
+          advance();
+        } else if constexpr (PROD) {
+          asm volatile(BIEM_FRAG_READS16 "s_waitcnt lgkmcnt(0)" : BIEM_FRAG_OUTS : [aA] "v"(aA), [aB] "v"(aB) : "memory");
+        } else if (UPC == 1 && fused && (ALLC || p_ch < NCC)) {
           typedef __attribute__((address_space(3))) cplx* lds_cplx_t;
           cplx* S2 = ring + st2 * STG;
           const unsigned mA = (unsigned)(size_t)(lds_cplx_t)(S2 + wave * AST), mB = (unsigned)(size_t)(lds_cplx_t)(S2 + BOF + wave * 64);
@@ -534,7 +581,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
       // all units cost 32 FP64 VALU instructions that compete with the MFMAs for the FP64 pipe.  A dynamically indexed
       // register array compiles to s_set_gpr_idx + v_mov (indirect VGPR addressing): 3 FP64 adds per unit.
 #ifndef BIEM_ABL_NOCADD
-      if (ALLC || c < NCC) {
+      if (!PROD && (ALLC || c < NCC)) {
 #pragma unroll
         for (int i = 0; i < UPC; ++i) {
           (&N1[0][0])[c * UPC + i] += cv[i].x;
@@ -609,6 +656,60 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
         }
       }
     } else if (full) {
+      if constexpr (PROD) {
+        // (only full tiles carry right-hand sides: launch_gemm_strip refuses Y with a partial tile column, so no tile of a launch
+        // with Y takes the clamped branch below, which would skip its term)
+        if (yr.Y != nullptr) {
+          __shared__ cplx red[2][4][64];                   // [q & 1][wave][column]: one barrier per right-hand side
+          // the tile's values take the accumulators' place (N1: real, N3: imaginary part); the stores below read them there
+#pragma unroll
+          for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              const double re = N1[n][g] + P2[n][g], im = N3[n][g] - N1[n][g] + P2[n][g];
+              N1[n][g] = re; N3[n][g] = im; P2[n][g] = 0.0;
+            }
+          cplx* Yq = yr.Y + (size_t)cs * yr.nrhs * yr.ld;
+#pragma unroll 1
+          for (int q = 0; q < yr.nrhs; ++q, Yq += yr.ld) {
+            const cplx* zq = Yq + row0 + wave * 16 + l4;   // z_j of this lane's four rows 16 w + 4 g + (lane >> 4)
+            cplx z[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) z[g] = zq[4 * g];
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+              cplx a = make_double2(0.0, 0.0);
+#pragma unroll
+              for (int g = 0; g < 4; ++g) a = cfma(make_double2(N1[n][g], N3[n][g]), z[g], a);
+              a.x += __shfl_xor(a.x, 16, 64); a.y += __shfl_xor(a.y, 16, 64);
+              a.x += __shfl_xor(a.x, 32, 64); a.y += __shfl_xor(a.y, 32, 64);
+              if (l4 == 0) red[q & 1][wave][16 * n + l15] = a;
+            }
+            __syncthreads();
+            if (wave == 0) {
+              const cplx r0 = red[q & 1][0][lane], r1 = red[q & 1][1][lane], r2 = red[q & 1][2][lane], r3 = red[q & 1][3][lane];
+              cplx* yp = Yq + col0 + lane;
+              cplx y = *yp;
+              y.x -= (r0.x + r1.x) + (r2.x + r3.x);
+              y.y -= (r0.y + r1.y) + (r2.y + r3.y);
+              *yp = y;
+            }
+          }
+          char* tb = (char*)(Cs + (size_t)row0 * lda + col0);
+#pragma unroll
+          for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              const long long du = ((long long)(4 * g) * lda + n * 16) * (long long)sizeof(cplx);
+              *(cplx*)(tb + du + offC) = make_double2(N1[n][g], N3[n][g]);
+              N1[n][g] = 0.0; N3[n][g] = 0.0;
+            }
+          if (++c_tiles == p_tiles) break;
+          stores_pending = 2;
+          cs = p_s; cty = p_ty; ctx = p_tx;
+          continue;
+        }
+      }
       char* tb = (char*)(Cs + (size_t)row0 * lda + col0);
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
@@ -655,6 +756,19 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
     for (int i = tid; i < 4 * 64 * 8; i += 256) g_gemm_trace[blockIdx.x * 4 + (i >> 9)][(i >> 3) & 63][i & 7] = s_tr[i];
   }
 #endif
+}
+
+template <int KD>
+__global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, long long lda, long long sys_stride,
+                                                         const cplx* __restrict__ Pw, long long ldp, long long p_stride,
+                                                         TileGrid tg) {
+  gemm3m_body<KD, false>(A, lda, sys_stride, Pw, ldp, p_stride, tg, StripRhs{nullptr, 0, 0});
+}
+// the strip pass of the symmetric factorisation, U12 = U11^{-T} C as the pure product -V^T C with V = -U11^{-T} (64 x 64 per system, K = 64)
+__global__ void __launch_bounds__(256, 2) k_gemm3m_strip(cplx* __restrict__ A, long long lda, long long sys_stride,
+                                                          const cplx* __restrict__ Pw, long long ldp, long long p_stride,
+                                                          TileGrid tg, StripRhs yr) {
+  gemm3m_body<64, true>(A, lda, sys_stride, Pw, ldp, p_stride, tg, yr);
 }
 
 void launch_tri_map(hipStream_t st, int* tri_map, int n_pad) {
@@ -704,6 +818,25 @@ int launch_gemm_stream(hipStream_t st, int nb, cplx* A, long long lda, long long
     hipLaunchKernelGGL(k_gemm3m_pipe<192>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, Pw, ldp, p_stride, tg);
   else
     hipLaunchKernelGGL(k_gemm3m_pipe<128>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, Pw, ldp, p_stride, tg);
+  return BIEM_OK;
+}
+
+// The strip of panel j of the symmetric factorisation: rows j .. j+63, columns j+64 .. col_end become -V^T times themselves (V: 64 x 64
+// per system, addressed by absolute row like the panels: pass V - j) - the product kernel, C is neither read nor added.  With Y (compact
+// right-hand sides Y[s][q][row], y_ld rows each, nrhs <= 8) every tile also takes its 64 columns' term of the forward substitution,
+// Y[.., c] -= U[j : j+64, c]^T Y[.., j : j+64]; col_end is then a multiple of 64 past j (full tiles only).
+int launch_gemm_strip(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, const cplx* V, long long v_stride, int j, int col_end,
+                      cplx* Y, int nrhs, int y_ld) {
+  if (col_end <= j + NB) return BIEM_OK;
+  if (Y != nullptr && ((col_end - j) % BN3 != 0 || nrhs < 1 || nrhs > 8)) { set_error("biem_sym: strip with right-hand sides over a partial tile column"); return BIEM_ERR_ARG; }
+  TileGrid tg;
+  tg.pout = nullptr; tg.pout_ld = 0; tg.pout_stride = 0; tg.pcol_tx = 0; tg.tri = 0; tg.tri_map = nullptr; tg.tri_full = 0; tg.full_bands = 0;
+  tg.ty_n = 1; tg.tx_n = (col_end - j - NB + BN3 - 1) / BN3;
+  tg.row_begin = j; tg.row_end = j + NB; tg.col_begin = j + NB; tg.col_end = col_end; tg.brow = j;
+  const int grid = finish_tile_grid(tg, tg.tx_n, nb);
+  if (grid == 0) return BIEM_ERR_ARG;
+  ProfScope ps(PK_PANEL, st, 8.0 * (double)nb * (col_end - j - NB) * NB * NB);
+  hipLaunchKernelGGL(k_gemm3m_strip, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, V, (long long)NB, v_stride, tg, StripRhs{Y, Y != nullptr ? nrhs : 0, y_ld});
   return BIEM_OK;
 }
 

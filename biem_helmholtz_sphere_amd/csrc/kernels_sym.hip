@@ -6,18 +6,20 @@
 // So the factorisation works in place on the upper triangle: no column-major panel workspace, no transposing panel load / store,
 // no transposed GEMM epilogue, no separate "U rows from L" pass - a panel is two passes over its strip instead of about six.
 //   k_diag_utu_reg (one workgroup per system, defined with the small-system kernel below; k_diag_utu_blk: four pivots per barrier): the 64 x 64 diagonal block: pivots d,
-//               U11 = D^{-1/2} (D L11^T), W = I - U11^{-T}, multiplier test inside the block
-//   strip:      U12 = U11^{-T} A12 = A12 - W A12 in place on the streaming zgemm (K = 64, B operand = the strip's own rows; the
-//               right-hand-side columns are columns of the strip: forward elimination rides along).  A one-thread-per-column
-//               VALU form with the triangle of U11^{-T} from the scalar cache or LDS was 5x slower (292 vs 53 ms per 256 systems)
+//               U11 = D^{-1/2} (D L11^T), V = -U11^{-T} (and W = I + V where the back substitution keeps it), multiplier test inside the block
+//   strip:      U12 = U11^{-T} A12 = -V^T A12 in place on the streaming zgemm's product form (k_gemm3m_strip, K = 64, B operand = the
+//               strip's own rows, V = -U11^{-T}: C is neither loaded nor added).  More than 8 right-hand sides are columns of the
+//               strip: forward elimination rides along; up to 8 live in the compact copy Y[s][q][row] - the diagonal-block kernel
+//               solves its 64 entries, the strip's epilogue subtracts every tile's term from the 64 entries under it.  A one-thread-
+//               per-column VALU form with the triangle of U11^{-T} from the scalar cache or LDS was 5x slower (292 vs 53 ms per 256 systems)
 //   checks:     multiplier test |u_ic| <= 100 |u_ii| and growth max |u_ii u_ic| of the strip entries are taken where the entries
 //               are read anyway: in the back substitution (k_back_update)
 //   in-group:   the next panel's 64 rows take the group's pending updates (K = 64 q) for all columns right of them
-//   K = 256:    one update of the UPPER triangle of tiles below the group (TileGrid.tri = 2), right-hand sides by k_rhs_update
+//   K = 256:    one update of the UPPER triangle of tiles below the group (TileGrid.tri = 2), more than 8 right-hand sides as tile columns
 // Only the upper triangle and the diagonal 64 x 64 tiles of A are read.  Growth check as in the L D L^T form, with moduli:
 // max |d_i l_ci| = max |u_ii u_ic| against max |a_ij| over the part read.
 // Large batches take the bulk update left-looking: launch_gemm_left before a group instead of the K = 256 update after it (sym_update_left).
-// The update kernel is kernels_gemm3m.hip's; the column-form back substitution and k_rhs_update are kernels_trisolve.hip's.
+// The update kernels are kernels_gemm3m.hip's; the column-form back substitution is kernels_trisolve.hip's.
 #include "dense.hpp"
 
 namespace biem {
@@ -207,43 +209,6 @@ __global__ void __launch_bounds__(256) k_back_step(const cplx* __restrict__ A, l
   }
 }
 
-// the left-looking form of the same update: rows row_begin .. row_end-1 take the terms of ALL finished rows, f[i] -= U[0:kd, i]^T y[0:kd],
-// walked in blocks of 256 (what sy holds); the four waves take a quarter of every block each and the sums are formed in a fixed order,
-// so two solves of the same data agree bit for bit
-__global__ void __launch_bounds__(256) k_rhs_update_left(cplx* __restrict__ A, long long lda, long long sys_stride, int n_pad, int row_begin,
-                                                          int row_end, int kd) {
-  __shared__ cplx sy[4 * NB];
-  __shared__ cplx part[3][64];
-  const int s = blockIdx.y, q = blockIdx.z;
-  cplx* F = A + (size_t)s * sys_stride + n_pad + q;
-  const int lane = threadIdx.x & 63, kq = threadIdx.x >> 6;
-  const int i = row_begin + blockIdx.x * RHS_UPD_ROWS + lane, ic = i < row_end ? i : row_end - 1;
-  const cplx* Ur = A + (size_t)s * sys_stride + ic;
-  cplx a0 = make_double2(0.0, 0.0), a1 = a0, a2 = a0, a3 = a0;
-  for (int kb = 0; kb < kd; kb += 4 * NB) {                          // kd is a multiple of 256 here (the rows of the finished groups)
-    __syncthreads();
-    sy[threadIdx.x] = F[(size_t)(kb + threadIdx.x) * lda];
-    __syncthreads();
-    const cplx* Pr = Ur + (size_t)(kb + NB * kq) * lda;
-    const cplx* yk = sy + NB * kq;
-    for (int k = 0; k < NB; k += 4) {
-      a0 = cfma(Pr[(size_t)k * lda], yk[k], a0);
-      a1 = cfma(Pr[(size_t)(k + 1) * lda], yk[k + 1], a1);
-      a2 = cfma(Pr[(size_t)(k + 2) * lda], yk[k + 2], a2);
-      a3 = cfma(Pr[(size_t)(k + 3) * lda], yk[k + 3], a3);
-    }
-  }
-  const cplx sum = make_double2((a0.x + a1.x) + (a2.x + a3.x), (a0.y + a1.y) + (a2.y + a3.y));
-  if (kq > 0) part[kq - 1][lane] = sum;
-  __syncthreads();
-  if (kq == 0 && i < row_end) {
-    cplx f = F[(size_t)i * lda];
-    f.x -= (sum.x + part[0][lane].x) + (part[1][lane].x + part[2][lane].x);
-    f.y -= (sum.y + part[0][lane].y) + (part[1][lane].y + part[2][lane].y);
-    F[(size_t)i * lda] = f;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Small systems (cfg 1: N = 72): the whole augmented system in LDS, one workgroup per system, ONE launch for factorisation,
 // forward elimination, checks and back substitution - the blocked path above spends its time in per-panel launches there
@@ -380,7 +345,8 @@ __global__ void __launch_bounds__(SMALL_THREADS, (KR <= 9 ? 4 : 2)) k_small_utu(
 // that the 64-column matrix block leaves idle.  Replaced an LDS form (64 steps of read-modify-write through LDS with a complex
 // division per thread, then 64 two-barrier steps for the inverse; git history): 125 -> ~50 us per launch of one workgroup per CU
 // (cfg 3: 56.4 -> 49.1 ms per 256-system step for strips + diagonal blocks; cfg 2: 61.9 -> 71.7 k systems/s, same box).
-// Writes U11 into the upper triangle of the block and W = I - U11^{-T} as W[k][i] (the A-operand order of the streaming zgemm).
+// Writes U11 into the upper triangle of the block and V = -U11^{-T} as V[k][i] (the A-operand order of the streaming zgemm: the strip is
+// the pure product U12 = -V^T C, k_gemm3m_strip), and W = I + V beside it where k_back_step multiplies by the stored inverses.
 // ---------------------------------------------------------------------------------------------
 #ifdef BIEM_DIAG_TRACE
 // diagnostic build only (tools/diag_trace.cpp): lane 0 of every wave of workgroup 0 stamps s_memtime at 4 points of each step
@@ -389,14 +355,35 @@ __device__ unsigned long long g_diag_trace[16][66][4];
 #else
 #define BIEM_DT(step, i)
 #endif
-constexpr int DIAG_LDS_CPLX = 2 * (NB * (NB + 1) / 2) + 2 * NB + NB + 2 * NB;          // packed U rows, packed L^-1 rows, multipliers [2][64], 1 / sqrt(d), combined rows [2][64]
+constexpr int DIAG_RHS_MAX = 8;                                                          // right-hand sides a diagonal-block kernel solves with its block (rhs_gemv)
+// The block's own part of the forward substitution, z_j = U11^{-T} y_j = D^{-1/2} L^{-1} y_j for up to 8 compact right-hand sides
+// Y[s][q][row] (rows j .. j+63 have taken every earlier panel's term from the strip kernel's epilogue), from the packed L^-1 rows and
+// 1 / sqrt(d) the kernel holds in LDS: wave = right-hand side, lane = row i, the sum over k <= i in ascending order.  Call behind a
+// barrier that orders sy and isq; ys: [nrhs][64] of LDS.
+__device__ __forceinline__ void diag_solve_rhs(cplx* __restrict__ Y, int nrhs, int n_pad, int s, int j, const cplx* sy, const cplx* isq, cplx* ys,
+                                               int tid, int nthreads) {
+  if (Y == nullptr) return;
+  cplx* Ys = Y + (size_t)s * nrhs * n_pad + j;
+  for (int e = tid; e < nrhs * NB; e += nthreads) ys[e] = Ys[(size_t)(e >> 6) * n_pad + (e & 63)];
+  __syncthreads();
+  const int lane = tid & 63;
+  const cplx* row = sy + (lane * (lane + 1)) / 2;
+  for (int q = tid >> 6; q < nrhs; q += nthreads >> 6) {
+    cplx a = make_double2(0.0, 0.0);
+    for (int k = 0; k < NB; ++k)
+      if (k <= lane) a = cfma(row[k], ys[q * NB + k], a);
+    Ys[(size_t)q * n_pad + lane] = cmul(a, isq[lane]);
+  }
+}
+
+constexpr int DIAG_LDS_CPLX = 2 * (NB * (NB + 1) / 2) + 2 * NB + NB + 2 * NB + DIAG_RHS_MAX * NB;   // packed U rows, packed L^-1 rows, multipliers [2][64], 1 / sqrt(d), combined rows [2][64], y_j [8][64]
 #ifndef BIEM_DIAG_THREADS
 #define BIEM_DIAG_THREADS 1024
 #endif
 constexpr int DIAG_THREADS = BIEM_DIAG_THREADS;         // 16 waves x 4 rows: the step is bound by the instructions a wave issues for its rows
 __global__ void __launch_bounds__(DIAG_THREADS) k_diag_utu_reg(cplx* __restrict__ A, long long lda, long long sys_stride, int j,
-                                                                 cplx* __restrict__ Wt, long long w_stride, int* __restrict__ info, double rel,
-                                                                 unsigned long long* __restrict__ growth) {
+                                                                 cplx* __restrict__ Wt, long long w_stride, cplx* __restrict__ Vt, long long v_stride, int* __restrict__ info, double rel,
+                                                                 unsigned long long* __restrict__ growth, cplx* __restrict__ Y, int nrhs, int n_pad) {
   extern __shared__ cplx sd[];
   __shared__ int bad;
   constexpr int NW = DIAG_THREADS / 64, KR = NB / NW;
@@ -480,13 +467,17 @@ __global__ void __launch_bounds__(DIAG_THREADS) k_diag_utu_reg(cplx* __restrict_
   // U11 = D^{-1/2} (D L^T) into the upper triangle of the block (lanes along the row)
   for (int r = w; r < NB; r += NW)
     if (lane >= r) Ab[(size_t)r * lda + lane] = cmul(su[uoff(r) + lane], isq[r]);
-  // W[k][i] = delta_ki - (U11^{-T})[i][k] = delta_ki - L^-1[i][k] / sqrt(d_i), k <= i (lanes along i)
-  cplx* Wo = Wt + (size_t)s * w_stride;
+  // V[k][i] = -(U11^{-T})[i][k] = -L^-1[i][k] / sqrt(d_i), k <= i (lanes along i): the strip's A operand; W = I + V only where the
+  // back substitution multiplies by the stored inverses (Wt != nullptr)
+  cplx* Vo = Vt + (size_t)s * v_stride;
+  cplx* Wo = Wt != nullptr ? Wt + (size_t)s * w_stride : nullptr;
   for (int k = w; k < NB; k += NW) {
-    cplx v = make_double2(0.0, 0.0);
-    if (k <= lane) { const cplx xt = cmul(sy[yoff(lane) + k], isq[lane]); v = make_double2((k == lane ? 1.0 : 0.0) - xt.x, -xt.y); }
-    Wo[k * NB + lane] = v;
+    cplx xt = make_double2(0.0, 0.0);
+    if (k <= lane) xt = cmul(sy[yoff(lane) + k], isq[lane]);
+    Vo[k * NB + lane] = make_double2(-xt.x, -xt.y);
+    if (Wo != nullptr) Wo[k * NB + lane] = k <= lane ? make_double2((k == lane ? 1.0 : 0.0) - xt.x, -xt.y) : make_double2(0.0, 0.0);
   }
+  diag_solve_rhs(Y, nrhs, n_pad, s, j, sy, isq, comb + 2 * NB, tid, DIAG_THREADS);
   BIEM_DT(64, 3)
   if (tid == 0 && bad && info[s] == 0) info[s] = -(j + 1);
 }
@@ -503,10 +494,10 @@ __global__ void __launch_bounds__(DIAG_THREADS) k_diag_utu_reg(cplx* __restrict_
 // broadcast), and the vector updates of the rows follow.  16 barriers and 16 broadcast round trips instead of 64 each.
 // Same arithmetic per entry as the form above (same order of the rank-1 updates), same acceptance tests, same outputs.
 // ---------------------------------------------------------------------------------------------
-constexpr int DIAGB_LDS_CPLX = 2 * (NB * (NB + 1) / 2) + NB + 2 * 2 * 4 * NB + 16;   // packed U rows, packed L^-1 rows, 1 / sqrt(d), combined rows and multipliers [2][4][64] each, the 4 x 4 sub-block
+constexpr int DIAGB_LDS_CPLX = 2 * (NB * (NB + 1) / 2) + NB + 2 * 2 * 4 * NB + 16 + DIAG_RHS_MAX * NB;   // packed U rows, packed L^-1 rows, 1 / sqrt(d), combined rows and multipliers [2][4][64] each, the 4 x 4 sub-block, y_j [8][64]
 __global__ void __launch_bounds__(1024) k_diag_utu_blk(cplx* __restrict__ A, long long lda, long long sys_stride, int j,
-                                                        cplx* __restrict__ Wt, long long w_stride, int* __restrict__ info, double rel,
-                                                        unsigned long long* __restrict__ growth) {
+                                                        cplx* __restrict__ Wt, long long w_stride, cplx* __restrict__ Vt, long long v_stride, int* __restrict__ info, double rel,
+                                                        unsigned long long* __restrict__ growth, cplx* __restrict__ Y, int nrhs, int n_pad) {
   extern __shared__ cplx sd[];
   __shared__ int bad;
   constexpr int NW = 16, KR = 4;
@@ -640,12 +631,16 @@ __global__ void __launch_bounds__(1024) k_diag_utu_blk(cplx* __restrict__ A, lon
   block_max_publish(sqrt(um), growth + 2 * (size_t)s + 1);       // (its barrier also orders isq)
   for (int r = w; r < NB; r += NW)
     if (lane >= r) Ab[(size_t)r * lda + lane] = cmul(su[uoff(r) + lane], isq[r]);
-  cplx* Wo = Wt + (size_t)s * w_stride;
+  // V = -U11^{-T} for the strip, W = I + V where the back substitution wants it (as in k_diag_utu_reg)
+  cplx* Vo = Vt + (size_t)s * v_stride;
+  cplx* Wo = Wt != nullptr ? Wt + (size_t)s * w_stride : nullptr;
   for (int k = w; k < NB; k += NW) {
-    cplx v = make_double2(0.0, 0.0);
-    if (k <= lane) { const cplx xt = cmul(sy[yoff(lane) + k], isq[lane]); v = make_double2((k == lane ? 1.0 : 0.0) - xt.x, -xt.y); }
-    Wo[k * NB + lane] = v;
+    cplx xt = make_double2(0.0, 0.0);
+    if (k <= lane) xt = cmul(sy[yoff(lane) + k], isq[lane]);
+    Vo[k * NB + lane] = make_double2(-xt.x, -xt.y);
+    if (Wo != nullptr) Wo[k * NB + lane] = k <= lane ? make_double2((k == lane ? 1.0 : 0.0) - xt.x, -xt.y) : make_double2(0.0, 0.0);
   }
+  diag_solve_rhs(Y, nrhs, n_pad, s, j, sy, isq, dsc + 16, tid, 1024);
   if (tid == 0 && bad && info[s] == 0) info[s] = -(j + 1);
 }
 
@@ -709,21 +704,32 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
   cplx* Wall = (cplx*)d_work;
   const long long wall_stride = (long long)n_pad * NB;
   cplx* Xsol = Wall + (size_t)nb * wall_stride;
+  // Few right-hand sides (rhs_gemv) do not ride in the matrix: the forward substitution works on the compact copy Y[s][q][row] the
+  // row-form back substitution uses anyway (the panel region of the workspace; with keep_w, whose W blocks live there, the place of the
+  // solutions behind them) - every diagonal-block kernel solves its own 64 entries, every strip tile takes its 64 columns' term from
+  // the tile it has in registers.  U is read once for the solve (the back substitution); the update launches end at column n_pad.
+  cplx* Yf = rhs_gemv ? (keep_w ? Xsol : (cplx*)d_work) : nullptr;
+  const int f_cols = rhs_gemv ? n_pad : n_cols;      // the factorisation's last column
+  if (rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Yf, nrhs, n_pad, 0);
   BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_diag_utu_reg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIAG_LDS_CPLX * sizeof(cplx))));
   BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_diag_utu_blk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIAGB_LDS_CPLX * sizeof(cplx))));
   const char* dform = getenv("BIEM_DIAG_FORM");                  // step: one pivot per barrier (the A/B of the tests); default: four
   const bool diag_blk = !(dform && dform[0] == 's');
   auto panel = [&](int j) {
-    cplx* Wp = keep_w ? Wall + (size_t)(j / NB) * NB * NB : Wt;
-    const long long w_stride = keep_w ? wall_stride : (long long)NB * NB;
+    // the strip's operand V = -U11^{-T} lives in the 64 x 64 block; a kept W = I + V goes to the panel region
+    cplx* Wp = keep_w ? Wall + (size_t)(j / NB) * NB * NB : nullptr;
+    const long long w_stride = keep_w ? wall_stride : 0, v_stride = (long long)NB * NB;
     {
       ProfScope ps(PK_PANEL, st, 0.0);
-      if (diag_blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(nb), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, d_info, nopiv, growth);
-      else hipLaunchKernelGGL(k_diag_utu_reg, dim3(nb), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, d_info, nopiv, growth);
+      if (diag_blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(nb), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Wt, v_stride, d_info, nopiv, growth, Yf, nrhs, n_pad);
+      else hipLaunchKernelGGL(k_diag_utu_reg, dim3(nb), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Wt, v_stride, d_info, nopiv, growth, Yf, nrhs, n_pad);
     }
-    // A operand W[k][i], i = row - j: the base shifted by -j rows (only rows j .. j+63 are addressed)
-    if (n_cols > j + NB)
-      gemm(st, nb, A, lda, sys_stride, Wp - j, NB, w_stride, j, j + NB, j + NB, n_cols, j, NB, PK_PANEL, 8.0 * (double)nb * (n_cols - j - NB) * NB * NB);
+    // U12 = U11^{-T} C = -V^T C in place over the 64 rows (every tile reads its own columns only); A operand V[k][i], i = row - j: the
+    // base shifted by -j rows (only rows j .. j+63 are addressed)
+    if (f_cols > j + NB) {
+      const int r = launch_gemm_strip(st, nb, A, lda, sys_stride, Wt - j, v_stride, j, f_cols, Yf, nrhs, n_pad);
+      if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r;
+    }
   };
   // (A fused form - the diagonal block updated alone, then ONE pass U12 = C - [(X P^T) | W] [Q ; C] with K = 64 (q + 1) over the strip
   // instead of the pending-update pass and the solve pass - was built and measured in round 3: these passes run at the zgemm
@@ -734,29 +740,24 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
   for (int J = 0; J < n_pad; J += 4 * NB) {
     const cplx* strip = A + (size_t)J * lda;        // both operands of this group's updates: rows J .. of the matrix itself
     if (left && J > 0) {
-      // left-looking: the group's rows take every pending update of the finished rows 0 .. J-1 now, in one K = J pass (few right-hand
-      // sides: matrix-vector work beside it; many: tile columns of the same launch)
+      // left-looking: the group's rows take every pending update of the finished rows 0 .. J-1 now, in one K = J pass (many right-hand
+      // sides: tile columns of the same launch; few: not in the matrix at all)
       const int row_end = J + 4 * NB < n_pad ? J + 4 * NB : n_pad;
-      { const int r = launch_gemm_left(st, nb, A, lda, sys_stride, J, row_end, rhs_gemv ? n_pad : n_cols); if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r; }
-      if (rhs_gemv) {
-        ProfScope ps(PK_OTHER, st, 0.0);
-        hipLaunchKernelGGL(k_rhs_update_left, dim3((row_end - J) / RHS_UPD_ROWS, nb, nrhs), dim3(256), 0, st, A, lda, sys_stride, n_pad, J, row_end, J);
-      }
+      { const int r = launch_gemm_left(st, nb, A, lda, sys_stride, J, row_end, f_cols); if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r; }
     }
     panel(J);
     for (int q = 1; q < 4; ++q) {
       const int jq = J + q * NB;
       if (jq >= n_pad) break;
-      // the next panel's 64 rows: all pending updates of the group (K = 64 q), every column right of them incl. the right-hand sides
-      gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, jq, jq + NB, jq, n_cols, J, q * NB, PK_OTHER);
+      // the next panel's 64 rows: all pending updates of the group (K = 64 q), every column right of them incl. right-hand sides in the matrix
+      gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, jq, jq + NB, jq, f_cols, J, q * NB, PK_OTHER);
       panel(jq);
     }
     if (J + 4 * NB >= n_pad) break;
     if (left) continue;                              // no update after the group: the rows below take it when their own group starts
     gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, J + 4 * NB, n_pad, J + 4 * NB, n_pad, J, 4 * NB, PK_GEMM, -1.0, nullptr, 0, 0, 0,
          tri_map, true);
-    if (rhs_gemv) launch_rhs_update(st, nb, nrhs, A, lda, sys_stride, strip, lda, sys_stride, n_pad, J + 4 * NB, J, 4 * NB);
-    else if (nrhs > 0) gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, J + 4 * NB, n_pad, n_pad, n_cols, J, 4 * NB, PK_OTHER);
+    if (nrhs > 0 && !rhs_gemv) gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, J + 4 * NB, n_pad, n_pad, n_cols, J, 4 * NB, PK_OTHER);
   }
   BIEM_LAUNCHCHK();
   if (gemm_rc != BIEM_OK) return gemm_rc;
@@ -770,6 +771,8 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
     // column-block form spreads a system's rows over workgroups (cfg 4, N = 4064: 64 systems 6.1 -> 5.1 ms, 8 systems 5.7 -> 2.6 ms,
     // one system per call 22.8 -> 20.6 ms; at 256+ systems the row form wins: it reads U once in long runs).  BIEM_BACK_FORM=row|col|step forces one.
     if (keep_w || nrhs > 4 * NB || (col_form && nrhs > 0)) {
+      // (these forms work on the augmented columns: the forward-substituted compact copy goes back there first)
+      if (rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Yf, nrhs, n_pad, 1);
       if (keep_w) {
         for (int jr = n_pad - BS; jr >= 0; jr -= BS)
           hipLaunchKernelGGL(k_back_step, dim3(jr > 0 ? (jr + BACK_ROWS - 1) / BACK_ROWS : 1, nb), dim3(256), 0, st, A, lda, sys_stride, A + n_pad, lda,
@@ -782,7 +785,7 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
       BIEM_LAUNCHCHK();
       return BIEM_OK;
     }
-    if (nrhs > 0) hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, 0);
+    if (nrhs > 0 && !rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, 0);
     int q0 = 0;
     do {
       const int nq = nrhs - q0 > 8 ? 8 : nrhs - q0;
@@ -818,14 +821,14 @@ extern "C" int biem_debug_diag(int reps, unsigned long long* trace_out, float* u
   const bool blk = getenv("BIEM_DIAG_FORM") == nullptr;
   hipFuncSetAttribute((const void*)k_diag_utu_blk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIAGB_LDS_CPLX * sizeof(cplx)));
   for (int r = 0; r < 3; ++r) {
-    if (blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(1), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), 0, A, lda, 0, 64 * r, W, (long long)NB * NB, info, 0.01, growth);
-    else hipLaunchKernelGGL(k_diag_utu_reg, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), 0, A, lda, 0, 64 * r, W, (long long)NB * NB, info, 0.01, growth);
+    if (blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(1), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), 0, A, lda, 0, 64 * r, nullptr, 0, W, (long long)NB * NB, info, 0.01, growth, nullptr, 0, n);
+    else hipLaunchKernelGGL(k_diag_utu_reg, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), 0, A, lda, 0, 64 * r, nullptr, 0, W, (long long)NB * NB, info, 0.01, growth, nullptr, 0, n);
   }
   hipDeviceSynchronize();
   hipEventRecord(e0, 0);
   for (int r = 0; r < reps; ++r) {
-    if (blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(1), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), 0, A, lda, 0, 64 * (3 + r % 12), W, (long long)NB * NB, info, 0.01, growth);
-    else hipLaunchKernelGGL(k_diag_utu_reg, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), 0, A, lda, 0, 64 * (3 + r % 12), W, (long long)NB * NB, info, 0.01, growth);
+    if (blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(1), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), 0, A, lda, 0, 64 * (3 + r % 12), nullptr, 0, W, (long long)NB * NB, info, 0.01, growth, nullptr, 0, n);
+    else hipLaunchKernelGGL(k_diag_utu_reg, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), 0, A, lda, 0, 64 * (3 + r % 12), nullptr, 0, W, (long long)NB * NB, info, 0.01, growth, nullptr, 0, n);
   }
   hipEventRecord(e1, 0); hipEventSynchronize(e1);
   float ms = 0; hipEventElapsedTime(&ms, e0, e1); *us_out = ms * 1e3f / reps;
