@@ -1,8 +1,8 @@
 """Standard chain trees "b" * (d - 2) + "a" on the host (no GPU): plan tables against an independent test-local chain tree.
 
 `Chain` restates the chain harmonics with SciPy (Gegenbauer polynomials, Gauss-Jacobi rules).  It equals the oracle's ba / bba
-(pinned by the reference goldens), which validates it; at d >= 5 no reference fixture exists ("parity unpinned") and it is the
-reference the plan tables are checked against.
+(pinned by the reference goldens), which validates it; at d >= 5 no reference fixture exists and it is the reference the plan tables
+are checked against.  The translation term lists at d = 5 .. 10 are checked term by term in test_chain_yardstick_host.py.
 """
 import ctypes as C
 import math
@@ -108,7 +108,7 @@ def test_chain_harness_equals_oracle_ba_bba():
         assert np.abs(y1 - y2).max() < 1e-14 and np.abs(w1 - w2).max() < 1e-14
 
 
-@pytest.mark.parametrize("d,n_end", [(5, 3), (6, 3), (7, 3), (5, 5)])
+@pytest.mark.parametrize("d,n_end", [(5, 3), (6, 3), (7, 3), (5, 5), (8, 3), (9, 3), (10, 3)])
 def test_chain_plan_tables(d, n_end):
     lib = _lib.load()
     ch = chain(d)
@@ -143,6 +143,8 @@ def test_chain_plan_tables(d, n_end):
         assert ptr[-1] == nt
         if n_end > 3:
             return
+        if d > 7:                            # the tensor rule of the cross-check below is (2 n_end)^(d-2) 4 n_end points: gigabytes of
+            return                           # harmonics from d = 8 on; test_chain_yardstick_host.py checks these lists term by term
         O._TREES[ch.name] = ch
         try:
             rng = np.random.default_rng(d)
@@ -203,8 +205,10 @@ def test_chain_plans_of_ba_bba_match_their_trees():
 def test_chain_over_limit_fails_cleanly():
     lib = _lib.load()
     p = C.c_void_p()
-    assert lib.biem_plan_create_chain_host(7, 8, C.byref(p)) == 3            # H2 = 67626 > 65535
+    assert lib.biem_plan_create_chain_host(7, 8, C.byref(p)) == 3            # H2 = 65892 > 65535
     assert b"16-bit" in lib.biem_last_error() and b"65535" in lib.biem_last_error()
+    assert lib.biem_plan_create_chain_host(10, 5, C.byref(p)) == 3            # H2 and the node tables fit, Q x H = 3906250 x 935 > 2^31 does not
+    assert b"projection matrix" in lib.biem_last_error()
     assert lib.biem_plan_create_chain_host(11, 2, C.byref(p)) == 3
     assert b"unsupported" in lib.biem_last_error()
     assert lib.biem_plan_create_host(7, 3, C.byref(p)) == 3

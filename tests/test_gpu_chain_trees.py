@@ -1,5 +1,6 @@
 """Standard chain trees "b" * (d - 2) + "a" on the GPU: the chain path on ba / bba against the default path and the goldens, and
-d >= 5 against the oracle with a registered test-local chain tree (parity unpinned: no reference fixture exists beyond d = 4)."""
+d >= 5 against the oracle's quadrature form with a registered test-local chain tree (no reference fixture exists beyond d = 4; the
+top orders of d = 5 .. 10 against the closed-form yardstick are in test_gpu_chain_full.py)."""
 import math
 
 import numpy as np

@@ -1121,7 +1121,8 @@ def test_sharded_solve_on_rccl_world_size_one(amd):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("form", ["default", "red", "entry", "sys"])
-@pytest.mark.parametrize("tree,n_end,B,robin", [("a", 9, 3, False), ("a", 40, 4, True), ("ba", 6, 3, True), ("ba", 12, 2, False), ("bba", 4, 3, True), ("caa", 4, 2, False)])
+@pytest.mark.parametrize("tree,n_end,B,robin", [("a", 9, 3, False), ("a", 40, 4, True), ("ba", 6, 3, True), ("ba", 12, 2, False), ("bba", 4, 3, True), ("caa", 4, 2, False),
+                                                ("bbba", 4, 3, True), ("bbbbbba", 3, 2, False)])
 def test_symmetric_fill_vs_transformed_general_fill(amd, lib, tree, n_end, B, robin, form, monkeypatch):
     """BIEM_FILL_SYMMETRIC (what the L D L^T path factors, written once by the fused kernel) against R W^H M W R^-1 formed in
     NumPy from the general BIEM_FILL_EQUILIBRATED matrix, on everything the factorisation reads (upper triangle + diagonal
@@ -1136,7 +1137,7 @@ def test_symmetric_fill_vs_transformed_general_fill(amd, lib, tree, n_end, B, ro
     else:
         monkeypatch.delenv("BIEM_FILL_FORM", raising=False)
     l, L = lib
-    d = O.tree(tree).d
+    d = O.tree(tree).d if tree in O._TREES else len(tree) + 1          # (the standard chains "b" * (d - 2) + "a" of d >= 5)
     rng = np.random.default_rng(n_end + B)
     cen = rng.normal(size=(B, d)) * 0.3 + np.arange(B)[:, None] * np.eye(d)[0] * 2.6
     rad = rng.uniform(0.6, 1.0, size=B)
