@@ -9,11 +9,14 @@ __version__ = "0.1.0"
 from ._biem import (
     BIEMFactorization,
     BIEMKwargs,
+    BIEMPower,
     BIEMResultCalculator,
     BIEMResultCalculatorProtocol,
     UinCallable,
     biem,
     biem_factorize,
+    biem_far_pattern,
+    biem_power,
     biem_u,
     biem_u_grad,
     biem_u_interior,
@@ -31,11 +34,14 @@ from ._coords import SphericalCoordinates, create_from_branching_types
 __all__ = [
     "BIEMFactorization",
     "BIEMKwargs",
+    "BIEMPower",
     "BIEMResultCalculator",
     "BIEMResultCalculatorProtocol",
     "UinCallable",
     "biem",
     "biem_factorize",
+    "biem_far_pattern",
+    "biem_power",
     "biem_u",
     "biem_u_grad",
     "biem_u_interior",

@@ -16,7 +16,7 @@ import ctypes as C
 import math
 import os
 import warnings
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Callable, Literal, Optional, Protocol, Tuple, TypedDict
 
 import numpy as np
@@ -36,8 +36,9 @@ warnings.filterwarnings("error", category=ComplexWarning)
 Array = Any
 
 __all__ = [
-    "BIEMFactorization", "BIEMKwargs", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
-    "biem_factorize", "biem_u", "biem_u_interior", "biem_u_interior_grad", "biem_u_total", "biem_u_total_grad", "fluid_inclusion_bc",
+    "BIEMFactorization", "BIEMKwargs", "BIEMPower", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
+    "biem_factorize", "biem_far_pattern", "biem_power", "biem_u", "biem_u_interior", "biem_u_interior_grad", "biem_u_total",
+    "biem_u_total_grad", "fluid_inclusion_bc",
     "max_memory", "max_n_end", "plane_wave", "point_source",
 ]
 
@@ -469,6 +470,15 @@ class BIEMResultCalculator:
                     expand_x: bool = True) -> Array:
         """Gradient of the total field inside and outside penetrable fluid balls (see :func:`biem_u_total_grad`)."""
         return biem_u_total_grad(self, x, k_interior=k_interior, density_ratio=density_ratio, uin_grad=uin_grad, expand_x=expand_x)
+
+    def power(self, *, uin_grad: Callable[[Array], Array], uin: Callable[[Array], Array] | None = None, alpha: Array | complex = 1.0,
+              beta: Array | complex = 0.0, alpha_n: Array | None = None, beta_n: Array | None = None) -> "BIEMPower":
+        """Extinction, absorbed and scattered power of the solved problem (see :func:`biem_power`)."""
+        return biem_power(self, uin_grad=uin_grad, uin=uin, alpha=alpha, beta=beta, alpha_n=alpha_n, beta_n=beta_n)
+
+    def far_pattern(self, directions: Array, /, per_ball: bool = False) -> Array:
+        """The far-field pattern of the whole cluster about the origin (see :func:`biem_far_pattern`)."""
+        return biem_far_pattern(self, directions, per_ball=per_ball)
 
 
 # --------------------------------------------------------------------------------------
@@ -1336,6 +1346,124 @@ def biem_u_total_grad(res: Any, x: Array, /, *, k_interior: Array, density_ratio
         x = _stacked(x)[(...,) + (None,) * len(_shape(res.k))]
     uin = uin_grad(x)
     return _inside_or(inside, outside, uin)
+
+
+# --------------------------------------------------------------------------------------
+# cross sections and the far-field pattern about the origin (an extension)
+# --------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class BIEMPower:
+    """What :func:`biem_power` returns: real float64 arrays in the caller's array type, batch axes (right-hand-side axes included)
+    in the caller's order."""
+
+    extinction: Array    # (...(first), B): power each ball removes from the incident field
+    absorption: Array    # (...(first), B): power each ball absorbs
+    scattering: Array    # (...(first)):    sum of the extinction minus sum of the absorption
+
+
+def biem_power(res: Any, /, *, uin_grad: Callable[[Array], Array], uin: Callable[[Array], Array] | None = None,
+               alpha: Array | complex = 1.0, beta: Array | complex = 0.0, alpha_n: Array | None = None,
+               beta_n: Array | None = None) -> BIEMPower:
+    r"""Power the cluster removes from the incident field (extinction), absorbs per ball, and re-radiates (scattering).
+
+    For real ``k``, in the far-field normalisation :math:`u_{scat} \sim F(\hat x) e^{ikr} / r^{(d-1)/2}`: "power" is
+    :math:`(1/k)\,\mathrm{Im} \oint \bar u\, \partial_n u\, dS`, for a unit plane wave the cross section.  Algebra on what the solve
+    left behind - the density, the projections of ``uin`` and ``uin_grad`` on every sphere and the per-ball tables - in one small
+    kernel: no second solve, no matrix, every coordinate tree :func:`biem` solves.  The extinction formula holds for any incident field.
+
+    ``uin_grad`` and the coefficients ``alpha`` / ``beta`` (or ``alpha_n`` / ``beta_n``) are the ones :func:`biem` took: the record
+    stores neither (the rule of ``utotal_grad``).  ``uin`` defaults to the one the record stores; both callables are always needed,
+    also for ``beta = 0``.  A ball whose coefficients have ``Im(alpha_n conj(beta_n)) == 0`` (sound-soft, sound-hard, real impedance,
+    a lossless fluid) absorbs exactly ``0.0``; ``Im(alpha_n conj(beta_n)) < 0`` is an active boundary and absorbs a negative power.
+    A lossy degree the ball does not scatter (``gj_n`` zero or not finite) makes that ball's absorption NaN, as in ``uinterior``.
+    ``scattering`` is a difference: where absorption dominates it carries the absolute error of the extinction, not its own size.
+
+    ``ValueError`` for ``kind="inner"``, any ``Im k != 0``, a result without density and a missing ``uin`` or ``uin_grad``.
+    """
+    if res.kind != "outer":
+        raise ValueError(f"Invalid kind: {res.kind} (the powers belong to an exterior problem, kind='outer')")
+    k_h = _host_array(res.k)
+    if np.iscomplexobj(k_h) and bool(np.any(k_h.imag != 0)):
+        raise ValueError("The powers are defined for a real wavenumber: Im k must be zero for every system.")
+    if res.density is None:
+        raise ValueError("The BIEMResult does not have density.")
+    if uin is None and res.uin is not None:
+        stored = res.uin
+        uin = lambda x: stored(x, expand_x=False)     # (the record's wrapper; _boundary_samples hands over the batch axes itself)
+    if uin is None:
+        raise ValueError("uin is None and the BIEMResult does not have uin. uin must be provided to compute the extinction.")
+    if uin_grad is None:
+        raise ValueError("uin_grad is None. uin_grad must be provided to compute the extinction.")
+    as_array = lambda a: a if isinstance(a, (torch.Tensor, np.ndarray)) else np.asarray(a)
+    centers = as_array(res.centers)
+    centers = torch.movedim(centers, 0, -1) if isinstance(centers, torch.Tensor) else np.moveaxis(centers, 0, -1)
+    with warnings.catch_warnings():                   # (biem() has given the warnings of these operands already)
+        warnings.simplefilter("ignore", UserWarning)
+        op = _operator(res.c, centers, as_array(res.radii), as_array(res.k), int(res.n_end), alpha, beta, as_array(res.eta), res.kind,
+                       alpha_n, beta_n)
+    plan, fl, dev = op.plan, op.fl, op.dev
+    nb, B, H = fl.nb, fl.B, plan.H
+    # the unweighted samples of the per-degree path, whatever the coefficients: U and V are projections of u_in and d_n u_in alone
+    (gu, gdn), full, op_axes, rhs_axes = _boundary_samples(replace(op, per_degree=True), uin, uin_grad)
+    nrhs = int(gu.shape[1])
+    dens_t = _to_dev(res.density, dev, torch.complex128)
+    if tuple(dens_t.shape) != tuple(full) + (B, H):
+        raise ValueError(f"density has shape {tuple(dens_t.shape)}, but uin / uin_grad and the operator give {tuple(full) + (B, H)}")
+    nf = len(full)
+    dens_t = dens_t.permute(list(op_axes) + list(rhs_axes) + [nf, nf + 1]).reshape(nb, nrhs, B, H).contiguous()
+    out = torch.empty((nb, nrhs, B, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        sp = _stream_ptr(dev)
+        if out.numel() > 0:
+            plain = replace(op, per_degree=False)     # (biem_rhs_project of one set: no coefficient enters)
+            pu, pv = (torch.empty((nb, nrhs, B * H), dtype=torch.complex128, device=dev) for _ in range(2))
+            _rhs_project(plain, nb, gu, 0, pu, nrhs * B * H, 1, B * H, sp)
+            _rhs_project(plain, nb, gdn, 0, pv, nrhs * B * H, 1, B * H, sp)
+            tab = _ball_tables(op, sp)
+            lib = L.load()
+            entry, what = (lib.biem_power_n, "biem_power_n") if op.per_degree else (lib.biem_power, "biem_power")
+            _check_built(lib, entry(plan.handle, nb, B, nrhs, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched, _ptr(fl.alpha),
+                                    _ptr(fl.beta), fl.ab_batched, _ptr(tab), _ptr(dens_t), _ptr(pu), _ptr(pv), _ptr(out), sp), what)
+    out = _restore_batch(out, full, op_axes, rhs_axes)
+    ext, ab = out[..., 0], out[..., 1]
+    give = lambda t: op.origin.give(t.contiguous(), complex_out=False)
+    return BIEMPower(extinction=give(ext), absorption=give(ab), scattering=give(ext.sum(-1) - ab.sum(-1)))
+
+
+def biem_far_pattern(res: Any, directions: Array, /, per_ball: bool = False) -> Array:
+    r"""Far-field pattern of the cluster about the origin: :math:`u_{scat}(r \hat x) \to F(\hat x)\, e^{ikr} / r^{(d-1)/2}`,
+
+        F(x^) = (ik)^{-(d-1)/2} sum_b e^{-ik x^.c_b} sum_h c_{b,h} (-i)^n Y_h(x^).
+
+    ``directions`` has shape ``(c_ndim, ...)`` and is normalised here (a zero vector gives NaN); the result has shape
+    ``(..., ...(first))``, with a trailing ``B`` for ``per_ball=True``, in the namespace of :func:`biem_u`.  Real and complex ``k``.
+    Unlike ``uscat(x, far_field=True)``, which keeps the reference's formula - harmonics at the direction of ``x - c_b`` and the phase
+    of ``x`` itself, the pattern of a ball at the origin only - this is the pattern of the whole cluster for balls anywhere.
+    """
+    if res.density is None:
+        raise ValueError("The BIEMResult does not have density.")
+    origin, dev = _origin_of(res.centers, res.radii, res.k, res.density, directions)
+    if getattr(res.density, "dtype", None) in (torch.complex64, np.complex64):
+        origin.real_dtype = torch.float32
+    f64 = torch.float64
+    x_t = _to_dev(_stacked(directions), dev, f64)
+    d = res.c.c_ndim
+    if x_t.shape[0] != d:
+        raise ValueError(f"directions must have shape ({d}, ...), got {tuple(x_t.shape)}")
+    xh = x_t / torch.linalg.vector_norm(x_t, dim=0, keepdim=True)
+    ok = torch.isfinite(xh).all(dim=0, keepdim=True)
+    e0 = torch.zeros((d,) + (1,) * (x_t.ndim - 1), dtype=f64, device=dev)
+    e0[0] = 1.0
+    cen_t = _to_dev(res.centers, dev, f64)             # [d, ...(first), B]
+    k_t = _to_dev(res.k, dev, torch.complex128 if _is_complex(res.k) else f64)
+    # every ball moved to the origin: there the reference's far-field formula IS the pattern of that ball
+    at_origin = BIEMResultCalculator(c=res.c, centers=torch.zeros_like(cen_t), radii=_to_dev(res.radii, dev, f64), k=k_t, n_end=res.n_end,
+                                     eta=_to_dev(res.eta, dev, f64), kind=res.kind, density=_to_dev(res.density, dev, torch.complex128))
+    pb = biem_u(at_origin, torch.where(ok, xh, e0), far_field=True, per_ball=True)         # (..., ...(first), B)
+    nd, nfirst = x_t.ndim - 1, cen_t.ndim - 2
+    dot = torch.sum(xh[(...,) + (None,) * (nfirst + 1)] * cen_t[(slice(None),) + (None,) * nd], dim=0)
+    out = pb * torch.exp(-1j * k_t[..., None] * dot)   # (a direction that was zero: NaN through the phase)
+    return origin.give(out if per_ball else out.sum(-1))
 
 
 # --------------------------------------------------------------------------------------

@@ -80,6 +80,8 @@ SIGNATURES = {
     "biem_factor_ldlt_n": (_i, [_vp, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _ll, _ll, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_factored_n": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _i, _dp, _dp, _dp, _vp, _sz, _vp]),
     "biem_flag_unscalable": (_i, [_vp, _i, _i, _dp, _ip, _i, _vp]),
+    "biem_power": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, _vp]),
+    "biem_power_n": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, _vp]),
     "biem_profile_begin": (_i, []),
     "biem_profile_end": (_i, [_vp, _vp, _vp]),
     "biem_bench_mfma_f64": (_i, [_i, C.POINTER(C.c_double), _vp]),

@@ -669,6 +669,45 @@ int biem_solve_factored_n(const biem_plan* plan, int nb, int B, int nrhs, const 
                              "biem_solve_factored_n");
 }
 
+// ---- extinction and absorbed power (kernels_power.hip) ----
+static int power_impl(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_radii,
+                      int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, const double* d_tab,
+                      const double* d_density, const double* d_pu, const double* d_pv, double* d_out, void* stream, bool per_degree,
+                      const char* who) {
+  NEED_DEV_AS(who, plan); NEED_AS(who, d_k, "d_k"); NEED_AS(who, d_eta, "d_eta"); NEED_AS(who, d_radii, "d_radii");
+  NEED_AS(who, d_alpha, per_degree ? "d_alpha_n" : "d_alpha"); NEED_AS(who, d_beta, per_degree ? "d_beta_n" : "d_beta");
+  NEED_AS(who, d_tab, "d_tab"); NEED_AS(who, d_density, "d_density"); NEED_AS(who, d_pu, "d_pu"); NEED_AS(who, d_pv, "d_pv");
+  NEED_AS(who, d_out, "d_out");
+  if (nb < 0 || nb > 65535 || nrhs < 0 || nrhs > 65535 || B < 0) {
+    set_error("%s: 0 .. 65535 systems / right-hand sides per call and B >= 0 (got nb=%d, nrhs=%d, B=%d)", who, nb, nrhs, B);
+    return BIEM_ERR_ARG;
+  }
+  if (nb == 0 || nrhs == 0 || B == 0) return BIEM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // the powers are defined for a lossless exterior: the wavenumbers come to the host for that test (one small copy, one wait)
+  std::vector<double> hk((size_t)nb * 2);
+  BIEM_HIPCHK(hipMemcpyAsync(hk.data(), d_k, hk.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  BIEM_HIPCHK(hipStreamSynchronize(st));
+  for (int s = 0; s < nb; ++s)
+    if (hk[2 * (size_t)s + 1] != 0.0) { set_error("%s: system %d has Im k = %g; the powers need a real wavenumber", who, s, hk[2 * (size_t)s + 1]); return BIEM_ERR_ARG; }
+  return launch_power(plan, nb, B, nrhs, d_k, d_radii, geom_batched, d_alpha, d_beta, ab_batched, per_degree, d_tab, d_density, d_pu,
+                      d_pv, d_out, st);
+}
+
+int biem_power(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_radii,
+               int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, const double* d_tab,
+               const double* d_density, const double* d_pu, const double* d_pv, double* d_out, void* stream) {
+  return power_impl(plan, nb, B, nrhs, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_tab, d_density, d_pu, d_pv, d_out,
+                    stream, false, "biem_power");
+}
+
+int biem_power_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_radii,
+                 int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched, const double* d_tab,
+                 const double* d_density, const double* d_pu, const double* d_pv, double* d_out, void* stream) {
+  return power_impl(plan, nb, B, nrhs, d_k, d_eta, d_radii, geom_batched, d_alpha_n, d_beta_n, ab_batched, d_tab, d_density, d_pu, d_pv,
+                    d_out, stream, true, "biem_power_n");
+}
+
 int biem_profile_begin(void) {
   Profiler& p = profiler();
   for (auto& r : p.recs) { p.pool.push_back(r.a); p.pool.push_back(r.b); }

@@ -46,6 +46,12 @@ __device__ __forceinline__ cplx cmulc(const cplx& a, const cplx& b) {           
   return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
 }
 
+// sum over the 64 lanes of a wave in a fixed order (no atomics: two runs give the same bits); the total is in lane 0
+__device__ inline double wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
 #define BIEM_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { biem::set_error("%s failed: %s", #x, hipGetErrorString(e_)); return BIEM_ERR_HIP; } } while (0)
 #define BIEM_LAUNCHCHK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { biem::set_error("kernel launch failed at %s:%d: %s", __FILE__, __LINE__, hipGetErrorString(e_)); return BIEM_ERR_HIP; } } while (0)
 
@@ -99,6 +105,11 @@ int launch_rhs_project_n(const biem_plan* p, int nb, int B, int nrhs, const doub
 // d_info[s] = code for every system with a (ball, degree) whose symmetric scaling 1 / sqrt(gj gh) is not finite (gj = 0); others untouched
 // (biem_flag_unscalable exposes it for tests)
 int launch_flag_unscalable(const biem_plan* p, int nb, int B, const double* d_tab, int* d_info, int code, hipStream_t st);
+// extinction and absorbed power per (system, right-hand side, ball) from the density, the projections pu / pv of u_in / d_n u_in
+// [nb][nrhs][B][H] and the ball tables (kernels_power.hip); alpha / beta [nb or 1][B], per_degree: [nb or 1][B][n_end]; real k only
+int launch_power(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_radii, int geom_batched,
+                 const double* d_alpha, const double* d_beta, int ab_batched, bool per_degree, const double* d_tab,
+                 const double* d_density, const double* d_pu, const double* d_pv, double* d_out, hipStream_t st);
 size_t fill_workspace_bytes(const biem_plan* p, int nb, int B);
 int launch_fill(const biem_plan* p, int nb, int B, const double* d_k, const double* d_centers, int geom_batched,
                 const double* d_tab, int scaling, double* d_A, long long lda, long long sys_stride, int n_pad,

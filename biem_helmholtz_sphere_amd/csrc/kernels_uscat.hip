@@ -47,11 +47,6 @@ __global__ void __launch_bounds__(64) k_uscat_coef(int d, int H, int n_end, cons
   for (int h = threadIdx.x; h < H; h += 64) c[base + h] = cmul(dens[base + h], sB[deg[h]]);
 }
 
-__device__ inline double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 __global__ void __launch_bounds__(256) k_uscat(int tree, int d, int H, int n_end, const int* __restrict__ labels,
                                                 const int* __restrict__ deg, int nb, int B, int P, const cplx* __restrict__ k,
                                                 const double* __restrict__ centers, const double* __restrict__ radii,

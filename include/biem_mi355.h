@@ -359,6 +359,28 @@ int biem_solve_factored_n(const biem_plan* plan, int nb, int B, int nrhs, const 
                           const double* d_tab, const double* d_alpha_n, const double* d_beta_n, int ab_batched, const double* d_gu,
                           const double* d_gdn, double* d_density, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- cross sections: extinction and absorbed power per ball from what the solve already has (no second solve, no
+ *      matrix, no workspace).  Real k only, in the far-field normalisation u_scat ~ F(x^) e^{ikr} / r^{(d-1)/2}: "power" is
+ *      (1/k) Im oint conj(u) d_n u dS, for a unit plane wave the cross section.  With c_h = density_h blc_n(rho_b), U_h / V_h the
+ *      projections of u_in / d_n u_in on the surface of ball b onto Y_h - biem_rhs_project of the unweighted samples d_gu / d_gdn of
+ *      biem_rhs_project_n, natural order, d_pu / d_pv [nb][nrhs][B][H] complex128 like d_density -
+ *        P_ext = -(rho^{d-1} / k) sum_h Im[ conj(U_h) k c_h h_n'(k rho) + conj(c_h h_n(k rho)) V_h ]      (any incident field)
+ *        P_abs = rho^{d-1} k (k rho)^{2-2d} sum_h Im(alpha_n conj beta_n) |c_h|^2 / |gj_n|^2
+ *      and d_out[s][r][b][0..1] = (P_ext, P_abs), doubles.  A degree with Im(alpha_n conj beta_n) == 0 adds exactly 0 and divides by
+ *      nothing (gj_n = 0 of a lossless ball is harmless); a lossy degree whose gj_n is zero or not finite makes P_abs of that ball NaN.
+ *      The scattered power is sum_b P_ext - sum_b P_abs, the caller's subtraction.  d_tab: the tables of biem_ball_tables (biem_power)
+ *      or biem_ball_tables_n (biem_power_n) for the same coefficients; d_alpha / d_beta [nb or 1][B], d_alpha_n / d_beta_n
+ *      [nb or 1][B][n_end], as there.  d_eta is not read (blc comes with the tables); it keeps the operands of biem_ball_tables in
+ *      their order.  Sums run in a fixed order: two calls give the same bits.  Every tree, the chains included, n_end <= 320.
+ *      BIEM_ERR_ARG for a system with Im k != 0 (the wavenumbers are copied to the host for this test: the one entry of the field
+ *      group that waits for the stream) and for nb or nrhs above 65535. ---- */
+int biem_power(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_radii,
+               int geom_batched, const double* d_alpha /*c128*/, const double* d_beta /*c128*/, int ab_batched, const double* d_tab,
+               const double* d_density, const double* d_pu, const double* d_pv, double* d_out, void* stream);
+int biem_power_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_radii,
+                 int geom_batched, const double* d_alpha_n /*c128*/, const double* d_beta_n /*c128*/, int ab_batched, const double* d_tab,
+                 const double* d_density, const double* d_pu, const double* d_pv, double* d_out, void* stream);
+
 /* ---- per-kernel-class timing with HIP events on the launch stream (thread-local; used by bench.py for the
  *      live `roofline` figures).  Between begin and end every launch of the calling thread is bracketed by two
  *      events; end synchronises on them and returns, per class, elapsed ms, algorithmic work and launch count.
