@@ -16,6 +16,7 @@ from ._biem import (
     biem,
     biem_factorize,
     biem_far_pattern,
+    biem_force,
     biem_power,
     biem_u,
     biem_u_grad,
@@ -41,6 +42,7 @@ __all__ = [
     "biem",
     "biem_factorize",
     "biem_far_pattern",
+    "biem_force",
     "biem_power",
     "biem_u",
     "biem_u_grad",

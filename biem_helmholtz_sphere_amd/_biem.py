@@ -37,7 +37,7 @@ Array = Any
 
 __all__ = [
     "BIEMFactorization", "BIEMKwargs", "BIEMPower", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
-    "biem_factorize", "biem_far_pattern", "biem_power", "biem_u", "biem_u_interior", "biem_u_interior_grad", "biem_u_total",
+    "biem_factorize", "biem_far_pattern", "biem_force", "biem_power", "biem_u", "biem_u_interior", "biem_u_interior_grad", "biem_u_total",
     "biem_u_total_grad", "fluid_inclusion_bc",
     "max_memory", "max_n_end", "plane_wave", "point_source",
 ]
@@ -475,6 +475,11 @@ class BIEMResultCalculator:
               beta: Array | complex = 0.0, alpha_n: Array | None = None, beta_n: Array | None = None) -> "BIEMPower":
         """Extinction, absorbed and scattered power of the solved problem (see :func:`biem_power`)."""
         return biem_power(self, uin_grad=uin_grad, uin=uin, alpha=alpha, beta=beta, alpha_n=alpha_n, beta_n=beta_n)
+
+    def force(self, *, alpha: Array | complex = 1.0, beta: Array | complex = 0.0, alpha_n: Array | None = None,
+              beta_n: Array | None = None) -> Array:
+        """Time-averaged radiation force on each ball (see :func:`biem_force`)."""
+        return biem_force(self, alpha=alpha, beta=beta, alpha_n=alpha_n, beta_n=beta_n)
 
     def far_pattern(self, directions: Array, /, per_ball: bool = False) -> Array:
         """The far-field pattern of the whole cluster about the origin (see :func:`biem_far_pattern`)."""
@@ -1428,6 +1433,69 @@ def biem_power(res: Any, /, *, uin_grad: Callable[[Array], Array], uin: Callable
     ext, ab = out[..., 0], out[..., 1]
     give = lambda t: op.origin.give(t.contiguous(), complex_out=False)
     return BIEMPower(extinction=give(ext), absorption=give(ab), scattering=give(ext.sum(-1) - ab.sum(-1)))
+
+
+def biem_force(res: Any, /, *, alpha: Array | complex = 1.0, beta: Array | complex = 0.0, alpha_n: Array | None = None,
+               beta_n: Array | None = None) -> Array:
+    r"""Time-averaged acoustic radiation force on each ball, real float64 of shape ``(c_ndim, ...(first), B)``: the component axis
+    first, in the caller's axis order like ``uscat_grad``, batch axes (right-hand-side axes included) as in ``BIEMPower.extinction``.
+
+    For real ``k`` and ``kind="outer"``, in the normalisation of :func:`biem_power` (for a unit plane wave an area, the
+    radiation-pressure cross section as a vector): with ``u`` the total exterior field (time factor :math:`e^{-i\omega t}`),
+    :math:`S_b` any closed surface in the fluid around ball ``b`` alone and ``n`` its outward normal,
+
+        Phi_b = -(1 / (2 k^2)) oint_{S_b} [ (k^2 |u|^2 - |grad u|^2) n + 2 Re( grad u conj(d_n u) ) ] dS.
+
+    The physical force on a ball in a fluid of density :math:`\rho_0` at angular frequency :math:`\omega` is
+    ``Phi k^2 / (2 rho_0 omega^2)`` for pressure amplitude ``u``.  Algebra on the density alone, in one small kernel: on the ball's own
+    surface the boundary condition fixes both traces of ``u``, so neither ``uin`` nor ``uin_grad`` is needed, nor a second solve, a
+    matrix or a field evaluation; every coordinate tree :func:`biem` solves.  For a plane wave along ``p^`` the forces obey the
+    momentum balance ``sum_b Phi_b = P_ext p^ - int |F(x^)|^2 x^ dOmega`` with :func:`biem_power` and :func:`biem_far_pattern`.
+
+    The coefficients ``alpha`` / ``beta`` (or ``alpha_n`` / ``beta_n``) are the ones :func:`biem` took: the record stores none.  A ball
+    with a degree it does not scatter (``gj_n`` zero or not finite, e.g. the transparent sphere ``k_b = k, delta = 1``) and a nonzero
+    coefficient there gets NaN in every component, as in ``uinterior``; the other balls are not affected.
+
+    ``ValueError`` for ``kind="inner"``, any ``Im k != 0`` and a result without density.
+    """
+    if res.kind != "outer":
+        raise ValueError(f"Invalid kind: {res.kind} (the force belongs to an exterior problem, kind='outer')")
+    k_h = _host_array(res.k)
+    if np.iscomplexobj(k_h) and bool(np.any(k_h.imag != 0)):
+        raise ValueError("The force is defined for a real wavenumber: Im k must be zero for every system.")
+    if res.density is None:
+        raise ValueError("The BIEMResult does not have density.")
+    as_array = lambda a: a if isinstance(a, (torch.Tensor, np.ndarray)) else np.asarray(a)
+    centers = as_array(res.centers)
+    centers = torch.movedim(centers, 0, -1) if isinstance(centers, torch.Tensor) else np.moveaxis(centers, 0, -1)
+    with warnings.catch_warnings():                   # (biem() has given the warnings of these operands already)
+        warnings.simplefilter("ignore", UserWarning)
+        op = _operator(res.c, centers, as_array(res.radii), as_array(res.k), int(res.n_end), alpha, beta, as_array(res.eta), res.kind,
+                       alpha_n, beta_n)
+    plan, fl, dev = op.plan, op.fl, op.dev
+    nb, B, H, d = fl.nb, fl.B, plan.H, plan.d
+    dens_t = _to_dev(res.density, dev, torch.complex128)
+    # batch axes of the density on which the operator has size 1 are right-hand sides (the layout of _boundary_samples)
+    full, nbt = tuple(dens_t.shape[:-2]), len(op.batch)
+    if len(full) != nbt or tuple(dens_t.shape[-2:]) != (B, H) or any(op.batch[i] not in (1, full[i]) for i in range(nbt)):
+        raise ValueError(f"density has shape {tuple(dens_t.shape)}, but the operator gives {tuple(op.batch) + (B, H)}")
+    op_axes = [i for i in range(nbt) if op.batch[i] == full[i]]
+    rhs_axes = [i for i in range(nbt) if op.batch[i] != full[i]]
+    nrhs = int(np.prod([full[i] for i in rhs_axes])) if rhs_axes else 1
+    dens_t = dens_t.permute(op_axes + rhs_axes + [nbt, nbt + 1]).reshape(nb, nrhs, B, H).contiguous()
+    out = torch.empty((nb, nrhs, B, d), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        sp = _stream_ptr(dev)
+        if out.numel() > 0:
+            tab = _ball_tables(op, sp)
+            lib = L.load()
+            entry, what = (lib.biem_force_n, "biem_force_n") if op.per_degree else (lib.biem_force, "biem_force")
+            _check_built(lib, entry(plan.handle, nb, B, nrhs, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched, _ptr(fl.alpha),
+                                    _ptr(fl.beta), fl.ab_batched, _ptr(tab), _ptr(dens_t), _ptr(out), sp), what)
+    out = torch.movedim(_restore_batch(out, full, op_axes, rhs_axes), -1, 0)     # (d, ...(first), B), the plan's axes
+    if list(op.perm) != list(range(d)):
+        out = out[_inverse_perm(op.perm)]
+    return op.origin.give(out.contiguous(), complex_out=False)
 
 
 def biem_far_pattern(res: Any, directions: Array, /, per_ball: bool = False) -> Array:

@@ -39,6 +39,7 @@ SIGNATURES = {
     "biem_plan_quadrature": (_i, [_vp, _vp, _vp]),
     "biem_plan_projection": (_i, [_vp, _vp]),
     "biem_plan_terms": (_i, [_vp, _vp, _vp, _vp]),
+    "biem_plan_force_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "biem_radial": (_i, [_i, _i, _i, _dp, _dp, _vp]),
     "biem_radial_complex": (_i, [_i, _i, _i, _dp, _dp, _vp]),
     "biem_harmonics": (_i, [_vp, _i, _dp, _dp, _vp]),
@@ -82,6 +83,8 @@ SIGNATURES = {
     "biem_flag_unscalable": (_i, [_vp, _i, _i, _dp, _ip, _i, _vp]),
     "biem_power": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, _vp]),
     "biem_power_n": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, _vp]),
+    "biem_force": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _vp]),
+    "biem_force_n": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _vp]),
     "biem_profile_begin": (_i, []),
     "biem_profile_end": (_i, [_vp, _vp, _vp]),
     "biem_bench_mfma_f64": (_i, [_i, C.POINTER(C.c_double), _vp]),

@@ -173,6 +173,24 @@ int biem_plan_terms(const biem_plan* plan, long long* h_ptr, double* h_coef, int
   return BIEM_OK;
 }
 
+int biem_plan_force_terms(biem_plan* plan, long long* n_entries, long long* h_ptr, int* h_col, int* h_comp, double* h_val) {
+  NEED(plan, "plan");
+  int rc = BIEM_OK;
+  try {
+    rc = plan_build_force(plan);
+  } catch (const std::bad_alloc&) {
+    set_error("out of host memory building the force coupling table for n_end=%d", plan->n_end);
+    rc = BIEM_ERR_ALLOC;
+  }
+  if (rc != BIEM_OK) return rc;
+  if (n_entries) *n_entries = (long long)plan->fcol.size();
+  if (h_ptr) for (size_t i = 0; i < plan->fptr.size(); ++i) h_ptr[i] = (long long)plan->fptr[i];
+  if (h_col) memcpy(h_col, plan->fcol.data(), plan->fcol.size() * sizeof(int));
+  if (h_comp) memcpy(h_comp, plan->fcomp.data(), plan->fcomp.size() * sizeof(int));
+  if (h_val) memcpy(h_val, plan->fval.data(), plan->fval.size() * sizeof(double));
+  return BIEM_OK;
+}
+
 int biem_radial(int d, int nmax, int count, const double* d_x, double* d_out, void* stream) {
   NEED(d_x, "d_x"); NEED(d_out, "d_out");
   return launch_radial(d, nmax, count, d_x, d_out, (hipStream_t)stream);
@@ -706,6 +724,50 @@ int biem_power_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d
                  const double* d_density, const double* d_pu, const double* d_pv, double* d_out, void* stream) {
   return power_impl(plan, nb, B, nrhs, d_k, d_eta, d_radii, geom_batched, d_alpha_n, d_beta_n, ab_batched, d_tab, d_density, d_pu, d_pv,
                     d_out, stream, true, "biem_power_n");
+}
+
+// ---- radiation force (kernels_force.hip) ----
+static int force_impl(biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_radii,
+                      int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, const double* d_tab,
+                      const double* d_density, double* d_out, void* stream, bool per_degree, const char* who) {
+  NEED_DEV_AS(who, plan); NEED_AS(who, d_k, "d_k"); NEED_AS(who, d_eta, "d_eta"); NEED_AS(who, d_radii, "d_radii");
+  NEED_AS(who, d_alpha, per_degree ? "d_alpha_n" : "d_alpha"); NEED_AS(who, d_beta, per_degree ? "d_beta_n" : "d_beta");
+  NEED_AS(who, d_tab, "d_tab"); NEED_AS(who, d_density, "d_density"); NEED_AS(who, d_out, "d_out");
+  if (nb < 0 || nb > 65535 || nrhs < 0 || nrhs > 65535 || B < 0) {
+    set_error("%s: 0 .. 65535 systems / right-hand sides per call and B >= 0 (got nb=%d, nrhs=%d, B=%d)", who, nb, nrhs, B);
+    return BIEM_ERR_ARG;
+  }
+  if (nb == 0 || nrhs == 0 || B == 0) return BIEM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // the force is defined for a lossless exterior: the wavenumbers come to the host for that test (one small copy, one wait)
+  std::vector<double> hk((size_t)nb * 2);
+  BIEM_HIPCHK(hipMemcpyAsync(hk.data(), d_k, hk.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  BIEM_HIPCHK(hipStreamSynchronize(st));
+  for (int s = 0; s < nb; ++s)
+    if (hk[2 * (size_t)s + 1] != 0.0) { set_error("%s: system %d has Im k = %g; the force needs a real wavenumber", who, s, hk[2 * (size_t)s + 1]); return BIEM_ERR_ARG; }
+  int rc = BIEM_OK;
+  try {
+    rc = plan_build_force(plan);             // (the first call of this plan: builds and uploads the coupling table)
+  } catch (const std::bad_alloc&) {
+    set_error("%s: out of host memory building the force coupling table for n_end=%d", who, plan->n_end);
+    rc = BIEM_ERR_ALLOC;
+  }
+  if (rc != BIEM_OK) return rc;
+  return launch_force(plan, nb, B, nrhs, d_k, d_radii, geom_batched, d_alpha, d_beta, ab_batched, per_degree, d_tab, d_density, d_out, st);
+}
+
+int biem_force(biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_radii, int geom_batched,
+               const double* d_alpha, const double* d_beta, int ab_batched, const double* d_tab, const double* d_density, double* d_out,
+               void* stream) {
+  return force_impl(plan, nb, B, nrhs, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_tab, d_density, d_out, stream,
+                    false, "biem_force");
+}
+
+int biem_force_n(biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_radii, int geom_batched,
+                 const double* d_alpha_n, const double* d_beta_n, int ab_batched, const double* d_tab, const double* d_density,
+                 double* d_out, void* stream) {
+  return force_impl(plan, nb, B, nrhs, d_k, d_eta, d_radii, geom_batched, d_alpha_n, d_beta_n, ab_batched, d_tab, d_density, d_out, stream,
+                    true, "biem_force_n");
 }
 
 int biem_profile_begin(void) {

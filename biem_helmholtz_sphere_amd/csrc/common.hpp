@@ -110,6 +110,11 @@ int launch_flag_unscalable(const biem_plan* p, int nb, int B, const double* d_ta
 int launch_power(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_radii, int geom_batched,
                  const double* d_alpha, const double* d_beta, int ab_batched, bool per_degree, const double* d_tab,
                  const double* d_density, const double* d_pu, const double* d_pv, double* d_out, hipStream_t st);
+// radiation force per (system, right-hand side, ball), out [nb][nrhs][B][d] (kernels_force.hip); operands as launch_power, the plan's
+// force coupling table uploaded (plan_build_force)
+int launch_force(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_radii, int geom_batched,
+                 const double* d_alpha, const double* d_beta, int ab_batched, bool per_degree, const double* d_tab,
+                 const double* d_density, double* d_out, hipStream_t st);
 size_t fill_workspace_bytes(const biem_plan* p, int nb, int B);
 int launch_fill(const biem_plan* p, int nb, int B, const double* d_k, const double* d_centers, int geom_batched,
                 const double* d_tab, int scaling, double* d_A, long long lda, long long sys_stride, int n_pad,

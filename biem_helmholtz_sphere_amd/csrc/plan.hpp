@@ -77,6 +77,14 @@ struct biem_plan {
   // the same lists cut into small chunks for the systems-in-lanes form of the symmetric fill (k_fill_sys: no LDS ceiling on H2)
   std::vector<int> schunk;
   int schunk_terms_max = 0, schunk_pairs_max = 0;
+  // ---- coupling table of the radiation force (kernels_force.hip), built on the first request (plan_build_force) ----
+  // T^i_{h'h} = int y_i Y_h conj(Y_h') dOmega, i = 0 .. d-1 along the plan's axes: Hermitian in (h', h), nonzero only for |n - n'| = 1.
+  // CSR over the rows h'; the entries of a row are ordered by (component, column).
+  bool force_built = false, force_uploaded = false;
+  std::vector<uint32_t> fptr;               // [H + 1]
+  std::vector<int32_t> fcol, fcomp;         // [entries] column h, component i
+  std::vector<double> fval;                 // [entries] complex128 interleaved
+  std::vector<uint32_t> fptr_comp;          // [H * d + 1]: the entries of (row h', component i) are [fptr_comp[h' d + i], fptr_comp[h' d + i + 1])
   // device mirrors (null until uploaded)
   int device = -1;
   int* d_labels = nullptr; int* d_deg = nullptr;
@@ -89,6 +97,7 @@ struct biem_plan {
   int* d_qchunk = nullptr; int* d_schunk = nullptr;
   int* d_lin2 = nullptr; uint32_t* d_q2ptr = nullptr; double* d_q2coef = nullptr; uint16_t* d_q2idx16 = nullptr;
   int* d_red_of = nullptr; int* d_red_first = nullptr; int* d_red_label = nullptr; int* d_ph_mu = nullptr;
+  uint32_t* d_fptr_comp = nullptr; int32_t* d_fcol = nullptr; double* d_fval = nullptr;     // uploaded by plan_build_force
   double* d_rcoef = nullptr; uint16_t* d_ridx = nullptr; uint16_t* d_rphsel = nullptr; int* d_rchunk = nullptr; int* d_rcrow = nullptr; int* d_rwrow = nullptr;
 };
 
@@ -96,6 +105,7 @@ namespace biem {
 int plan_build_host(biem_plan* p, int tree, int n_end);   // returns BIEM_* status
 int plan_build_chain_host(biem_plan* p, int d, int n_end);  // the standard chain tree "b" * (d - 2) + "a", 3 <= d <= kChainDimMax
 int plan_upload(biem_plan* p);
+int plan_build_force(biem_plan* p);         // the force coupling table, and its device mirror if the plan is uploaded; a no-op once built
 void plan_free(biem_plan* p);
 void set_error(const char* fmt, ...);
 }  // namespace biem

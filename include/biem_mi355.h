@@ -107,6 +107,12 @@ int biem_plan_projection(const biem_plan* plan, double* h_W);
 /* translation terms in CSR over entries e = h*H + h' (row h = test index, column h' = unknown):
  * (S|R)_{h'->h}(t) = sum_{p in [ptr[e],ptr[e+1])} coef[p] * T[tidx[p]],  T[l] = C_d h_{n''}(k|t|) Y_l(t^), l over labels of degree < 2 n_end - 1 */
 int biem_plan_terms(const biem_plan* plan, long long* h_ptr /*[H*H+1]*/, double* h_coef, int* h_tidx);
+/* coupling table of the radiation force, T^i_{h'h} = int y_i Y_h conj(Y_h') dOmega, in CSR over the rows h': entry p in
+ * [ptr[h'], ptr[h'+1]) is T^{comp[p]}_{h', col[p]} = val[p] (complex128), ordered by (component, column) within a row.  Hermitian in
+ * (h', h), entries only where |n - n'| = 1.  Built on the first request (this call or biem_force; host work only unless the plan is
+ * uploaded, then its device mirror too), so plans that never compute a force keep their build time and memory.  Any array may be null;
+ * n_entries alone sizes the others. */
+int biem_plan_force_terms(biem_plan* plan, long long* n_entries, long long* h_ptr /*[H+1]*/, int* h_col, int* h_comp, double* h_val);
 
 /* ---- special functions on the device, exposed for parity tests (ultrasphere.shn1 / potential_coef) ---- */
 /* z[i][0..nmax] (j) and [nmax+1 .. 2nmax+1] (y): d-dimensional spherical Bessel functions at x[i] */
@@ -380,6 +386,26 @@ int biem_power(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k
 int biem_power_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_radii,
                  int geom_batched, const double* d_alpha_n /*c128*/, const double* d_beta_n /*c128*/, int ab_batched, const double* d_tab,
                  const double* d_density, const double* d_pu, const double* d_pv, double* d_out, void* stream);
+
+/* ---- radiation force: the time-averaged force on each ball from what the solve already has (no second solve, no
+ *      matrix, no workspace, no incident field).  Real k, exterior problems, in the normalisation of biem_power: with u the total field,
+ *        Phi_b = -(1 / (2 k^2)) oint_{S_b} [ (k^2 |u|^2 - |grad u|^2) n + 2 Re(grad u conj(d_n u)) ] dS
+ *      over any closed surface in the fluid around ball b alone (for a unit plane wave an area; the physical force on a ball in a
+ *      fluid of density rho_0 at angular frequency omega is Phi k^2 / (2 rho_0 omega^2) for pressure amplitude u).  Evaluated on the
+ *      ball's own surface, where the boundary condition gives both traces from c_h = density_h blc_n: s_h = c_h k Wr / gj_n,
+ *      Wr = i (k rho)^{1-d}, u_h = -beta_n s_h, v_h = alpha_n s_h, contracted with the plan's coupling table (biem_plan_force_terms,
+ *      built by the first call).  d_out[s][r][b][0..d-1] doubles, component i along axis i of the plan's tree.  A degree with a nonzero
+ *      coefficient whose gj_n is zero (to the rounding of its two terms) or not finite makes every component of that ball NaN.
+ *      Operands as biem_power: d_tab the tables of biem_ball_tables (biem_force) or biem_ball_tables_n (biem_force_n) for the same
+ *      coefficients, d_eta not read.  Sums run in a fixed order: two calls give the same bits.  Every tree, the chains included,
+ *      n_end <= 320 (beyond: BIEM_ERR_UNSUPPORTED).  BIEM_ERR_ARG for a system with Im k != 0 (one copy of the wavenumbers to the host,
+ *      one wait for the stream) and for nb or nrhs above 65535. ---- */
+int biem_force(biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_radii,
+               int geom_batched, const double* d_alpha /*c128*/, const double* d_beta /*c128*/, int ab_batched, const double* d_tab,
+               const double* d_density, double* d_out, void* stream);
+int biem_force_n(biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_radii,
+                 int geom_batched, const double* d_alpha_n /*c128*/, const double* d_beta_n /*c128*/, int ab_batched, const double* d_tab,
+                 const double* d_density, double* d_out, void* stream);
 
 /* ---- per-kernel-class timing with HIP events on the launch stream (thread-local; used by bench.py for the
  *      live `roofline` figures).  Between begin and end every launch of the calling thread is bracketed by two
