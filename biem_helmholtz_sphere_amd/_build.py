@@ -98,6 +98,18 @@ STRIP = "strip"
 EXPECTED_LDS_DMA_STRIP = 24
 EXPECTED_STORES_STRIP = 65
 EXPECTED_LOADS_STRIP = 5
+# k_gemm3m_stack<KD>, the product form at K = 128 / 192 / 256 (the stacked pass of the panels b, c, d of a group): the text of the strip
+# kernel with a longer chunk loop and the tile decode of a single tile row, so the strip's pins hold for every instance - 24 LDS-DMA,
+# 65 stores, 5 loads of the right-hand-side epilogue outside the chunk loop - with no tile-map load at all and, as for the K-long
+# kernel, no v_readlane / v_writelane in the chunk loop (the strip kernel has 5, on the path that decodes the producer's next tile).
+# Keys (STACK, KD), handed out by check_isa_stack().
+STACK = "stack"
+SLAB = "slab"
+STACK_KD = (128, 192, 256)
+EXPECTED_LDS_DMA_STACK = 24
+EXPECTED_STORES_STACK = 65
+EXPECTED_LOADS_STACK = 5
+MAX_LANE_SPILL_OPS_STACK = 0
 EXPECTED_STORES = 48
 MFMA_PER_CHUNK = 96
 MAX_TILE_MAP_LOADS = 2
@@ -161,6 +173,10 @@ def _chunk_loop(ins):
     return best, n_mfma
 
 
+def _label(kd) -> str:
+    return "k_gemm3m_strip" if kd == STRIP else "k_sym_slab" if kd == SLAB else f"k_gemm3m_stack<{kd[1]}>" if isinstance(kd, tuple) else f"k_gemm3m_pipe<{kd}>"
+
+
 def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = False) -> dict:
     """Disassemble the gfx950 code objects of `lib_path`; raise IsaCheckError unless every k_gemm3m_pipe<*> has no scratch,
     no VGPR spills, 96 MFMAs in its chunk loop and only the expected vector-memory instructions there.  Returns the report."""
@@ -178,13 +194,24 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = F
         for o in objs:
             path = os.path.join(tmp, o)
             metas = _kernel_meta(readelf, path)
-            gemm = [n for n in metas if "k_gemm3m_pipe" in n or "k_gemm3m_strip" in n]
+            for n in metas:
+                # k_sym_slab, the small VALU kernel in front of every stacked pass: a build of it with its loops unrolled spilled 1164
+                # registers to scratch and cost the stage a third of its time, so no scratch and no spills are pinned for it too
+                if "k_sym_slab" in n:
+                    rep = {"scratch_bytes": int(metas[n].get("private_segment_fixed_size", -1)), "vgpr_spills": int(metas[n].get("vgpr_spill_count", -1)),
+                           "vgprs": int(metas[n].get("vgpr_count", -1))}
+                    report[SLAB] = rep
+                    if rep["scratch_bytes"] != 0 or rep["vgpr_spills"] != 0:
+                        raise IsaCheckError(f"k_sym_slab: scratch {rep['scratch_bytes']} B, {rep['vgpr_spills']} VGPR spills")
+            gemm = [n for n in metas if "k_gemm3m_pipe" in n or "k_gemm3m_strip" in n or "k_gemm3m_stack" in n]
             if not gemm:
                 continue
             dis = _disassemble(objdump, path)
             for name in gemm:
-                kd = STRIP if "k_gemm3m_strip" in name else int(re.search(r"k_gemm3m_pipeILi(\d+)E", name).group(1))
-                label = "k_gemm3m_strip" if kd == STRIP else f"k_gemm3m_pipe<{kd}>"
+                stack = "k_gemm3m_stack" in name
+                kd = STRIP if "k_gemm3m_strip" in name else (STACK, int(re.search(r"k_gemm3m_stackILi(\d+)E", name).group(1))) if stack else \
+                    int(re.search(r"k_gemm3m_pipeILi(\d+)E", name).group(1))
+                label = _label(kd)
                 meta, ins = metas[name], dis[name]
                 loop, n_mfma = _chunk_loop(ins)
                 if loop is None:
@@ -205,31 +232,37 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = F
                 if rep["mfma_in_chunk_loop"] != MFMA_PER_CHUNK or n_mfma != MFMA_PER_CHUNK:
                     bad.append(f"{rep['mfma_in_chunk_loop']} MFMAs in the chunk loop, {n_mfma} in the kernel (expected {MFMA_PER_CHUNK})")
                 extra = {op: c for op, c in vm.items() if op not in ("global_load_lds_dwordx4", "global_load_dword", "global_store_dwordx4")}
-                if kd == STRIP and extra.get("global_load_dwordx4") == EXPECTED_LOADS_STRIP and \
+                if (kd == STRIP or stack) and extra.get("global_load_dwordx4") == (EXPECTED_LOADS_STACK if stack else EXPECTED_LOADS_STRIP) and \
                         not any(op == "global_load_dwordx4" for _, op, _ in loop):
                     del extra["global_load_dwordx4"]
                 if extra:
                     bad.append(f"unexpected vector-memory instructions: {extra}")
-                want_dma = EXPECTED_LDS_DMA_STRIP if kd == STRIP else EXPECTED_LDS_DMA_KLONG if kd == KLONG else EXPECTED_LDS_DMA.get(kd)
+                want_dma = EXPECTED_LDS_DMA_STACK if stack else EXPECTED_LDS_DMA_STRIP if kd == STRIP else EXPECTED_LDS_DMA_KLONG if kd == KLONG else \
+                    EXPECTED_LDS_DMA.get(kd)
                 if vm.get("global_load_lds_dwordx4", 0) != want_dma:
                     bad.append(f"{vm.get('global_load_lds_dwordx4', 0)} LDS-DMA instructions (reviewed build: {want_dma})")
-                want_stores = EXPECTED_STORES_STRIP if kd == STRIP else EXPECTED_STORES
+                want_stores = EXPECTED_STORES_STACK if stack else EXPECTED_STORES_STRIP if kd == STRIP else EXPECTED_STORES
                 if vm.get("global_store_dwordx4", 0) != want_stores:
                     bad.append(f"{vm.get('global_store_dwordx4', 0)} result stores (reviewed build: {want_stores})")
                 if kd == KLONG and rep["lane_spill_ops_in_chunk_loop"] > MAX_LANE_SPILL_OPS_KLONG:
                     bad.append(f"{rep['lane_spill_ops_in_chunk_loop']} lane-spill instructions in the chunk loop (reviewed build: {MAX_LANE_SPILL_OPS_KLONG})")
+                if stack and rep["lane_spill_ops_in_chunk_loop"] > MAX_LANE_SPILL_OPS_STACK:
+                    bad.append(f"{rep['lane_spill_ops_in_chunk_loop']} lane-spill instructions in the chunk loop (reviewed build: {MAX_LANE_SPILL_OPS_STACK})")
+                if stack and vm.get("global_load_dword", 0) != 0:
+                    bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (the stacked pass reads no tile map)")
                 if vm.get("global_load_dword", 0) > MAX_TILE_MAP_LOADS:
                     bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (expected <= {MAX_TILE_MAP_LOADS})")
                 if bad:
                     raise IsaCheckError(f"{label}: the hand-counted vmcnt scheme is not safe with this code object: " + "; ".join(bad))
-    if set(report) != set(EXPECTED_LDS_DMA) | {KLONG, STRIP}:
-        raise IsaCheckError(f"update kernels found: {sorted(report, key=str)}, expected {sorted(set(EXPECTED_LDS_DMA) | {KLONG, STRIP}, key=str)}")
+    want = set(EXPECTED_LDS_DMA) | {KLONG, STRIP, SLAB} | {(STACK, k) for k in STACK_KD}
+    if set(report) != want:
+        raise IsaCheckError(f"update kernels found: {sorted(report, key=str)}, expected {sorted(want, key=str)}")
     if verbose:
         for kd in sorted(report, key=str):
-            print(f"isa check {'k_gemm3m_strip' if kd == STRIP else f'k_gemm3m_pipe<{kd}>'}: {report[kd]}")
+            print(f"isa check {_label(kd)}: {report[kd]}")
     # (tests/test_host_logic.py pins the key set of this report to the fixed-K instances [64, 128, 192, 256]: the K-long instance and the
     # strip kernel are checked above like the others and handed out by check_isa_klong / check_isa_strip)
-    return report if _all_kernels else {kd: r for kd, r in report.items() if kd not in (KLONG, STRIP)}
+    return report if _all_kernels else {kd: r for kd, r in report.items() if kd in EXPECTED_LDS_DMA}
 
 
 def check_isa_klong(lib_path: str = LIB) -> dict:
@@ -240,6 +273,12 @@ def check_isa_klong(lib_path: str = LIB) -> dict:
 def check_isa_strip(lib_path: str = LIB) -> dict:
     """The report of k_gemm3m_strip (same checks as check_isa, which raises for it as well)."""
     return check_isa(lib_path, _all_kernels=True)[STRIP]
+
+
+def check_isa_stack(lib_path: str = LIB) -> dict:
+    """The reports of k_gemm3m_stack<KD>, keyed by KD, and of k_sym_slab under SLAB (same checks as check_isa, which raises for them as well)."""
+    rep = check_isa(lib_path, _all_kernels=True)
+    return {**{k: rep[(STACK, k)] for k in STACK_KD}, SLAB: rep[SLAB]}
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

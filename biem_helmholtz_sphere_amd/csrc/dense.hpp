@@ -53,6 +53,7 @@ __device__ inline double lane_bcast(double v, int i) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), i), hi = __builtin_amdgcn_readlane(__double2hiint(v), i);
   return __hiloint2double(hi, lo);
 }
+constexpr int SYM_SLAB_CPLX = 4 * NB * NB;   // [S_J ; S_{J+64} ; S_{J+128} ; V_p] of the stacked pass: up to 256 rows of 64 per system
 constexpr int BACK_ROWS = 16;   // rows per workgroup (4 per wave)
 constexpr int RHS_UPD_ROWS = 64;  // rows per workgroup of k_rhs_update
 
@@ -69,6 +70,10 @@ int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long s
 // with Y (compact Y[s][q][row], y_ld rows per right-hand side, nrhs <= 8) also Y[.., c] -= U[j:j+64, c]^T Y[.., j:j+64] for the strip's columns
 int launch_gemm_strip(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, const cplx* V, long long v_stride, int j, int col_end,
                       cplx* Y = nullptr, int nrhs = 0, int y_ld = 0);
+// the stacked pass of panel p of the group at row J: A[p:p+64, p+64:col_end] = -slab^T A[J:p+64, p+64:col_end], slab = [S_J ; .. ; V_p] of
+// (p - J + 64) x 64 per system; Y as in launch_gemm_strip
+int launch_gemm_stack(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, const cplx* slab, long long slab_stride, int J, int p,
+                      int col_end, cplx* Y = nullptr, int nrhs = 0, int y_ld = 0);
 void launch_tri_map(hipStream_t st, int* tri_map, int n_pad);   // tile map of the triangular updates of an n_pad system
 // ---- kernels_trisolve.hip
 void launch_zero_int(hipStream_t st, int* p, int n);
@@ -80,6 +85,7 @@ void launch_rhs_update(hipStream_t st, int nb, int nrhs, cplx* A, long long lda,
 void back_substitute_cols(hipStream_t st, int nb, int n_pad, int nrhs, const cplx* A, long long lda, long long sys_stride, cplx* F,
                           long long ldf, long long f_stride, int* d_info = nullptr, unsigned long long* growth = nullptr, double inv_rel2 = 0.0);
 // ---- kernels_lu.hip
+cplx* sym_slab(void* d_work, int nb, int n_pad, int nrhs);   // the stacked pass's A operand, SYM_SLAB_CPLX per system: the workspace's last region
 int check_factor_args(const char* who, int nb, int n_pad, int nrhs, long long lda, size_t work_bytes);   // shared by the two factorisations; who: biem_lu / biem_sym
 // BIEM_LDLT_PIVOT_REL / BIEM_LDLT_GROWTH_MAX (tests): acceptance threshold of the diagonal pivots (multipliers <= 1 / threshold; 1e30
 // rejects every system) and accepted max |U| / max |A|; a value that does not parse to something positive is the default

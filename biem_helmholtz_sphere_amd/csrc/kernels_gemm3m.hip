@@ -102,9 +102,15 @@ __device__ __host__ inline void band_decode(int r, int h, int& ty, int& tx) {
     else { const int c = rem / h; tx = h + c; ty = rem - c * h; }
   }
 }
-template <int KD>
+// ROW1: a launch of ONE tile row without a tile map (the stacked pass): tile r of a system is tile column r
+template <int KD, bool ROW1 = false>
 __device__ inline void tile_decode_of(const TileGrid& tg, int t, int& s, int& ty, int& tx) {
-  if constexpr (KD == 0) {
+  if constexpr (ROW1) {
+    s = (int)(((unsigned long long)(unsigned)t * tg.per_sys_magic) >> 40);
+    tx = t - s * tg.per_sys;
+    if (tx >= tg.per_sys) { tx -= tg.per_sys; ++s; }
+    ty = 0;
+  } else if constexpr (KD == 0) {
     s = (int)(((unsigned long long)(unsigned)t * tg.per_sys_magic) >> 40);
     int r = t - s * tg.per_sys;
     if (r >= tg.per_sys) { r -= tg.per_sys; ++s; }
@@ -194,9 +200,10 @@ __device__ unsigned long long g_gemm_trace[16][64][8];
   [a6] "=&v"(fa[1][2]), [a7] "=&v"(fa[1][3]), [b0] "=&v"(fb[0][0]), [b1] "=&v"(fb[0][1]), [b2] "=&v"(fb[0][2]), [b3] "=&v"(fb[0][3]),       \
   [b4] "=&v"(fb[1][0]), [b5] "=&v"(fb[1][1]), [b6] "=&v"(fb[1][2]), [b7] "=&v"(fb[1][3])
 
-// One text of the tile loop for two kernels (as fast_layout.hpp does for the field kernels): k_gemm3m_pipe<KD> is the body with
-// PROD = false.  PROD = true is the pure product of the symmetric strip pass (k_gemm3m_strip, K = 64): no C slots in the stage, four
-// DMAs and 16 fragment reads per chunk, no C additions; the accumulators start at zero, so the tile stored is -A^T B.
+// One text of the tile loop for three kernels (as fast_layout.hpp does for the field kernels): k_gemm3m_pipe<KD> is the body with
+// PROD = false.  PROD = true is the pure product of the symmetric strip pass (k_gemm3m_strip, K = 64) and of the stacked pass of a
+// later panel of a group (k_gemm3m_stack<KD>, K = 128 / 192 / 256): no C slots in the stage, four DMAs and 16 fragment reads per
+// chunk, no C additions; the accumulators start at zero, so the tile stored is -A^T B.
 //
 // The product form also carries the forward substitution of up to 8 right-hand sides (StripRhs, Y[s][q][row] compact): the strip of
 // panel j holds the finished rows U[j .. j+63, :], and y[c] -= sum_r U[j + r, c] z_j[r] for the 64 columns c of a tile is taken from the
@@ -204,10 +211,10 @@ __device__ unsigned long long g_gemm_trace[16][64][8];
 // Exactly one workgroup per (panel, tile column, system) touches those 64 entries: no atomics, two solves agree bit for bit.  Its
 // loads and stores are unknown to the ring's vmcnt counts: such a tile ends with stores_pending = 2 (vmcnt(0) at the next first chunk).
 struct StripRhs { cplx* Y; int nrhs; int ld; };   // Y == nullptr: none; ld = rows per right-hand side (n_pad)
-template <int KD, bool PROD>
+template <int KD, bool PROD, bool ROW1 = false>
 __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda, long long sys_stride, const cplx* __restrict__ Pw,
                                             long long ldp, long long p_stride, const TileGrid& tg, const StripRhs& yr) {
-  static_assert(!PROD || KD == 64, "the product form exists for the K = 64 strip only");
+  static_assert(!PROD || KD == 64 || KD == 128 || KD == 192 || KD == 256, "the product form exists for K = 64 (strip) and K = 128 / 192 / 256 (stacked pass)");
   const int n_pad = tg.row_end, n_cols = tg.col_end;
   // KD = 0 is the K-long form of the left-looking update: the chunk count is a run-time value (TileGrid.nch = kd / 8 >= 16), the
   // accumulators stay in registers over the whole K, C is read in the first 16 chunks and stored once
@@ -252,7 +259,7 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   typedef const __attribute__((address_space(1))) void* glb_ptr_t;
   int cs, cty, ctx;
-  tile_decode_of<KD>(tg, t, cs, cty, ctx);
+  tile_decode_of<KD, ROW1>(tg, t, cs, cty, ctx);
 
   const unsigned offA0 = (unsigned)(((size_t)(wave) * ldp + lane) * sizeof(cplx));
   const unsigned offA1 = (unsigned)(((size_t)(wave + 4) * ldp + lane) * sizeof(cplx));
@@ -329,7 +336,7 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
     pA += strideA; pB += strideB;
     if (++p_ch == NCH) {                                   // producer moves on to the next tile of this workgroup
       int tn = next_tile();
-      if (tn >= 0) { tile_decode_of<KD>(tg, tn, p_s, p_ty, p_tx); producer_tile(); }
+      if (tn >= 0) { tile_decode_of<KD, ROW1>(tg, tn, p_s, p_ty, p_tx); producer_tile(); }
       else p_valid = false;
     }
   };
@@ -771,6 +778,16 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_strip(cplx* __restrict__ A, l
   gemm3m_body<64, true>(A, lda, sys_stride, Pw, ldp, p_stride, tg, yr);
 }
 
+// the stacked pass of panel p = J + 64 q (q = 1 .. 3) of a group that starts at row J: the pending updates of the group and the solve
+// with the panel's diagonal block as ONE pure product over K = 64 (q + 1), -[S_J ; .. ; S_{p-64} ; V_p]^T A[J : p+64, tile column]
+// (launch_gemm_stack); the tile is stored over the panel's own rows, epilogue and right-hand sides as in k_gemm3m_strip
+template <int KD>
+__global__ void __launch_bounds__(256, 2) k_gemm3m_stack(cplx* __restrict__ A, long long lda, long long sys_stride,
+                                                          const cplx* __restrict__ Pw, long long ldp, long long p_stride,
+                                                          TileGrid tg, StripRhs yr) {
+  gemm3m_body<KD, true, true>(A, lda, sys_stride, Pw, ldp, p_stride, tg, yr);
+}
+
 void launch_tri_map(hipStream_t st, int* tri_map, int n_pad) {
   const int T = n_pad / NB, fb = T / 8, n_map = 32 * fb * fb + 4 * fb;
   if (n_map > 0) hipLaunchKernelGGL(k_tri_map, dim3((n_map + 255) / 256), dim3(256), 0, st, tri_map, n_map);
@@ -837,6 +854,31 @@ int launch_gemm_strip(hipStream_t st, int nb, cplx* A, long long lda, long long 
   if (grid == 0) return BIEM_ERR_ARG;
   ProfScope ps(PK_PANEL, st, 8.0 * (double)nb * (col_end - j - NB) * NB * NB);
   hipLaunchKernelGGL(k_gemm3m_strip, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, V, (long long)NB, v_stride, tg, StripRhs{Y, Y != nullptr ? nrhs : 0, y_ld});
+  return BIEM_OK;
+}
+
+// The stacked pass of panel p (J < p <= J + 192, a multiple of 64 past J): rows p .. p+63, columns p+64 .. col_end become
+//   -slab^T A[J : p+64, same columns],   slab = [S_J ; .. ; S_{p-64} ; V_p]  ((p - J + 64) x 64 per system, slab_stride apart)
+// i.e. the B operand is the rows J .. p+63 of the matrix itself - the group's finished U rows, then the panel's own rows as the bulk
+// update left them - and a tile overwrites rows that it alone reads at its columns.  Y as in launch_gemm_strip.
+int launch_gemm_stack(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, const cplx* slab, long long slab_stride, int J, int p,
+                      int col_end, cplx* Y, int nrhs, int y_ld) {
+  if (col_end <= p + NB) return BIEM_OK;
+  const int kd = p - J + NB;
+  if (p <= J || (p - J) % NB != 0 || kd > 4 * NB) { set_error("biem_sym: stacked pass outside its group"); return BIEM_ERR_ARG; }
+  if (Y != nullptr && ((col_end - p) % BN3 != 0 || nrhs < 1 || nrhs > 8)) { set_error("biem_sym: stacked pass with right-hand sides over a partial tile column"); return BIEM_ERR_ARG; }
+  TileGrid tg;
+  tg.pout = nullptr; tg.pout_ld = 0; tg.pout_stride = 0; tg.pcol_tx = 0; tg.tri = 0; tg.tri_map = nullptr; tg.tri_full = 0; tg.full_bands = 0;
+  tg.ty_n = 1; tg.tx_n = (col_end - p - NB + BN3 - 1) / BN3;
+  tg.row_begin = p; tg.row_end = p + NB; tg.col_begin = p + NB; tg.col_end = col_end; tg.brow = J;
+  const int grid = finish_tile_grid(tg, tg.tx_n, nb);
+  if (grid == 0) return BIEM_ERR_ARG;
+  ProfScope ps(PK_PANEL, st, 8.0 * (double)nb * (col_end - p - NB) * NB * (double)kd);
+  const StripRhs yr{Y, Y != nullptr ? nrhs : 0, y_ld};
+  // (the A operand is addressed by absolute row like the panels: slab - p)
+  if (kd == 128) hipLaunchKernelGGL(k_gemm3m_stack<128>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, slab - p, (long long)NB, slab_stride, tg, yr);
+  else if (kd == 192) hipLaunchKernelGGL(k_gemm3m_stack<192>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, slab - p, (long long)NB, slab_stride, tg, yr);
+  else hipLaunchKernelGGL(k_gemm3m_stack<256>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, slab - p, (long long)NB, slab_stride, tg, yr);
   return BIEM_OK;
 }
 

@@ -25,8 +25,12 @@ size_t lu_workspace_bytes(int nb, int n_pad, int nrhs) {
   const size_t T = (size_t)n_pad / NB;
   // + two doubles per system: max |A| over what the symmetric factorisation reads and max |U| (a-posteriori growth check)
   // (the row-panel form of the symmetric path needs no panels, only (64 x 64 + 64) complex per system; one layout serves all)
+  // + at the end the slab of the symmetric path's stacked pass: [S ; S ; S ; V] of a group, 256 x 64 complex per system (sym_slab)
   return (size_t)nb * (4 * NB * (size_t)ldp_of(n_pad) + (size_t)NB * NB) * sizeof(cplx) + ((T * (T + 1) / 2 + 63) / 64) * 64 * sizeof(int) +
-         (size_t)nb * 2 * sizeof(double) + (size_t)nb * NB * sizeof(cplx);
+         (size_t)nb * 2 * sizeof(double) + (size_t)nb * NB * sizeof(cplx) + (size_t)nb * SYM_SLAB_CPLX * sizeof(cplx);
+}
+cplx* sym_slab(void* d_work, int nb, int n_pad, int nrhs) {
+  return (cplx*)((char*)d_work + lu_workspace_bytes(nb, n_pad, nrhs)) - (size_t)nb * SYM_SLAB_CPLX;
 }
 
 int check_factor_args(const char* who, int nb, int n_pad, int nrhs, long long lda, size_t work_bytes) {

@@ -15,6 +15,8 @@
 //   checks:     multiplier test |u_ic| <= 100 |u_ii| and growth max |u_ii u_ic| of the strip entries are taken where the entries
 //               are read anyway: in the back substitution (k_back_update)
 //   in-group:   the next panel's 64 rows take the group's pending updates (K = 64 q) for all columns right of them
+//   stacked:    under the left-looking bulk update the in-group pass and the strip of the panels b, c, d are ONE pure product over
+//               K = 64 (q + 1) (k_sym_slab, k_gemm3m_stack<KD>; the diagonal tile alone takes the pending update first)
 //   K = 256:    one update of the UPPER triangle of tiles below the group (TileGrid.tri = 2), more than 8 right-hand sides as tile columns
 // Only the upper triangle and the diagonal 64 x 64 tiles of A are read.  Growth check as in the L D L^T form, with moduli:
 // max |d_i l_ci| = max |u_ii u_ic| against max |a_ij| over the part read.
@@ -644,6 +646,70 @@ __global__ void __launch_bounds__(1024) k_diag_utu_blk(cplx* __restrict__ A, lon
   if (tid == 0 && bad && info[s] == 0) info[s] = -(j + 1);
 }
 
+// The head of the stacked pass of panel p = J + 64 q of the group at row J (launch_gemm_stack): with V_p = -U11^{-T} of the panel's
+// diagonal block in rows p - J .. of the slab (k_diag_utu_* writes it there), the blocks above it,
+//   S_r[k][i] = -sum_m U[r + k, p + m] V_p[m][i]     for the finished panels r = J, J + 64, .. < p   (64 x 64 each, rows r - J .. of the slab),
+// so that  -[S ; V]^T A[J : p+64, c]  is  U11^{-T} (C[p, c] - sum_r U[r, p]^T U[r, c]):  pending updates and solve in one product.
+// One workgroup per block and system; thread (tk, ti) holds rows tk + 16 a, columns ti + 16 b of the block; m in steps of 16 through LDS.
+__global__ void __launch_bounds__(256, 2) k_sym_slab(const cplx* __restrict__ A, long long lda, long long sys_stride, cplx* __restrict__ slab, int J, int p) {
+  __shared__ cplx su[NB][17];
+  __shared__ cplx sv[16][NB];
+  const int s = blockIdx.y, r = blockIdx.x, tid = threadIdx.x, ti = tid & 15, tk = tid >> 4;
+  const cplx* Ut = A + (size_t)s * sys_stride + (size_t)(J + r * NB) * lda + p;
+  cplx* Ss = slab + (size_t)s * SYM_SLAB_CPLX;
+  const cplx* V = Ss + (size_t)(p - J) * NB;
+  cplx acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = make_double2(0.0, 0.0);
+  // (V_p[m][i] = 0 for m > i: the column groups b < m0 / 16 of a step hold zeros and are skipped; the loops stay rolled - unrolled,
+  // hipcc hoisted every LDS read of a step and spilled a thousand registers)
+#pragma unroll 1
+  for (int m0 = 0; m0 < NB; m0 += 16) {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int e = tid + 256 * x;
+      su[e >> 4][e & 15] = Ut[(size_t)(e >> 4) * lda + m0 + (e & 15)];
+      sv[e >> 6][e & 63] = V[(m0 + (e >> 6)) * NB + (e & 63)];
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int m = 0; m < 16; ++m) {
+      cplx u[4], v[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) u[a] = su[tk + 16 * a][m];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) v[b] = sv[m][ti + 16 * b];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          if (16 * b + 15 >= m0) acc[a][b] = cfma(u[a], v[b], acc[a][b]);
+    }
+    __syncthreads();
+  }
+  cplx* So = Ss + (size_t)r * NB * NB;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) So[(tk + 16 * a) * NB + ti + 16 * b] = make_double2(-acc[a][b].x, -acc[a][b].y);
+}
+
+// Form of the panels b, c, d of a group (launch_sym_factor_solve): the stacked pass runs only where the bulk update is left-looking, and
+// there from SYM_STACK_MIN_SYSTEMS systems per call.  What the passes save grows with the batch (14.0 ms per cfg 3 step at 256 systems),
+// the three small head launches per panel cost the same few ms at any batch size (5.0 ms): they break even near 90 systems, and the
+// form lost 1.2 % at 64 systems of cfg 4 and 2 % at 32 systems of cfg 3 (profiles/r06_other_shapes.txt) - so twice the break-even.
+// BIEM_SYM_GROUP=twopass|stacked forces a form under the left-looking update (tests, A/B).  Read per call.
+constexpr int SYM_STACK_MIN_SYSTEMS = 192;
+bool sym_group_stacked(bool left, int nb) {
+  if (!left) return false;
+  const char* e = getenv("BIEM_SYM_GROUP");
+  if (e && e[0] == 't') return false;
+  if (e && e[0] == 's') return true;
+  return nb >= SYM_STACK_MIN_SYSTEMS;
+}
+
 bool sym_small_path(int n_active, int nrhs) {
   return n_active > 0 && n_active <= SMALL_N_MAX && nrhs <= SMALL_RHS_MAX && n_active + nrhs <= 128 && small_utu_lds(n_active, nrhs) <= 160 * 1024 - 2048 &&
          !getenv("BIEM_NO_SMALL_PATH");
@@ -715,28 +781,44 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
   BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_diag_utu_blk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIAGB_LDS_CPLX * sizeof(cplx))));
   const char* dform = getenv("BIEM_DIAG_FORM");                  // step: one pivot per barrier (the A/B of the tests); default: four
   const bool diag_blk = !(dform && dform[0] == 's');
-  auto panel = [&](int j) {
+  // slab != nullptr: the panel p = j of the group at row J takes the stacked pass (below) - V goes to rows j - J .. of the slab
+  auto panel = [&](int j, int J = 0, cplx* slab = nullptr) {
     // the strip's operand V = -U11^{-T} lives in the 64 x 64 block; a kept W = I + V goes to the panel region
     cplx* Wp = keep_w ? Wall + (size_t)(j / NB) * NB * NB : nullptr;
-    const long long w_stride = keep_w ? wall_stride : 0, v_stride = (long long)NB * NB;
+    cplx* Vp = slab != nullptr ? slab + (size_t)(j - J) * NB : Wt;
+    const long long w_stride = keep_w ? wall_stride : 0, v_stride = slab != nullptr ? (long long)SYM_SLAB_CPLX : (long long)NB * NB;
     {
       ProfScope ps(PK_PANEL, st, 0.0);
-      if (diag_blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(nb), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Wt, v_stride, d_info, nopiv, growth, Yf, nrhs, n_pad);
-      else hipLaunchKernelGGL(k_diag_utu_reg, dim3(nb), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Wt, v_stride, d_info, nopiv, growth, Yf, nrhs, n_pad);
+      if (diag_blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(nb), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Vp, v_stride, d_info, nopiv, growth, Yf, nrhs, n_pad);
+      else hipLaunchKernelGGL(k_diag_utu_reg, dim3(nb), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Vp, v_stride, d_info, nopiv, growth, Yf, nrhs, n_pad);
+    }
+    if (f_cols <= j + NB) return;
+    if (slab != nullptr) {
+      // the blocks S_r = -U[r, j] V of the finished panels of the group, then pending updates and solve as one product over K = j - J + 64
+      {
+        ProfScope ps(PK_PANEL, st, 8.0 * (double)nb * (j - J) * NB * NB);
+        hipLaunchKernelGGL(k_sym_slab, dim3((j - J) / NB, nb), dim3(256), 0, st, A, lda, sys_stride, slab, J, j);
+      }
+      const int r = launch_gemm_stack(st, nb, A, lda, sys_stride, slab, (long long)SYM_SLAB_CPLX, J, j, f_cols, Yf, nrhs, n_pad);
+      if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r;
+      return;
     }
     // U12 = U11^{-T} C = -V^T C in place over the 64 rows (every tile reads its own columns only); A operand V[k][i], i = row - j: the
     // base shifted by -j rows (only rows j .. j+63 are addressed)
-    if (f_cols > j + NB) {
-      const int r = launch_gemm_strip(st, nb, A, lda, sys_stride, Wt - j, v_stride, j, f_cols, Yf, nrhs, n_pad);
-      if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r;
-    }
+    const int r = launch_gemm_strip(st, nb, A, lda, sys_stride, Wt - j, v_stride, j, f_cols, Yf, nrhs, n_pad);
+    if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r;
   };
-  // (A fused form - the diagonal block updated alone, then ONE pass U12 = C - [(X P^T) | W] [Q ; C] with K = 64 (q + 1) over the strip
-  // instead of the pending-update pass and the solve pass - was built and measured in round 3: these passes run at the zgemm
-  // pipeline's rate per K-chunk like the bulk update (0.445 / 0.79 / 1.22 ms for K = 64 / 128 / 192 at cfg 3), not at a bandwidth
-  // limit, so the same K-chunks in fewer passes gain 2.5 % of panel + in-group time at cfg 3, nothing at cfg 5, and lose 27 % at
-  // cfg 4 and 30 % for one system per call (three more small launches per panel).  Not kept)
   const bool left = sym_update_left(nb, n_pad, nrhs) != 0;       // form of the bulk update (one rule, BIEM_SYM_UPDATE forces one)
+  // The panels b, c, d of a group, two forms.  Two-pass: the panel's 64 rows take the group's pending updates in a C-streaming launch
+  // (K = 64 q), then the strip solves them (K = 64) - every row is read and written twice.  Stacked (sym_group_stacked: under the left-
+  // looking bulk update, large batches): only the diagonal tile takes the pending update; behind the diagonal block
+  // the rest of the rows is ONE pure product over K = 64 (q + 1) (k_sym_slab, launch_gemm_stack) - no C slots, one set of stores per tile.
+  // (Round 3 built a first fused form, U12 = C - [(X P^T) | W] [Q ; C] on the C-streaming kernel for every batch size: 2.5 % of panel +
+  // in-group time at cfg 3, and a loss of 27 - 30 % where few systems are in flight - three more small launches per panel.  Since then
+  // the strip became a pure product and the right-hand sides left the matrix; this form runs only where the launches are large.
+  // DESIGN.md section 5 has both measurements.)
+  const bool stacked = sym_group_stacked(left, nb);
+  cplx* slab = stacked ? sym_slab(d_work, nb, n_pad, nrhs) : nullptr;
   for (int J = 0; J < n_pad; J += 4 * NB) {
     const cplx* strip = A + (size_t)J * lda;        // both operands of this group's updates: rows J .. of the matrix itself
     if (left && J > 0) {
@@ -749,6 +831,12 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
     for (int q = 1; q < 4; ++q) {
       const int jq = J + q * NB;
       if (jq >= n_pad) break;
+      if (stacked) {
+        // the diagonal tile alone takes the group's pending updates (K = 64 q); the rest of the rows waits for the stacked pass
+        gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, jq, jq + NB, jq, jq + NB, J, q * NB, PK_OTHER);
+        panel(jq, J, slab);
+        continue;
+      }
       // the next panel's 64 rows: all pending updates of the group (K = 64 q), every column right of them incl. right-hand sides in the matrix
       gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, jq, jq + NB, jq, f_cols, J, q * NB, PK_OTHER);
       panel(jq);
