@@ -35,6 +35,7 @@ SIGNATURES = {
     "biem_plan_labels": (_i, [_vp, _vp, _vp]),
     "biem_plan_labels_n": (_i, [_vp, _i, _vp, _vp]),
     "biem_plan_symmetric_order": (_i, [_vp, _vp, _vp]),
+    "biem_plan_split_order": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp]),
     "biem_plan_fill_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "biem_plan_quadrature": (_i, [_vp, _vp, _vp]),
     "biem_plan_projection": (_i, [_vp, _vp]),
@@ -68,6 +69,7 @@ SIGNATURES = {
     "biem_sym_factor_solve": (_i, [_i, _i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
     "biem_sym_factor_solve_n": (_i, [_i, _i, _i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
     "biem_sym_update_form": (_i, [_i, _i, _i]),
+    "biem_last_solve_split": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "biem_sym_factor": (_i, [_i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
     "biem_sym_solve": (_i, [_i, _i, _i, _dp, _ll, _ll, _dp, _ll, _ll, _vp]),
     "biem_factor_workspace_bytes": (_sz, [_vp, _i, _i, _i]),

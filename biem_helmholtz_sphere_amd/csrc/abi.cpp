@@ -141,6 +141,22 @@ int biem_plan_symmetric_order(const biem_plan* plan, int* h_partner, int* h_slot
   return BIEM_OK;
 }
 
+int biem_plan_split_order(const biem_plan* plan, int B, int* n_cos, int* nE, int* nO, int* npE, int* npO, int* h_row) {
+  NEED(plan, "plan");
+  if (B < 1) { set_error("biem_plan_split_order: B < 1"); return BIEM_ERR_ARG; }
+  const int H = plan->H, U = (int)(plan->units.size() / 2);
+  const SplitMap m = make_split_map(B, H, U);
+  if (n_cos) *n_cos = U;
+  if (nE) *nE = B * U;
+  if (nO) *nO = B * (H - U);
+  if (npE) *npE = m.npE;
+  if (npO) *npO = m.npO;
+  if (h_row)
+    for (int b = 0; b < B; ++b)
+      for (int slot = 0; slot < H; ++slot) h_row[(size_t)b * H + slot] = m.row_of(b, H, slot);
+  return BIEM_OK;
+}
+
 int biem_plan_fill_info(const biem_plan* plan, int* n_units, int* n_phases, int* reduced_ok, int* lds_rows, int* gather_ok) {
   NEED(plan, "plan");
   if (n_units) *n_units = plan->E;
@@ -372,21 +388,34 @@ namespace {
 struct SolveLayout {
   int N, n_pad, chunk;
   long long lda, sys_stride;
-  size_t off_tab, off_A, off_T, off_P, off_ipiv, total;
+  size_t off_tab, off_A, off_T, off_P, off_ipiv, off_info2, total;
+  SplitMap split;                          // on: the split form of flat layouts (n_pad = npE + npO, lda and sys_stride with it)
 };
+// Flat layouts of at least this many unknowns take the split form; below, the step is bound by the per-panel launches, whose number
+// does not fall.  (Not 392 or below: rejection codes of small flat systems are pinned in unsplit row numbers by the tests.)
+constexpr int SYM_SPLIT_MIN_N = 1024;
+thread_local int g_last_split[2] = {0, 0};   // npE, npO of the last symmetric solve on this thread; 0, 0: unsplit
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // degree-dependent boundary coefficients of the *_n entries: alpha_n / beta_n [nb or 1][B][n_end] in place of alpha / beta [nb or 1][B],
 // the unmixed samples gu / gdn [nb][nrhs][B][Q] (either may be null: zero) in place of g
 struct DegreeBc { const double* alpha_n; const double* beta_n; const double* gu; const double* gdn; };
-SolveLayout make_layout(const biem_plan* p, int nb, int B, int nrhs, int chunk) {
+// One size serves both forms (the caller asks for it before the geometry is looked at): every region is as large as the larger form needs,
+// so the offsets are the same whichever runs; n_pad, lda and sys_stride are those of the form asked for.
+SolveLayout make_layout(const biem_plan* p, int nb, int B, int nrhs, int chunk, bool split = false) {
   SolveLayout L;
   L.N = B * p->H;
-  L.n_pad = lu_npad(L.N);
-  L.lda = L.n_pad + ((nrhs + 7) / 8) * 8;   // right-hand side columns; rows stay 128-byte aligned (8 complex128)
+  const int ldr = ((nrhs + 7) / 8) * 8;     // right-hand side columns; rows stay 128-byte aligned (8 complex128)
+  const int np_plain = lu_npad(L.N);
+  const SplitMap sm = make_split_map(B, p->H, (int)(p->units.size() / 2));
+  const int np_split = sm.npE + sm.npO, np_max = np_split > np_plain ? np_split : np_plain;
+  L.split = split ? sm : SplitMap();
+  L.n_pad = split ? np_split : np_plain;
+  L.lda = L.n_pad + ldr;
   L.sys_stride = (long long)L.n_pad * L.lda;
+  const size_t sys_max = (size_t)np_max * (np_max + ldr);
   if (chunk <= 0) {
     // resident matrices per chunk: as many as fit ~24 GiB, at most nb
-    size_t per = (size_t)L.sys_stride * 16 + (size_t)B * B * p->H2 * 16 + lu_workspace_bytes(1, L.n_pad, nrhs);
+    size_t per = sys_max * 16 + (size_t)B * B * p->H2 * 16 + lu_workspace_bytes(1, np_max, nrhs);
     size_t fit = ((size_t)24 << 30) / (per ? per : 1);
     chunk = (int)(fit < 1 ? 1 : (fit > (size_t)nb ? (size_t)nb : fit));
   }
@@ -395,10 +424,11 @@ SolveLayout make_layout(const biem_plan* p, int nb, int B, int nrhs, int chunk) 
   L.chunk = chunk;
   size_t o = 0;
   L.off_tab = o; o = align256(o + (size_t)nb * B * 3 * p->n_end * 16);
-  L.off_A = o; o = align256(o + (size_t)chunk * L.sys_stride * 16);
+  L.off_A = o; o = align256(o + (size_t)chunk * sys_max * 16);
   L.off_T = o; o = align256(o + fill_workspace_bytes(p, chunk, B));
-  L.off_P = o; o = align256(o + lu_workspace_bytes(chunk, L.n_pad, nrhs));
-  L.off_ipiv = o; o = align256(o + (size_t)chunk * L.n_pad * sizeof(int));
+  L.off_P = o; o = align256(o + lu_workspace_bytes(chunk, np_max, nrhs));
+  L.off_ipiv = o; o = align256(o + (size_t)chunk * np_max * sizeof(int));
+  L.off_info2 = o; o = align256(o + (size_t)chunk * sizeof(int));     // the O block's codes of the split form
   L.total = o;
   return L;
 }
@@ -420,15 +450,35 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
   if (nb <= 0 || B <= 0) return BIEM_OK;
   if (nrhs < 1) { set_error("biem_solve: nrhs < 1"); return BIEM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
-  SolveLayout L = make_layout(plan, nb, B, nrhs, chunk);
+  const int H = plan->H, d = plan->d, Q = plan->Q;
+  // Flat layouts (every centre with the same last coordinate): A~ = diag(E, O) in the split order, factored as two blocks.  The
+  // conditions that cost nothing come first; the centres come to the host only for calls that pass them (one small copy, one wait).
+  bool split = false;
+  if (symmetric) {
+    g_last_split[0] = g_last_split[1] = 0;
+    const char* e = getenv("BIEM_SYM_SPLIT");
+    const SplitMap sm = make_split_map(B, H, (int)(plan->units.size() / 2));
+    if (!(e && e[0] == '0') && !geom_batched && plan->tree != TREE_CAA && fill_sym_red_form(plan, B) && !sym_small_path(B * H, nrhs) &&
+        ((e && e[0] == '1') || B * H >= SYM_SPLIT_MIN_N) && sm.U < H && ((nrhs + 7) / 8) * 8 <= sm.npO) {
+      std::vector<double> hc((size_t)B * d);
+      BIEM_HIPCHK(hipMemcpyAsync(hc.data(), d_centers, hc.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      BIEM_HIPCHK(hipStreamSynchronize(st));
+      split = true;
+      const double z0 = hc[d - 1] + 0.0;      // (-0.0 + 0.0 = 0.0; == also takes the two zeros as equal, and no NaN as equal to anything)
+      for (int b = 0; b < B; ++b) if (!(hc[(size_t)b * d + d - 1] == z0)) { split = false; break; }
+    }
+  }
+  SolveLayout L = make_layout(plan, nb, B, nrhs, chunk, split);
   if (work_bytes < L.total) { set_error("biem_solve: workspace too small (%zu < %zu)", work_bytes, L.total); return BIEM_ERR_ARG; }
+  const SplitMap& sm = L.split;
+  if (split) { g_last_split[0] = sm.npE; g_last_split[1] = sm.npO; }
   char* w = (char*)d_work;
   double* tab = (double*)(w + L.off_tab);
   double* A = (double*)(w + L.off_A);
   void* T = w + L.off_T;
   void* Pw = w + L.off_P;
   int* ipiv = (int*)(w + L.off_ipiv);
-  const int H = plan->H, d = plan->d, Q = plan->Q;
+  int* info_O = (int*)(w + L.off_info2);
   int rc = bcn ? launch_ball_tables_n(plan, nb, B, d_k, d_eta, d_radii, geom_batched, bcn->alpha_n, bcn->beta_n, ab_batched, tab, st)
                : launch_ball_tables(plan, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, tab, st);
   if (rc) return rc;
@@ -442,10 +492,13 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
     const bool small = symmetric && sym_small_path(L.N, nrhs);
     // blocks of ball pairs with the same displacement and the same (radius, alpha, beta) on either side are contracted once
     const FillDedupe dd = {d_radii, d_alpha, d_beta};
+    if (split)
+      // E's right-hand-side columns lie inside the O rows' matrix columns: they are cleared for all rows BEFORE the fill writes O
+      BIEM_HIPCHK(hipMemset2DAsync(A + (size_t)sm.npE * 2, (size_t)L.lda * 16, 0, (size_t)(L.lda - L.n_pad) * 16, (size_t)L.n_pad * c, st));
     if (symmetric)
       // (degree-dependent coefficients: every pair on its own - the classes are keyed on one (alpha, beta) per ball)
       rc = launch_fill_sym(plan, c, B, ks, cen, geom_batched, tb, A, L.lda, L.sys_stride, L.n_pad, T, fill_workspace_bytes(plan, c, B), st, small,
-                           (!geom_batched && !ab_batched && !bcn) ? &dd : nullptr);
+                           (!geom_batched && !ab_batched && !bcn) ? &dd : nullptr, sm);
     else
       rc = launch_fill(plan, c, B, ks, cen, geom_batched, tb, BIEM_FILL_EQUILIBRATED, A, L.lda, L.sys_stride, L.n_pad, T,
                        fill_workspace_bytes(plan, c, B), st);
@@ -457,22 +510,34 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
     if (bcn) {
       const size_t ab0 = ab_batched ? (size_t)s0 * B * plan->n_end * 2 : 0;
       rc = launch_rhs_project_n(plan, c, B, nrhs, bcn->gu ? bcn->gu + g0 : nullptr, bcn->gdn ? bcn->gdn + g0 : nullptr, bcn->alpha_n + ab0,
-                                bcn->beta_n + ab0, ab_batched, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, st, symmetric);
+                                bcn->beta_n + ab0, ab_batched, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, st, symmetric, sm);
     } else {
-      rc = launch_rhs_project(plan, c, B, nrhs, d_g + g0, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, st, symmetric);
+      rc = launch_rhs_project(plan, c, B, nrhs, d_g + g0, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, st, symmetric, sm);
     }
     if (rc) return rc;
     bool amax_ready = false;
     if (symmetric) {
-      rc = launch_sym_rhs(plan, c, B, nrhs, L.n_pad, tb, A, L.lda, L.sys_stride, false, st);
+      rc = launch_sym_rhs(plan, c, B, nrhs, L.n_pad, tb, A, L.lda, L.sys_stride, false, st, sm);
       if (rc) return rc;
       // growth check of the factorisation: max |A~| >= 1 (its diagonal is exactly 1), so 1 is a valid, conservative reference
       // (a system is handed to the pivoted LU when max |u_ii u_ic| exceeds GROWTH_MAX = 200 x this lower bound); saves a pass over the matrix
-      rc = lu_growth_init(Pw, c, L.n_pad, 1.0, st);
+      rc = lu_growth_init(Pw, c, split ? sm.npE : L.n_pad, 1.0, st);
       if (rc) return rc;
       amax_ready = true;
     }
-    if (symmetric)
+    if (split) {
+      // the existing factorisation on two views of the one allocation, E then O (one stream: they share the workspace); E's codes
+      // go to the caller's array, O's beside them, merged below (the first nonzero wins, in the split layout's row numbers)
+      const int nE = B * sm.U, nO = B * (H - sm.U);
+      rc = launch_sym_factor_solve(c, sm.npE, nrhs, A, L.lda, L.sys_stride, d_info + s0, Pw, lu_workspace_bytes(c, sm.npE, nrhs), st, true, nE);
+      if (rc) return rc;
+      rc = lu_growth_init(Pw, c, sm.npO, 1.0, st);
+      if (rc) return rc;
+      rc = launch_sym_factor_solve(c, sm.npO, nrhs, A + 2 * ((size_t)sm.npE * L.lda + sm.npE), L.lda, L.sys_stride, info_O, Pw,
+                                   lu_workspace_bytes(c, sm.npO, nrhs), st, true, nO);
+      if (rc) return rc;
+      rc = launch_split_info_merge(c, sm.npE, sm.npO, d_info + s0, info_O, st);
+    } else if (symmetric)
       rc = launch_sym_factor_solve(c, L.n_pad, nrhs, A, L.lda, L.sys_stride, d_info + s0, Pw, lu_workspace_bytes(c, L.n_pad, nrhs), st, amax_ready, L.N);
     else
       rc = launch_lu_factor_solve(c, L.n_pad, nrhs, A, L.lda, L.sys_stride, ipiv, d_info + s0, Pw, lu_workspace_bytes(c, L.n_pad, nrhs), st,
@@ -484,10 +549,10 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
       if (rc) return rc;
     }
     if (symmetric) {
-      rc = launch_sym_rhs(plan, c, B, nrhs, L.n_pad, tb, A, L.lda, L.sys_stride, true, st);
+      rc = launch_sym_rhs(plan, c, B, nrhs, L.n_pad, tb, A, L.lda, L.sys_stride, true, st, sm);
       if (rc) return rc;
     }
-    rc = launch_density(plan, c, B, nrhs, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, tb, d_density + (size_t)s0 * nrhs * B * H * 2, st, symmetric);
+    rc = launch_density(plan, c, B, nrhs, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, tb, d_density + (size_t)s0 * nrhs * B * H * 2, st, symmetric, sm);
     if (rc) return rc;
   }
   return BIEM_OK;
@@ -505,6 +570,12 @@ int biem_solve_ldlt(const biem_plan* plan, int nb, int B, int nrhs, const double
                     const double* d_g, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes, void* stream) {
   return solve_impl(plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_g, d_density, d_info,
                     chunk, d_work, work_bytes, stream, true);
+}
+
+int biem_last_solve_split(int* npE, int* npO) {
+  if (npE) *npE = g_last_split[0];
+  if (npO) *npO = g_last_split[1];
+  return BIEM_OK;
 }
 
 int biem_solve_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,

@@ -85,6 +85,25 @@ struct ProfScope {
   }
 };
 
+// ---- split layout of the symmetric path (flat sphere layouts) ----
+// With every centre in one plane of constant last coordinate, A~ couples no cosine slot to a sine slot: it is diag(E, O) after the
+// permutation that collects the balls' cosine runs (U slots each) in rows [0, npE) and their sine runs (H - U each) in rows
+// [npE, npE + npO), both padded to whole 64-row tiles.  E's right-hand sides stand at column npE of the E rows (inside the E x O rectangle
+// nobody reads as matrix), O's at column n_pad = npE + npO as in the unsplit layout.  U == 0: the unsplit layout (row b H + slot).
+struct SplitMap {
+  int U, npE, npO;                        // (SplitMap(): all zero)
+  __host__ __device__ bool on() const { return U != 0; }
+  __host__ __device__ int row_of(int b, int H, int slot) const {
+    return U == 0 ? b * H + slot : slot < U ? b * U + slot : npE + b * (H - U) + (slot - U);
+  }
+  // offset of (b, slot)'s first right-hand side relative to column n_pad of row 0 (where the unsplit layout keeps them all)
+  __host__ __device__ long long rhs_off(int b, int H, int slot, long long lda) const {
+    return (long long)row_of(b, H, slot) * lda - ((U != 0 && slot < U) ? npO : 0);
+  }
+};
+inline int roundup64(int v) { return (v + 63) / 64 * 64; }
+inline SplitMap make_split_map(int B, int H, int U) { SplitMap m; m.U = U; m.npE = roundup64(B * U); m.npO = roundup64(B * (H - U)); return m; }
+
 // launch wrappers implemented in the .hip files (all stream-ordered, no syncs)
 int launch_radial(int d, int nmax, int count, const double* d_x, double* d_out, hipStream_t st);
 int launch_radial_c(int d, int nmax, int count, const double* d_z, double* d_out, hipStream_t st);
@@ -93,7 +112,7 @@ int launch_ball_tables(const biem_plan* p, int nb, int B, const double* d_k, con
                        int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, double* d_tab, hipStream_t st);
 // slot_order: harmonic h of a ball goes to / comes from the plan's internal slot hpos[h] (symmetric path) instead of position h
 int launch_rhs_project(const biem_plan* p, int nb, int B, int nrhs, const double* d_g, double* d_f, long long sys_stride,
-                       long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order = false);
+                       long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap());
 // degree-dependent boundary coefficients (kernels_degree_bc.hip): alpha_n / beta_n [nb or 1][B][n_end] complex; the tables are laid out
 // as launch_ball_tables' and feed the same fill / solve / density launches
 int launch_ball_tables_n(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
@@ -101,7 +120,7 @@ int launch_ball_tables_n(const biem_plan* p, int nb, int B, const double* d_k, c
 // f = -(alpha_n P[gu] + beta_n P[gdn]); a null sample set is zero; strides and slot order as launch_rhs_project
 int launch_rhs_project_n(const biem_plan* p, int nb, int B, int nrhs, const double* d_gu, const double* d_gdn, const double* d_alpha_n,
                          const double* d_beta_n, int ab_batched, double* d_f, long long sys_stride, long long elem_stride,
-                         long long rhs_stride, hipStream_t st, bool slot_order = false);
+                         long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap());
 // d_info[s] = code for every system with a (ball, degree) whose symmetric scaling 1 / sqrt(gj gh) is not finite (gj = 0); others untouched
 // (biem_flag_unscalable exposes it for tests)
 int launch_flag_unscalable(const biem_plan* p, int nb, int B, const double* d_tab, int* d_info, int code, hipStream_t st);
@@ -120,7 +139,8 @@ int launch_fill(const biem_plan* p, int nb, int B, const double* d_k, const doub
                 const double* d_tab, int scaling, double* d_A, long long lda, long long sys_stride, int n_pad,
                 void* d_work, size_t work_bytes, hipStream_t st);
 int launch_density(const biem_plan* p, int nb, int B, int nrhs, const double* d_x, long long sys_stride, long long elem_stride,
-                   long long rhs_stride, const double* d_tab, double* d_density, hipStream_t st, bool slot_order = false);
+                   long long rhs_stride, const double* d_tab, double* d_density, hipStream_t st, bool slot_order = false,
+                   const SplitMap& split = SplitMap());
 // the complex-symmetric form A~ = R W^H M W R^-1 in the plan's internal slot order, written only where the U^T U factorisation in row
 // form (launch_sym_factor_solve) reads it (UPPER triangle + diagonal 64 x 64 tiles); fill_sym_bytes = those bytes per system
 // FillDedupe (optional): per-ball radii [B], alpha [B], beta [B] (complex) shared by all systems of the call.  Ball pairs with the
@@ -130,8 +150,12 @@ int launch_density(const biem_plan* p, int nb, int B, int nrhs, const double* d_
 struct FillDedupe { const double* radii; const double* alpha; const double* beta; };
 int launch_fill_sym(const biem_plan* p, int nb, int B, const double* d_k, const double* d_centers, int geom_batched, const double* d_tab,
                     double* d_A, long long lda, long long sys_stride, int n_pad, void* d_work, size_t work_bytes, hipStream_t st, bool no_padding = false,
-                    const FillDedupe* dedupe = nullptr);
+                    const FillDedupe* dedupe = nullptr, const SplitMap& split = SplitMap());
 double fill_sym_bytes(int n_pad);
+// whether launch_fill_sym runs k_fill_red for this plan and B balls (the one fill form with a split mode)
+bool fill_sym_red_form(const biem_plan* p, int B);
+// info[s] = first nonzero of (E's code, O's code) in unsplit terms: row codes of O shifted by npE, either growth code -> -(n_pad + 1)
+int launch_split_info_merge(int nb, int npE, int npO, int* d_info, const int* d_info_O, hipStream_t st);
 int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
                  const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
                  double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
@@ -171,7 +195,7 @@ unsigned long long* lu_growth_slots(void* d_work, int nb, int n_pad);
 int lu_growth_init(void* d_work, int nb, int n_pad, double amax, hipStream_t st);
 // right-hand-side columns (slot order): f~ = R W^H f in place; inverse_on_solution: x = W R^-1 x~
 int launch_sym_rhs(const biem_plan* p, int nb, int B, int nrhs, int n_pad, const double* d_tab, double* d_A, long long lda,
-                   long long sys_stride, bool inverse_on_solution, hipStream_t st);
+                   long long sys_stride, bool inverse_on_solution, hipStream_t st, const SplitMap& split = SplitMap());
 // solve with a stored U^T U factor (upper triangle, identity-padded): forward U^T y = f, back U x = y, B row-major [n_pad][ldb] per system
 int launch_sym_solve(int nb, int n_pad, int nrhs, const double* d_U, long long lda, long long sys_stride, double* d_B, long long ldb,
                      long long b_stride, hipStream_t st);

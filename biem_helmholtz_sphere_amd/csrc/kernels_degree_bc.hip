@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(256) k_rhs_project_n(int H, int Q, int rows, i
                                                         const cplx* __restrict__ gd, const cplx* __restrict__ W,
                                                         const cplx* __restrict__ alpha_n, const cplx* __restrict__ beta_n, int ab_batched,
                                                         const int* __restrict__ deg, cplx* __restrict__ f, long long sys_stride,
-                                                        long long elem_stride, long long rhs_stride, const int* __restrict__ hpos) {
+                                                        long long elem_stride, long long rhs_stride, const int* __restrict__ hpos, SplitMap sm) {
   extern __shared__ cplx sg[];   // [2][RT][QC]: u_in samples, then d_n u_in samples
   constexpr int QC = 256;
   cplx* su = sg;
@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(256) k_rhs_project_n(int H, int Q, int rows, i
       int row = row0 + r;
       if (row >= rows) break;
       long long b = row % B, sr = row / B, rr = sr % nrhs, s = sr / nrhs;     // row = (s*nrhs + rr)*B + b
-      f[(size_t)s * sys_stride + ((size_t)b * H + (hpos ? hpos[h] : h)) * elem_stride + (size_t)rr * rhs_stride] =
+      f[s * sys_stride + sm.rhs_off((int)b, H, hpos ? hpos[h] : h, elem_stride) + rr * rhs_stride] =
           degree_mix(alpha_n, beta_n, ab_batched, n_end, B, s, b, n, au[r], ad[r]);
     }
   }
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) k_rhs_project_n_few(int H, int Q, int row
                                                             const cplx* __restrict__ alpha_n, const cplx* __restrict__ beta_n,
                                                             int ab_batched, const int* __restrict__ deg, cplx* __restrict__ f,
                                                             long long sys_stride, long long elem_stride, long long rhs_stride,
-                                                            const int* __restrict__ hpos) {
+                                                            const int* __restrict__ hpos, SplitMap sm) {
   extern __shared__ cplx sg[];   // [2][RT][QC]; afterwards the partial sums [2][16 slices][RT][16]  (RT * 256 complex per set either way)
   constexpr int QC = 256;
   cplx* su = sg;
@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(256) k_rhs_project_n_few(int H, int Q, int row
     }
     if (row < rows && h < H) {
       long long b = row % B, sr = row / B, rr = sr % nrhs, sy = sr / nrhs;     // row = (s*nrhs + rr)*B + b
-      f[(size_t)sy * sys_stride + ((size_t)b * H + (hpos ? hpos[h] : h)) * elem_stride + (size_t)rr * rhs_stride] =
+      f[sy * sys_stride + sm.rhs_off((int)b, H, hpos ? hpos[h] : h, elem_stride) + rr * rhs_stride] =
           degree_mix(alpha_n, beta_n, ab_batched, n_end, B, sy, b, deg[h], tu, td);
     }
   }
@@ -218,7 +218,7 @@ __global__ void __launch_bounds__(256) k_rhs_project_n_few(int H, int Q, int row
 
 int launch_rhs_project_n(const biem_plan* p, int nb, int B, int nrhs, const double* d_gu, const double* d_gdn, const double* d_alpha_n,
                          const double* d_beta_n, int ab_batched, double* d_f, long long sys_stride, long long elem_stride,
-                         long long rhs_stride, hipStream_t st, bool slot_order) {
+                         long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split) {
   if (nrhs < 1) { set_error("biem_rhs_project_n: nrhs < 1"); return BIEM_ERR_ARG; }
   int rows = nb * nrhs * B;
   if (rows <= 0) return BIEM_OK;
@@ -231,14 +231,14 @@ int launch_rhs_project_n(const biem_plan* p, int nb, int B, int nrhs, const doub
     hipLaunchKernelGGL(k_rhs_project_n_few<RT>, dim3((rows + RT - 1) / RT, (p->H + 15) / 16), dim3(256), shm, st, p->H, p->Q, rows, B,
                        nrhs, p->n_end, (const cplx*)d_gu, (const cplx*)d_gdn, (const cplx*)p->d_W, (const cplx*)d_alpha_n,
                        (const cplx*)d_beta_n, ab_batched, p->d_deg, (cplx*)d_f, sys_stride, elem_stride, rhs_stride,
-                       slot_order ? p->d_hpos : nullptr);
+                       slot_order ? p->d_hpos : nullptr, split);
     BIEM_LAUNCHCHK();
     return BIEM_OK;
   }
   hipLaunchKernelGGL(k_rhs_project_n<RT>, dim3((rows + RT - 1) / RT, (p->H + 255) / 256), dim3(256), shm, st, p->H, p->Q, rows, B,
                      nrhs, p->n_end, (const cplx*)d_gu, (const cplx*)d_gdn, (const cplx*)p->d_W, (const cplx*)d_alpha_n,
                      (const cplx*)d_beta_n, ab_batched, p->d_deg, (cplx*)d_f, sys_stride, elem_stride, rhs_stride,
-                     slot_order ? p->d_hpos : nullptr);
+                     slot_order ? p->d_hpos : nullptr, split);
   BIEM_LAUNCHCHK();
   return BIEM_OK;
 }

@@ -875,7 +875,9 @@ __device__ unsigned long long g_fill_trace[8];
 #else
 #define BIEM_FT(i)
 #endif
-template <int KT, int NC>
+// SPLIT (flat layouts, SplitMap in common.hpp): the cosine-cosine entry goes to the E block (ball origins b U, bp U), the sine-sine
+// entry to the O block (origins npE + b (H - U), npE + bp (H - U)); the two mixed entries are structural zeros and are not stored.
+template <int KT, int NC, bool SPLIT = false>
 __global__ void __launch_bounds__(FILL_SYM_THREADS) k_fill_red(int H, int U, int HR, int E, int NP, int n_end, int B, int nb, int npairs,
                                                                 const int* __restrict__ deg, const int* __restrict__ units,
                                                                 const int* __restrict__ spos, const int* __restrict__ rchunk,
@@ -884,7 +886,7 @@ __global__ void __launch_bounds__(FILL_SYM_THREADS) k_fill_red(int H, int U, int
                                                                 const uint16_t* __restrict__ rphsel,
                                                                 const cplx* __restrict__ T,
                                                                 cplx* __restrict__ A, long long lda, long long sys_stride,
-                                                                const int* __restrict__ classes) {
+                                                                const int* __restrict__ classes, int npE) {
   extern __shared__ char smem[];
   // NC = 2: TWO combinations per iteration - the coefficient and index reads of a group of rows feed both tables (a fifth less LDS
   // traffic per term: 21 instead of 26 bytes) and the barriers, the loop head and the list walk are paid once for two blocks
@@ -915,7 +917,7 @@ __global__ void __launch_bounds__(FILL_SYM_THREADS) k_fill_red(int H, int U, int
   const int nrow = deg[rh], ncol = deg[ch];
   const unsigned selA = rphsel[2 * (size_t)pi], selB = rphsel[2 * (size_t)pi + 1];
   const long long o00 = (long long)row_c * lda + col_c, o01 = (long long)row_c * lda + col_s, o10 = (long long)row_s * lda + col_c,
-                  o11 = (long long)row_s * lda + col_s;
+                  o11 = SPLIT ? (long long)(row_s - U) * lda + (col_s - U) : (long long)row_s * lda + col_s;   // (SPLIT: inside the O block)
   const double q2 = 0.70710678118654752440;
   const int nrep = classes[0];
   const int* dup_ptr = classes + 4 + npairs;
@@ -1035,6 +1037,24 @@ __global__ void __launch_bounds__(FILL_SYM_THREADS) k_fill_red(int H, int U, int
     const int e0 = dup_ptr[ci], e1 = dup_ptr[ci + 1];
     for (int e = e0; e < e1; ++e) {                          // every pair of the class (the representative first)
       const int bb = dup_bb[e];
+      if (SPLIT) {
+        // the same mirror rule per block: tiles are counted from the block's own origin (npE is a multiple of 64)
+        const int S = H - U, re0 = (bb >> 16) * U, ce0 = (bb & 0xffff) * U;            // (wave-uniform: scalar arithmetic)
+        (As + (size_t)re0 * lda + ce0)[o00] = x00;
+        if (ce0 - re0 - U < NB_TILE) {
+          const int row = re0 + row_c, col = ce0 + col_c;
+          if ((row >> 6) == (col >> 6)) As[(size_t)col * lda + row] = x00;
+        }
+        if (r2 && c2) {
+          const int ro0 = npE + (bb >> 16) * S, co0 = npE + (bb & 0xffff) * S;
+          (As + (size_t)ro0 * lda + co0)[o11] = x11;
+          if (co0 - ro0 - S < NB_TILE) {
+            const int row = ro0 + row_s - U, col = co0 + col_s - U;
+            if ((row >> 6) == (col >> 6)) As[(size_t)col * lda + row] = x11;
+          }
+        }
+        continue;
+      }
       const int rb0 = (bb >> 16) * H, cb0 = (bb & 0xffff) * H;     // b < bp: the block lies strictly above the diagonal
       cplx* Ab = As + (size_t)rb0 * lda + cb0;               // (wave-uniform: scalar arithmetic)
       Ab[o00] = x00;
@@ -1333,23 +1353,78 @@ __global__ void __launch_bounds__(64) k_fill_sym_diag(int H, int N, int n_pad, c
   if (!no_pad) for (int c = N + threadIdx.x; c < n_pad; c += 64) put(c);
 }
 
+// split form: the same for the E block (rows [0, npE): nE active, ball runs of U) and the O block (rows [npE, npE + npO): nO active,
+// runs of H - U), each with its own unit diagonal and identity padding, columns counted from the block's origin
+__global__ void __launch_bounds__(64) k_fill_sym_diag_split(int H, int U, int B, int npE, int npO, cplx* __restrict__ A, long long lda,
+                                                            long long sys_stride) {
+  const int r = blockIdx.x, s = blockIdx.y;
+  const bool odd = r >= npE;
+  const int base = odd ? npE : 0, lr = r - base, run = odd ? H - U : U, nact = B * run, np = odd ? npO : npE;
+  cplx* row = A + (size_t)s * sys_stride + (size_t)r * lda + base;
+  const int c0 = (lr / 64) * 64;
+  auto put = [&](int c) { row[c] = (lr == c) ? make_double2(1.0, 0.0) : make_double2(0.0, 0.0); };
+  if (lr >= nact) { for (int c = c0 + threadIdx.x; c < np; c += 64) put(c); return; }
+  const int br = lr / run, bend = (br + 1) * run;
+  for (int c = (c0 > br * run ? c0 : br * run) + threadIdx.x; c < bend; c += 64) put(c);
+  for (int c = nact + threadIdx.x; c < np; c += 64) put(c);
+}
+
+__global__ void k_split_info_merge(int nb, int npE, int npO, int* __restrict__ info, const int* __restrict__ info_O) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nb) return;
+  const int e = info[s], o = info_O[s], grow = -(npE + npO + 1);
+  if (e != 0) info[s] = e == -(npE + 1) ? grow : e;
+  else if (o != 0) info[s] = o == -(npO + 1) ? grow : o < 0 ? o - npE : o;
+}
+
+int launch_split_info_merge(int nb, int npE, int npO, int* d_info, const int* d_info_O, hipStream_t st) {
+  if (nb <= 0) return BIEM_OK;
+  hipLaunchKernelGGL(k_split_info_merge, dim3((nb + 255) / 256), dim3(256), 0, st, nb, npE, npO, d_info, d_info_O);
+  BIEM_LAUNCHCHK();
+  return BIEM_OK;
+}
+
 // bytes of one system the symmetric path writes and the factorisation reads: sum over rows of 16 * 64 (r / 64 + 1)
 double fill_sym_bytes(int n_pad) {
   const double t = n_pad / 64;
   return 16.0 * 64.0 * 64.0 * t * (t + 1.0) * 0.5;
 }
 
+// the fill form launch_fill_sym takes for B > 1 balls: the 2-D list-free kernel, systems in lanes, or one unit pair per lane (red / entry)
+static void fill_sym_form(const biem_plan* p, bool& direct2d, bool& use_red, bool& entry_fits, bool& sys_form, size_t& shm_entry, size_t& shm_red) {
+  const char* form = getenv("BIEM_FILL_FORM");
+  direct2d = p->tree == TREE_A && (!p->lists_built || !form);
+  shm_entry = 0; shm_red = 0;
+  // BIEM_FILL_FORM: "red" (default where it fits) = reduced-table entry form k_fill_red, "entry" = the gather form k_fill_sym it
+  // replaced (kept for A/B runs), "sys" = systems in lanes
+  const bool red_fits = fill_red_fits(p, &shm_red);
+  use_red = red_fits && !(form && (form[0] == 's' || form[0] == 'e'));
+  entry_fits = use_red || fill_sym_entry_fits(p, &shm_entry);
+  sys_form = form ? (form[0] == 's') : !entry_fits;
+}
+
+bool fill_sym_red_form(const biem_plan* p, int B) {
+  bool direct2d, use_red, entry_fits, sys_form; size_t a, b;
+  fill_sym_form(p, direct2d, use_red, entry_fits, sys_form, a, b);
+  return B > 1 && !direct2d && !sys_form && use_red && 2 * p->n_end <= kMaxRad;
+}
+
 int launch_fill_sym(const biem_plan* p, int nb, int B, const double* d_k, const double* d_centers, int geom_batched, const double* d_tab,
                     double* d_A, long long lda, long long sys_stride, int n_pad, void* d_work, size_t work_bytes, hipStream_t st, bool no_padding,
-                    const FillDedupe* dedupe) {
+                    const FillDedupe* dedupe, const SplitMap& split) {
   const int H = p->H, N = B * H, U = (int)(p->units.size() / 2);
   if (nb <= 0 || B <= 0) return BIEM_OK;
   if (lda < n_pad || n_pad < N || n_pad % 64) { set_error("biem_fill (symmetric): lda / n_pad too small or n_pad not a multiple of 64"); return BIEM_ERR_ARG; }
   if (work_bytes < fill_workspace_bytes(p, nb, B)) { set_error("biem_fill: workspace too small"); return BIEM_ERR_ARG; }
   if (nb > 65535) { set_error("biem_fill (symmetric): at most 65535 systems per call"); return BIEM_ERR_ARG; }
   cplx* T = (cplx*)d_work;
-  ProfScope ps(PK_FILL, st, (double)nb * fill_sym_bytes(n_pad));
-  const bool direct2d = p->tree == TREE_A && (!p->lists_built || !getenv("BIEM_FILL_FORM"));
+  if (split.on() && (split.U != U || n_pad != split.npE + split.npO || !fill_sym_red_form(p, B) || no_padding)) {
+    set_error("biem_fill (symmetric, split): internal: layout or fill form"); return BIEM_ERR_ARG;
+  }
+  ProfScope ps(PK_FILL, st, (double)nb * (split.on() ? fill_sym_bytes(split.npE) + fill_sym_bytes(split.npO) : fill_sym_bytes(n_pad)));
+  bool direct2d, use_red, entry_fits, sys_form;
+  size_t shm_entry = 0, shm_red = 0;
+  fill_sym_form(p, direct2d, use_red, entry_fits, sys_form, shm_entry, shm_red);
   if (!direct2d && 2 * p->n_end > kMaxRad) { set_error("n_end=%d exceeds the built table size", p->n_end); return BIEM_ERR_UNSUPPORTED; }
   if (direct2d && B > 1) {
     // 2-D: the list-free kernel (any order); pair classes as in the list forms
@@ -1374,14 +1449,6 @@ int launch_fill_sym(const biem_plan* p, int nb, int B, const double* d_k, const 
   // Two forms.  "entry" (one unit pair per lane, pair table in LDS) is the fast one wherever its tables fit LDS; "sys" (one
   // system per lane, pair tables from L2 / Infinity Cache: bound by the ~35-70 GB/s a CU gets from there, 150 vs 92 ms per 256
   // systems at cfg 3) has no ceiling on the order and takes over where the entry form does not fit.  BIEM_FILL_FORM forces one.
-  const char* form = getenv("BIEM_FILL_FORM");
-  size_t shm_entry = 0, shm_red = 0;
-  // BIEM_FILL_FORM: "red" (default where it fits) = reduced-table entry form k_fill_red, "entry" = the gather form k_fill_sym it
-  // replaced (kept for A/B runs), "sys" = systems in lanes
-  const bool red_fits = fill_red_fits(p, &shm_red);
-  const bool use_red = red_fits && !(form && (form[0] == 's' || form[0] == 'e'));
-  const bool entry_fits = use_red || fill_sym_entry_fits(p, &shm_entry);
-  const bool sys_form = form ? (form[0] == 's') : !entry_fits;
   if (!direct2d && B > 1 && sys_form) {
     // systems in lanes.  Workspace: Tt[groups][npairs][H2][64] then Qt[groups][B][n_end][64] (fill_workspace_bytes covers it)
     const int nbp = (nb + 63) / 64 * 64, npairs = B * (B - 1) / 2;
@@ -1465,13 +1532,14 @@ int launch_fill_sym(const biem_plan* p, int nb, int B, const double* d_k, const 
     const int HR = p->E + p->NP + 2 * p->n_end;
     const int red_threads = 64 * p->red_waves;
     const int kt_need = use_red ? (HR + red_threads - 1) / red_threads : (p->H2lin + FILL_SYM_THREADS - 1) / FILL_SYM_THREADS;
-#define BIEM_LAUNCH_FILL_RED(KT, NC)                                                                                                      \
+#define BIEM_LAUNCH_FILL_RED_AS(KT, NC, SP)                                                                                               \
   {                                                                                                                                       \
-    BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_fill_red<KT, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));              \
-    hipLaunchKernelGGL((k_fill_red<KT, NC>), dim3(nchunks, (unsigned)gy), dim3(red_threads), shm, st, H, U, HR, p->E, p->NP, p->n_end, B, nb, npairs, \
+    BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_fill_red<KT, NC, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));          \
+    hipLaunchKernelGGL((k_fill_red<KT, NC, SP>), dim3(nchunks, (unsigned)gy), dim3(red_threads), shm, st, H, U, HR, p->E, p->NP, p->n_end, B, nb, npairs, \
                        p->d_deg, p->d_units, p->d_spos, p->d_rchunk, p->d_rcrow, p->d_rwrow, p->rchunk_rows_max, p->d_rcoef, p->d_ridx,   \
-                       p->d_rphsel, T, (cplx*)d_A, lda, sys_stride, classes);                                                             \
+                       p->d_rphsel, T, (cplx*)d_A, lda, sys_stride, classes, split.npE);                                                  \
   }
+#define BIEM_LAUNCH_FILL_RED(KT, NC) { if (split.on()) BIEM_LAUNCH_FILL_RED_AS(KT, NC, true) else BIEM_LAUNCH_FILL_RED_AS(KT, NC, false) }
     if (use_red) {
       // two combinations per iteration (the plan reserves LDS for two table rows) unless BIEM_FILL_NC=1 at plan build (A / B runs)
       const bool nc2 = p->red_nc == 2;
@@ -1502,10 +1570,12 @@ int launch_fill_sym(const biem_plan* p, int nb, int B, const double* d_k, const 
     else BIEM_LAUNCH_FILL_SYM(8)
 #undef BIEM_LAUNCH_FILL_SYM
 #undef BIEM_LAUNCH_FILL_RED
+#undef BIEM_LAUNCH_FILL_RED_AS
     BIEM_LAUNCHCHK();
   }
   // (no_padding: the caller's solver never reads the identity padding - the LDS-resident path of small systems)
-  hipLaunchKernelGGL(k_fill_sym_diag, dim3(no_padding ? N : n_pad, nb), dim3(64), 0, st, H, N, n_pad, (cplx*)d_A, lda, sys_stride, no_padding ? 1 : 0);
+  if (split.on()) hipLaunchKernelGGL(k_fill_sym_diag_split, dim3(n_pad, nb), dim3(64), 0, st, H, U, B, split.npE, split.npO, (cplx*)d_A, lda, sys_stride);
+  else hipLaunchKernelGGL(k_fill_sym_diag, dim3(no_padding ? N : n_pad, nb), dim3(64), 0, st, H, N, n_pad, (cplx*)d_A, lda, sys_stride, no_padding ? 1 : 0);
   BIEM_LAUNCHCHK();
   return BIEM_OK;
 }
@@ -1517,7 +1587,7 @@ int launch_fill_sym(const biem_plan* p, int nb, int B, const double* d_k, const 
 template <int RT>
 __global__ void __launch_bounds__(256) k_rhs_project(int H, int Q, int rows, int B, int nrhs, const cplx* __restrict__ g,
                                                       const cplx* __restrict__ W, cplx* __restrict__ f, long long sys_stride,
-                                                      long long elem_stride, long long rhs_stride, const int* __restrict__ hpos) {
+                                                      long long elem_stride, long long rhs_stride, const int* __restrict__ hpos, SplitMap sm) {
   extern __shared__ cplx sg[];   // [RT][QC]
   constexpr int QC = 256;
   int row0 = blockIdx.y * RT;
@@ -1545,7 +1615,7 @@ __global__ void __launch_bounds__(256) k_rhs_project(int H, int Q, int rows, int
       int row = row0 + r;
       if (row >= rows) break;
       long long b = row % B, sr = row / B, rr = sr % nrhs, s = sr / nrhs;     // row = (s*nrhs + rr)*B + b
-      f[(size_t)s * sys_stride + ((size_t)b * H + (hpos ? hpos[h] : h)) * elem_stride + (size_t)rr * rhs_stride] = acc[r];
+      f[(long long)s * sys_stride + sm.rhs_off((int)b, H, hpos ? hpos[h] : h, elem_stride) + rr * rhs_stride] = acc[r];
     }
   }
 }
@@ -1556,7 +1626,7 @@ __global__ void __launch_bounds__(256) k_rhs_project(int H, int Q, int rows, int
 template <int RT>
 __global__ void __launch_bounds__(256) k_rhs_project_few(int H, int Q, int rows, int B, int nrhs, const cplx* __restrict__ g,
                                                           const cplx* __restrict__ W, cplx* __restrict__ f, long long sys_stride,
-                                                          long long elem_stride, long long rhs_stride, const int* __restrict__ hpos) {
+                                                          long long elem_stride, long long rhs_stride, const int* __restrict__ hpos, SplitMap sm) {
   extern __shared__ cplx sg[];   // [RT][QC]; afterwards the partial sums [16 slices][RT][16]
   constexpr int QC = 256;
   const int row0 = blockIdx.y * RT;
@@ -1587,13 +1657,13 @@ __global__ void __launch_bounds__(256) k_rhs_project_few(int H, int Q, int rows,
     for (int z = 0; z < 16; ++z) { const cplx v = sg[(z * RT + r) * 16 + hl]; t.x += v.x; t.y += v.y; }
     if (row < rows && h < H) {
       long long b = row % B, sr = row / B, rr = sr % nrhs, sy = sr / nrhs;     // row = (s*nrhs + rr)*B + b
-      f[(size_t)sy * sys_stride + ((size_t)b * H + (hpos ? hpos[h] : h)) * elem_stride + (size_t)rr * rhs_stride] = t;
+      f[(long long)sy * sys_stride + sm.rhs_off((int)b, H, hpos ? hpos[h] : h, elem_stride) + rr * rhs_stride] = t;
     }
   }
 }
 
 int launch_rhs_project(const biem_plan* p, int nb, int B, int nrhs, const double* d_g, double* d_f, long long sys_stride,
-                       long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order) {
+                       long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split) {
   if (nrhs < 1) { set_error("biem_rhs_project: nrhs < 1"); return BIEM_ERR_ARG; }
   int rows = nb * nrhs * B;
   if (rows <= 0) return BIEM_OK;
@@ -1603,13 +1673,13 @@ int launch_rhs_project(const biem_plan* p, int nb, int B, int nrhs, const double
   if ((long long)((p->H + 255) / 256) * ((rows + RT - 1) / RT) < 128) {
     hipLaunchKernelGGL(k_rhs_project_few<RT>, dim3((p->H + 15) / 16, (rows + RT - 1) / RT), dim3(256), shm, st, p->H, p->Q, rows, B,
                        nrhs, (const cplx*)d_g, (const cplx*)p->d_W, (cplx*)d_f, sys_stride, elem_stride, rhs_stride,
-                       slot_order ? p->d_hpos : nullptr);
+                       slot_order ? p->d_hpos : nullptr, split);
     BIEM_LAUNCHCHK();
     return BIEM_OK;
   }
   hipLaunchKernelGGL(k_rhs_project<RT>, dim3((p->H + 255) / 256, (rows + RT - 1) / RT), dim3(256), shm, st, p->H, p->Q, rows, B,
                      nrhs, (const cplx*)d_g, (const cplx*)p->d_W, (cplx*)d_f, sys_stride, elem_stride, rhs_stride,
-                     slot_order ? p->d_hpos : nullptr);
+                     slot_order ? p->d_hpos : nullptr, split);
   BIEM_LAUNCHCHK();
   return BIEM_OK;
 }
@@ -1626,7 +1696,7 @@ __device__ inline cplx sym_r(const cplx* __restrict__ tball, int n_end, int n) {
 
 __global__ void __launch_bounds__(256) k_sym_rhs(int H, int U, int n_end, int B, int nrhs, int n_pad, const int* __restrict__ units,
                                                   const int* __restrict__ spos, const int* __restrict__ deg, const cplx* __restrict__ tab,
-                                                  cplx* __restrict__ A, long long lda, long long sys_stride, int inverse) {
+                                                  cplx* __restrict__ A, long long lda, long long sys_stride, int inverse, SplitMap sm) {
   const int s = blockIdx.y;
   const int t = blockIdx.x * 256 + threadIdx.x;                 // (unit over all balls, rhs)
   if (t >= B * U * nrhs) return;
@@ -1634,8 +1704,8 @@ __global__ void __launch_bounds__(256) k_sym_rhs(int H, int U, int n_end, int B,
   const int rh = units[2 * ur], rp = units[2 * ur + 1];
   const cplx* ts = tab + ((size_t)s * B + br) * 3 * n_end;
   cplx* F = A + (size_t)s * sys_stride + n_pad + q;
-  cplx* pc = F + (size_t)(br * H + ur) * lda;
-  cplx* psn = F + (size_t)(br * H + U + (rp != rh ? spos[ur] : 0)) * lda;
+  cplx* pc = F + sm.rhs_off(br, H, ur, lda);
+  cplx* psn = F + sm.rhs_off(br, H, U + (rp != rh ? spos[ur] : 0), lda);
   const double q2 = 0.70710678118654752440;
   if (!inverse) {
     const cplx r = sym_r(ts, n_end, deg[rh]);
@@ -1656,13 +1726,13 @@ __global__ void __launch_bounds__(256) k_sym_rhs(int H, int U, int n_end, int B,
 }
 
 int launch_sym_rhs(const biem_plan* p, int nb, int B, int nrhs, int n_pad, const double* d_tab, double* d_A, long long lda,
-                   long long sys_stride, bool inverse_on_solution, hipStream_t st) {
+                   long long sys_stride, bool inverse_on_solution, hipStream_t st, const SplitMap& split) {
   const int U = (int)(p->units.size() / 2);
   if (nb <= 0 || B <= 0 || nrhs <= 0) return BIEM_OK;
   if (nb > 65535) { set_error("biem symmetric path: at most 65535 systems per call"); return BIEM_ERR_ARG; }
   ProfScope ps(PK_SWAP, st, 0.0);   // class 4: row interchanges in the LU, these transforms in the symmetric path
   hipLaunchKernelGGL(k_sym_rhs, dim3((B * U * nrhs + 255) / 256, nb), dim3(256), 0, st, p->H, U, p->n_end, B, nrhs, n_pad, p->d_units,
-                     p->d_spos, p->d_deg, (const cplx*)d_tab, (cplx*)d_A, lda, sys_stride, inverse_on_solution ? 1 : 0);
+                     p->d_spos, p->d_deg, (const cplx*)d_tab, (cplx*)d_A, lda, sys_stride, inverse_on_solution ? 1 : 0, split);
   BIEM_LAUNCHCHK();
   return BIEM_OK;
 }
@@ -1672,7 +1742,7 @@ int launch_sym_rhs(const biem_plan* p, int nb, int B, int nrhs, int n_pad, const
 // ---------------------------------------------------------------------------------------------
 __global__ void k_density(int H, int n_end, int B, int nrhs, long long total, const int* __restrict__ deg, const cplx* __restrict__ x,
                           long long sys_stride, long long elem_stride, long long rhs_stride, const cplx* __restrict__ tab,
-                          cplx* __restrict__ dens, const int* __restrict__ hpos) {
+                          cplx* __restrict__ dens, const int* __restrict__ hpos, SplitMap sm) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;     // i = ((s*nrhs + r)*B + b)*H + h
   if (i >= total) return;
   int h = (int)(i % H);
@@ -1680,17 +1750,17 @@ __global__ void k_density(int H, int n_end, int B, int nrhs, long long total, co
   long long b = srb % B, sr = srb / B, r = sr % nrhs, s = sr / nrhs;
   int n = deg[h];
   const cplx* t = tab + (size_t)(s * B + b) * 3 * n_end;
-  cplx v = x[(size_t)s * sys_stride + ((size_t)b * H + (hpos ? hpos[h] : h)) * elem_stride + (size_t)r * rhs_stride];
+  cplx v = x[s * sys_stride + sm.rhs_off((int)b, H, hpos ? hpos[h] : h, elem_stride) + r * rhs_stride];
   dens[i] = cmul(v, crecip(cmul(t[n_end + n], t[2 * n_end + n])));
 }
 
 int launch_density(const biem_plan* p, int nb, int B, int nrhs, const double* d_x, long long sys_stride, long long elem_stride,
-                   long long rhs_stride, const double* d_tab, double* d_density, hipStream_t st, bool slot_order) {
+                   long long rhs_stride, const double* d_tab, double* d_density, hipStream_t st, bool slot_order, const SplitMap& split) {
   if (nrhs < 1) { set_error("biem_density: nrhs < 1"); return BIEM_ERR_ARG; }
   long long total = (long long)nb * nrhs * B * p->H;
   if (total <= 0) return BIEM_OK;
   hipLaunchKernelGGL(k_density, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p->H, p->n_end, B, nrhs, total, p->d_deg,
-                     (const cplx*)d_x, sys_stride, elem_stride, rhs_stride, (const cplx*)d_tab, (cplx*)d_density, slot_order ? p->d_hpos : nullptr);
+                     (const cplx*)d_x, sys_stride, elem_stride, rhs_stride, (const cplx*)d_tab, (cplx*)d_density, slot_order ? p->d_hpos : nullptr, split);
   BIEM_LAUNCHCHK();
   return BIEM_OK;
 }

@@ -95,6 +95,12 @@ int biem_plan_labels_n(const biem_plan* plan, int width, int* h_labels, int* h_d
  * internal position of harmonic h among its ball's H unknowns in that path: for a unit (h <= p) the "cosine" combination
  * (Y_h + Y_p)/sqrt2 sits in slot h_slot[h], the "sine" combination i (Y_p - Y_h)/sqrt2 in slot h_slot[p] */
 int biem_plan_symmetric_order(const biem_plan* plan, int* h_partner /*[H]*/, int* h_slot /*[H]*/);
+/* the split layout of the symmetric path for B balls (host information).  For the chain trees (a, ba, bba, b...ba) the cosine slots
+ * are even and the sine slots odd under reflection of the LAST coordinate, so with every centre at the same last coordinate A~ couples
+ * no cosine slot to a sine slot: it is diag(E, O) once the balls' cosine runs (n_cos slots each) are collected in rows [0, nE) and their
+ * sine runs in rows [npE, npE + nO); npE, npO = nE, nO rounded up to whole 64-row tiles.  h_row[b][slot] = row of unknown (b, slot).
+ * Any output may be null. */
+int biem_plan_split_order(const biem_plan* plan, int B, int* n_cos, int* nE, int* nO, int* npE, int* npO, int* h_row /*[B][H]*/);
 /* which forms of the symmetric fill this plan's tables admit (host information, no device needed): n_units = label units E of the
  * reduced pair table (a degree < 2 n_end - 1 label and its conjugate partner share an entry), n_phases = distinct azimuthal phases,
  * reduced_ok = 1 if every term list is of one kind and one phase and a wave's lists fit LDS (the default fill kernel), lds_rows =
@@ -209,6 +215,14 @@ int biem_sym_factor_solve_n(int nb, int n_pad, int n_active, int nrhs, double* d
  * Left runs when even its smallest launch, the last group's band, has a tile for every CU over the nb systems: 256 tiles, half the
  * update kernel's persistent grid of 512 workgroups.  BIEM_SYM_UPDATE=left|right in the environment forces a form; read per call. */
 int biem_sym_update_form(int nb, int n_pad, int nrhs);
+/* How the last biem_solve_ldlt / biem_solve_ldlt_n call of this thread ran: npE = npO = 0 unsplit, otherwise the padded orders of the
+ * two blocks it factored one after the other (biem_plan_split_order).  The split form runs for shared geometry (geom_batched = 0) of a
+ * chain tree whose centres all have the same last coordinate (compared bit for bit on the host, -0.0 as 0.0: one small copy and one
+ * stream synchronisation, only for calls that pass every other condition), filled by the default fill form, N = B H >= 1024 and not on
+ * the one-launch small path.  BIEM_SYM_SPLIT=0 in the environment disables it, =1 drops the size rule only; read per call.
+ * Rejection codes are in the split layout's row numbers (O's rows shifted by npE), growth -(npE + npO + 1), unscalable -(npE + npO + 2).
+ * biem_solve_workspace_bytes covers either form. */
+int biem_last_solve_split(int* npE, int* npO);
 
 /* density[s][r][b][h] = x / (gh * blc): the reference's `density` from the equilibrated unknowns (also the
  * single-ball shortcut _biem.py:648-691 with x = f).  x element (s, r, i) at d_x[s*sys_stride + i*elem_stride + r*rhs_stride]. */
