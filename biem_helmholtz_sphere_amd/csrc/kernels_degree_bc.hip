@@ -3,7 +3,7 @@
 //
 // Only the two places where alpha and beta enter are here: the per-ball tables and the projection of the incident field.  Fill,
 // factorisations, density and the field kernels read the tables and never see where gj and gh came from; they are the kernels of
-// kernels_fill.hip / kernels_lu.hip / kernels_uscat.hip, launched unchanged.
+// kernels_fill.hip / kernels_fill_sym.hip / kernels_rhs.hip / kernels_lu.hip / kernels_uscat.hip, launched unchanged.
 #include "common.hpp"
 
 namespace biem {
