@@ -318,6 +318,7 @@ int biem_sym_factor_solve_n(int nb, int n_pad, int n_active, int nrhs, double* d
 }
 
 int biem_sym_update_form(int nb, int n_pad, int nrhs) { return sym_update_left(nb, n_pad, nrhs); }
+int biem_sym_form(int nb, int n_pad, int n_active, int nrhs, int* form, size_t* work) { return sym_form_query(nb, n_pad, n_active, nrhs, form, work); }
 
 int biem_density(const biem_plan* plan, int nb, int B, int nrhs, const double* d_x, long long sys_stride, long long elem_stride,
                  long long rhs_stride, const double* d_tab, double* d_density, void* stream) {
@@ -439,6 +440,44 @@ size_t biem_solve_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs
   return make_layout(plan, nb, B, nrhs, chunk).total;
 }
 
+// Flat layouts (every centre with the same last coordinate): A~ = diag(E, O) in the split order, factored as two blocks.  Whether this
+// call takes the split form: `split` is set, or left off (SplitMap()).  The conditions that cost nothing come first; the centres come
+// to the host only for calls that pass them (one small copy, one wait).
+static int flat_layout_split(const biem_plan* plan, int B, int nrhs, const double* d_centers, int geom_batched, hipStream_t st, SplitMap& split) {
+  split = SplitMap();
+  const int H = plan->H, d = plan->d;
+  const char* e = getenv("BIEM_SYM_SPLIT");
+  const SplitMap sm = make_split_map(B, H, (int)(plan->units.size() / 2));
+  if ((e && e[0] == '0') || geom_batched || plan->tree == TREE_CAA || !fill_sym_red_form(plan, B) || sym_small_path(B * H, nrhs) ||
+      !((e && e[0] == '1') || B * H >= SYM_SPLIT_MIN_N) || sm.U >= H || ((nrhs + 7) / 8) * 8 > sm.npO)
+    return BIEM_OK;
+  std::vector<double> hc((size_t)B * d);
+  BIEM_HIPCHK(hipMemcpyAsync(hc.data(), d_centers, hc.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  BIEM_HIPCHK(hipStreamSynchronize(st));
+  const double z0 = hc[d - 1] + 0.0;      // (-0.0 + 0.0 = 0.0; == also takes the two zeros as equal, and no NaN as equal to anything)
+  for (int b = 0; b < B; ++b) if (!(hc[(size_t)b * d + d - 1] == z0)) return BIEM_OK;
+  split = sm;
+  return BIEM_OK;
+}
+
+// The symmetric factorisation of a chunk of c systems as a list of diagonal blocks of the one allocation: the whole matrix, or E then O
+// of the split form.  One stream and one workspace: the blocks run one after the other.  Each block's growth slots are preset first -
+// max |A~| >= 1 (its diagonal is exactly 1), so 1 is a valid, conservative reference (a system is handed to the pivoted LU when
+// max |u_ii u_ic| exceeds GROWTH_MAX = 200 x this lower bound); saves a pass over the matrix.  Two blocks: the first one's codes are
+// the caller's array, the second one's stand beside them and are merged (the first nonzero wins, in the split layout's row numbers).
+struct SymBlock { size_t view; int n_pad, n_active; int* info; };       // view: the block's first entry, in doubles from A
+static int factor_sym_blocks(int c, int nrhs, double* A, long long lda, long long sys_stride, const SymBlock* blocks, int n_blocks, void* Pw,
+                             hipStream_t st) {
+  for (int i = 0; i < n_blocks; ++i) {
+    const SymBlock& b = blocks[i];
+    int rc = lu_growth_init(Pw, c, b.n_pad, 1.0, st);
+    if (rc) return rc;
+    rc = launch_sym_factor_solve(c, b.n_pad, nrhs, A + b.view, lda, sys_stride, b.info, Pw, lu_workspace_bytes(c, b.n_pad, nrhs), st, true, b.n_active);
+    if (rc) return rc;
+  }
+  return n_blocks == 2 ? launch_split_info_merge(c, blocks[0].n_pad, blocks[1].n_pad, blocks[0].info, blocks[1].info, st) : BIEM_OK;
+}
+
 static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
                const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched,
                const double* d_g, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes, void* stream,
@@ -451,23 +490,12 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
   if (nrhs < 1) { set_error("biem_solve: nrhs < 1"); return BIEM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   const int H = plan->H, d = plan->d, Q = plan->Q;
-  // Flat layouts (every centre with the same last coordinate): A~ = diag(E, O) in the split order, factored as two blocks.  The
-  // conditions that cost nothing come first; the centres come to the host only for calls that pass them (one small copy, one wait).
-  bool split = false;
+  SplitMap flat = SplitMap();              // (off: the pivoted LU has no split form)
   if (symmetric) {
     g_last_split[0] = g_last_split[1] = 0;
-    const char* e = getenv("BIEM_SYM_SPLIT");
-    const SplitMap sm = make_split_map(B, H, (int)(plan->units.size() / 2));
-    if (!(e && e[0] == '0') && !geom_batched && plan->tree != TREE_CAA && fill_sym_red_form(plan, B) && !sym_small_path(B * H, nrhs) &&
-        ((e && e[0] == '1') || B * H >= SYM_SPLIT_MIN_N) && sm.U < H && ((nrhs + 7) / 8) * 8 <= sm.npO) {
-      std::vector<double> hc((size_t)B * d);
-      BIEM_HIPCHK(hipMemcpyAsync(hc.data(), d_centers, hc.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      BIEM_HIPCHK(hipStreamSynchronize(st));
-      split = true;
-      const double z0 = hc[d - 1] + 0.0;      // (-0.0 + 0.0 = 0.0; == also takes the two zeros as equal, and no NaN as equal to anything)
-      for (int b = 0; b < B; ++b) if (!(hc[(size_t)b * d + d - 1] == z0)) { split = false; break; }
-    }
+    if (const int rc = flat_layout_split(plan, B, nrhs, d_centers, geom_batched, st, flat)) return rc;
   }
+  const bool split = flat.on();
   SolveLayout L = make_layout(plan, nb, B, nrhs, chunk, split);
   if (work_bytes < L.total) { set_error("biem_solve: workspace too small (%zu < %zu)", work_bytes, L.total); return BIEM_ERR_ARG; }
   const SplitMap& sm = L.split;
@@ -515,31 +543,15 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
       rc = launch_rhs_project(plan, c, B, nrhs, d_g + g0, A + (size_t)L.n_pad * 2, L.sys_stride, L.lda, 1, st, symmetric, sm);
     }
     if (rc) return rc;
-    bool amax_ready = false;
     if (symmetric) {
       rc = launch_sym_rhs(plan, c, B, nrhs, L.n_pad, tb, A, L.lda, L.sys_stride, false, st, sm);
       if (rc) return rc;
-      // growth check of the factorisation: max |A~| >= 1 (its diagonal is exactly 1), so 1 is a valid, conservative reference
-      // (a system is handed to the pivoted LU when max |u_ii u_ic| exceeds GROWTH_MAX = 200 x this lower bound); saves a pass over the matrix
-      rc = lu_growth_init(Pw, c, split ? sm.npE : L.n_pad, 1.0, st);
-      if (rc) return rc;
-      amax_ready = true;
-    }
-    if (split) {
-      // the existing factorisation on two views of the one allocation, E then O (one stream: they share the workspace); E's codes
-      // go to the caller's array, O's beside them, merged below (the first nonzero wins, in the split layout's row numbers)
-      const int nE = B * sm.U, nO = B * (H - sm.U);
-      rc = launch_sym_factor_solve(c, sm.npE, nrhs, A, L.lda, L.sys_stride, d_info + s0, Pw, lu_workspace_bytes(c, sm.npE, nrhs), st, true, nE);
-      if (rc) return rc;
-      rc = lu_growth_init(Pw, c, sm.npO, 1.0, st);
-      if (rc) return rc;
-      rc = launch_sym_factor_solve(c, sm.npO, nrhs, A + 2 * ((size_t)sm.npE * L.lda + sm.npE), L.lda, L.sys_stride, info_O, Pw,
-                                   lu_workspace_bytes(c, sm.npO, nrhs), st, true, nO);
-      if (rc) return rc;
-      rc = launch_split_info_merge(c, sm.npE, sm.npO, d_info + s0, info_O, st);
-    } else if (symmetric)
-      rc = launch_sym_factor_solve(c, L.n_pad, nrhs, A, L.lda, L.sys_stride, d_info + s0, Pw, lu_workspace_bytes(c, L.n_pad, nrhs), st, amax_ready, L.N);
-    else
+      // the existing factorisation on the whole matrix, or on two views of the one allocation, E then O
+      const SymBlock whole[1] = {{0, L.n_pad, L.N, d_info + s0}};
+      const SymBlock halves[2] = {{0, sm.npE, B * sm.U, d_info + s0},
+                                  {2 * ((size_t)sm.npE * L.lda + sm.npE), sm.npO, B * (H - sm.U), info_O}};
+      rc = factor_sym_blocks(c, nrhs, A, L.lda, L.sys_stride, split ? halves : whole, split ? 2 : 1, Pw, st);
+    } else
       rc = launch_lu_factor_solve(c, L.n_pad, nrhs, A, L.lda, L.sys_stride, ipiv, d_info + s0, Pw, lu_workspace_bytes(c, L.n_pad, nrhs), st,
                                   /*keep_multipliers=*/false, false, false);   // the fused path only needs the solution
     if (rc) return rc;
@@ -675,9 +687,8 @@ static int factor_impl(const biem_plan* plan, int nb, int B, const double* d_k, 
     rc = launch_fill_sym(plan, c, B, ks, cen, geom_batched, tb, A, lda, sys_stride, L.n_pad, T, fill_workspace_bytes(plan, c, B), st, false,
                          (!geom_batched && !ab_batched && !per_degree) ? &dd : nullptr);
     if (rc) return rc;
-    rc = lu_growth_init(Pw, c, L.n_pad, 1.0, st);     // max |A~| >= 1 (unit diagonal), as in biem_solve_ldlt
-    if (rc) return rc;
-    rc = launch_sym_factor_solve(c, L.n_pad, 0, A, lda, sys_stride, d_info + s0, Pw, lu_workspace_bytes(c, L.n_pad, 0), st, true, L.N);
+    const SymBlock whole[1] = {{0, L.n_pad, L.N, d_info + s0}};      // (growth preset as in biem_solve_ldlt)
+    rc = factor_sym_blocks(c, 0, A, lda, sys_stride, whole, 1, Pw, st);
     if (rc) return rc;
     if (per_degree) {     // a degree with gj = 0 has no symmetric scaling (biem_solve_ldlt_n)
       rc = launch_flag_unscalable(plan, c, B, tb, d_info + s0, -(L.n_pad + 2), st);

@@ -57,7 +57,73 @@ constexpr int SYM_SLAB_CPLX = 4 * NB * NB;   // [S_J ; S_{J+64} ; S_{J+128} ; V_
 constexpr int BACK_ROWS = 16;   // rows per workgroup (4 per wave)
 constexpr int RHS_UPD_ROWS = 64;  // rows per workgroup of k_rhs_update
 
+// ---------------------------------------------------------------------------------------------
+// The one workspace of the dense factorisations: lu_workspace_bytes(nb, n_pad, nrhs) bytes at d_work serve the pivoted LU, the
+// L D L^T column form and the U^T U row form.  Regions in this order, byte offsets from d_work (dense_work fills them; a region ends
+// where the next one starts):
+//   panels   four 64-column panels per system, column-major with ldp = n_pad (two K = 128 blocks = one K = 256 update):
+//            PANEL_COLS * n_pad complex per system.  The row form factors in place and needs no panels: it hands the region out
+//            again under other names (SymAliases below)
+//   block    64 x 64 complex per system: I - L11^{-1} of the MFMA triangular solve (LU), U11^{-1} (column form), V = -U11^{-T} (row form)
+//   tri_map  the tile map of the triangular updates: one int per lower-triangle tile of the largest trailing matrix, T (T + 1) / 2
+//            with T = n_pad / 64, rounded up to 64 ints
+//   growth   two doubles per system as 64-bit patterns: max |A| over what the symmetric factorisation reads, max |U| (see above)
+//   spare    64 complex per system that NO code reads or writes (an earlier row form kept a vector per system there); its bytes stay,
+//            because biem_lu_workspace_bytes is public and the slab's place is counted from the end
+//   slab     [S ; S ; S ; V] of a group of the row form's stacked pass: SYM_SLAB_CPLX complex per system
+// nrhs does not enter today; it stays an argument of the public size.
+// ---------------------------------------------------------------------------------------------
+constexpr int PANEL_COLS = 4 * NB;           // columns of n_pad complex per system in the panel region
+struct DenseWork {
+  size_t panels, block, tri_map, growth, spare, slab, total;
+  cplx* panels_at(void* w) const { return (cplx*)((char*)w + panels); }
+  cplx* block_at(void* w) const { return (cplx*)((char*)w + block); }
+  int* tri_map_at(void* w) const { return (int*)((char*)w + tri_map); }
+  unsigned long long* growth_at(void* w) const { return (unsigned long long*)((char*)w + growth); }
+  cplx* slab_at(void* w) const { return (cplx*)((char*)w + slab); }
+};
+inline DenseWork dense_work(int nb, int n_pad, int nrhs) {
+  (void)nrhs;
+  const size_t T = (size_t)n_pad / NB;
+  DenseWork w;
+  w.panels = 0;
+  w.block = w.panels + (size_t)nb * PANEL_COLS * (size_t)ldp_of(n_pad) * sizeof(cplx);
+  w.tri_map = w.block + (size_t)nb * NB * NB * sizeof(cplx);
+  w.growth = w.tri_map + ((T * (T + 1) / 2 + 63) / 64) * 64 * sizeof(int);
+  w.spare = w.growth + (size_t)nb * 2 * sizeof(double);
+  w.slab = w.spare + (size_t)nb * NB * sizeof(cplx);
+  w.total = w.slab + (size_t)nb * SYM_SLAB_CPLX * sizeof(cplx);
+  return w;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The form of one call of launch_sym_factor_solve, decided once by sym_form (kernels_sym.hip, with the rules and their measurements);
+// the launcher's three stages switch on it and decide nothing themselves.  With `small` the other fields are not used.
+// ---------------------------------------------------------------------------------------------
+struct SymForm {
+  bool small; int kr; bool two;     // the one-launch LDS-resident path and its instantiation k_small_utu<kr, two>
+  bool left;                        // bulk update left-looking (launch_gemm_left before a group), else the K = 256 update after it
+  bool stacked;                     // panels b, c, d of a group in one stacked product pass, else in-group update + strip
+  bool rhs_gemv;                    // the right-hand sides ride in the compact copy Y[s][q][row], else as columns of the matrix
+  enum Back { BACK_ROW = 0, BACK_COL = 1, BACK_STEP = 2 } back;   // back substitution: k_back_row / back_substitute_cols / k_back_step
+  bool keep_w() const { return back == BACK_STEP; }               // every panel's W = I - U11^{-T} is kept for k_back_step
+  bool diag_blk;                    // diagonal kernel k_diag_utu_blk (four pivots per barrier), else k_diag_utu_reg
+};
+// What the row form keeps in the panel region (nullptr: not used by this form):
+//   Wall  keep_w: the kept W blocks, n_pad x 64 complex per system (wall_stride), system after system
+//   Xsol  keep_w: behind them the solutions of k_back_step, nrhs x n_pad per system
+//   Y     the compact copy Y[s][q][row], nrhs x n_pad per system, of the forward substitution (rhs_gemv) and of the row-form back
+//         substitution: at the region's start, or at Xsol where the W blocks are kept
+// Capacity: Wall takes NB of the PANEL_COLS columns per system, so keep_w holds PANEL_COLS - NB right-hand sides and the row form's
+// copy PANEL_COLS; sym_form sends more to the form that needs no copy.
+constexpr int SYM_ROW_RHS_MAX = PANEL_COLS, SYM_STEP_RHS_MAX = PANEL_COLS - NB;
+struct SymAliases { cplx *Wall, *Xsol, *Y; long long wall_stride; size_t wall_bytes, y_off, y_bytes; };
+
 #pragma GCC visibility push(hidden)   // between the units of one library: none of these is exported
+// ---- kernels_sym.hip
+SymForm sym_form(int nb, int n_pad, int n_active, int nrhs);
+// the aliases of form f at d_work (which may be null: offsets and sizes only); BIEM_ERR_ARG if one would leave the panel region
+int sym_aliases(const SymForm& f, const DenseWork& w, void* d_work, int nb, int n_pad, int nrhs, SymAliases& a);
 // ---- kernels_gemm3m.hip
 // C[row_begin:row_end, col_begin:col_end] -= P[0:kd]^T (rows of the region) * M[brow:brow+kd, cols of the region]
 int launch_gemm_stream(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, const cplx* Pw, long long ldp,
@@ -75,6 +141,8 @@ int launch_gemm_strip(hipStream_t st, int nb, cplx* A, long long lda, long long 
 int launch_gemm_stack(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, const cplx* slab, long long slab_stride, int J, int p,
                       int col_end, cplx* Y = nullptr, int nrhs = 0, int y_ld = 0);
 void launch_tri_map(hipStream_t st, int* tri_map, int n_pad);   // tile map of the triangular updates of an n_pad system
+// sym_form's default rule for the bulk update: whether the smallest launch of the left-looking form has a tile for every CU
+bool gemm_left_fills_grid(int nb, int n_pad, int nrhs);
 // ---- kernels_trisolve.hip
 void launch_zero_int(hipStream_t st, int* p, int n);
 void launch_growth_check(hipStream_t st, int nb, int n_pad, const unsigned long long* growth, int* d_info, double limit);
@@ -85,7 +153,6 @@ void launch_rhs_update(hipStream_t st, int nb, int nrhs, cplx* A, long long lda,
 void back_substitute_cols(hipStream_t st, int nb, int n_pad, int nrhs, const cplx* A, long long lda, long long sys_stride, cplx* F,
                           long long ldf, long long f_stride, int* d_info = nullptr, unsigned long long* growth = nullptr, double inv_rel2 = 0.0);
 // ---- kernels_lu.hip
-cplx* sym_slab(void* d_work, int nb, int n_pad, int nrhs);   // the stacked pass's A operand, SYM_SLAB_CPLX per system: the workspace's last region
 int check_factor_args(const char* who, int nb, int n_pad, int nrhs, long long lda, size_t work_bytes);   // shared by the two factorisations; who: biem_lu / biem_sym
 // BIEM_LDLT_PIVOT_REL / BIEM_LDLT_GROWTH_MAX (tests): acceptance threshold of the diagonal pivots (multipliers <= 1 / threshold; 1e30
 // rejects every system) and accepted max |U| / max |A|; a value that does not parse to something positive is the default

@@ -899,22 +899,18 @@ int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long s
   return BIEM_OK;
 }
 
-// Which form of the bulk update launch_sym_factor_solve runs: 1 = left-looking (launch_gemm_left before every group), 0 = right-
-// looking (the K = 256 update after every group).  Left-looking tiles of late groups are long and few: a launch with fewer tiles
-// than the chip has CUs leaves CUs idle for a whole K = J tile, where the right-looking form spreads the same work over every tile
-// below the group.  So the left form runs when even the SMALLEST of its launches - the last group's band - has a tile for every CU,
-// i.e. half the persistent grid of two workgroups per CU (one workgroup per CU runs at 75-80 % of the two-workgroup rate).
-// Measured at N = 6400: 8 systems per call (80 tiles) right by 4 %, 32 systems (320 tiles) left by 3 %, more
-// systems left by 3-6 %.  BIEM_SYM_UPDATE=left|right forces a form (read per call).
-int sym_update_left(int nb, int n_pad, int nrhs) {
-  if (n_pad <= 4 * NB) return 0;                                   // one group: no bulk update at all
-  const char* e = getenv("BIEM_SYM_UPDATE");
-  if (e && e[0] == 'l') return 1;
-  if (e && e[0] == 'r') return 0;
+// Which form of the bulk update launch_sym_factor_solve runs by default (sym_form, kernels_sym.hip: SymForm.left): left-looking
+// (launch_gemm_left before every group) or right-looking (the K = 256 update after every group).  Left-looking tiles of late groups are
+// long and few: a launch with fewer tiles than the chip has CUs leaves CUs idle for a whole K = J tile, where the right-looking form
+// spreads the same work over every tile below the group.  So the left form runs when even the SMALLEST of its launches - the last
+// group's band - has a tile for every CU, i.e. half the persistent grid of two workgroups per CU (one workgroup per CU runs at 75-80 %
+// of the two-workgroup rate).  Measured at N = 6400: 8 systems per call (80 tiles) right by 4 %, 32 systems
+// (320 tiles) left by 3 %, more systems left by 3-6 %.
+bool gemm_left_fills_grid(int nb, int n_pad, int nrhs) {
   const int T = n_pad / NB, h_last = T % 4 ? T % 4 : 4;
   const int cols_last = h_last + (nrhs > 8 ? (nrhs + BN3 - 1) / BN3 : 0);
   const long long smallest = (long long)band_tiles(h_last, cols_last) * nb;
-  return 2 * smallest >= GEMM_GRID_CAP ? 1 : 0;
+  return 2 * smallest >= GEMM_GRID_CAP;
 }
 
 // ---------------------------------------------------------------------------------------------

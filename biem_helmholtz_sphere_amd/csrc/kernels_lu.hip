@@ -18,20 +18,8 @@ namespace biem {
 
 int lu_npad(int N) { return ((N + NB - 1) / NB) * NB; }
 
-size_t lu_workspace_bytes(int nb, int n_pad, int nrhs) {
-  (void)nrhs;
-  // four 64-column panels (two K = 128 blocks = one K = 256 update) + the 64 x 64 operand I - L11^{-1} of the MFMA triangular solve
-  // + the tile map of the triangular (symmetric) update: one int per lower-triangle tile of the largest trailing matrix
-  const size_t T = (size_t)n_pad / NB;
-  // + two doubles per system: max |A| over what the symmetric factorisation reads and max |U| (a-posteriori growth check)
-  // (the row-panel form of the symmetric path needs no panels, only (64 x 64 + 64) complex per system; one layout serves all)
-  // + at the end the slab of the symmetric path's stacked pass: [S ; S ; S ; V] of a group, 256 x 64 complex per system (sym_slab)
-  return (size_t)nb * (4 * NB * (size_t)ldp_of(n_pad) + (size_t)NB * NB) * sizeof(cplx) + ((T * (T + 1) / 2 + 63) / 64) * 64 * sizeof(int) +
-         (size_t)nb * 2 * sizeof(double) + (size_t)nb * NB * sizeof(cplx) + (size_t)nb * SYM_SLAB_CPLX * sizeof(cplx);
-}
-cplx* sym_slab(void* d_work, int nb, int n_pad, int nrhs) {
-  return (cplx*)((char*)d_work + lu_workspace_bytes(nb, n_pad, nrhs)) - (size_t)nb * SYM_SLAB_CPLX;
-}
+// (the layout: DenseWork, dense.hpp)
+size_t lu_workspace_bytes(int nb, int n_pad, int nrhs) { return dense_work(nb, n_pad, nrhs).total; }
 
 int check_factor_args(const char* who, int nb, int n_pad, int nrhs, long long lda, size_t work_bytes) {
   if (n_pad % NB) { set_error("%s: n_pad=%d is not a multiple of %d (use biem_lu_npad)", who, n_pad, NB); return BIEM_ERR_ARG; }
@@ -530,8 +518,9 @@ int launch_lu_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long l
   if (nb <= 0 || n_pad <= 0) return BIEM_OK;
   if (const int rc = check_factor_args("biem_lu", nb, n_pad, nrhs, lda, work_bytes)) return rc;
   cplx* A = (cplx*)d_A;
-  cplx* Pw = (cplx*)d_work;
-  const long long ldp = ldp_of(n_pad), p_stride = 4LL * NB * ldp;
+  const DenseWork W = dense_work(nb, n_pad, nrhs);
+  cplx* Pw = W.panels_at(d_work);
+  const long long ldp = ldp_of(n_pad), p_stride = (long long)PANEL_COLS * ldp;
   const int n_cols = n_pad + nrhs;
   launch_zero_int(st, d_info, nb);
   const size_t strip_lds = (size_t)PW * STRIP_CACHE_ROWS * sizeof(cplx);
@@ -543,9 +532,9 @@ int launch_lu_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long l
   // status of the update launches (the lambdas below cannot return it themselves): the first failure is kept and returned
   int gemm_rc = BIEM_OK;
   auto gemm = [&](auto&&... a) { const int r = launch_gemm_stream(a...); if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r; };
-  cplx* Winv = Pw + (size_t)nb * p_stride;      // 64 x 64 per system: I - L11^{-1} (LU) / U11^{-1} (symmetric path)
-  int* const tri_map = (int*)(Winv + (size_t)nb * NB * NB);      // tile map of the triangular updates, then the growth slots
-  unsigned long long* growth = lu_growth_slots(d_work, nb, n_pad);  // [nb][2]: max |A|, max |U| (symmetric path)
+  cplx* Winv = W.block_at(d_work);              // 64 x 64 per system: I - L11^{-1} (LU) / U11^{-1} (symmetric path)
+  int* const tri_map = W.tri_map_at(d_work);    // tile map of the triangular updates
+  unsigned long long* growth = W.growth_at(d_work);                 // [nb][2]: max |A|, max |U| (symmetric path)
   double nopiv, growth_max; ldlt_thresholds(nopiv, growth_max);   // pivot acceptance, accepted max |U| / max |A| (symmetric path)
   // factor the 64-column panel at column j, multipliers into P columns [pc, pc + NB)
   auto panel = [&](int j, int pc, bool in_workspace = false) {

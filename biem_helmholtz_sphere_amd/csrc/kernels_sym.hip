@@ -696,101 +696,176 @@ __global__ void __launch_bounds__(256, 2) k_sym_slab(const cplx* __restrict__ A,
     for (int b = 0; b < 4; ++b) So[(tk + 16 * a) * NB + ti + 16 * b] = make_double2(-acc[a][b].x, -acc[a][b].y);
 }
 
-// Form of the panels b, c, d of a group (launch_sym_factor_solve): the stacked pass runs only where the bulk update is left-looking, and
+// ---------------------------------------------------------------------------------------------
+// The form of a call (SymForm, dense.hpp): every rule and every switch that forces a form, in this one place.
+// ---------------------------------------------------------------------------------------------
+// The five switches (tests, A/B), read per call.  Of a value only its first letter counts; -1: not set.  A letter no rule names leaves
+// the rule in place for BIEM_SYM_UPDATE, BIEM_SYM_GROUP and BIEM_DIAG_FORM; for BIEM_BACK_FORM it selects the row form (any value
+// that starts with neither c nor s does); BIEM_NO_SMALL_PATH counts as soon as it is set, whatever its value.
+struct SymEnv { int update, group, back, diag; bool no_small; };
+static SymEnv sym_env() {
+  auto first = [](const char* name) { const char* e = getenv(name); return e ? (int)(unsigned char)e[0] : -1; };
+  return {first("BIEM_SYM_UPDATE"), first("BIEM_SYM_GROUP"), first("BIEM_BACK_FORM"), first("BIEM_DIAG_FORM"), getenv("BIEM_NO_SMALL_PATH") != nullptr};
+}
+
+// the whole system fits LDS: one launch does everything (k_small_utu)
+static bool small_rule(const SymEnv& e, int n_active, int nrhs) {
+  return n_active > 0 && n_active <= SMALL_N_MAX && nrhs <= SMALL_RHS_MAX && n_active + nrhs <= 128 && small_utu_lds(n_active, nrhs) <= 160 * 1024 - 2048 &&
+         !e.no_small;
+}
+// form of the bulk update: BIEM_SYM_UPDATE=left|right forces one; the rule and its measurements: gemm_left_fills_grid, kernels_gemm3m.hip
+static bool left_rule(const SymEnv& e, int nb, int n_pad, int nrhs) {
+  if (n_pad <= 4 * NB) return false;                               // one group: no bulk update at all
+  if (e.update == 'l') return true;
+  if (e.update == 'r') return false;
+  return gemm_left_fills_grid(nb, n_pad, nrhs);
+}
+// Form of the panels b, c, d of a group: the stacked pass runs only where the bulk update is left-looking, and
 // there from SYM_STACK_MIN_SYSTEMS systems per call.  What the passes save grows with the batch (14.0 ms per cfg 3 step at 256 systems),
 // the three small head launches per panel cost the same few ms at any batch size (5.0 ms): they break even near 90 systems, and the
 // form lost 1.2 % at 64 systems of cfg 4 and 2 % at 32 systems of cfg 3 (profiles/r06_other_shapes.txt) - so twice the break-even.
-// BIEM_SYM_GROUP=twopass|stacked forces a form under the left-looking update (tests, A/B).  Read per call.
+// BIEM_SYM_GROUP=twopass|stacked forces a form under the left-looking update (tests, A/B).
 constexpr int SYM_STACK_MIN_SYSTEMS = 192;
-bool sym_group_stacked(bool left, int nb) {
+static bool stacked_rule(const SymEnv& e, bool left, int nb) {
   if (!left) return false;
-  const char* e = getenv("BIEM_SYM_GROUP");
-  if (e && e[0] == 't') return false;
-  if (e && e[0] == 's') return true;
+  if (e.group == 't') return false;
+  if (e.group == 's') return true;
   return nb >= SYM_STACK_MIN_SYSTEMS;
 }
-
-bool sym_small_path(int n_active, int nrhs) {
-  return n_active > 0 && n_active <= SMALL_N_MAX && nrhs <= SMALL_RHS_MAX && n_active + nrhs <= 128 && small_utu_lds(n_active, nrhs) <= 160 * 1024 - 2048 &&
-         !getenv("BIEM_NO_SMALL_PATH");
+// Back substitution.  Few systems: the row form has one workgroup per system and 64-row block (a quarter of the CUs busy at 64 systems);
+// the column-block form spreads a system's rows over workgroups (cfg 4, N = 4064: 64 systems 6.1 -> 5.1 ms, 8 systems 5.7 -> 2.6 ms,
+// one system per call 22.8 -> 20.6 ms; at 256+ systems the row form wins: it reads U once in long runs).  Fewer still (STEP, keep_w):
+// every panel's W = I - U11^{-T} is kept and the back substitution multiplies by the stored inverses instead of solving with the
+// diagonal blocks (k_back_step) - every workgroup of a block step forms x_b for itself from the 64 KB inverse: a latency trade that
+// pays for a handful of systems (at 64 systems of cfg 4 the back substitution went from 4.4 to 11.5 ms with it).
+// BIEM_BACK_FORM=row|col|step forces one: step the stored inverses, col the two-launch column form.  What the panel region cannot hold
+// (SymAliases, dense.hpp) goes to the column form, which works on the augmented columns; no right-hand sides: the row form's pass for
+// the checks alone.
+constexpr int SYM_BACK_COL_MAX_SYSTEMS = 64, SYM_BACK_STEP_MAX_SYSTEMS = 8;
+static SymForm::Back back_rule(const SymEnv& e, int nb, int nrhs) {
+  const bool col_form = e.back >= 0 ? e.back == 'c' || e.back == 's' : nb <= SYM_BACK_COL_MAX_SYSTEMS;
+  const bool keep_w = col_form && nrhs > 0 && nrhs <= SYM_STEP_RHS_MAX && (e.back >= 0 ? e.back == 's' : nb <= SYM_BACK_STEP_MAX_SYSTEMS);
+  if (keep_w) return SymForm::BACK_STEP;
+  return nrhs > SYM_ROW_RHS_MAX || (col_form && nrhs > 0) ? SymForm::BACK_COL : SymForm::BACK_ROW;
 }
 
-int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long lda, long long sys_stride, int* d_info, void* d_work,
-                            size_t work_bytes, hipStream_t st, bool amax_ready, int n_active) {
-  if (nb <= 0 || n_pad <= 0) return BIEM_OK;
-  if (n_active <= 0 || n_active > n_pad) n_active = n_pad;        // rows n_active .. n_pad-1: identity padding (the caller's promise)
-  if (const int rc = check_factor_args("biem_sym", nb, n_pad, nrhs, lda, work_bytes)) return rc;
-  cplx* A = (cplx*)d_A;
-  const int n_cols = n_pad + nrhs;
-  cplx* Wt = (cplx*)d_work + (size_t)nb * 4 * NB * (size_t)ldp_of(n_pad);      // same place as the 64 x 64 block of the other paths
-  int* tri_map = (int*)(Wt + (size_t)nb * NB * NB);
-  unsigned long long* growth = lu_growth_slots(d_work, nb, n_pad);
-  launch_zero_int(st, d_info, nb);
-  double nopiv, growth_max; ldlt_thresholds(nopiv, growth_max);
-  if (sym_small_path(n_active, nrhs)) {
-    // the whole system fits LDS: one launch does everything
-    if (!amax_ready) launch_zero_int(st, (int*)growth, 4 * nb);   // max|A| is measured by the kernel
-    ProfScope ps(PK_PANEL, st, 0.0);
-    const size_t shm = small_utu_lds(n_active, nrhs);
-    const bool two = n_active + nrhs > 64;
-    const int kr = (n_active + SMALL_THREADS / 64 - 1) / (SMALL_THREADS / 64);
+SymForm sym_form(int nb, int n_pad, int n_active, int nrhs) {
+  const SymEnv e = sym_env();
+  SymForm f;
+  f.small = small_rule(e, n_active, nrhs);
+  f.two = f.small && n_active + nrhs > 64;
+  const int kr = (n_active + SMALL_THREADS / 64 - 1) / (SMALL_THREADS / 64);      // rows per wave; the instantiation that holds them
+  f.kr = !f.small ? 0 : !f.two ? (kr <= 4 ? 4 : 8) : kr <= 8 ? 8 : kr <= 9 ? 9 : kr <= 12 ? 12 : 16;
+  f.left = left_rule(e, nb, n_pad, nrhs);
+  f.stacked = stacked_rule(e, f.left, nb);
+  // Few right-hand sides do not ride in the matrix: the forward substitution works on the compact copy Y[s][q][row] the row-form back
+  // substitution uses anyway - every diagonal-block kernel solves its own 64 entries, every strip tile takes its 64 columns' term from
+  // the tile it has in registers.  U is read once for the solve (the back substitution); the update launches end at column n_pad.
+  f.rhs_gemv = nrhs > 0 && nrhs <= 8;
+  f.back = back_rule(e, nb, nrhs);
+  f.diag_blk = e.diag != 's';        // BIEM_DIAG_FORM=step: one pivot per barrier (the A/B of the tests); default: four
+  return f;
+}
+// the single decisions other units and the tests ask for
+int sym_update_left(int nb, int n_pad, int nrhs) { return left_rule(sym_env(), nb, n_pad, nrhs) ? 1 : 0; }
+bool sym_group_stacked(bool left, int nb) { return stacked_rule(sym_env(), left, nb); }
+bool sym_small_path(int n_active, int nrhs) { return small_rule(sym_env(), n_active, nrhs); }
+
+int sym_aliases(const SymForm& f, const DenseWork& w, void* d_work, int nb, int n_pad, int nrhs, SymAliases& a) {
+  a = SymAliases{nullptr, nullptr, nullptr, 0, 0, 0, 0};
+  if (f.small) return BIEM_OK;
+  a.wall_stride = (long long)n_pad * NB;
+  if (f.keep_w()) a.wall_bytes = (size_t)nb * a.wall_stride * sizeof(cplx);
+  a.y_off = w.panels + a.wall_bytes;
+  if (f.rhs_gemv || f.keep_w() || (f.back == SymForm::BACK_ROW && nrhs > 0)) a.y_bytes = (size_t)nb * nrhs * n_pad * sizeof(cplx);
+  if (a.y_off + a.y_bytes > w.block) {
+    set_error("biem_sym: %d right-hand sides of %d systems with n_pad=%d do not fit the panel region (back form %d)", nrhs, nb, n_pad, (int)f.back);
+    return BIEM_ERR_ARG;
+  }
+  if (d_work != nullptr) {
+    cplx* P = w.panels_at(d_work);
+    if (f.keep_w()) { a.Wall = P; a.Xsol = P + a.wall_bytes / sizeof(cplx); }
+    a.Y = f.keep_w() ? a.Xsol : P;
+  }
+  return BIEM_OK;
+}
+
+int sym_form_query(int nb, int n_pad, int n_active, int nrhs, int* form, size_t* work) {
+  if (nb <= 0 || n_pad <= 0 || n_pad % NB || n_active < 1 || n_active > n_pad || nrhs < 0) {
+    set_error("biem_sym_form: nb=%d, n_pad=%d (a multiple of %d), n_active=%d in 1 .. n_pad, nrhs=%d >= 0 expected", nb, n_pad, NB, n_active, nrhs);
+    return BIEM_ERR_ARG;
+  }
+  const SymForm f = sym_form(nb, n_pad, n_active, nrhs);
+  const DenseWork w = dense_work(nb, n_pad, nrhs);
+  SymAliases a;
+  if (const int rc = sym_aliases(f, w, nullptr, nb, n_pad, nrhs, a)) return rc;
+  if (form) {
+    const int v[BIEM_SYM_FORM_LEN] = {f.small, f.kr, f.two, f.left, f.stacked, f.rhs_gemv, (int)f.back, f.keep_w(), f.diag_blk};
+    for (int i = 0; i < BIEM_SYM_FORM_LEN; ++i) form[i] = v[i];
+  }
+  if (work) {
+    const size_t v[BIEM_SYM_WORK_LEN] = {w.panels, w.block, w.tri_map, w.growth, w.spare, w.slab, w.total, w.panels, a.wall_bytes, a.y_off, a.y_bytes};
+    for (int i = 0; i < BIEM_SYM_WORK_LEN; ++i) work[i] = v[i];
+  }
+  return BIEM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// launch_sym_factor_solve: the operands of one call, and its three stages
+// ---------------------------------------------------------------------------------------------
+struct SymCall {
+  int nb, n_pad, n_active, nrhs; cplx* A; long long lda, sys_stride; int* d_info; hipStream_t st; bool amax_ready;
+  double nopiv, growth_max;                  // ldlt_thresholds
+  cplx* Wt; int* tri_map; unsigned long long* growth; cplx* slab;     // DenseWork: the 64 x 64 block, the tile map, the growth slots, the slab
+  SymAliases al;
+};
+
+static int sym_one_launch(const SymForm& f, const SymCall& c) {
+  if (!c.amax_ready) launch_zero_int(c.st, (int*)c.growth, 4 * c.nb);   // max|A| is measured by the kernel
+  ProfScope ps(PK_PANEL, c.st, 0.0);
+  const size_t shm = small_utu_lds(c.n_active, c.nrhs);
 #define BIEM_SMALL(KR, TWO)                                                                                                         \
   {                                                                                                                                  \
     BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_small_utu<KR, TWO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));        \
-    hipLaunchKernelGGL((k_small_utu<KR, TWO>), dim3(nb), dim3(SMALL_THREADS), shm, st, A, lda, sys_stride, n_active, n_pad, nrhs, d_info, \
-                       growth, nopiv, amax_ready ? 1 : 0);                                                                              \
+    hipLaunchKernelGGL((k_small_utu<KR, TWO>), dim3(c.nb), dim3(SMALL_THREADS), shm, c.st, c.A, c.lda, c.sys_stride, c.n_active, c.n_pad, c.nrhs, \
+                       c.d_info, c.growth, c.nopiv, c.amax_ready ? 1 : 0);                                                            \
   }
-    if (!two) { if (kr <= 4) BIEM_SMALL(4, false) else BIEM_SMALL(8, false) }
-    else if (kr <= 8) BIEM_SMALL(8, true)
-    else if (kr <= 9) BIEM_SMALL(9, true)
-    else if (kr <= 12) BIEM_SMALL(12, true)
-    else BIEM_SMALL(16, true)
+  if (!f.two) { if (f.kr == 4) BIEM_SMALL(4, false) else BIEM_SMALL(8, false) }
+  else if (f.kr == 8) BIEM_SMALL(8, true)
+  else if (f.kr == 9) BIEM_SMALL(9, true)
+  else if (f.kr == 12) BIEM_SMALL(12, true)
+  else BIEM_SMALL(16, true)
 #undef BIEM_SMALL
-    launch_growth_check(st, nb, n_pad, growth, d_info, growth_max);
-    BIEM_LAUNCHCHK();
-    return BIEM_OK;
-  }
-  launch_tri_map(st, tri_map, n_pad);
-  if (!amax_ready) {
-    launch_zero_int(st, (int*)growth, 4 * nb);
+  return BIEM_OK;
+}
+
+static int sym_factor(const SymForm& f, const SymCall& c) {
+  const int nb = c.nb, n_pad = c.n_pad, nrhs = c.nrhs, n_cols = n_pad + nrhs;
+  cplx* const A = c.A; const long long lda = c.lda, sys_stride = c.sys_stride; hipStream_t st = c.st;
+  launch_tri_map(st, c.tri_map, n_pad);
+  if (!c.amax_ready) {
+    launch_zero_int(st, (int*)c.growth, 4 * nb);
     ProfScope ps(PK_SWAP, st, 0.0);
-    hipLaunchKernelGGL(k_absmax_upper, dim3((n_pad + 7) / 8, nb), dim3(256), 0, st, A, lda, sys_stride, n_pad, growth);
+    hipLaunchKernelGGL(k_absmax_upper, dim3((n_pad + 7) / 8, nb), dim3(256), 0, st, A, lda, sys_stride, n_pad, c.growth);
   }
   int gemm_rc = BIEM_OK;
-  auto gemm = [&](auto&&... a) { const int r = launch_gemm_stream(a...); if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r; };
-  const bool rhs_gemv = nrhs > 0 && nrhs <= 8;
-  // Few systems (the column-block form of the back substitution below): every panel's W = I - U11^{-T} is kept - in the panel region of
-  // the workspace, which the row form does not use: n_pad x 64 complex per system, then the solutions (nrhs x n_pad) - and the back
-  // substitution multiplies by the stored inverses instead of solving with the diagonal blocks (k_back_step).
-  const char* bf = getenv("BIEM_BACK_FORM");
-  const bool col_form = bf ? bf[0] == 'c' || bf[0] == 's' : nb <= 64;
-  // (every workgroup of a block step forms x_b for itself from the 64 KB inverse: a latency trade that pays for a handful of systems -
-  // at 64 systems of cfg 4 the back substitution went from 4.4 to 11.5 ms with it; BIEM_BACK_FORM=step forces it, =col the two-launch form)
-  const bool keep_w = col_form && nrhs > 0 && nrhs <= 3 * NB && (bf ? bf[0] == 's' : nb <= 8);
-  cplx* Wall = (cplx*)d_work;
-  const long long wall_stride = (long long)n_pad * NB;
-  cplx* Xsol = Wall + (size_t)nb * wall_stride;
-  // Few right-hand sides (rhs_gemv) do not ride in the matrix: the forward substitution works on the compact copy Y[s][q][row] the
-  // row-form back substitution uses anyway (the panel region of the workspace; with keep_w, whose W blocks live there, the place of the
-  // solutions behind them) - every diagonal-block kernel solves its own 64 entries, every strip tile takes its 64 columns' term from
-  // the tile it has in registers.  U is read once for the solve (the back substitution); the update launches end at column n_pad.
-  cplx* Yf = rhs_gemv ? (keep_w ? Xsol : (cplx*)d_work) : nullptr;
-  const int f_cols = rhs_gemv ? n_pad : n_cols;      // the factorisation's last column
-  if (rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Yf, nrhs, n_pad, 0);
+  auto keep = [&](int r) { if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r; };      // the first failure of an update launch is kept and returned
+  auto gemm = [&](auto&&... a) { keep(launch_gemm_stream(a...)); };
+  cplx* const Yf = f.rhs_gemv ? c.al.Y : nullptr;      // the compact copy the forward substitution works on
+  const int f_cols = f.rhs_gemv ? n_pad : n_cols;      // the factorisation's last column
+  if (f.rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Yf, nrhs, n_pad, 0);
   BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_diag_utu_reg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIAG_LDS_CPLX * sizeof(cplx))));
   BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_diag_utu_blk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIAGB_LDS_CPLX * sizeof(cplx))));
-  const char* dform = getenv("BIEM_DIAG_FORM");                  // step: one pivot per barrier (the A/B of the tests); default: four
-  const bool diag_blk = !(dform && dform[0] == 's');
   // slab != nullptr: the panel p = j of the group at row J takes the stacked pass (below) - V goes to rows j - J .. of the slab
   auto panel = [&](int j, int J = 0, cplx* slab = nullptr) {
     // the strip's operand V = -U11^{-T} lives in the 64 x 64 block; a kept W = I + V goes to the panel region
-    cplx* Wp = keep_w ? Wall + (size_t)(j / NB) * NB * NB : nullptr;
-    cplx* Vp = slab != nullptr ? slab + (size_t)(j - J) * NB : Wt;
-    const long long w_stride = keep_w ? wall_stride : 0, v_stride = slab != nullptr ? (long long)SYM_SLAB_CPLX : (long long)NB * NB;
+    cplx* Wp = f.keep_w() ? c.al.Wall + (size_t)(j / NB) * NB * NB : nullptr;
+    cplx* Vp = slab != nullptr ? slab + (size_t)(j - J) * NB : c.Wt;
+    const long long w_stride = f.keep_w() ? c.al.wall_stride : 0, v_stride = slab != nullptr ? (long long)SYM_SLAB_CPLX : (long long)NB * NB;
     {
       ProfScope ps(PK_PANEL, st, 0.0);
-      if (diag_blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(nb), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Vp, v_stride, d_info, nopiv, growth, Yf, nrhs, n_pad);
-      else hipLaunchKernelGGL(k_diag_utu_reg, dim3(nb), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Vp, v_stride, d_info, nopiv, growth, Yf, nrhs, n_pad);
+      if (f.diag_blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(nb), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Vp, v_stride, c.d_info, c.nopiv, c.growth, Yf, nrhs, n_pad);
+      else hipLaunchKernelGGL(k_diag_utu_reg, dim3(nb), dim3(DIAG_THREADS), DIAG_LDS_CPLX * sizeof(cplx), st, A, lda, sys_stride, j, Wp, w_stride, Vp, v_stride, c.d_info, c.nopiv, c.growth, Yf, nrhs, n_pad);
     }
     if (f_cols <= j + NB) return;
     if (slab != nullptr) {
@@ -799,39 +874,35 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
         ProfScope ps(PK_PANEL, st, 8.0 * (double)nb * (j - J) * NB * NB);
         hipLaunchKernelGGL(k_sym_slab, dim3((j - J) / NB, nb), dim3(256), 0, st, A, lda, sys_stride, slab, J, j);
       }
-      const int r = launch_gemm_stack(st, nb, A, lda, sys_stride, slab, (long long)SYM_SLAB_CPLX, J, j, f_cols, Yf, nrhs, n_pad);
-      if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r;
+      keep(launch_gemm_stack(st, nb, A, lda, sys_stride, slab, (long long)SYM_SLAB_CPLX, J, j, f_cols, Yf, nrhs, n_pad));
       return;
     }
     // U12 = U11^{-T} C = -V^T C in place over the 64 rows (every tile reads its own columns only); A operand V[k][i], i = row - j: the
     // base shifted by -j rows (only rows j .. j+63 are addressed)
-    const int r = launch_gemm_strip(st, nb, A, lda, sys_stride, Wt - j, v_stride, j, f_cols, Yf, nrhs, n_pad);
-    if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r;
+    keep(launch_gemm_strip(st, nb, A, lda, sys_stride, c.Wt - j, v_stride, j, f_cols, Yf, nrhs, n_pad));
   };
-  const bool left = sym_update_left(nb, n_pad, nrhs) != 0;       // form of the bulk update (one rule, BIEM_SYM_UPDATE forces one)
   // The panels b, c, d of a group, two forms.  Two-pass: the panel's 64 rows take the group's pending updates in a C-streaming launch
-  // (K = 64 q), then the strip solves them (K = 64) - every row is read and written twice.  Stacked (sym_group_stacked: under the left-
+  // (K = 64 q), then the strip solves them (K = 64) - every row is read and written twice.  Stacked (SymForm.stacked: under the left-
   // looking bulk update, large batches): only the diagonal tile takes the pending update; behind the diagonal block
   // the rest of the rows is ONE pure product over K = 64 (q + 1) (k_sym_slab, launch_gemm_stack) - no C slots, one set of stores per tile.
   // (Round 3 built a first fused form, U12 = C - [(X P^T) | W] [Q ; C] on the C-streaming kernel for every batch size: 2.5 % of panel +
   // in-group time at cfg 3, and a loss of 27 - 30 % where few systems are in flight - three more small launches per panel.  Since then
   // the strip became a pure product and the right-hand sides left the matrix; this form runs only where the launches are large.
   // DESIGN.md section 5 has both measurements.)
-  const bool stacked = sym_group_stacked(left, nb);
-  cplx* slab = stacked ? sym_slab(d_work, nb, n_pad, nrhs) : nullptr;
+  cplx* const slab = f.stacked ? c.slab : nullptr;
   for (int J = 0; J < n_pad; J += 4 * NB) {
     const cplx* strip = A + (size_t)J * lda;        // both operands of this group's updates: rows J .. of the matrix itself
-    if (left && J > 0) {
+    if (f.left && J > 0) {
       // left-looking: the group's rows take every pending update of the finished rows 0 .. J-1 now, in one K = J pass (many right-hand
       // sides: tile columns of the same launch; few: not in the matrix at all)
       const int row_end = J + 4 * NB < n_pad ? J + 4 * NB : n_pad;
-      { const int r = launch_gemm_left(st, nb, A, lda, sys_stride, J, row_end, f_cols); if (r != BIEM_OK && gemm_rc == BIEM_OK) gemm_rc = r; }
+      keep(launch_gemm_left(st, nb, A, lda, sys_stride, J, row_end, f_cols));
     }
     panel(J);
     for (int q = 1; q < 4; ++q) {
       const int jq = J + q * NB;
       if (jq >= n_pad) break;
-      if (stacked) {
+      if (f.stacked) {
         // the diagonal tile alone takes the group's pending updates (K = 64 q); the rest of the rows waits for the stacked pass
         gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, jq, jq + NB, jq, jq + NB, J, q * NB, PK_OTHER);
         panel(jq, J, slab);
@@ -842,54 +913,74 @@ int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long 
       panel(jq);
     }
     if (J + 4 * NB >= n_pad) break;
-    if (left) continue;                              // no update after the group: the rows below take it when their own group starts
+    if (f.left) continue;                            // no update after the group: the rows below take it when their own group starts
     gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, J + 4 * NB, n_pad, J + 4 * NB, n_pad, J, 4 * NB, PK_GEMM, -1.0, nullptr, 0, 0, 0,
-         tri_map, true);
-    if (nrhs > 0 && !rhs_gemv) gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, J + 4 * NB, n_pad, n_pad, n_cols, J, 4 * NB, PK_OTHER);
+         c.tri_map, true);
+    if (nrhs > 0 && !f.rhs_gemv) gemm(st, nb, A, lda, sys_stride, strip, lda, sys_stride, J + 4 * NB, n_pad, n_pad, n_cols, J, 4 * NB, PK_OTHER);
   }
   BIEM_LAUNCHCHK();
-  if (gemm_rc != BIEM_OK) return gemm_rc;
-  {
-    // back substitution (k_back_row, bottom block row first); its pass over U also takes the multiplier / growth checks of the
-    // strip entries (nrhs == 0: one pass for the checks alone); right-hand sides in groups of up to 8
-    ProfScope ps(PK_BACK, st, 4.0 * (double)nb * n_pad * (double)n_pad * nrhs);
-    const double inv_rel2 = 1.0 / (nopiv * nopiv);
-    cplx* Y = (cplx*)d_work;         // the panel region of the workspace is free in the row form: room for 4 * 64 right-hand sides per system
-    // Few systems: the row form has one workgroup per system and 64-row block (a quarter of the CUs busy at 64 systems); the
-    // column-block form spreads a system's rows over workgroups (cfg 4, N = 4064: 64 systems 6.1 -> 5.1 ms, 8 systems 5.7 -> 2.6 ms,
-    // one system per call 22.8 -> 20.6 ms; at 256+ systems the row form wins: it reads U once in long runs).  BIEM_BACK_FORM=row|col|step forces one.
-    if (keep_w || nrhs > 4 * NB || (col_form && nrhs > 0)) {
-      // (these forms work on the augmented columns: the forward-substituted compact copy goes back there first)
-      if (rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Yf, nrhs, n_pad, 1);
-      if (keep_w) {
-        for (int jr = n_pad - BS; jr >= 0; jr -= BS)
-          hipLaunchKernelGGL(k_back_step, dim3(jr > 0 ? (jr + BACK_ROWS - 1) / BACK_ROWS : 1, nb), dim3(256), 0, st, A, lda, sys_stride, A + n_pad, lda,
-                             sys_stride, Wall, wall_stride, Xsol, n_pad, nrhs, jr, d_info, growth, inv_rel2);
-        hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Xsol, nrhs, n_pad, 1);
-      } else   // (also: more right-hand sides than the compact copy of the row form holds) the column-block form on the augmented columns, same checks
-        back_substitute_cols(st, nb, n_pad, nrhs, A, lda, sys_stride, A + n_pad, lda, sys_stride, d_info, growth, inv_rel2);
-      BIEM_LAUNCHCHK();
-      launch_growth_check(st, nb, n_pad, growth, d_info, growth_max);
-      BIEM_LAUNCHCHK();
-      return BIEM_OK;
-    }
-    if (nrhs > 0 && !rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, 0);
-    int q0 = 0;
-    do {
-      const int nq = nrhs - q0 > 8 ? 8 : nrhs - q0;
-      const int chk = q0 == 0 ? 1 : 0;
-      for (int ib = n_pad / NB - 1; ib >= 0; --ib) {
-        if (nq <= 1) hipLaunchKernelGGL(k_back_row<1>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, d_info, growth, inv_rel2);
-        else if (nq == 2) hipLaunchKernelGGL(k_back_row<2>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, d_info, growth, inv_rel2);
-        else if (nq <= 4) hipLaunchKernelGGL(k_back_row<4>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, d_info, growth, inv_rel2);
-        else hipLaunchKernelGGL(k_back_row<8>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, d_info, growth, inv_rel2);
-      }
-      q0 += nq;
-    } while (q0 < nrhs);
-    if (nrhs > 0) hipLaunchKernelGGL(k_rhs_compact, dim3((n_pad + 255) / 256, nrhs, nb), dim3(256), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, 1);
+  return gemm_rc;
+}
+
+// back substitution, bottom block row first; its pass over U also takes the multiplier / growth checks of the strip entries
+static int sym_back(const SymForm& f, const SymCall& c) {
+  const int nb = c.nb, n_pad = c.n_pad, nrhs = c.nrhs;
+  cplx* const A = c.A; const long long lda = c.lda, sys_stride = c.sys_stride; hipStream_t st = c.st;
+  ProfScope ps(PK_BACK, st, 4.0 * (double)nb * n_pad * (double)n_pad * nrhs);
+  const double inv_rel2 = 1.0 / (c.nopiv * c.nopiv);
+  const dim3 compact_grid((n_pad + 255) / 256, nrhs, nb);
+  if (f.back != SymForm::BACK_ROW) {
+    // (these forms work on the augmented columns: the forward-substituted compact copy goes back there first)
+    if (f.rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, compact_grid, dim3(256), 0, st, A, lda, sys_stride, c.al.Y, nrhs, n_pad, 1);
+    if (f.back == SymForm::BACK_STEP) {
+      for (int jr = n_pad - BS; jr >= 0; jr -= BS)
+        hipLaunchKernelGGL(k_back_step, dim3(jr > 0 ? (jr + BACK_ROWS - 1) / BACK_ROWS : 1, nb), dim3(256), 0, st, A, lda, sys_stride, A + n_pad, lda,
+                           sys_stride, c.al.Wall, c.al.wall_stride, c.al.Xsol, n_pad, nrhs, jr, c.d_info, c.growth, inv_rel2);
+      hipLaunchKernelGGL(k_rhs_compact, compact_grid, dim3(256), 0, st, A, lda, sys_stride, c.al.Xsol, nrhs, n_pad, 1);
+    } else   // the column-block form on the augmented columns, same checks
+      back_substitute_cols(st, nb, n_pad, nrhs, A, lda, sys_stride, A + n_pad, lda, sys_stride, c.d_info, c.growth, inv_rel2);
     BIEM_LAUNCHCHK();
+    return BIEM_OK;
   }
-  launch_growth_check(st, nb, n_pad, growth, d_info, growth_max);
+  // the row form (k_back_row) on the compact copy; nrhs == 0: one pass for the checks alone; right-hand sides in groups of up to 8
+  cplx* const Y = c.al.Y;
+  if (nrhs > 0 && !f.rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, compact_grid, dim3(256), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, 0);
+  int q0 = 0;
+  do {
+    const int nq = nrhs - q0 > 8 ? 8 : nrhs - q0;
+    const int chk = q0 == 0 ? 1 : 0;
+    for (int ib = n_pad / NB - 1; ib >= 0; --ib) {
+      if (nq <= 1) hipLaunchKernelGGL(k_back_row<1>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
+      else if (nq == 2) hipLaunchKernelGGL(k_back_row<2>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
+      else if (nq <= 4) hipLaunchKernelGGL(k_back_row<4>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
+      else hipLaunchKernelGGL(k_back_row<8>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
+    }
+    q0 += nq;
+  } while (q0 < nrhs);
+  if (nrhs > 0) hipLaunchKernelGGL(k_rhs_compact, compact_grid, dim3(256), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, 1);
+  BIEM_LAUNCHCHK();
+  return BIEM_OK;
+}
+
+int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long lda, long long sys_stride, int* d_info, void* d_work,
+                            size_t work_bytes, hipStream_t st, bool amax_ready, int n_active) {
+  if (nb <= 0 || n_pad <= 0) return BIEM_OK;
+  if (n_active <= 0 || n_active > n_pad) n_active = n_pad;        // rows n_active .. n_pad-1: identity padding (the caller's promise)
+  if (const int rc = check_factor_args("biem_sym", nb, n_pad, nrhs, lda, work_bytes)) return rc;
+  const SymForm f = sym_form(nb, n_pad, n_active, nrhs);
+  const DenseWork w = dense_work(nb, n_pad, nrhs);
+  SymCall c{nb, n_pad, n_active, nrhs, (cplx*)d_A, lda, sys_stride, d_info, st, amax_ready, 0.0, 0.0,
+            w.block_at(d_work), w.tri_map_at(d_work), w.growth_at(d_work), w.slab_at(d_work), SymAliases()};
+  if (const int rc = sym_aliases(f, w, d_work, nb, n_pad, nrhs, c.al)) return rc;
+  ldlt_thresholds(c.nopiv, c.growth_max);
+  launch_zero_int(st, d_info, nb);
+  if (f.small) {
+    if (const int rc = sym_one_launch(f, c)) return rc;
+  } else {
+    if (const int rc = sym_factor(f, c)) return rc;
+    if (const int rc = sym_back(f, c)) return rc;
+  }
+  launch_growth_check(st, nb, n_pad, c.growth, d_info, c.growth_max);
   BIEM_LAUNCHCHK();
   return BIEM_OK;
 }
@@ -906,7 +997,7 @@ extern "C" int biem_debug_diag(int reps, unsigned long long* trace_out, float* u
   hipMemset(info, 0, 64); hipMemset(growth, 0, 64);
   hipFuncSetAttribute((const void*)k_diag_utu_reg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIAG_LDS_CPLX * sizeof(cplx)));
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  const bool blk = getenv("BIEM_DIAG_FORM") == nullptr;
+  const bool blk = sym_form(1, n, n, 0).diag_blk;      // (BIEM_DIAG_FORM=step as in production: the reg kernel)
   hipFuncSetAttribute((const void*)k_diag_utu_blk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIAGB_LDS_CPLX * sizeof(cplx)));
   for (int r = 0; r < 3; ++r) {
     if (blk) hipLaunchKernelGGL(k_diag_utu_blk, dim3(1), dim3(1024), DIAGB_LDS_CPLX * sizeof(cplx), 0, A, lda, 0, 64 * r, nullptr, 0, W, (long long)NB * NB, info, 0.01, growth, nullptr, 0, n);

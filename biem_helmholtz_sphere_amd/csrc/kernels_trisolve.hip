@@ -5,12 +5,7 @@
 
 namespace biem {
 
-unsigned long long* lu_growth_slots(void* d_work, int nb, int n_pad) {
-  const size_t T = (size_t)n_pad / NB;
-  cplx* Winv = (cplx*)d_work + (size_t)nb * 4 * NB * (size_t)ldp_of(n_pad);
-  int* tri = (int*)(Winv + (size_t)nb * NB * NB);
-  return (unsigned long long*)(tri + ((T * (T + 1) / 2 + 63) / 64) * 64);
-}
+unsigned long long* lu_growth_slots(void* d_work, int nb, int n_pad) { return dense_work(nb, n_pad, 0).growth_at(d_work); }
 __global__ void k_growth_preset(int nb, unsigned long long* __restrict__ growth, double amax) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nb) return;

@@ -215,6 +215,20 @@ int biem_sym_factor_solve_n(int nb, int n_pad, int n_active, int nrhs, double* d
  * Left runs when even its smallest launch, the last group's band, has a tile for every CU over the nb systems: 256 tiles, half the
  * update kernel's persistent grid of 512 workgroups.  BIEM_SYM_UPDATE=left|right in the environment forces a form; read per call. */
 int biem_sym_update_form(int nb, int n_pad, int nrhs);
+/* The whole form biem_sym_factor_solve_n takes for a call of this shape, and the layout of its workspace (host only, no GPU work;
+ * either array may be null).  n_pad a multiple of 64, 1 <= n_active <= n_pad.
+ *   form[BIEM_SYM_FORM_LEN] = one-launch small path (0 / 1), KR and TWO of its k_small_utu<KR, TWO> (0 off that path), bulk update
+ *     left-looking, stacked group pass, right-hand sides in the compact copy, back substitution (0 rows, 1 column blocks, 2 block
+ *     steps with the kept inverses), kept inverses (1 exactly with form 2), diagonal kernel with four pivots per barrier.
+ *     Off the small path the fields behind KR and TWO are what the blocked path runs; on it they are not used.
+ *   work[BIEM_SYM_WORK_LEN] = byte offsets of the regions of the biem_lu_workspace_bytes(nb, n_pad, nrhs) bytes, in order: the four
+ *     panels, the 64 x 64 block per system, the tile map, the growth slots, 64 unused complex per system, the slab of the stacked pass;
+ *     then the total; then what this form keeps in the panel region: offset and bytes of the kept inverses, offset and bytes of the
+ *     compact copy of the right-hand sides (0 bytes: not used).
+ * The environment switches BIEM_SYM_UPDATE, BIEM_SYM_GROUP, BIEM_BACK_FORM, BIEM_DIAG_FORM and BIEM_NO_SMALL_PATH enter as in a call. */
+#define BIEM_SYM_FORM_LEN 9
+#define BIEM_SYM_WORK_LEN 11
+int biem_sym_form(int nb, int n_pad, int n_active, int nrhs, int* form, size_t* work);
 /* How the last biem_solve_ldlt / biem_solve_ldlt_n call of this thread ran: npE = npO = 0 unsplit, otherwise the padded orders of the
  * two blocks it factored one after the other (biem_plan_split_order).  The split form runs for shared geometry (geom_batched = 0) of a
  * chain tree whose centres all have the same last coordinate (compared bit for bit on the host, -0.0 as 0.0: one small copy and one

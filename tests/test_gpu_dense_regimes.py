@@ -67,15 +67,16 @@ def small_instance(n_active, nrhs):
     return (16, True)
 
 
-def sym_schedule(nb, n_pad, nrhs, n_active=None, no_small=False):
-    """launch_sym_factor_solve (row form A = U^T U, kernels_sym.hip) with the default environment."""
+def sym_schedule(nb, n_pad, nrhs, n_active=None, no_small=False, back_form=None):
+    """launch_sym_factor_solve (row form A = U^T U, kernels_sym.hip; the form: sym_form there) with the right-looking bulk update.
+    no_small: BIEM_NO_SMALL_PATH is set; back_form: the value of BIEM_BACK_FORM (row, col or step), None: not set."""
     n_active = n_pad if n_active is None else n_active
     if sym_small_path(n_active, nrhs, no_small):
         return dict(small=small_instance(n_active, nrhs), launches=[], back=None)
     n_cols = n_pad + nrhs
     rhs_gemv = 0 < nrhs <= 8
-    col_form = nb <= 64
-    keep_w = col_form and 0 < nrhs <= 3 * NB and nb <= 8
+    col_form = nb <= 64 if back_form is None else back_form[0] in "cs"
+    keep_w = col_form and 0 < nrhs <= 3 * NB and (nb <= 8 if back_form is None else back_form[0] == "s")
     back = "keep_w" if keep_w else "col" if (nrhs > 4 * NB or (col_form and nrhs > 0)) else "row"
     out = []
 
@@ -101,7 +102,7 @@ def sym_schedule(nb, n_pad, nrhs, n_active=None, no_small=False):
         add("k256", nb, J + 4 * NB, n_pad, J + 4 * NB, n_pad, 4 * NB, tri=2)       # (upper triangle of tiles)
         if not rhs_gemv and nrhs > 0:
             add("rhs", nb, J + 4 * NB, n_pad, n_pad, n_cols, 4 * NB)
-    return dict(small=None, launches=out, back=back)
+    return dict(small=None, launches=out, back=back, rhs_gemv=rhs_gemv, keep_w=keep_w)
 
 
 def lu_schedule(nb, n_pad, nrhs, symmetric=False):

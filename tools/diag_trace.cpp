@@ -15,7 +15,8 @@ int main() {
   printf("%.1f us per launch (events, back to back)\n", us);
   const unsigned long long t0 = T(0, 64, 0);
   printf("wave 0 (s_memtime: shader cycles): start 0, loads done + row 0 published %llu, loop end %llu, kernel end %llu\n", T(0, 64, 1) - t0, T(0, 64, 2) - t0, T(0, 64, 3) - t0);
-  if (!getenv("BIEM_DIAG_FORM")) {
+  const char* dform = getenv("BIEM_DIAG_FORM");      // as the library reads it (sym_form): only a leading s selects k_diag_utu_reg
+  if (!(dform && dform[0] == 's')) {
     // four pivots per barrier (k_diag_utu_blk): the chain is the owner of block b + 1 in block step b
     double s_bar = 0, s_app = 0, s_bc = 0, s_sc = 0, s_vec = 0, s_tot = 0; int n = 0;
     for (int b = 1; b < 15; ++b) {
