@@ -8,6 +8,20 @@
 constexpr int kChainNodeTab = 4096;        // doubles of node-factor tables the chain kernels keep in LDS
 constexpr int kLists2dMax = 160;            // 2-D plans up to this order also carry term lists (tests, the generic fill forms)
 
+// The table list: every std::vector of a plan once, as DEV(type, name) - it has the device mirror d_<name> - or HOST(type, name).
+// The mirrors' declarations, plan_upload, plan_free and the digests of tools/plan_digest.cpp are generated from it, so a table
+// cannot be uploaded and not freed, or built and not compared.  (tidx: the fills read tidx16, biem_plan_terms the host vector.)
+#define BIEM_PLAN_TABLES(DEV, HOST) \
+  DEV(int, labels) DEV(int, deg) DEV(int, labels2) DEV(int, deg2) DEV(int, units) HOST(double, qy) HOST(double, qw) DEV(double, W) \
+  DEV(uint32_t, ptr) DEV(double, coef) HOST(int32_t, tidx) DEV(uint16_t, tidx16) DEV(int, chunk_ent) \
+  DEV(int, spos) DEV(int, hpos) DEV(uint32_t, qptr) DEV(double, qcoef) DEV(uint16_t, qidx16) \
+  DEV(int, lin2) DEV(uint32_t, q2ptr) DEV(double, q2coef) DEV(uint16_t, q2idx16) DEV(int, qchunk) \
+  DEV(int, red_of) DEV(int, red_first) HOST(int, red_label) DEV(int, ph_mu) HOST(int, ph_of_unit) \
+  DEV(double, rcoef) DEV(uint16_t, ridx) DEV(uint16_t, rphsel) DEV(int, rchunk) DEV(int, rcrow) DEV(int, rwrow) DEV(int, schunk)
+// the force tables in a list of their own: plan_build_force builds and uploads them on the first request, not with the plan
+#define BIEM_PLAN_FORCE_TABLES(DEV, HOST) \
+  HOST(uint32_t, fptr) DEV(int32_t, fcol) HOST(int32_t, fcomp) DEV(double, fval) DEV(uint32_t, fptr_comp)
+
 struct biem_plan {
   int tree = 0, d = 0, n_end = 0, n2 = 0;   // n2 = 2 n_end - 1 (degrees of the translation table)
   int H = 0, H2 = 0, Q = 0;
@@ -85,20 +99,14 @@ struct biem_plan {
   std::vector<int32_t> fcol, fcomp;         // [entries] column h, component i
   std::vector<double> fval;                 // [entries] complex128 interleaved
   std::vector<uint32_t> fptr_comp;          // [H * d + 1]: the entries of (row h', component i) are [fptr_comp[h' d + i], fptr_comp[h' d + i + 1])
-  // device mirrors (null until uploaded)
+  // device mirrors d_<table> of the table lists above (null until uploaded)
   int device = -1;
-  int* d_labels = nullptr; int* d_deg = nullptr;
-  int* d_labels2 = nullptr; int* d_deg2 = nullptr;
-  int* d_units = nullptr;
-  double* d_W = nullptr;
-  uint32_t* d_ptr = nullptr; double* d_coef = nullptr; int32_t* d_tidx = nullptr;
-  uint16_t* d_tidx16 = nullptr; int* d_chunk_ent = nullptr;
-  int* d_spos = nullptr; int* d_hpos = nullptr; uint32_t* d_qptr = nullptr; double* d_qcoef = nullptr; uint16_t* d_qidx16 = nullptr;
-  int* d_qchunk = nullptr; int* d_schunk = nullptr;
-  int* d_lin2 = nullptr; uint32_t* d_q2ptr = nullptr; double* d_q2coef = nullptr; uint16_t* d_q2idx16 = nullptr;
-  int* d_red_of = nullptr; int* d_red_first = nullptr; int* d_red_label = nullptr; int* d_ph_mu = nullptr;
-  uint32_t* d_fptr_comp = nullptr; int32_t* d_fcol = nullptr; double* d_fval = nullptr;     // uploaded by plan_build_force
-  double* d_rcoef = nullptr; uint16_t* d_ridx = nullptr; uint16_t* d_rphsel = nullptr; int* d_rchunk = nullptr; int* d_rcrow = nullptr; int* d_rwrow = nullptr;
+#define BIEM_PLAN_MIRROR(T, name) T* d_##name = nullptr;
+#define BIEM_PLAN_HOST_ONLY(T, name)
+  BIEM_PLAN_TABLES(BIEM_PLAN_MIRROR, BIEM_PLAN_HOST_ONLY)
+  BIEM_PLAN_FORCE_TABLES(BIEM_PLAN_MIRROR, BIEM_PLAN_HOST_ONLY)
+#undef BIEM_PLAN_MIRROR
+#undef BIEM_PLAN_HOST_ONLY
 };
 
 namespace biem {

@@ -1,0 +1,391 @@
+// plan_fill.cpp -- the tree-independent tables behind the labels and term lists: fill chunks, unit-pair lists, the reduced-table form.
+// plan_build_fill_tables (at the end) runs the stages in the order their members depend on; the comment above a stage names the plan
+// members it writes and, beside the scalars tree, lw, n_end, H, H2, the ones it reads.
+#include "plan_build.hpp"
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+
+namespace biem {
+namespace {
+
+// the experiment switches of the plan build, read once (the only getenv of the plan sources)
+struct PlanEnv {
+  int red_waves, red_nc;     // BIEM_FILL_RED_WAVES=8, BIEM_FILL_NC=1: workgroup of k_fill_red and combinations per iteration
+  bool reorder_lists;        // BIEM_FILL_LIST_ORDER=natural keeps the natural order of a lane's terms (A/B)
+  bool stats;                // BIEM_PLAN_STATS: print the gather statistic
+};
+PlanEnv read_plan_env() {
+  const char *ew = getenv("BIEM_FILL_RED_WAVES"), *en = getenv("BIEM_FILL_NC"), *elo = getenv("BIEM_FILL_LIST_ORDER");
+  return {(ew && atoi(ew) == 8) ? 8 : 16, (en && en[0] == '1') ? 1 : 2, !(elo && elo[0] == 'n'), getenv("BIEM_PLAN_STATS") != nullptr};
+}
+
+// Greedy chunks of consecutive items: a chunk is extended while it has fewer than max_items items and its terms
+// prefix(end) - prefix(begin) stay within cap_terms.  bound: the chunk boundaries from 0 on; the largest chunk in terms and in items.
+// single_over_cap_fails: an item that alone exceeds cap_terms ends the cut with fits = false (otherwise it becomes a chunk of its own)
+struct Chunks { std::vector<int> bound{0}; int terms_max = 0, items_max = 0; bool fits = true; };
+template <class Prefix>
+Chunks cut_chunks(long long total, long long max_items, long long cap_terms, Prefix prefix, bool single_over_cap_fails) {
+  Chunks c;
+  for (long long e0 = 0; e0 < total;) {
+    long long e1 = e0 + 1;
+    if (single_over_cap_fails && (long long)(prefix(e1) - prefix(e0)) > cap_terms) { c.fits = false; break; }
+    while (e1 < total && e1 - e0 < max_items && (long long)(prefix(e1 + 1) - prefix(e0)) <= cap_terms) ++e1;
+    c.terms_max = std::max(c.terms_max, (int)(prefix(e1) - prefix(e0)));
+    c.items_max = std::max(c.items_max, (int)(e1 - e0));
+    c.bound.push_back((int)e1);
+    e0 = e1;
+  }
+  return c;
+}
+
+// ---- entry chunks of the fill kernel: term slice + row pointers + pair table + column factors must fit LDS ----
+// writes tidx16, fill_table_global, chunk_ent, chunk_terms_max, chunk_ents_max; reads lists_built, ptr, tidx
+void build_entry_chunks(biem_plan* p) {
+  const int H = p->H;
+  p->tidx16.resize(p->tidx.size());
+  for (size_t i = 0; i < p->tidx.size(); ++i) p->tidx16[i] = (uint16_t)p->tidx[i];
+  const int max_ents = 1024;                                     // = FILL_THREADS of the fill kernel: one entry per thread
+  long long budget = 150 * 1024 - (long long)(p->H2 + 2 * H) * 16 - (long long)(max_ents + 1) * 4 - 64;
+  // large orders (3-D n_end >= 40, 4-D >= 15): the pair table no longer leaves room for a useful slice of the term list - the
+  // kernel then reads the pair table from global memory (L2) and LDS holds only the column factors and the term slice
+  p->fill_table_global = budget < 2048 * 10;
+  if (p->fill_table_global) budget = 150 * 1024 - (long long)(2 * H) * 16 - (long long)(max_ents + 1) * 4 - 64;
+  long long cap_terms = budget > 0 ? budget / 10 : 0;            // 8-byte coefficient + 2-byte table index per term
+  if (cap_terms > 16384) cap_terms = 16384;
+  Chunks c = cut_chunks(p->lists_built ? (long long)H * H : 0, max_ents, cap_terms, [&](long long e) { return p->ptr[e]; }, false);
+  p->chunk_ent = c.bound; p->chunk_terms_max = c.terms_max; p->chunk_ents_max = c.items_max;
+}
+
+// ---- unit slots and the four term lists ("slots") per unit pair of the symmetric fill (plan.hpp) ----
+// writes spos, hpos, qptr, qcoef, qidx16; reads units, lists_built, ptr, coef, tidx
+void build_unit_slots(biem_plan* p) {
+  const int H = p->H, U = (int)(p->units.size() / 2);
+  p->spos.assign(U, -1); p->hpos.assign(H, 0);
+  int ns = 0;
+  for (int u = 0; u < U; ++u) {
+    const int h = p->units[2 * u], pp = p->units[2 * u + 1];
+    p->hpos[h] = u;
+    if (pp != h) { p->spos[u] = ns; p->hpos[pp] = U + ns; ++ns; }
+  }
+  p->qptr.assign(p->lists_built ? (size_t)4 * U * U + 1 : 1, 0);
+  p->qcoef.clear(); p->qidx16.clear();
+  p->qcoef.reserve(p->coef.size()); p->qidx16.reserve(p->coef.size());
+  for (int u = 0; u < (p->lists_built ? U : 0); ++u)
+    for (int v = 0; v < U; ++v) {
+      const int hh[2] = {p->units[2 * u], p->units[2 * u + 1]}, cc[2] = {p->units[2 * v], p->units[2 * v + 1]};
+      for (int slot = 0; slot < 4; ++slot) {
+        const int ri = slot >> 1, ci = slot & 1;
+        const bool present = (ri == 0 || hh[1] != hh[0]) && (ci == 0 || cc[1] != cc[0]);
+        if (present) {
+          const size_t e = (size_t)hh[ri] * H + cc[ci];
+          for (uint32_t q = p->ptr[e]; q < p->ptr[e + 1]; ++q) { p->qcoef.push_back(p->coef[q]); p->qidx16.push_back((uint16_t)p->tidx[q]); }
+        }
+        p->qptr[((size_t)u * U + v) * 4 + slot + 1] = (uint32_t)p->qcoef.size();
+      }
+    }
+}
+
+// the conjugate partner of every degree < 2 n_end - 1 label; ok: every later stage's forms may still be built (a stage that finds its
+// form impossible clears it for the stages behind it)
+struct LabelPairing { std::vector<int> partner2; bool ok; };
+
+// ---- label pairing: partners adjacent in the paired table layout ----
+// writes lin2, H2lin; reads labels2
+LabelPairing pair_labels(biem_plan* p) {
+  LabelPairing lp;
+  lp.ok = conjugate_partners(p->tree, p->lw, p->labels2, p->H2, lp.partner2);
+  p->lin2.assign(p->H2, 0);
+  int ne = 0;
+  for (int l = 0; l < p->H2 && lp.ok; ++l)
+    if (l <= lp.partner2[l]) { p->lin2[l] = 2 * ne; if (lp.partner2[l] != l) p->lin2[lp.partner2[l]] = 2 * ne + 1; ++ne; }
+  p->H2lin = 2 * ne;
+  if (p->H2lin > 65535) lp.ok = false;
+  return lp;
+}
+
+// ---- the two-list form of the entry-per-lane kernel ----
+// writes q2ptr, q2coef, q2idx16, pair_lists_ok (and clears lp.ok where a mirrored list is not the mirror); reads units, lists_built, ptr, coef, tidx, lin2
+void build_pair_lists(biem_plan* p, LabelPairing& lp) {
+  const int H = p->H, U = (int)(p->units.size() / 2);
+  const std::vector<int>& partner2 = lp.partner2;
+  bool& ok = lp.ok;
+  p->q2ptr.assign(p->lists_built ? (size_t)2 * U * U + 1 : 1, 0);
+  p->q2coef.clear(); p->q2idx16.clear();
+  const int Ul = p->lists_built ? U : 0;            // (no lists: the loops over unit pairs below do nothing)
+  auto same_mirrored = [&](size_t ea, size_t eb) {      // list of entry eb == list of entry ea with partner indices?
+    if (p->ptr[ea + 1] - p->ptr[ea] != p->ptr[eb + 1] - p->ptr[eb]) return false;
+    for (uint32_t q = p->ptr[ea], r = p->ptr[eb]; q < p->ptr[ea + 1]; ++q, ++r) {
+      if (fabs(p->coef[q] - p->coef[r]) > 1e-13 * (fabs(p->coef[q]) + 1e-300)) return false;
+      if (partner2[p->tidx[q]] != p->tidx[r]) return false;
+    }
+    return true;
+  };
+  auto append = [&](size_t e) {
+    for (uint32_t q = p->ptr[e]; q < p->ptr[e + 1]; ++q) { p->q2coef.push_back(p->coef[q]); p->q2idx16.push_back((uint16_t)p->lin2[p->tidx[q]]); }
+  };
+  for (int u = 0; u < Ul && ok; ++u)
+    for (int v = 0; v < U && ok; ++v) {
+      const int h = p->units[2 * u], pp = p->units[2 * u + 1], ch = p->units[2 * v], cp = p->units[2 * v + 1];
+      const bool r2 = pp != h, c2 = cp != ch;
+      const size_t eA = (size_t)h * H + ch;
+      append(eA);
+      p->q2ptr[((size_t)u * U + v) * 2 + 1] = (uint32_t)p->q2coef.size();
+      // the mirror of list A: (p,p') when both units are doubles, (p,h') when only the row unit is, (h,p') when only the column unit is
+      if (r2 && c2) ok = ok && same_mirrored(eA, (size_t)pp * H + cp);
+      else if (r2) ok = ok && same_mirrored(eA, (size_t)pp * H + ch);
+      else if (c2) ok = ok && same_mirrored(eA, (size_t)h * H + cp);
+      if (r2 && c2) {
+        const size_t eB = (size_t)h * H + cp;
+        append(eB);
+        ok = ok && same_mirrored(eB, (size_t)pp * H + ch);
+      }
+      p->q2ptr[((size_t)u * U + v) * 2 + 2] = (uint32_t)p->q2coef.size();
+    }
+  p->pair_lists_ok = ok && p->lists_built;
+}
+
+// ---- reduced-table form: T'[e] shared by a label and its partner, one phase per list (plan.hpp) ----
+// writes E, red_of, red_first, red_label, ph_mu, ph_of_unit, NP; reads labels2, lin2, H2lin.  Returns whether the reduced lists may be built
+bool build_reduced_units(biem_plan* p, const LabelPairing& lp) {
+  const int H2 = p->H2, ne = p->H2lin / 2;
+  bool rok = lp.ok;
+  p->E = ne; p->red_of.assign(H2, 0); p->red_first.assign(H2, 0); p->red_label.assign(ne, 0);
+  for (int l = 0; l < H2 && rok; ++l) {
+    p->red_of[l] = p->lin2[l] >> 1;
+    p->red_first[l] = (l <= lp.partner2[l]) ? 1 : 0;
+    if (l <= lp.partner2[l]) p->red_label[p->lin2[l] >> 1] = l;
+  }
+  // phase ids: one per distinct azimuthal order vector of the first members
+  std::map<std::pair<int, int>, int> phid;
+  p->ph_mu.clear(); p->ph_of_unit.assign(ne, 0);
+  for (int e = 0; e < ne && rok; ++e) {
+    int m1, m2; azimuthal_orders(p->tree, p->lw, &p->labels2[(size_t)p->lw * p->red_label[e]], m1, m2);
+    auto it = phid.find(std::make_pair(m1, m2));
+    if (it == phid.end()) { it = phid.insert(std::make_pair(std::make_pair(m1, m2), (int)phid.size())).first; p->ph_mu.push_back(m1); p->ph_mu.push_back(m2); }
+    p->ph_of_unit[e] = it->second;
+  }
+  p->NP = (int)phid.size();
+  if (p->E + p->NP > 65535 || p->NP > 32767) rok = false;
+  return rok;
+}
+
+// per list: all terms of one kind (first members / partners / self-conjugate) and of one phase id.
+// The phase selector of entry e's list; false if the list is not uniform.  Reads ptr, tidx, red_of, red_first, ph_of_unit, ph_mu
+bool list_phase_selector(const biem_plan* p, const std::vector<int>& partner2, size_t e, uint16_t& sel) {
+  int kind = -1, id = -1;
+  for (uint32_t q = p->ptr[e]; q < p->ptr[e + 1]; ++q) {
+    const int l = p->tidx[q], u2 = p->red_of[l];
+    const int k2 = partner2[l] == l ? 0 : (p->red_first[l] ? 1 : 2);          // 0 self, 1 first, 2 partner
+    if (kind < 0) { kind = k2; id = p->ph_of_unit[u2]; }
+    else if (kind != k2 || id != p->ph_of_unit[u2]) return false;
+  }
+  if (kind < 0) { sel = 0; return true; }            // empty list: value 0 whatever the phase
+  if (kind == 0) {                                    // self-conjugate labels: azimuthal vector 0, phase 1
+    if (p->ph_mu[2 * id] != 0 || p->ph_mu[2 * id + 1] != 0) return false;
+  }
+  sel = (uint16_t)(2 * id + (kind == 2 ? 1 : 0));
+  return true;
+}
+
+// lanes of the four groups in which a ds_read_b128 is serviced (MI355X_MICROARCH.md, LDS table)
+const int kB128Group[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
+                               {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
+                               {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
+                               {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
+typedef std::pair<double, uint16_t> RTerm;            // coefficient, index e into T' (0xffff: no term)
+typedef std::vector<std::vector<RTerm>> RTerms;       // [lane][term] going in, [row][lane] coming out
+
+// the greedy deal of one lane group's terms to the L rows: lanes with the fewest choices first, each takes the term whose slot is least
+// loaded in this row; equal entries share a read
+void deal_group_rows(const RTerms& terms, const int* lanes, uint32_t L, RTerms& rowterm) {
+  std::vector<std::vector<char>> used(16);
+  for (int q = 0; q < 16; ++q) used[q].assign(terms[lanes[q]].size(), 0);
+  for (uint32_t t = 0; t < L; ++t) {
+    int load[16] = {0};                           // distinct entries per slot in this row and group
+    std::vector<uint16_t> chosen;                 // entries already read in this row and group
+    // lanes in the order of their number of distinct remaining slots (fewest first)
+    int order[16], nd[16];
+    for (int q = 0; q < 16; ++q) {
+      order[q] = q;
+      bool seen[16] = {false}; nd[q] = 0;
+      const auto& tl = terms[lanes[q]];
+      for (size_t x = 0; x < tl.size(); ++x) if (!used[q][x] && !seen[tl[x].second & 15]) { seen[tl[x].second & 15] = true; ++nd[q]; }
+    }
+    std::stable_sort(order, order + 16, [&](int a, int b) { return nd[a] < nd[b]; });
+    for (int oq = 0; oq < 16; ++oq) {
+      const int q = order[oq], lane_i = lanes[q];
+      const auto& tl = terms[lane_i];
+      int best = -1, best_cost = 1 << 30, best_cnt = -1;
+      int cnt[16] = {0};
+      for (size_t x = 0; x < tl.size(); ++x) if (!used[q][x]) ++cnt[tl[x].second & 15];
+      for (size_t x = 0; x < tl.size(); ++x) {
+        if (used[q][x]) continue;
+        const int sl = tl[x].second & 15;
+        const bool shared = std::find(chosen.begin(), chosen.end(), tl[x].second) != chosen.end();
+        const int cost = shared ? 0 : load[sl] * 2 + 1;      // a shared entry is free; then the least loaded slot
+        if (cost < best_cost || (cost == best_cost && cnt[sl] > best_cnt)) { best = (int)x; best_cost = cost; best_cnt = cnt[sl]; }
+      }
+      if (best < 0) continue;                     // this lane's list has run out
+      used[q][best] = 1;
+      rowterm[t][lane_i] = tl[best];
+      if (std::find(chosen.begin(), chosen.end(), tl[best].second) == chosen.end()) { chosen.push_back(tl[best].second); ++load[tl[best].second & 15]; }
+    }
+    // lanes without a term in this row (coefficient 0) read an entry somebody else of the group reads anyway: the one of
+    // the lowest degree (T' is degree-major: the smallest index; entry 0 itself, h_0, was the padding before)
+    const uint16_t filler = chosen.empty() ? 0 : *std::min_element(chosen.begin(), chosen.end());
+    for (int q = 0; q < 16; ++q) if (rowterm[t][lanes[q]].second == 0xffff) rowterm[t][lanes[q]] = std::make_pair(0.0, filler);
+  }
+}
+
+// The rows of one wave's transposed list: in the 64 lanes' terms and the padded length L, out rowterm[row][lane].
+// The order of a lane's terms is free (a sum), and row t of the transposed list is ONE ds_read_b128 gather of the table
+// per combination: 16-byte entries, 16 slots of 4 banks per 256-byte bank row, serviced in four fixed groups of 16 lanes
+// (MI355X_MICROARCH.md, LDS); lanes of a group that read different entries of one slot take one more LDS cycle each.
+// So the terms are dealt to the rows group by group such that the lanes of a group meet on as few slots as possible
+// (deal_group_rows).  Natural order: ~1.6 LDS cycles per group and row at cfg 3, i.e. 30 % of all LDS cycles of the kernel were
+// bank conflicts (profiles/r03_pmc_summary.txt).  BIEM_FILL_LIST_ORDER=natural keeps the natural order (A/B).
+RTerms order_wave_rows(const RTerms& terms, uint32_t L, bool reorder) {
+  RTerms rowterm(L, std::vector<RTerm>(64, std::make_pair(0.0, (uint16_t)0xffff)));
+  if (!reorder) {
+    for (int i = 0; i < 64; ++i) for (size_t t = 0; t < terms[i].size(); ++t) rowterm[t][i] = terms[i][t];
+  } else {
+    for (int g = 0; g < 4; ++g) deal_group_rows(terms, kB128Group[g], L, rowterm);
+  }
+  return rowterm;
+}
+
+// statistics of the gather: LDS cycles per row and group = most distinct entries on one slot, summed over the 4 L (row, group) of the
+// L rows written at ridx[base ..]
+long long gather_cycles_of_rows(const std::vector<uint16_t>& ridx, size_t base, uint32_t L) {
+  long long cycles = 0;
+  for (uint32_t t = 0; t < L; ++t)
+    for (int g = 0; g < 4; ++g) {
+      int mx = 0;
+      for (int sl = 0; sl < 16; ++sl) {
+        uint16_t seen_e[16]; int ns = 0;
+        for (int q = 0; q < 16; ++q) {
+          const uint16_t ix = ridx[base + ((size_t)(t >> 2) * 64 + kB128Group[g][q]) * 4 + (t & 3)];
+          if ((ix & 15) != sl) continue;
+          if (std::find(seen_e, seen_e + ns, ix) == seen_e + ns) seen_e[ns++] = ix;
+        }
+        if (ns > mx) mx = ns;
+      }
+      cycles += mx;
+    }
+  return cycles;
+}
+
+void clear_reduced_lists(biem_plan* p) {
+  p->rcoef.clear(); p->ridx.clear(); p->rchunk.assign(1, 0); p->rcrow.assign(1, 0); p->rwrow.clear(); p->rchunk_rows_max = 0;
+}
+
+// ---- reduced lists: transposed, padded lists per wave of 64 unit pairs; chunks of at most red_waves waves within the LDS budget ----
+// writes red_waves, red_nc, rphsel, rcoef, ridx, rchunk, rcrow, rwrow, rchunk_rows_max, red_gather_cycles, red_lists_ok (the lists cleared
+// where they cannot be built); reads units, lists_built, ptr, coef, tidx, E, NP, red_of, red_first, ph_of_unit, ph_mu
+void build_reduced_lists(biem_plan* p, const LabelPairing& lp, const PlanEnv& env, bool rok) {
+  const int H = p->H, U = (int)(p->units.size() / 2);
+  p->rphsel.assign(p->lists_built ? (size_t)2 * U * U : 0, 0);
+  clear_reduced_lists(p);
+  const long long total_pairs = p->lists_built ? (long long)U * U : 0;
+  p->red_waves = env.red_waves; p->red_nc = env.red_nc;
+  // LDS of a workgroup: 16 waves - the CU to itself; 8 waves - two workgroups per CU (their phases overlap); red_nc table rows
+  const long long lds_budget = (p->red_waves == 16 ? 156 : 76) * 1024 - p->red_nc * ((long long)(p->E + p->NP) * 16 + (long long)2 * p->n_end * 16) - 33 * 4 - 256;
+  const long long cap_rows = lds_budget > 0 ? lds_budget / (64 * 10) : 0;          // a row: 64 x (8-byte coefficient + 2-byte index)
+  std::vector<int> wr(33, 0);
+  long long crows = 0; int cw = 0;                     // rows / waves of the open chunk
+  long long gather_cycles = 0, gather_groups = 0;
+  auto close_chunk = [&](long long pair_end) {
+    for (int w = cw; w < 16; ++w) { wr[2 * w + 1] = wr[2 * w]; wr[2 * w + 2] = wr[2 * w]; }
+    p->rwrow.insert(p->rwrow.end(), wr.begin(), wr.end());
+    p->rchunk.push_back((int)pair_end);
+    p->rcrow.push_back((int)(p->rcoef.size() / 64));
+    if (crows > p->rchunk_rows_max) p->rchunk_rows_max = (int)crows;
+    crows = 0; cw = 0; wr.assign(33, 0);
+  };
+  for (long long w0 = 0; w0 < total_pairs && rok; w0 += 64) {
+    const int nl = (int)((total_pairs - w0 < 64) ? total_pairs - w0 : 64);
+    size_t eA[64], eB[64]; bool hasB[64];
+    uint32_t LA = 0, LB = 0;
+    for (int i = 0; i < nl; ++i) {
+      const long long pi = w0 + i; const int u = (int)(pi / U), v = (int)(pi - (long long)u * U);
+      const int h = p->units[2 * u], pp = p->units[2 * u + 1], ch = p->units[2 * v], cp = p->units[2 * v + 1];
+      eA[i] = (size_t)h * H + ch; eB[i] = (size_t)h * H + cp; hasB[i] = (pp != h) && (cp != ch);
+      uint16_t sA = 0, sB = 0;
+      rok = rok && list_phase_selector(p, lp.partner2, eA[i], sA);
+      if (hasB[i]) rok = rok && list_phase_selector(p, lp.partner2, eB[i], sB);
+      p->rphsel[2 * (size_t)pi] = sA; p->rphsel[2 * (size_t)pi + 1] = sB;
+      const uint32_t la = p->ptr[eA[i] + 1] - p->ptr[eA[i]], lb = hasB[i] ? p->ptr[eB[i] + 1] - p->ptr[eB[i]] : 0;
+      if (la > LA) LA = la;
+      if (lb > LB) LB = lb;
+    }
+    LA = (LA + 3) & ~3u; LB = (LB + 3) & ~3u;           // the kernel walks the lists in groups of four rows
+    if (!rok) break;
+    if ((long long)(LA + LB) > cap_rows) { rok = false; break; }                    // one wave alone exceeds the LDS budget
+    if (cw == p->red_waves || crows + LA + LB > cap_rows) close_chunk(w0);
+    wr[2 * cw] = (int)crows; wr[2 * cw + 1] = (int)(crows + LA); wr[2 * cw + 2] = (int)(crows + LA + LB);
+    for (int pass = 0; pass < 2; ++pass) {
+      const uint32_t L = pass ? LB : LA;
+      const size_t base = p->rcoef.size();                // coefficients [row][lane]; indices [group of 4 rows][lane][4]
+      p->rcoef.resize(base + (size_t)L * 64, 0.0); p->ridx.resize(base + (size_t)L * 64, 0);
+      RTerms terms(64);
+      for (int i = 0; i < nl; ++i)
+        if (pass == 0 || hasB[i]) {
+          const size_t e = pass ? eB[i] : eA[i];
+          for (uint32_t q = p->ptr[e]; q < p->ptr[e + 1]; ++q) terms[i].push_back(std::make_pair(p->coef[q], (uint16_t)p->red_of[p->tidx[q]]));
+        }
+      const RTerms rowterm = order_wave_rows(terms, L, env.reorder_lists);
+      for (uint32_t t = 0; t < L; ++t)
+        for (int i = 0; i < 64; ++i) {
+          double cf = rowterm[t][i].first; uint16_t ix = rowterm[t][i].second;
+          if (ix == 0xffff) { cf = 0.0; ix = 0; }
+          p->rcoef[base + (size_t)t * 64 + i] = cf;
+          p->ridx[base + ((size_t)(t >> 2) * 64 + i) * 4 + (t & 3)] = ix;
+        }
+      gather_cycles += gather_cycles_of_rows(p->ridx, base, L); gather_groups += 4 * (long long)L;
+    }
+    crows += LA + LB; ++cw;
+  }
+  if (rok && cw > 0) close_chunk(total_pairs);
+  p->red_gather_cycles = gather_groups > 0 ? (double)gather_cycles / (double)gather_groups : 0.0;
+  if (env.stats) fprintf(stderr, "plan tree %d n_end %d: table gather %.3f LDS cycles per row and lane group (1 = conflict-free), %lld rows\n", p->tree, p->n_end, p->red_gather_cycles, gather_groups / 4);
+  p->red_lists_ok = rok && (int)p->rchunk.size() > 1;
+  if (!p->red_lists_ok) clear_reduced_lists(p);
+}
+
+// ---- pair chunks and small chunks of the unit pairs ----
+// writes qchunk, qchunk_terms_max, qchunk_pairs_max, schunk, schunk_terms_max, schunk_pairs_max; reads units, lists_built, H2lin, pair_lists_ok, q2ptr, qptr
+void build_pair_chunks(biem_plan* p) {
+  const long long U = (long long)(p->units.size() / 2), total = p->lists_built ? U * U : 0;
+  // chunks: the paired pair table (H2lin complex), the per-degree factors of two balls, the list pointers and the term slice share LDS
+  const int max_pairs = 1024;                                    // = FILL_SYM_THREADS: one unit pair per thread
+  const long long budget = 158 * 1024 - (long long)p->H2lin * 16 - (long long)2 * p->n_end * 16 - (long long)(2 * max_pairs + 1) * 4 - 64;
+  const long long cap_terms = budget > 0 ? budget / 10 : 0;
+  Chunks q;
+  q.fits = cap_terms > 0 && p->pair_lists_ok;
+  if (q.fits) q = cut_chunks(total, max_pairs, cap_terms, [&](long long e) { return p->q2ptr[2 * e]; }, true);   // (fails: one pair alone exceeds the budget)
+  if (!q.fits) q = Chunks();                                     // {0}: the systems-in-lanes form takes over
+  p->qchunk = q.bound; p->qchunk_terms_max = q.terms_max; p->qchunk_pairs_max = q.items_max;
+  // small chunks of the systems-in-lanes form: at most 3072 terms (36 KB of LDS: several workgroups per CU) and 256 unit pairs;
+  // a single pair always fits: its four lists hold at most 4 * (2 n_end) * ... terms, checked at launch
+  Chunks s = cut_chunks(total, 256, 3072, [&](long long e) { return p->qptr[4 * e]; }, false);
+  p->schunk = s.bound; p->schunk_terms_max = s.terms_max; p->schunk_pairs_max = s.items_max;
+}
+
+}  // namespace
+
+int plan_build_fill_tables(biem_plan* p) {
+  const PlanEnv env = read_plan_env();
+  build_entry_chunks(p);
+  build_unit_slots(p);
+  LabelPairing lp = pair_labels(p);
+  build_pair_lists(p, lp);
+  const bool rok = build_reduced_units(p, lp);
+  build_reduced_lists(p, lp, env, rok);
+  build_pair_chunks(p);
+  return BIEM_OK;
+}
+
+}  // namespace biem
