@@ -6,55 +6,8 @@ typing helpers, plus the coordinate-tree factory the reference imports from ``ul
 """
 __version__ = "0.1.0"
 
-from ._biem import (
-    BIEMFactorization,
-    BIEMKwargs,
-    BIEMPower,
-    BIEMResultCalculator,
-    BIEMResultCalculatorProtocol,
-    UinCallable,
-    biem,
-    biem_factorize,
-    biem_far_pattern,
-    biem_force,
-    biem_power,
-    biem_u,
-    biem_u_grad,
-    biem_u_interior,
-    biem_u_interior_grad,
-    biem_u_total,
-    biem_u_total_grad,
-    fluid_inclusion_bc,
-    max_memory,
-    max_n_end,
-    plane_wave,
-    point_source,
-)
+from . import _biem
+from ._biem import *  # noqa: F401,F403  (every name of _biem.__all__, the one list of the binding's public names)
 from ._coords import SphericalCoordinates, create_from_branching_types
 
-__all__ = [
-    "BIEMFactorization",
-    "BIEMKwargs",
-    "BIEMPower",
-    "BIEMResultCalculator",
-    "BIEMResultCalculatorProtocol",
-    "UinCallable",
-    "biem",
-    "biem_factorize",
-    "biem_far_pattern",
-    "biem_force",
-    "biem_power",
-    "biem_u",
-    "biem_u_grad",
-    "biem_u_interior",
-    "biem_u_interior_grad",
-    "biem_u_total",
-    "biem_u_total_grad",
-    "fluid_inclusion_bc",
-    "max_memory",
-    "max_n_end",
-    "plane_wave",
-    "point_source",
-    "SphericalCoordinates",
-    "create_from_branching_types",
-]
+__all__ = [*_biem.__all__, "SphericalCoordinates", "create_from_branching_types"]

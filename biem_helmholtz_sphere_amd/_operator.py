@@ -1,0 +1,380 @@
+"""The operator of one call: input checks (reference ``_biem.py:240-326``), the operands on the device, the plan, the boundary
+samples of an incident field and the small library calls that biem(), biem_factorize() and the observables share."""
+from __future__ import annotations
+
+import math
+import warnings
+from dataclasses import dataclass
+from typing import Any, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from ._arrays import _Origin, _host_array, _inverse_perm, _is_complex, _origin_of, _ptr, _shape, _to_dev
+from ._coords import canonical_tree
+from ._plans import _Plan, _plan
+
+
+# --------------------------------------------------------------------------------------
+# input checking (reference :240-326; error and warning texts are part of the API)
+# --------------------------------------------------------------------------------------
+def _validate_biem_inputs(c, centers, radii, k, eta, alpha, beta) -> Tuple[int, ...]:
+    """Shape / dtype checks of reference :240-326 on metadata only (no device needed); returns the batch shape."""
+    for nm, a in (("centers", centers), ("radii", radii), ("k", k)):
+        if not isinstance(a, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{nm} must be an array (torch.Tensor or numpy.ndarray), got {type(a).__name__}")
+    if eta is not None and _is_complex(eta):
+        raise ValueError("The decoupling parameter must be real.")
+    ks, cs, rs = _shape(k), _shape(centers), _shape(radii)
+    es = (1,) * len(ks) if eta is None else _shape(eta)
+    als = _shape(alpha) or (1,) * (len(ks) + 1)
+    bes = _shape(beta) or (1,) * (len(ks) + 1)
+    if len({len(ks), len(es), len(cs) - 2, len(rs) - 1}) != 1:
+        raise ValueError(f"k.ndim={len(ks)}, eta.ndim={len(es)}, centers.ndim - 2={len(cs) - 2}, radii.ndim -1={len(rs) - 1}are not the same.")
+    if len(als) != len(ks) + 1 or len(bes) != len(ks) + 1:
+        raise ValueError(f"alpha and beta must be scalars or arrays of shape (..., B) with {len(ks) + 1} axes")
+    try:
+        batch = np.broadcast_shapes(ks, es, cs[:-2], rs[:-1], als[:-1], bes[:-1])
+    except ValueError as e:
+        raise ValueError(
+            "Shapes of k, eta and " "centers.shape[:-2], radii.shape[:-1] " "are not broadcastable\n"
+            f"tuple(k.shape)={ks}\ntuple(eta.shape)={es}\ntuple(centers.shape)={cs}\ntuple(radii.shape)={rs}\n"
+            f"tuple(alpha.shape)={als}\ntuple(beta.shape)={bes}"
+        ) from e
+    try:
+        np.broadcast_shapes(cs[:-1], rs, als, bes)
+    except ValueError as e:
+        raise ValueError(
+            "centers.shape[:-1] and radii.shape " "are not broadcastable\n"
+            f"tuple(centers.shape)={cs}\ntuple(radii.shape)={rs}\ntuple(alpha.shape)={als}\ntuple(beta.shape)={bes}"
+        ) from e
+    if cs[-1] != c.c_ndim:
+        raise ValueError(f"The last dimension of centers must be c.c_ndim={c.c_ndim}, but got {cs[-1]}")
+    return tuple(batch)
+
+
+def _is_default(v: Any, default: float) -> bool:
+    return isinstance(v, (int, float, complex)) and not isinstance(v, bool) and v == default
+
+
+def _validate_degree_bc(batch, ks, B: int, n_end: int, alpha, beta, alpha_n, beta_n) -> Tuple[int, ...]:
+    """Checks of the degree-dependent pair alpha_n / beta_n of shape (..., B, n_end) on metadata only; returns the batch shape
+    with their leading axes broadcast in."""
+    if (alpha_n is None) != (beta_n is None):
+        raise ValueError("alpha_n and beta_n must be given together")
+    if not (_is_default(alpha, 1.0) and _is_default(beta, 0.0)):
+        raise ValueError("alpha_n / beta_n replace alpha / beta: leave alpha and beta at their defaults when alpha_n and beta_n are given")
+    ans, bns = _shape(alpha_n), _shape(beta_n)
+    for nm, sh in (("alpha_n", ans), ("beta_n", bns)):
+        if len(sh) != len(ks) + 2:
+            raise ValueError(f"{nm} must be an array of shape (..., B, n_end) with {len(ks) + 2} axes, got shape {sh}")
+        if sh[-1] != n_end:
+            raise ValueError(f"The last dimension of {nm} must be n_end={n_end}, but got {sh[-1]}")
+    try:
+        np.broadcast_shapes(ans[-2:-1], bns[-2:-1], (B,))
+        if np.broadcast_shapes(ans[-2:-1], (B,)) != (B,) or np.broadcast_shapes(bns[-2:-1], (B,)) != (B,):
+            raise ValueError
+        return tuple(np.broadcast_shapes(tuple(batch), ans[:-2], bns[:-2]))
+    except ValueError as e:
+        raise ValueError(
+            "Shapes of alpha_n, beta_n and the batch shape + (B, n_end) " "are not broadcastable\n"
+            f"tuple(alpha_n.shape)={ans}\ntuple(beta_n.shape)={bns}\nbatch shape={tuple(batch)}, B={B}, n_end={n_end}"
+        ) from e
+
+
+def _warn_biem_inputs(k: Any, eta: Any) -> None:
+    """The two UserWarnings of reference :269-285 (texts verbatim, missing blanks included): eta == 0 somewhere; Im k < 0 or
+    eta Re k < 0 somewhere.  Like the reference, which warns after ``xp.asarray(eta)``, the test runs on CONVERTED arrays, so
+    k and eta may mix torch tensors (any device), NumPy arrays, lists and scalars.  (The reference's own test of the second
+    one, :278-280, guards the Im k term with "eta is not castable to float64", which is never true once the complex-eta check
+    above it has passed, so there only eta Re k < 0 can fire; here the condition the message states is checked.)"""
+    if isinstance(k, torch.Tensor) and isinstance(eta, torch.Tensor) and k.is_cuda and eta.is_cuda and k.device == eta.device:
+        # both on one GPU: ONE device -> host copy (each copy is a synchronisation; a call with one small system pays for every one)
+        nk = k.numel()
+        buf = torch.cat([k.detach().reshape(-1).to(torch.complex128), eta.detach().reshape(-1).to(torch.complex128)]).cpu().numpy()
+        k_h = buf[:nk].reshape(tuple(k.shape))
+        if not k.is_complex():
+            k_h = k_h.real
+        eta_h = buf[nk:].real.reshape(tuple(eta.shape))
+    else:
+        k_h = _host_array(k)
+        eta_h = None if eta is None else _host_array(eta)
+    if eta_h is not None and bool(np.any(eta_h == 0)):
+        warnings.warn("The solution may be incorrect" "if k is an eigenvalue for laplacian" "on the interior region with"
+                      "Neumann boundary condition.", UserWarning, stacklevel=4)
+    k_re = k_h.real
+    bad = (np.iscomplexobj(k_h) and bool(np.any(k_h.imag < 0))) or bool(np.any((k_re if eta_h is None else eta_h * k_re) < 0))
+    if bad:
+        warnings.warn("The solution may be incorrectif not (Im k >= 0 and eta Re k >= 0).", UserWarning, stacklevel=4)
+
+
+@dataclass
+class _Flat:
+    """Flattened, contiguous device operands of one biem() call (biem_u: the geometry only, alpha / beta None)."""
+
+    nb: int
+    B: int
+    k: torch.Tensor          # [nb]
+    eta: torch.Tensor        # [nb]
+    centers: torch.Tensor    # [nb or 1, B, d]
+    radii: torch.Tensor      # [nb or 1, B]
+    geom_batched: int
+    alpha: Optional[torch.Tensor] = None     # [nb or 1, B] complex128; degree-dependent: [nb or 1, B, n_end]
+    beta: Optional[torch.Tensor] = None
+    ab_batched: int = 0
+
+
+def _flatten(batch, centers_t, radii_t, k_t, eta_t, alpha_t=None, beta_t=None, degree_axis: int = 0) -> _Flat:
+    nb = int(np.prod(batch)) if len(batch) else 1
+    B, d = int(radii_t.shape[-1]), centers_t.shape[-1]
+    kf = k_t.expand(batch).reshape(nb).contiguous()
+    ef = eta_t.expand(batch).reshape(nb).contiguous()
+    geom_b = any(s != 1 for s in tuple(centers_t.shape[:-2]) + tuple(radii_t.shape[:-1]))
+    if geom_b:
+        cf = centers_t.expand(tuple(batch) + (B, d)).reshape(nb, B, d).contiguous()
+        rf = radii_t.expand(tuple(batch) + (B,)).reshape(nb, B).contiguous()
+    else:
+        cf = centers_t.reshape(1, B, d).contiguous()
+        rf = radii_t.reshape(1, B).contiguous()
+    if alpha_t is None:
+        return _Flat(nb, B, kf, ef, cf, rf, int(geom_b))
+    if degree_axis:
+        ab_b = any(s != 1 for s in tuple(alpha_t.shape[:-2]) + tuple(beta_t.shape[:-2]))
+        lead = (tuple(batch), nb) if ab_b else ((1,) * len(batch), 1)
+        af, bf = (t.expand(lead[0] + (B, degree_axis)).reshape(lead[1], B, degree_axis).contiguous() for t in (alpha_t, beta_t))
+        return _Flat(nb, B, kf, ef, cf, rf, int(geom_b), af, bf, int(ab_b))
+    ab_b = any(s != 1 for s in tuple(alpha_t.shape[:-1]) + tuple(beta_t.shape[:-1]))
+    if ab_b:
+        af, bf = (t.expand(tuple(batch) + (B,)).reshape(nb, B).contiguous() for t in (alpha_t, beta_t))
+    else:
+        af, bf = (t.reshape(-1)[-t.shape[-1]:].expand(B).reshape(1, B).contiguous() for t in (alpha_t, beta_t))
+    return _Flat(nb, B, kf, ef, cf, rf, int(geom_b), af, bf, int(ab_b))
+
+
+@dataclass
+class _Operator:
+    """Everything of one biem() / biem_factorize() call that does not depend on the incident field."""
+
+    c: Any
+    n_end: int
+    kind: str
+    origin: _Origin
+    dev: torch.device
+    batch: Tuple[int, ...]
+    perm: Tuple[int, ...]    # canonical axis i = the caller's axis perm[i]
+    plan: _Plan
+    fl: _Flat                # in canonical axes
+    centers_t: torch.Tensor  # the caller's arrays on the device, caller's axes
+    radii_t: torch.Tensor
+    k_t: torch.Tensor
+    eta_t: torch.Tensor
+    k_complex: bool
+    alpha: Any               # alpha / beta as given (Python scalars are tested for zero on the host) and on the device
+    beta: Any
+    alpha_t: torch.Tensor
+    beta_t: torch.Tensor
+    per_degree: bool = False # alpha / beta are the degree-dependent alpha_n / beta_n of shape (..., B, n_end); fl.alpha / fl.beta likewise
+
+
+def _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n=None, beta_n=None) -> _Operator:
+    """Input checks of reference :240-326, the operands on the device and the plan."""
+    batch = _validate_biem_inputs(c, centers, radii, k, eta, alpha, beta)
+    per_degree = alpha_n is not None or beta_n is not None
+    if per_degree:
+        batch = _validate_degree_bc(batch, _shape(k), _shape(radii)[-1], int(n_end), alpha, beta, alpha_n, beta_n)
+        alpha, beta = alpha_n, beta_n                  # from here on the pair is (alpha_n, beta_n), one more trailing axis
+    _warn_biem_inputs(k, eta)
+    origin, dev = _origin_of(centers, radii, k, eta, alpha, beta)
+    f64 = torch.float64
+    centers_t = _to_dev(centers, dev, f64)
+    radii_t = _to_dev(radii, dev, f64)
+    k_t = _to_dev(k, dev, torch.complex128)     # the kernels take complex wavenumbers (Im k = 0: real special functions)
+    if eta is None:
+        eta_t = torch.ones((1,) * k_t.ndim, dtype=f64, device=dev)
+    else:
+        eta_t = _to_dev(eta, dev, f64)
+    alpha_t, beta_t = (_to_dev(a, dev, torch.complex128) for a in (alpha, beta))
+    alpha_t, beta_t = (t[(None,) * (k_t.ndim + 1)] if t.ndim == 0 else t for t in (alpha_t, beta_t))
+    # trees with primed nodes run as their canonical tree in permuted axes (canonical component i = original perm[i])
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    plan = _plan(tree, n_end, dev)
+    fl = _flatten(batch, centers_t if list(perm) == list(range(len(perm))) else centers_t[..., list(perm)], radii_t, k_t, eta_t,
+                  alpha_t, beta_t, int(n_end) if per_degree else 0)
+    return _Operator(c, n_end, kind, origin, dev, tuple(batch), perm, plan, fl, centers_t, radii_t, k_t, eta_t, _is_complex(k),
+                     alpha, beta, alpha_t, beta_t, per_degree)
+
+
+def _result_operator(res: Any, what: str, alpha, beta, alpha_n, beta_n, require=()) -> _Operator:
+    """The operator of a result record and the coefficients biem() took (the record stores none), for an observable named `what`
+    ("powers", "force").  ValueError for kind != "outer", any Im k != 0 and a record without density, then for the first None among
+    the caller's own operands `require`, (value, message) pairs - all before any device work."""
+    plural = what.endswith("s")
+    if res.kind != "outer":
+        raise ValueError(f"Invalid kind: {res.kind} (the {what} belong{'' if plural else 's'} to an exterior problem, kind='outer')")
+    k_h = _host_array(res.k)
+    if np.iscomplexobj(k_h) and bool(np.any(k_h.imag != 0)):
+        raise ValueError(f"The {what} {'are' if plural else 'is'} defined for a real wavenumber: Im k must be zero for every system.")
+    if res.density is None:
+        raise ValueError("The BIEMResult does not have density.")
+    for value, message in require:
+        if value is None:
+            raise ValueError(message)
+    as_array = lambda a: a if isinstance(a, (torch.Tensor, np.ndarray)) else np.asarray(a)
+    centers = as_array(res.centers)
+    centers = torch.movedim(centers, 0, -1) if isinstance(centers, torch.Tensor) else np.moveaxis(centers, 0, -1)
+    with warnings.catch_warnings():                   # (biem() has given the warnings of these operands already)
+        warnings.simplefilter("ignore", UserWarning)
+        return _operator(res.c, centers, as_array(res.radii), as_array(res.k), int(res.n_end), alpha, beta, as_array(res.eta), res.kind,
+                         alpha_n, beta_n)
+
+
+def _check_incident(op: _Operator, uin, uin_grad) -> None:
+    """The boundary condition needs uin where alpha != 0 and uin_grad where beta != 0.  The zero tests run only when the matching
+    callable is missing; Python scalars are decided on the host (a device tensor costs a synchronisation)."""
+    def all_zero(v, v_t):
+        return (v == 0) if isinstance(v, (int, float, complex)) else bool(torch.all(v_t == 0))
+    if uin is None and not all_zero(op.alpha, op.alpha_t):
+        raise ValueError("alpha is not zero, but uin is None. uin must be provided to compute the boundary condition.")
+    if uin_grad is None and not all_zero(op.beta, op.beta_t):
+        raise ValueError("beta is not zero, but uin_grad is None. uin_grad must be provided to compute the boundary condition.")
+
+
+@dataclass(frozen=True)
+class _RhsAxes:
+    """Batch axes of the right-hand sides.  The incident field (or a density), of batch shape `full`, may vary along batch axes on
+    which the operator (k, eta, geometry, alpha, beta) has size 1 (e.g. many incidence directions for one wavenumber): those axes
+    become right-hand sides of ONE factorisation.  The reference broadcasts the matrix over them in btensorsolve (_biem.py:797),
+    i.e. factors it again per incidence."""
+
+    full: Tuple[int, ...]
+    op_axes: Tuple[int, ...]
+    rhs_axes: Tuple[int, ...]
+    nrhs: int
+
+    @classmethod
+    def of(cls, batch, full) -> "_RhsAxes":     # batch: the operator's batch shape; full: as many axes
+        op_axes = tuple(i for i in range(len(batch)) if batch[i] == full[i])
+        rhs_axes = tuple(i for i in range(len(batch)) if batch[i] != full[i])
+        return cls(tuple(full), op_axes, rhs_axes, int(np.prod([full[i] for i in rhs_axes])) if rhs_axes else 1)
+
+    def lay_out(self, t: torch.Tensor) -> torch.Tensor:
+        """(*full, *tail) in the caller's axis order -> contiguous [nb, nrhs, *tail] in (op axes, rhs axes) order."""
+        nf = len(self.full)
+        tail = tuple(t.shape[nf:])
+        nb = math.prod(self.full[i] for i in self.op_axes)
+        t = t.permute(list(self.op_axes) + list(self.rhs_axes) + [nf + j for j in range(len(tail))])
+        return t.reshape((nb, self.nrhs) + tail).contiguous()
+
+    def restore(self, t: torch.Tensor) -> torch.Tensor:
+        """[nb, nrhs, ...] in (op axes, rhs axes) order -> (*full, ...) in the caller's axis order."""
+        full = self.full
+        tail = tuple(t.shape[2:])
+        t = t.reshape(tuple(full[i] for i in self.op_axes) + tuple(full[i] for i in self.rhs_axes) + tail)
+        order = self.op_axes + self.rhs_axes
+        inv = [order.index(i) for i in range(len(full))]
+        return t.permute(inv + [len(full) + j for j in range(len(tail))])
+
+
+def _boundary_samples(op: _Operator, uin, uin_grad):
+    """g[nb, nrhs, B, Q] = (-alpha u_in - beta d_n u_in)(c_b + rho_b y_q): the closure `f` of reference :611-624.  With degree-dependent
+    coefficients the two parts stay apart and unweighted, g = (gu, gdn) = (u_in, d_n u_in) at those points (a missing callable: None):
+    the degree is known only after the projection (biem_rhs_project_n).  Returns g and the _RhsAxes of its layout.
+
+    fl.centers are in the plan's canonical axes; the user's callables see ORIGINAL axes (x_orig[perm[i]] = x_canon[i])."""
+    plan, origin, fl, batch, perm = op.plan, op.origin, op.fl, op.batch, op.perm
+    dev, d, Q, B, nb = plan.dev, plan.d, plan.Q, fl.B, fl.nb
+    qshape = plan.quad_shape()
+    nbt = len(batch)
+    inv = _inverse_perm(perm)
+    ident = inv == list(range(d))                                      # (no primed nodes: no gather kernels for the axis order)
+    ykey = tuple(inv)
+    y = plan.y_by_axes.get(ykey)
+    if y is None:
+        y = plan.y_by_axes[ykey] = (plan.quad_y.T if ident else plan.quad_y.T[inv]).reshape((d,) + qshape).contiguous()   # (d, ...(f)), original axes
+    x_rel = y[(...,) + (None,) * (nbt + 1)]                            # (d, ...(f), 1.., 1)
+    gbatch = tuple(batch) if fl.geom_batched else (1,) * nbt
+    cen = (fl.centers if ident else fl.centers[..., inv]).reshape(gbatch + (B, d))
+    rad = fl.radii.reshape(gbatch + (B,))
+    # (d, ...(f), ...batch, B)
+    cen_m = torch.movedim(cen, -1, 0)[(slice(None),) + (None,) * len(qshape)]
+    x = rad[(None,) * (1 + len(qshape))] * x_rel + cen_m
+    # (d, ...(f), B, ...batch): the layout the reference hands to uin (:620-621)
+    x = torch.movedim(x, -1, 1 + len(qshape))
+    x = x.expand((d,) + qshape + (B,) + tuple(batch))
+    xu = origin.user_array(x)
+    # alpha/beta along (B, ...batch)
+    def ab(t):
+        t = t.reshape((tuple(batch) if fl.ab_batched else (1,) * nbt) + (B,))
+        return torch.movedim(t, -1, 0)[(None,) * len(qshape)]       # (1.., B, ...batch)
+    g = None
+    lead = qshape + (B,) + tuple(batch)
+    if op.per_degree:
+        parts = [None if uin is None else _to_dev(uin(xu), dev, torch.complex128),
+                 None if uin_grad is None else torch.sum(_to_dev(uin_grad(xu), dev, torch.complex128) * x_rel.to(torch.complex128), dim=0)]
+        tgt = tuple(torch.broadcast_shapes(lead, *(tuple(t.shape) for t in parts if t is not None)))
+        parts = [None if t is None else t.expand(tgt) for t in parts]
+        g = next(t for t in parts if t is not None)
+    else:
+        if uin is not None:
+            u = _to_dev(uin(xu), dev, torch.complex128)
+            g = (ab(fl.alpha) * u).neg_()                                  # (a fresh tensor: negated in place)
+        if uin_grad is not None:
+            gu = _to_dev(uin_grad(xu), dev, torch.complex128)
+            t = ab(fl.beta) * torch.sum(gu * x_rel.to(torch.complex128), dim=0)
+            g = t.neg_() if g is None else g - t
+        if g is None:
+            g = torch.zeros(lead, dtype=torch.complex128, device=dev)
+        else:
+            tgt = tuple(torch.broadcast_shapes(tuple(g.shape), lead))       # (a callable that returned fewer / shorter axes than it was given)
+            if tuple(g.shape) != tgt:
+                g = g.expand(tgt)
+        parts = [g]
+    nq = len(qshape)
+    full = tuple(g.shape[nq + 1:])
+    if len(full) != nbt:
+        raise ValueError(f"uin/uin_grad returned an array with batch shape {full}, expected {nbt} batch axes like k")
+    axes = _RhsAxes.of(batch, full)
+    def laid_out(t):
+        t = t.reshape((Q, B) + full)
+        return axes.lay_out(t.permute([2 + i for i in range(nbt)] + [1, 0]))      # (*full, B, Q) -> (*op, *rhs, B, Q) as [nb, nrhs, B, Q]
+    parts = [None if t is None else laid_out(t) for t in parts]
+    return (tuple(parts) if op.per_degree else parts[0]), axes
+
+
+def _nrhs(g) -> int:
+    """Right-hand sides per system of the samples of _boundary_samples (a tensor, or the unmixed pair of the degree-dependent case)."""
+    return int((g if isinstance(g, torch.Tensor) else next(t for t in g if t is not None)).shape[1])
+
+
+def _sample_ptrs(g, s0: int = 0):
+    """The sample arguments of an entry point from system s0 on: (d_g,) or (d_gu, d_gdn), a missing set as the null pointer."""
+    if isinstance(g, torch.Tensor):
+        return (_ptr(g[s0:]),)
+    return tuple(_ptr(None if t is None else t[s0:]) for t in g)
+
+
+def _entry(base: str, per_degree: bool, label: Optional[str] = None):
+    """The library entry `base`, with degree-dependent coefficients its `_n` form, and its label for L.check (`label`: one label for
+    both forms)."""
+    name = base + "_n" if per_degree else base
+    return getattr(L.load(), name), label or name
+
+
+def _ball_tables(op: _Operator, sp: int, fill: bool = True) -> torch.Tensor:
+    """The per-ball tables [nb, B, 3, n_end] of biem_ball_tables (fill=False: only allocated, for an entry that writes them)."""
+    fl, plan = op.fl, op.plan
+    tab = torch.empty((fl.nb, fl.B, 3, op.n_end), dtype=torch.complex128, device=op.dev)
+    if fill:
+        entry, what = _entry("biem_ball_tables", op.per_degree)
+        L.check(entry(plan.handle, fl.nb, fl.B, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.radii), fl.geom_batched,
+                      _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, _ptr(tab), sp), what)
+    return tab
+
+
+def _rhs_project(op: _Operator, n: int, g, s0: int, f: torch.Tensor, sys_stride: int, elem_stride: int, rhs_stride: int, sp: int) -> None:
+    """biem_rhs_project / biem_rhs_project_n of the n systems from s0 on into f (natural order)."""
+    fl, a0 = op.fl, s0 if op.fl.ab_batched else 0
+    entry, what = _entry("biem_rhs_project", op.per_degree)
+    coef = (_ptr(fl.alpha[a0:]), _ptr(fl.beta[a0:]), fl.ab_batched) if op.per_degree else ()
+    L.check(entry(op.plan.handle, n, fl.B, _nrhs(g), *_sample_ptrs(g, s0), *coef, _ptr(f), sys_stride, elem_stride, rhs_stride, sp), what)

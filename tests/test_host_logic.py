@@ -192,6 +192,10 @@ def test_result_object_is_frozen():
     assert r.matrix is None and r.density is None
 
 
+def test_binding_module_lists_every_public_name():
+    assert set(amd.__all__) - {"SphericalCoordinates", "create_from_branching_types"} == set(_biem.__all__)
+
+
 def test_shard_bounds_cover_batch():
     for n in (0, 1, 7, 256, 257):
         for world in (1, 2, 3, 8):

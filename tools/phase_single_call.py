@@ -4,7 +4,7 @@ import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import biem_helmholtz_sphere_amd as amd
-from biem_helmholtz_sphere_amd import _biem as M
+from biem_helmholtz_sphere_amd import _biem as M, _operator as O
 t = lambda a: torch.as_tensor(np.array(a), dtype=torch.float64, device="cuda")
 c = amd.create_from_branching_types("ba")
 k = t(1.0)
@@ -16,8 +16,10 @@ def wrap(mod, name):
     def g(*a, **kw):
         t0 = time.perf_counter(); r = f(*a, **kw); acc[name] = acc.get(name, 0.0) + time.perf_counter() - t0; return r
     setattr(mod, name, g)
-for n in ("_check_biem_inputs", "_flatten", "_plan", "_boundary_samples", "_restore_batch", "_warn_biem_inputs", "_validate_biem_inputs", "canonical_tree"):
-    if hasattr(M, n): wrap(M, n)
+# each helper in the module where biem() looks it up: _operator() resolves its own in _operator, biem() the ones it imported by name
+for mod, names in ((O, ("_flatten", "_plan", "_warn_biem_inputs", "_validate_biem_inputs", "canonical_tree")),
+                   (M, ("_boundary_samples", "_lu_systems", "_result")), (O._RhsAxes, ("lay_out", "restore"))):
+    for n in names: wrap(mod, n)
 lib = M.L.load()
 class P:
     def __init__(s, l): s.l = l
