@@ -105,6 +105,11 @@ EXPECTED_LOADS_STRIP = 5
 # Keys (STACK, KD), handed out by check_isa_stack().
 STACK = "stack"
 SLAB = "slab"
+# k_back_sweep<NQ>, the row-form back substitution in one launch per group of right-hand sides: one 1024-thread workgroup per system,
+# so 128 VGPRs per lane is all there is - a spill puts scratch traffic into the stream over U.  No scratch and no VGPR spills are pinned
+# for every instance.  Keys (SWEEP, NQ), handed out by check_isa_sweep().
+SWEEP = "sweep"
+SWEEP_NQ = (1, 2, 4, 8)
 STACK_KD = (128, 192, 256)
 EXPECTED_LDS_DMA_STACK = 24
 EXPECTED_STORES_STACK = 65
@@ -174,7 +179,9 @@ def _chunk_loop(ins):
 
 
 def _label(kd) -> str:
-    return "k_gemm3m_strip" if kd == STRIP else "k_sym_slab" if kd == SLAB else f"k_gemm3m_stack<{kd[1]}>" if isinstance(kd, tuple) else f"k_gemm3m_pipe<{kd}>"
+    if isinstance(kd, tuple):
+        return f"k_back_sweep<{kd[1]}>" if kd[0] == SWEEP else f"k_gemm3m_stack<{kd[1]}>"
+    return "k_gemm3m_strip" if kd == STRIP else "k_sym_slab" if kd == SLAB else f"k_gemm3m_pipe<{kd}>"
 
 
 def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = False) -> dict:
@@ -203,6 +210,13 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = F
                     report[SLAB] = rep
                     if rep["scratch_bytes"] != 0 or rep["vgpr_spills"] != 0:
                         raise IsaCheckError(f"k_sym_slab: scratch {rep['scratch_bytes']} B, {rep['vgpr_spills']} VGPR spills")
+                m = re.search(r"k_back_sweepILi(\d+)E", n)
+                if m:
+                    rep = {"scratch_bytes": int(metas[n].get("private_segment_fixed_size", -1)), "vgpr_spills": int(metas[n].get("vgpr_spill_count", -1)),
+                           "vgprs": int(metas[n].get("vgpr_count", -1))}
+                    report[(SWEEP, int(m.group(1)))] = rep
+                    if rep["scratch_bytes"] != 0 or rep["vgpr_spills"] != 0:
+                        raise IsaCheckError(f"k_back_sweep<{m.group(1)}>: scratch {rep['scratch_bytes']} B, {rep['vgpr_spills']} VGPR spills")
             gemm = [n for n in metas if "k_gemm3m_pipe" in n or "k_gemm3m_strip" in n or "k_gemm3m_stack" in n]
             if not gemm:
                 continue
@@ -254,7 +268,7 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = F
                     bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (expected <= {MAX_TILE_MAP_LOADS})")
                 if bad:
                     raise IsaCheckError(f"{label}: the hand-counted vmcnt scheme is not safe with this code object: " + "; ".join(bad))
-    want = set(EXPECTED_LDS_DMA) | {KLONG, STRIP, SLAB} | {(STACK, k) for k in STACK_KD}
+    want = set(EXPECTED_LDS_DMA) | {KLONG, STRIP, SLAB} | {(STACK, k) for k in STACK_KD} | {(SWEEP, q) for q in SWEEP_NQ}
     if set(report) != want:
         raise IsaCheckError(f"update kernels found: {sorted(report, key=str)}, expected {sorted(want, key=str)}")
     if verbose:
@@ -279,6 +293,12 @@ def check_isa_stack(lib_path: str = LIB) -> dict:
     """The reports of k_gemm3m_stack<KD>, keyed by KD, and of k_sym_slab under SLAB (same checks as check_isa, which raises for them as well)."""
     rep = check_isa(lib_path, _all_kernels=True)
     return {**{k: rep[(STACK, k)] for k in STACK_KD}, SLAB: rep[SLAB]}
+
+
+def check_isa_sweep(lib_path: str = LIB) -> dict:
+    """The reports of k_back_sweep<NQ>, keyed by NQ (same checks as check_isa, which raises for them as well)."""
+    rep = check_isa(lib_path, _all_kernels=True)
+    return {q: rep[(SWEEP, q)] for q in SWEEP_NQ}
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

@@ -522,7 +522,7 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
     const FillDedupe dd = {d_radii, d_alpha, d_beta};
     if (split)
       // E's right-hand-side columns lie inside the O rows' matrix columns: they are cleared for all rows BEFORE the fill writes O
-      BIEM_HIPCHK(hipMemset2DAsync(A + (size_t)sm.npE * 2, (size_t)L.lda * 16, 0, (size_t)(L.lda - L.n_pad) * 16, (size_t)L.n_pad * c, st));
+      launch_clear_cols(st, A + (size_t)sm.npE * 2, L.lda, L.lda - L.n_pad, (long long)L.n_pad * c);
     if (symmetric)
       // (degree-dependent coefficients: every pair on its own - the classes are keyed on one (alpha, beta) per ball)
       rc = launch_fill_sym(plan, c, B, ks, cen, geom_batched, tb, A, L.lda, L.sys_stride, L.n_pad, T, fill_workspace_bytes(plan, c, B), st, small,
@@ -532,8 +532,7 @@ static int solve_impl(const biem_plan* plan, int nb, int B, int nrhs, const doub
                        fill_workspace_bytes(plan, c, B), st);
     if (rc) return rc;
     if (!small)
-      BIEM_HIPCHK(hipMemset2DAsync(A + (size_t)L.n_pad * 2, (size_t)L.lda * 16, 0, (size_t)(L.lda - L.n_pad) * 16,
-                                   (size_t)L.n_pad * c, st));
+      launch_clear_cols(st, A + (size_t)L.n_pad * 2, L.lda, L.lda - L.n_pad, (long long)L.n_pad * c);
     const size_t g0 = (size_t)s0 * nrhs * B * Q * 2;
     if (bcn) {
       const size_t ab0 = ab_batched ? (size_t)s0 * B * plan->n_end * 2 : 0;

@@ -192,6 +192,8 @@ __attribute__((visibility("hidden"))) int sym_form_query(int nb, int n_pad, int 
 // (n_active: rows n_active .. n_pad-1 are identity padding; systems of at most 128 active rows run in one LDS-resident launch)
 int launch_sym_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long lda, long long sys_stride, int* d_info, void* d_work,
                             size_t work_bytes, hipStream_t st, bool amax_ready = false, int n_active = 0);
+// zero `width` complex columns from d_A on in `rows` consecutive rows of lda complex (right-hand-side columns of a chunk's systems)
+void launch_clear_cols(hipStream_t st, double* d_A, long long lda, int width, long long rows);
 // where the symmetric factorisation keeps max |A|, max |U| per system inside its workspace (unsigned 64-bit patterns of doubles)
 unsigned long long* lu_growth_slots(void* d_work, int nb, int n_pad);
 // preset the slots for a caller that knows (a lower bound of) max |A|: growth[s] = (amax, 0); then pass amax_ready = true

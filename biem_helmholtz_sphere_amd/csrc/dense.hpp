@@ -105,7 +105,7 @@ struct SymForm {
   bool left;                        // bulk update left-looking (launch_gemm_left before a group), else the K = 256 update after it
   bool stacked;                     // panels b, c, d of a group in one stacked product pass, else in-group update + strip
   bool rhs_gemv;                    // the right-hand sides ride in the compact copy Y[s][q][row], else as columns of the matrix
-  enum Back { BACK_ROW = 0, BACK_COL = 1, BACK_STEP = 2 } back;   // back substitution: k_back_row / back_substitute_cols / k_back_step
+  enum Back { BACK_ROW = 0, BACK_COL = 1, BACK_STEP = 2 } back;   // back substitution: k_back_sweep (k_back_row) / back_substitute_cols / k_back_step
   bool keep_w() const { return back == BACK_STEP; }               // every panel's W = I - U11^{-T} is kept for k_back_step
   bool diag_blk;                    // diagonal kernel k_diag_utu_blk (four pivots per barrier), else k_diag_utu_reg
 };

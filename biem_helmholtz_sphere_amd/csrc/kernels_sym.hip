@@ -13,7 +13,10 @@
 //               solves its 64 entries, the strip's epilogue subtracts every tile's term from the 64 entries under it.  A one-thread-
 //               per-column VALU form with the triangle of U11^{-T} from the scalar cache or LDS was 5x slower (292 vs 53 ms per 256 systems)
 //   checks:     multiplier test |u_ic| <= 100 |u_ii| and growth max |u_ii u_ic| of the strip entries are taken where the entries
-//               are read anyway: in the back substitution (k_back_update)
+//               are read anyway: in the back substitution
+//   back:       row form (large batches): ONE launch per group of up to 8 right-hand sides, the system's workgroup walks the block rows
+//               bottom up (k_back_sweep; BIEM_BACK_ROW=blocks: one launch per block row, k_back_row); few systems: the column form
+//               (k_back_update, kernels_trisolve.hip) or the stored inverses (k_back_step)
 //   in-group:   the next panel's 64 rows take the group's pending updates (K = 64 q) for all columns right of them
 //   stacked:    under the left-looking bulk update the in-group pass and the strip of the panels b, c, d are ONE pure product over
 //               K = 64 (q + 1) (k_sym_slab, k_gemm3m_stack<KD>; the diagonal tile alone takes the pending update first)
@@ -39,7 +42,8 @@ __global__ void __launch_bounds__(256) k_absmax_upper(const cplx* __restrict__ A
   block_max_publish(m, growth + 2 * (size_t)s);
 }
 
-// Back substitution of the row form, one launch per 64-row block (bottom up), one 1024-thread workgroup per system:
+// Back substitution of the row form as one launch per 64-row block (bottom up; BIEM_BACK_ROW=blocks - production runs the one-launch
+// k_back_sweep below, whose iterations are this kernel), one 1024-thread workgroup per system:
 //   y_R -= U[R, C] x_C over all solved columns C right of the block - the 16 waves stream 4 rows each across the strip, 64 columns
 //   per step, partial sums per lane and ONE reduction per row at the end - then the 64 x 64 triangular solve U[R,R] x_R = y_R in
 //   the same launch (diagonal block in LDS, one wave).  Reads U exactly once in long contiguous runs (the column-block form
@@ -125,6 +129,189 @@ __global__ void __launch_bounds__(1024) k_back_row(const cplx* __restrict__ A, l
       Ys[(size_t)(q0 + q) * n_pad + rb + lane] = y;
     }
   }
+}
+
+// The same back substitution as ONE launch per group of right-hand sides: the system's workgroup walks its block rows bottom up itself,
+// every iteration the arithmetic of one k_back_row launch in the same order (same lane-to-row/column mapping, per-lane sums over c0
+// ascending, same shuffle reduction, same wave-0 solve), so X, info and the growth slot come out bit for bit as from the per-block
+// launches (BIEM_BACK_ROW=blocks).  What the per-block launches wait for and this kernel does not: the launch boundary, and the loads
+// that do not depend on x - while wave 0 solves block ib, block ib - 1's diagonal block (four registers per lane, then the second sU
+// buffer; |d|^2 is read from there) and, with up to two accumulators per row, the c0 = rb + 64 entries of its strip are already in
+// flight.  x stays in Y (global): the
+// barrier behind the solve orders its stores before the next block row's loads (one workgroup, one CU, one L1).  The multiplier verdict
+// and the growth maximum are kept per thread and published once at the end: the bottom-most offending block row is the smallest code,
+// the maximum is order-free.  Every workgroup touches its own system only, every loop is bounded by n_pad.
+// NQ = 8 walks the strip twice with four accumulators per row (128 VGPRs per lane is all a 1024-thread workgroup has; k_back_row<8>
+// spills 440 of them): each sum keeps its order.
+// one 64-column step of a wave's four rows; sd: the wave's first diagonal entry in the LDS copy of the block (wide instantiations read
+// |d|^2 from there instead of keeping it in registers)
+template <int NA>
+__device__ __forceinline__ void sweep_step(const cplx (&u)[4], const cplx (&x)[NA], cplx (&acc)[4][NA], const double (&d2)[4], const cplx* sd,
+                                           bool chk, double inv_rel2, bool& badm, double& um2) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (chk) {
+      double dd = d2[k];
+      if (NA > 2) { const cplx d = sd[k * (NB + 2)]; dd = d.x * d.x + d.y * d.y; }
+      const double m2 = u[k].x * u[k].x + u[k].y * u[k].y;
+      if (!(m2 <= inv_rel2 * dd)) badm = true;
+      um2 = nan_max(um2, m2 * dd);
+    }
+#pragma unroll
+    for (int q = 0; q < NA; ++q) acc[k][q] = cfma(u[k], x[q], acc[k][q]);
+  }
+}
+constexpr int SWEEP_SU = NB * (NB + 1);                 // one padded diagonal block, in complex
+static size_t sweep_lds(int nq) { return (size_t)(2 * SWEEP_SU + NB * nq + 16) * sizeof(cplx); }
+template <int NQ>
+__global__ void __launch_bounds__(1024) k_back_sweep(const cplx* __restrict__ A, long long lda, long long sys_stride, cplx* __restrict__ Y,
+                                                      int nrhs, int n_pad, int q0, int nq, int do_checks,
+                                                      int* __restrict__ info, unsigned long long* __restrict__ growth, double inv_rel2) {
+  constexpr int NA = NQ > 4 ? 4 : NQ, NPASS = NQ / NA;   // accumulators per row and passes over the strip
+  constexpr bool PRE = NA <= 2;                          // the strip's first entries ride in registers across the solve
+  constexpr bool YPRE = NA <= 2;
+  extern __shared__ cplx sw[];
+  cplx* const sy = sw + 2 * SWEEP_SU;                    // [NB][NQ]
+  double* const sm_max2 = (double*)(sy + NB * NQ);       // [16]
+  int* const s_code = (int*)(sm_max2 + 16);
+  // (the wave index as a scalar: the row addresses of the strip and of the block loads stay in SGPRs)
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const cplx* As = A + (size_t)s * sys_stride;
+  cplx* Ys = Y + (size_t)s * nrhs * n_pad;
+  double d2[4];
+  cplx upre[4];
+  {
+    const int rb = n_pad - NB;
+    for (int e = tid; e < NB * NB; e += 1024) { const int r = e >> 6, c = e & 63; sw[r * (NB + 1) + c] = As[(size_t)(rb + r) * lda + rb + c]; }
+    if (tid == 0) *s_code = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const cplx d = sw[(4 * wave + k) * (NB + 2)];
+      d2[k] = d.x * d.x + d.y * d.y;
+      upre[k] = make_double2(0.0, 0.0);
+    }
+  }
+  double um2 = 0.0;
+  int code = 0;
+  int cur = 0;
+  for (int ib = n_pad / NB - 1; ib >= 0; --ib) {
+    const int rb = ib * NB;
+    const cplx* sU = sw + cur * SWEEP_SU;
+    const cplx* sd = sU + 4 * wave * (NB + 2);
+    const cplx* Ur = As + (size_t)(rb + 4 * wave) * lda + lane;
+    bool badm = false;
+#pragma unroll
+    for (int h = 0; h < NPASS; ++h) {
+      const int qh = h * NA;
+      cplx acc[4][NA];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int q = 0; q < NA; ++q) acc[k][q] = make_double2(0.0, 0.0);
+      const bool chk = do_checks && h == 0;
+      int c0 = rb + NB;
+      if (PRE && h == 0 && c0 < n_pad) {         // the entries that came in while the block below was solved
+        cplx x[NA];
+#pragma unroll
+        for (int q = 0; q < NA; ++q) x[q] = q < nq ? Ys[(size_t)(q0 + q) * n_pad + c0 + lane] : make_double2(0.0, 0.0);
+        sweep_step<NA>(upre, x, acc, d2, sd, chk, inv_rel2, badm, um2);
+        c0 += NB;
+      }
+#pragma unroll NA <= 2 ? 2 : 1
+      for (; c0 < n_pad; c0 += NB) {
+        cplx x[NA], u[4];
+#pragma unroll
+        for (int q = 0; q < NA; ++q) x[q] = qh + q < nq ? Ys[(size_t)(q0 + qh + q) * n_pad + c0 + lane] : make_double2(0.0, 0.0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) u[k] = Ur[(size_t)k * lda + c0];
+        sweep_step<NA>(u, x, acc, d2, sd, chk, inv_rel2, badm, um2);
+      }
+      // (narrow instantiations fetch the rows' y in one go, every lane the same address, instead of one dependent load per row)
+      cplx yv[YPRE ? 4 : 1][YPRE ? NA : 1];
+      if (YPRE) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+          for (int q = 0; q < NA; ++q) yv[k][q] = q < nq ? Ys[(size_t)(q0 + q) * n_pad + rb + 4 * wave + k] : make_double2(0.0, 0.0);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int q = 0; q < NA; ++q) {
+          double vr = acc[k][q].x, vi = acc[k][q].y;
+          for (int o = 32; o > 0; o >>= 1) { vr += __shfl_down(vr, o, 64); vi += __shfl_down(vi, o, 64); }
+          if (lane == 0) {
+            cplx y;
+            if (YPRE) y = yv[k][q];
+            else y = qh + q < nq ? Ys[(size_t)(q0 + qh + q) * n_pad + rb + 4 * wave + k] : make_double2(0.0, 0.0);
+            y.x -= vr; y.y -= vi;
+            sy[(4 * wave + k) * NQ + qh + q] = y;
+          }
+        }
+    }
+    if (badm && code == 0) code = -(rb + 1);
+    __syncthreads();            // sy and this block's sU are complete
+    // the next block row's loads that do not wait for x: issued now, in flight while wave 0 solves
+    // (the top block row loads its own block once more instead of branching: unconditional loads stay in registers)
+    const int rbn = ib > 0 ? rb - NB : rb, cpre = ib > 0 ? rb : 0;
+    const cplx* Tn = As + (size_t)(rbn + wave) * lda + rbn + lane;       // (entry tid + 1024 x of the block: row wave + 16 x, column lane)
+    const cplx t0 = Tn[0], t1 = Tn[(size_t)16 * lda], t2 = Tn[(size_t)32 * lda], t3 = Tn[(size_t)48 * lda];
+    if (PRE) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) upre[k] = As[(size_t)(rbn + 4 * wave + k) * lda + cpre + lane];
+    }
+    if (wave == 0) {            // the triangular solve of the block: lane = row, wave-synchronous
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        if (q >= nq) break;
+        cplx y = sy[lane * NQ + q];
+#pragma unroll NA <= 2 ? 8 : 2
+        for (int c = NB - 1; c >= 0; --c) {
+          if (lane == c) y = cmul(y, crecip(sU[c * (NB + 1) + c]));
+          const double xr = lane_bcast(y.x, c), xi = lane_bcast(y.y, c);
+          if (lane < c) y = cfnma(sU[lane * (NB + 1) + c], make_double2(xr, xi), y);
+        }
+        Ys[(size_t)(q0 + q) * n_pad + rb + lane] = y;
+      }
+    }
+    cur ^= 1;
+    cplx* sN = sw + cur * SWEEP_SU;
+    cplx* Sn = sN + wave * (NB + 1) + lane;
+    Sn[0] = t0; Sn[16 * (NB + 1)] = t1; Sn[32 * (NB + 1)] = t2; Sn[48 * (NB + 1)] = t3;
+    __syncthreads();            // x of this block is stored, sy is free again, the next diagonal block is in LDS
+    if (NA <= 2) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { const cplx d = sN[(4 * wave + k) * (NB + 2)]; d2[k] = d.x * d.x + d.y * d.y; }
+    }
+  }
+  if (!do_checks) return;
+  if (code != 0) atomicMin(s_code, code);
+  double m = sqrt(um2);
+  for (int o = 32; o > 0; o >>= 1) m = nan_max(m, __shfl_down(m, o, 64));
+  if (lane == 0) sm_max2[wave] = m;
+  __syncthreads();
+  if (tid == 0) {
+    m = sm_max2[0];
+    for (int w = 1; w < 16; ++w) m = nan_max(m, sm_max2[w]);
+    unsigned long long* dst = growth + 2 * (size_t)s + 1;
+    if (!(m <= __longlong_as_double((long long)*(volatile unsigned long long*)dst))) atomicMax(dst, (unsigned long long)__double_as_longlong(m));
+    if (*s_code != 0 && info[s] == 0) info[s] = *s_code;
+  }
+}
+
+// Zeroes `width` complex columns from A on, in `rows` rows of lda complex (the right-hand-side columns of every row of every system of
+// a chunk, whose systems lie one behind the other): one 16-byte store per thread, consecutive threads on consecutive entries of a row segment
+__global__ void __launch_bounds__(256) k_clear_cols(cplx* __restrict__ A, long long lda, int width, long long rows) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long r = t / width;
+  if (r >= rows) return;
+  A[r * lda + (t - r * width)] = make_double2(0.0, 0.0);
+}
+void launch_clear_cols(hipStream_t st, double* d_A, long long lda, int width, long long rows) {
+  if (width <= 0 || rows <= 0) return;
+  const long long n = rows * width;
+  hipLaunchKernelGGL(k_clear_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (cplx*)d_A, lda, width, rows);
 }
 
 // right-hand-side columns of the augmented matrix <-> compact Y[s][q][row]
@@ -702,10 +889,12 @@ __global__ void __launch_bounds__(256, 2) k_sym_slab(const cplx* __restrict__ A,
 // The five switches (tests, A/B), read per call.  Of a value only its first letter counts; -1: not set.  A letter no rule names leaves
 // the rule in place for BIEM_SYM_UPDATE, BIEM_SYM_GROUP and BIEM_DIAG_FORM; for BIEM_BACK_FORM it selects the row form (any value
 // that starts with neither c nor s does); BIEM_NO_SMALL_PATH counts as soon as it is set, whatever its value.
-struct SymEnv { int update, group, back, diag; bool no_small; };
+// A sixth, BIEM_BACK_ROW=blocks, picks no form: inside the row form it runs the per-block launches (k_back_row) instead of the sweep.
+struct SymEnv { int update, group, back, diag; bool no_small; int back_row; };
 static SymEnv sym_env() {
   auto first = [](const char* name) { const char* e = getenv(name); return e ? (int)(unsigned char)e[0] : -1; };
-  return {first("BIEM_SYM_UPDATE"), first("BIEM_SYM_GROUP"), first("BIEM_BACK_FORM"), first("BIEM_DIAG_FORM"), getenv("BIEM_NO_SMALL_PATH") != nullptr};
+  return {first("BIEM_SYM_UPDATE"), first("BIEM_SYM_GROUP"), first("BIEM_BACK_FORM"), first("BIEM_DIAG_FORM"), getenv("BIEM_NO_SMALL_PATH") != nullptr,
+          first("BIEM_BACK_ROW")};
 }
 
 // the whole system fits LDS: one launch does everything (k_small_utu)
@@ -942,19 +1131,32 @@ static int sym_back(const SymForm& f, const SymCall& c) {
     BIEM_LAUNCHCHK();
     return BIEM_OK;
   }
-  // the row form (k_back_row) on the compact copy; nrhs == 0: one pass for the checks alone; right-hand sides in groups of up to 8
+  // the row form on the compact copy; nrhs == 0: one pass for the checks alone; right-hand sides in groups of up to 8.  One launch per
+  // group (k_back_sweep); BIEM_BACK_ROW=blocks: one launch per group and 64-row block (k_back_row), the same arithmetic
   cplx* const Y = c.al.Y;
   if (nrhs > 0 && !f.rhs_gemv) hipLaunchKernelGGL(k_rhs_compact, compact_grid, dim3(256), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, 0);
+  const bool blocks = sym_env().back_row == 'b';
   int q0 = 0;
   do {
     const int nq = nrhs - q0 > 8 ? 8 : nrhs - q0;
     const int chk = q0 == 0 ? 1 : 0;
-    for (int ib = n_pad / NB - 1; ib >= 0; --ib) {
-      if (nq <= 1) hipLaunchKernelGGL(k_back_row<1>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
-      else if (nq == 2) hipLaunchKernelGGL(k_back_row<2>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
-      else if (nq <= 4) hipLaunchKernelGGL(k_back_row<4>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
-      else hipLaunchKernelGGL(k_back_row<8>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
-    }
+    const int NQ = nq <= 1 ? 1 : nq == 2 ? 2 : nq <= 4 ? 4 : 8;
+    if (!blocks) {
+#define BIEM_SWEEP(Q)                                                                                                                       \
+      {                                                                                                                                      \
+        BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_back_sweep<Q>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sweep_lds(Q)));        \
+        hipLaunchKernelGGL(k_back_sweep<Q>, dim3(nb), dim3(1024), sweep_lds(Q), st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, chk, c.d_info, \
+                           c.growth, inv_rel2);                                                                                               \
+      }
+      if (NQ == 1) BIEM_SWEEP(1) else if (NQ == 2) BIEM_SWEEP(2) else if (NQ == 4) BIEM_SWEEP(4) else BIEM_SWEEP(8)
+#undef BIEM_SWEEP
+    } else
+      for (int ib = n_pad / NB - 1; ib >= 0; --ib) {
+        if (NQ == 1) hipLaunchKernelGGL(k_back_row<1>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
+        else if (NQ == 2) hipLaunchKernelGGL(k_back_row<2>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
+        else if (NQ == 4) hipLaunchKernelGGL(k_back_row<4>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
+        else hipLaunchKernelGGL(k_back_row<8>, dim3(nb), dim3(1024), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, q0, nq, ib, chk, c.d_info, c.growth, inv_rel2);
+      }
     q0 += nq;
   } while (q0 < nrhs);
   if (nrhs > 0) hipLaunchKernelGGL(k_rhs_compact, compact_grid, dim3(256), 0, st, A, lda, sys_stride, Y, nrhs, n_pad, 1);
