@@ -24,8 +24,8 @@ import torch
 
 from . import _lib as L
 from ._arrays import Array, _ptr, _stream_ptr
-from ._fields import (USCAT_GRAD_N_END_MAX, biem_far_pattern, biem_u, biem_u_grad, biem_u_interior, biem_u_interior_grad, biem_u_total,
-                      biem_u_total_grad)
+from ._fields import (USCAT_GRAD_N_END_MAX, biem_far_pattern, biem_u, biem_u_grad, biem_u_hess, biem_u_interior, biem_u_interior_grad,
+                      biem_u_total, biem_u_total_grad)
 from ._incident import fluid_inclusion_bc, max_memory, max_n_end, plane_wave, point_source
 from ._observables import BIEMPower, biem_force, biem_power
 from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_incident, _entry, _nrhs, _operator, _rhs_project,
@@ -44,8 +44,8 @@ warnings.filterwarnings("error", category=ComplexWarning)
 # _validate_biem_inputs, _warn_biem_inputs, USCAT_GRAD_N_END_MAX, L (imported above) and _last_solve_stats.
 __all__ = [
     "BIEMFactorization", "BIEMKwargs", "BIEMPower", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
-    "biem_factorize", "biem_far_pattern", "biem_force", "biem_power", "biem_u", "biem_u_grad", "biem_u_interior", "biem_u_interior_grad",
-    "biem_u_total", "biem_u_total_grad", "fluid_inclusion_bc", "max_memory", "max_n_end", "plane_wave", "point_source",
+    "biem_factorize", "biem_far_pattern", "biem_force", "biem_power", "biem_u", "biem_u_grad", "biem_u_hess", "biem_u_interior",
+    "biem_u_interior_grad", "biem_u_total", "biem_u_total_grad", "fluid_inclusion_bc", "max_memory", "max_n_end", "plane_wave", "point_source",
 ]
 
 _last_solve_stats: dict = {}   # how the last biem() call solved its systems (tests / bench)
@@ -83,6 +83,8 @@ class BIEMResultCalculatorProtocol(Protocol):
     def uscat(self, x: Array, /, far_field: bool = False, per_ball: bool = False, expand_x: bool = True) -> Array: ...
 
     def uscat_grad(self, x: Array, /, per_ball: bool = False, expand_x: bool = True) -> Array: ...
+
+    def uscat_hess(self, x: Array, /, per_ball: bool = False, expand_x: bool = True) -> Array: ...
 
 
 # --------------------------------------------------------------------------------------
@@ -129,6 +131,10 @@ class BIEMResultCalculator:
     def uscat_grad(self, x: Array, /, per_ball: bool = False, expand_x: bool = True) -> Array:
         """Cartesian gradient of the scattered field, component axis first (see :func:`biem_u_grad`)."""
         return biem_u_grad(self, x, per_ball=per_ball, expand_x=expand_x)
+
+    def uscat_hess(self, x: Array, /, per_ball: bool = False, expand_x: bool = True) -> Array:
+        """Cartesian Hessian of the scattered field, both component axes first (see :func:`biem_u_hess`)."""
+        return biem_u_hess(self, x, per_ball=per_ball, expand_x=expand_x)
 
     def uinterior(self, x: Array, /, *, k_interior: Array, density_ratio: Array, expand_x: bool = True) -> Array:
         """Total field inside penetrable fluid balls, NaN outside them (see :func:`biem_u_interior`)."""

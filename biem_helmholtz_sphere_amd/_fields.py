@@ -46,6 +46,81 @@ def biem_u_grad(res: Any, x: Array, /, per_ball: bool = False, expand_x: bool = 
     return _field(res, x, far_field=False, per_ball=per_ball, expand_x=expand_x, grad=True)
 
 
+# order of the radial tables the plan build and the field kernels share (csrc/common.hpp: kMaxRad)
+RADIAL_TABLE_ORDER = 320
+_HESS_LAYOUTS: dict = {}
+
+
+def _hess_layout(tree: str, n_end: int, dev: torch.device) -> Tuple[_Plan, torch.Tensor]:
+    """The plan of order n_end + 2 and, per harmonic of the order-n_end plan, its place in that plan's layout (matched by label: the
+    shorter list is no prefix of the longer one - tree a lists m = 0 .. n_end - 1 and then the negative m).  Cached like the plans."""
+    big = _plan(tree, n_end + 2, dev)
+    key = (tree, int(n_end), big.dev.index, big.chain)
+    hit = _HESS_LAYOUTS.get(key)
+    if hit is None:
+        small = _plan(tree, n_end, dev)
+        where = {tuple(lab) + (int(n),): i for i, (lab, n) in enumerate(zip(big.labels.tolist(), big.degrees.tolist()))}
+        idx = [where[tuple(lab) + (int(n),)] for lab, n in zip(small.labels.tolist(), small.degrees.tolist())]
+        if len(set(idx)) != small.H:
+            raise RuntimeError(f"the labels of tree {tree!r} at n_end={n_end} do not embed one to one into those at n_end={n_end + 2}")
+        hit = _HESS_LAYOUTS[key] = (big, torch.as_tensor(idx, dtype=torch.long, device=big.dev))
+    return hit
+
+
+def biem_u_hess(res: Any, x: Array, /, per_ball: bool = False, expand_x: bool = True) -> Array:
+    r"""Cartesian Hessian of the scattered field at x (as :func:`biem_u` takes it), both component axes first.
+
+    Shape ``(c_ndim, c_ndim, ...(x), ...(first))``, with a trailing ``B`` for ``per_ball=True``, complex128, in the namespace of
+    :func:`biem_u_grad`.  Both component axes are in the caller's axis order for every tree; the result is exactly symmetric (the
+    lower triangle is a copy of the upper) and NaN in all components exactly where :func:`biem_u` is NaN.  Both kinds.
+
+    Nothing is differenced: a derivative of a multipole expansion is a multipole expansion about the same centre, one degree longer,
+    :math:`(D_i c)_{h'} = k\,\mathrm{sgn}(n_h - n_{h'}) \sum_h T^i_{h'h} c_h` with the coupling table of :func:`biem_force`, so the
+    Hessian is the value kernels of :func:`biem_u` applied to :math:`D_j D_i c` at order ``n_end + 2``.  Every tree
+    and order :func:`biem_u` covers at ``n_end + 2`` is covered - the chain trees d >= 5 and orders above the ceilings of
+    :func:`biem_u_grad` included; ``NotImplementedError`` beyond that.  The first call of a (tree, n_end, device) builds the plan of
+    order ``n_end + 2``.
+    """
+    if res.density is None:
+        raise ValueError("The BIEMResult does not have density.")
+    if res.kind not in ("outer", "inner"):
+        raise ValueError(f"Invalid kind: {res.kind}")
+    c = res.c
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    d = c.c_ndim
+    n_end = n_end_from_harm(tree, int(res.density.shape[-1]))
+    if d >= 3 and 2 * (n_end + 2) > RADIAL_TABLE_ORDER:
+        raise NotImplementedError(
+            f"uscat_hess evaluates the field at order n_end + 2 = {n_end + 2}; for tree {c.branching_types_expression_str!r} the plan of "
+            f"that order needs radial tables of order {2 * (n_end + 2)}, above the built {RADIAL_TABLE_ORDER}")
+    lib = L.load()                                         # (a library that is missing is reported before a device that is)
+    f = _field_operands(res, x, tree, perm, expand_x)
+    plan, idx = _hess_layout(tree, n_end, f.dev)
+    fl, dev = f.fl, f.dev
+    nb, B, P = fl.nb, fl.B, int(f.pts.shape[1])
+    dens = torch.zeros((nb, B, plan.H), dtype=torch.complex128, device=dev)
+    dens[:, :, idx] = f.density
+    flags = f.flags | (L.USCAT_PER_BALL if per_ball else 0) | (L.USCAT_KIND_INNER if res.kind == "inner" else 0)
+    balls = (B,) if per_ball else ()
+    pairs = [(i, j) for i in range(d) for j in range(i, d)]
+    upper = torch.empty((len(pairs), P, nb) + balls, dtype=torch.complex128, device=dev)
+    with torch.cuda.device(dev):
+        wb = int(lib.biem_uscat_hess_workspace_bytes(plan.handle, nb, B))
+        work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+        if P > 0 and nb > 0:
+            rc = lib.biem_uscat_hess(plan.handle, nb, B, P, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
+                                     _ptr(dens), _ptr(f.pts), flags, _ptr(upper), _ptr(work), wb, _stream_ptr(dev))
+            _check_built(lib, rc, "biem_uscat_hess")
+    inv = _inverse_perm(perm)                              # canonical component of each of the caller's axes
+    at = {p: q for q, p in enumerate(pairs)}
+    out = torch.empty((d, d, P, nb) + balls, dtype=torch.complex128, device=dev)
+    for i in range(d):
+        for j in range(d):
+            a, b = inv[i], inv[j]
+            out[i, j] = upper[at[(min(a, b), max(a, b))]]
+    return f.origin.give(out.reshape((d, d) + f.xshape + f.batch + balls))
+
+
 def _check_built(lib, rc: int, entry: str) -> None:
     """L.check, with BIEM_ERR_UNSUPPORTED (a limit only the library knows: the LDS of the per-lane rows in 2-D) as NotImplementedError."""
     if rc == L.BIEM_ERR_UNSUPPORTED:

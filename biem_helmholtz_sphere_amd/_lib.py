@@ -58,6 +58,8 @@ SIGNATURES = {
     "biem_uscat_workspace_bytes": (_sz, [_vp, _i, _i]),
     "biem_uscat": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _vp, _sz, _vp]),
     "biem_uscat_grad": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _vp, _sz, _vp]),
+    "biem_uscat_hess_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "biem_uscat_hess": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _vp, _sz, _vp]),
     "biem_interior_coef": (_i, [_vp, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _vp]),
     "biem_uinterior_workspace_bytes": (_sz, [_vp, _i, _i]),
     "biem_uinterior": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _i, _dp, _vp, _sz, _vp]),

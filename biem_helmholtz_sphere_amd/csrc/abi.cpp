@@ -348,6 +348,26 @@ int biem_uscat_grad(const biem_plan* plan, int nb, int B, int P, const double* d
                            work_bytes, (hipStream_t)stream);
 }
 
+// ---- Hessian of the scattered field (kernels_ladder.hip) ----
+size_t biem_uscat_hess_workspace_bytes(const biem_plan* plan, int nb, int B) { return plan ? uscat_hess_workspace_bytes(plan, nb, B) : 0; }
+
+int biem_uscat_hess(biem_plan* plan, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                    const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags, double* d_out,
+                    void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_eta, "d_eta"); NEED(d_centers, "d_centers"); NEED(d_radii, "d_radii");
+  NEED(d_density, "d_density"); NEED(d_points, "d_points"); NEED(d_out, "d_out"); NEED(d_work, "d_work");
+  int rc = BIEM_OK;
+  try {
+    rc = plan_build_force(plan);             // (the first call of this plan: builds and uploads the coupling table)
+  } catch (const std::bad_alloc&) {
+    set_error("%s: out of host memory building the force coupling table for n_end=%d", __func__, plan->n_end);
+    rc = BIEM_ERR_ALLOC;
+  }
+  if (rc != BIEM_OK) return rc;
+  return launch_uscat_hess(plan, nb, B, P, d_k, d_eta, d_centers, d_radii, geom_batched, d_density, d_points, flags, d_out, d_work,
+                           work_bytes, (hipStream_t)stream);
+}
+
 // ---- total field inside penetrable fluid balls (kernels_uinterior.hip) ----
 int biem_interior_coef(const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
                        int geom_batched, const double* d_kint, const double* d_delta, int fluid_batched, const double* d_density,

@@ -162,6 +162,19 @@ int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, co
 int launch_uscat_grad(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
                       const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
                       double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
+// the host steps of launch_uscat (kernels_uscat.hip): what biem_uscat refuses at this plan (BIEM_ERR_UNSUPPORTED, nothing launched),
+// c[nb][B][H] = density * blc, and the field of a coefficient set c at the points (out and flags as launch_uscat)
+int uscat_covered(const biem_plan* p, int nb, int B, int flags);
+int uscat_form_coef(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii, int geom_batched,
+                    const double* d_density, int flags, cplx* c, hipStream_t st);
+int uscat_eval_coef(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_centers, const double* d_radii,
+                    int geom_batched, const cplx* c, const double* d_points, int flags, double* d_out, hipStream_t st);
+// Hessian of the near field (kernels_ladder.hip): p is the plan of order n_end + 2 with its force coupling table uploaded, the density
+// in that plan's layout (degrees < n_end(p) - 2 are read); out[d (d + 1) / 2][P][nb] ([..][B] per ball), the pairs i <= j row-major
+size_t uscat_hess_workspace_bytes(const biem_plan* p, int nb, int B);
+int launch_uscat_hess(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                      const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
+                      double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
 // per-lane order ceiling of a tree (kernels_uscat.hip: kFastNendMax*; 0 for the chain trees)
 int uscat_fast_nend_max(int tree);
 // total field inside penetrable fluid balls (kernels_uinterior.hip).  d_kint / d_delta [nb or 1][B] complex; the coefficient step

@@ -445,19 +445,26 @@ __global__ void __launch_bounds__(256) k_uscat_chain(int d, int H, int n_end, co
   }
 }
 
-int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
-                 const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
-                 double* d_out, void* d_work, size_t work_bytes, hipStream_t st) {
-  if (nb <= 0 || B <= 0 || P <= 0) return BIEM_OK;
+// The field of a plan in three host steps, so that biem_uscat_hess (kernels_ladder.hip) can put its coefficient ladder between the
+// second and the third: what the kernels do not cover at this plan (uscat_covered), c = density * blc (uscat_form_coef), the field of
+// a coefficient set (uscat_eval_coef: the per-lane / generic / chain choice and the BIEM_USCAT_GENERIC switch).
+int uscat_covered(const biem_plan* p, int nb, int B, int flags) {
   // orders beyond the LDS tables: 2-D only, through the per-lane kernel (its only table is the ball's 2 n_end - 1 coefficients)
   const bool big = p->n_end > kMaxRadU;
   if (big && (p->tree != TREE_A || (size_t)(2 * p->n_end - 1) * sizeof(cplx) > 150 * 1024 ||
               ((flags & BIEM_USCAT_KIND_INNER) && !(flags & BIEM_USCAT_FAR_FIELD)) || nb > 65535)) {
     set_error("biem_uscat: n_end=%d too large for this tree / kind", p->n_end); return BIEM_ERR_UNSUPPORTED;
   }
-  size_t need = (size_t)nb * B * p->H * sizeof(cplx);
-  if (work_bytes < need) { set_error("biem_uscat: workspace too small"); return BIEM_ERR_ARG; }
-  cplx* c = (cplx*)d_work;
+  if (p->tree == TREE_CHAIN && (p->n_end + 1 + kRadShiftMax > kChainRadU || (p->d - 2) * p->n_end * p->n_end > kChainTabU || nb > 65535 ||
+                                (size_t)B * sizeof(cplx) > 64 * 1024)) {
+    set_error("biem_uscat: chain tree d=%d n_end=%d (%d balls) exceeds the field kernel's tables", p->d, p->n_end, B); return BIEM_ERR_UNSUPPORTED;
+  }
+  return BIEM_OK;
+}
+
+int uscat_form_coef(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii, int geom_batched,
+                    const double* d_density, int flags, cplx* c, hipStream_t st) {
+  const bool big = p->n_end > kMaxRadU;
   cplx* scratch = nullptr;
   if (big) BIEM_HIPCHK(hipMallocAsync((void**)&scratch, (size_t)nb * B * 3 * (p->n_end + 3) * sizeof(cplx), st));
   hipLaunchKernelGGL(k_uscat_coef, dim3(B, nb), dim3(64), 0, st, p->d, p->H, p->n_end, p->d_deg, B,
@@ -465,11 +472,26 @@ int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, co
                      geom_batched, (const cplx*)d_density, c, scratch);
   BIEM_LAUNCHCHK();
   if (scratch) BIEM_HIPCHK(hipFreeAsync(scratch, st));
+  return BIEM_OK;
+}
+
+int launch_uscat(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
+                 const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
+                 double* d_out, void* d_work, size_t work_bytes, hipStream_t st) {
+  if (nb <= 0 || B <= 0 || P <= 0) return BIEM_OK;
+  int rc = uscat_covered(p, nb, B, flags);
+  if (rc != BIEM_OK) return rc;
+  size_t need = (size_t)nb * B * p->H * sizeof(cplx);
+  if (work_bytes < need) { set_error("biem_uscat: workspace too small"); return BIEM_ERR_ARG; }
+  cplx* c = (cplx*)d_work;
+  if ((rc = uscat_form_coef(p, nb, B, d_k, d_eta, d_radii, geom_batched, d_density, flags, c, st)) != BIEM_OK) return rc;
+  return uscat_eval_coef(p, nb, B, P, d_k, d_centers, d_radii, geom_batched, c, d_points, flags, d_out, st);
+}
+
+int uscat_eval_coef(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_centers, const double* d_radii,
+                    int geom_batched, const cplx* c, const double* d_points, int flags, double* d_out, hipStream_t st) {
+  const bool big = p->n_end > kMaxRadU;
   if (p->tree == TREE_CHAIN) {
-    if (p->n_end + 1 + kRadShiftMax > kChainRadU || (p->d - 2) * p->n_end * p->n_end > kChainTabU || nb > 65535 ||
-        (size_t)B * sizeof(cplx) > 64 * 1024) {
-      set_error("biem_uscat: chain tree d=%d n_end=%d (%d balls) exceeds the field kernel's tables", p->d, p->n_end, B); return BIEM_ERR_UNSUPPORTED;
-    }
     hipLaunchKernelGGL(k_uscat_chain, dim3(P, nb), dim3(256), (size_t)B * sizeof(cplx), st, p->d, p->H, p->n_end, p->d_labels,
                        p->d_deg, nb, B, P, (const cplx*)d_k, d_centers, d_radii, geom_batched, (const cplx*)c, d_points, flags, (cplx*)d_out);
     BIEM_LAUNCHCHK();

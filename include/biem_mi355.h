@@ -260,6 +260,21 @@ int biem_uscat_grad(const biem_plan* plan, int nb, int B, int P, const double* d
                     const double* d_centers, const double* d_radii, int geom_batched, const double* d_density,
                     const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes, void* stream);
 
+/* Hessian of the near field at the same points by a coefficient ladder: out[d (d + 1) / 2][P][nb] or [..][P][nb][B]
+ * (per ball), complex128, the component pairs i <= j in row-major order along the axes of the plan's tree (the Hessian is symmetric:
+ * the caller copies the lower triangle); NaN in every pair where biem_uscat gives NaN.  Arguments and flags as biem_uscat, with
+ * one difference: `plan` is the plan of order n_end + 2, where n_end is the order of the density, and d_density[nb][B][H] is in THAT
+ * plan's harmonic layout.  Only its degrees < n_end(plan) - 2 are read; the two top degrees are left free for the result (a
+ * derivative of a multipole expansion is one degree longer) and may hold anything.  The plan is not const: the first call builds and
+ * uploads its force coupling table (as biem_force does); no other table is added.
+ * Workspace: biem_uscat_hess_workspace_bytes (d + 2 coefficient sets).  BIEM_USCAT_FAR_FIELD is BIEM_ERR_ARG (a pattern has no
+ * Hessian in space), a plan of n_end < 3 too.  Covered: every tree and order biem_uscat covers at that plan - the chain trees and
+ * orders above the per-lane ceilings included; what biem_uscat refuses there is BIEM_ERR_UNSUPPORTED with the order in the message. */
+size_t biem_uscat_hess_workspace_bytes(const biem_plan* plan, int nb, int B);
+int biem_uscat_hess(biem_plan* plan, int nb, int B, int P, const double* d_k /*c128*/, const double* d_eta,
+                    const double* d_centers, const double* d_radii, int geom_batched, const double* d_density,
+                    const double* d_points, int flags, double* d_out, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- total field inside penetrable fluid balls ----
  * Ball b holds a fluid of wavenumber d_kint[b] and density d_delta[b] times the exterior's (what fluid_inclusion_bc takes; both
  * complex128, [nb][B] when fluid_batched != 0, else [B] shared by all systems).  With s = density blc_n the interior field is
