@@ -55,6 +55,10 @@ __device__ inline double wave_sum(double v) {
 #define BIEM_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { biem::set_error("%s failed: %s", #x, hipGetErrorString(e_)); return BIEM_ERR_HIP; } } while (0)
 #define BIEM_LAUNCHCHK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { biem::set_error("kernel launch failed at %s:%d: %s", __FILE__, __LINE__, hipGetErrorString(e_)); return BIEM_ERR_HIP; } } while (0)
 
+// (a body shared by several entry points reports under the name of the one that was called: `who`)
+#define NEED_AS(who, p, what) do { if (!(p)) { biem::set_error("%s: null %s", who, what); return BIEM_ERR_ARG; } } while (0)
+#define NEED_DEV_AS(who, pl) do { NEED_AS(who, pl, "plan"); if ((pl)->device < 0) { biem::set_error("%s: plan not uploaded to a device (biem_plan_upload)", who); return BIEM_ERR_ARG; } } while (0)
+
 const char* last_error();
 
 // ---- optional HIP-event profiler (thread-local; off unless biem_profile_begin was called on this thread) ----
@@ -211,8 +215,9 @@ void launch_clear_cols(hipStream_t st, double* d_A, long long lda, int width, lo
 unsigned long long* lu_growth_slots(void* d_work, int nb, int n_pad);
 // preset the slots for a caller that knows (a lower bound of) max |A|: growth[s] = (amax, 0); then pass amax_ready = true
 int lu_growth_init(void* d_work, int nb, int n_pad, double amax, hipStream_t st);
-// right-hand-side columns (slot order): f~ = R W^H f in place; inverse_on_solution: x = W R^-1 x~
-int launch_sym_rhs(const biem_plan* p, int nb, int B, int nrhs, int n_pad, const double* d_tab, double* d_A, long long lda,
+// right-hand-side columns (slot order): f~ = R W^H f in place; inverse_on_solution: x = W R^-1 x~.  d_rhs: the first right-hand-side entry
+// of the first system (column n_pad of an augmented matrix, or an array of its own), rows lda complex apart
+int launch_sym_rhs(const biem_plan* p, int nb, int B, int nrhs, int n_pad, const double* d_tab, double* d_rhs, long long lda,
                    long long sys_stride, bool inverse_on_solution, hipStream_t st, const SplitMap& split = SplitMap());
 // solve with a stored U^T U factor (upper triangle, identity-padded): forward U^T y = f, back U x = y, B row-major [n_pad][ldb] per system
 int launch_sym_solve(int nb, int n_pad, int nrhs, const double* d_U, long long lda, long long sys_stride, double* d_B, long long ldb,
@@ -220,5 +225,46 @@ int launch_sym_solve(int nb, int n_pad, int nrhs, const double* d_U, long long l
 int launch_lu_solve(int nb, int n_pad, int nrhs, const double* d_LU, long long lda, long long sys_stride, const int* d_ipiv, double* d_B,
                     long long ldb, long long b_stride, hipStream_t st);
 int bench_mfma_f64(int iters, double* tflops, hipStream_t st, int variant = 0);
+
+// ---- the whole-path driver (solve_path.cpp) as the entry points of abi.cpp see it, and what both files check with ----
+// boundary coefficients: alpha / beta [nb or 1][B] complex, or per degree (the *_n entries) [nb or 1][B][n_end]; batched: one set per system
+struct BoundaryCoef {
+  const double* alpha; const double* beta; int batched; bool per_degree;
+  const char* alpha_name() const { return per_degree ? "d_alpha_n" : "d_alpha"; }
+  const char* beta_name() const { return per_degree ? "d_beta_n" : "d_beta"; }
+};
+// boundary samples [nb][nrhs][B][Q] complex: g of plain coefficients; per degree the unmixed gu / gdn (either may be null: zero)
+struct Samples { const double* g; const double* gu; const double* gdn; };
+
+inline long long rhs_ld(long long nrhs) { return (nrhs + 7) / 8 * 8; }   // right-hand-side columns; rows stay 128-byte aligned (8 complex128)
+
+inline int check_counts(const char* who, int nb, int nrhs, int B) {
+  if (nb >= 0 && nb <= 65535 && nrhs >= 0 && nrhs <= 65535 && B >= 0) return BIEM_OK;
+  set_error("%s: 0 .. 65535 systems / right-hand sides per call and B >= 0 (got nb=%d, nrhs=%d, B=%d)", who, nb, nrhs, B);
+  return BIEM_ERR_ARG;
+}
+
+// the one place that picks the per-degree launcher: ball tables, and the projection f of the samples (strides as launch_rhs_project)
+int ball_tables(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii, int geom_batched,
+                const BoundaryCoef& bc, double* d_tab, hipStream_t st);
+int rhs_project(const biem_plan* p, int nb, int B, int nrhs, const BoundaryCoef& bc, const Samples& smp, double* d_f, long long sys_stride,
+                long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap());
+
+size_t solve_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int chunk);
+size_t factor_workspace_bytes(const biem_plan* p, int nb, int B, int chunk);
+size_t solve_factored_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs);
+void last_solve_split(int* npE, int* npO);
+
+// tables -> fill -> right-hand side -> factor and solve -> density; symmetric: U^T U (LDL^T entries), else the pivoted LU
+int solve_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+               const double* d_radii, int geom_batched, const BoundaryCoef& bc, const Samples& smp, double* d_density, int* d_info, int chunk,
+               void* d_work, size_t work_bytes, hipStream_t st, bool symmetric);
+// the same path cut at the factorisation: factors and tables stay with the caller, right-hand sides come later
+int factor_path(const char* who, const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_centers,
+                const double* d_radii, int geom_batched, const BoundaryCoef& bc, double* d_F, long long lda, long long sys_stride,
+                double* d_tab, int* d_info, int chunk, void* d_work, size_t work_bytes, hipStream_t st);
+int solve_factored_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                        const double* d_tab, const BoundaryCoef& bc, const Samples& smp, double* d_density, void* d_work, size_t work_bytes,
+                        hipStream_t st);
 
 }  // namespace biem

@@ -150,14 +150,17 @@ __global__ void __launch_bounds__(256) k_sym_rhs(int H, int U, int n_end, int B,
   }
 }
 
-int launch_sym_rhs(const biem_plan* p, int nb, int B, int nrhs, int n_pad, const double* d_tab, double* d_A, long long lda,
+int launch_sym_rhs(const biem_plan* p, int nb, int B, int nrhs, int n_pad, const double* d_tab, double* d_rhs, long long lda,
                    long long sys_stride, bool inverse_on_solution, hipStream_t st, const SplitMap& split) {
   const int U = (int)(p->units.size() / 2);
   if (nb <= 0 || B <= 0 || nrhs <= 0) return BIEM_OK;
   if (nb > 65535) { set_error("biem symmetric path: at most 65535 systems per call"); return BIEM_ERR_ARG; }
   ProfScope ps(PK_SWAP, st, 0.0);   // class 4: row interchanges in the LU, these transforms in the symmetric path
+  // the kernel addresses the right-hand sides as column n_pad of its pointer argument: it gets the device address n_pad entries in front
+  // of them (formed as a number: where the columns are an array of their own there is no such object, and none is touched)
+  cplx* base = reinterpret_cast<cplx*>(reinterpret_cast<uintptr_t>(d_rhs) - (uintptr_t)n_pad * sizeof(cplx));
   hipLaunchKernelGGL(k_sym_rhs, dim3((B * U * nrhs + 255) / 256, nb), dim3(256), 0, st, p->H, U, p->n_end, B, nrhs, n_pad, p->d_units,
-                     p->d_spos, p->d_deg, (const cplx*)d_tab, (cplx*)d_A, lda, sys_stride, inverse_on_solution ? 1 : 0, split);
+                     p->d_spos, p->d_deg, (const cplx*)d_tab, base, lda, sys_stride, inverse_on_solution ? 1 : 0, split);
   BIEM_LAUNCHCHK();
   return BIEM_OK;
 }
