@@ -28,8 +28,9 @@ from ._fields import (USCAT_GRAD_N_END_MAX, biem_far_pattern, biem_u, biem_u_gra
                       biem_u_total, biem_u_total_grad)
 from ._incident import fluid_inclusion_bc, max_memory, max_n_end, plane_wave, point_source
 from ._observables import BIEMPower, biem_force, biem_power
-from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_incident, _entry, _nrhs, _operator, _rhs_project,
-                        _sample_ptrs, _validate_biem_inputs, _warn_biem_inputs)
+from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_incident, _check_plane_wave_direction, _entry,
+                        _factored_source_args, _nrhs, _operator, _pick_systems, _plane_wave_source, _rhs_project, _sample_ptrs,
+                        _source_entry, _source_workspace_bytes, _validate_biem_inputs, _warn_biem_inputs)
 from ._plans import _chain_plan_dim, _plan
 
 try:  # numpy >= 1.25
@@ -208,6 +209,17 @@ def _result(op: _Operator, uin, density_t: Optional[torch.Tensor], axes: Optiona
 # --------------------------------------------------------------------------------------
 # the solver (reference :453-819)
 # --------------------------------------------------------------------------------------
+def _incident_source(op: _Operator, uin, uin_grad, directions, given=None):
+    """The source of the right-hand sides, the _RhsAxes of its layout and the callable the result keeps as `.uin`: the samples of
+    (uin, uin_grad), or - `directions`: the checked plane_wave_direction, `given`: as the caller passed it - plane waves in closed form,
+    whose `.uin` is plane_wave's for the caller's k and direction (a floating tensor as it is, anything else as float64)."""
+    if directions is None:
+        _check_incident(op, uin, uin_grad)
+        return _boundary_samples(op, uin, uin_grad) + (uin,)
+    as_given = isinstance(given, torch.Tensor) and given.is_floating_point()
+    return _plane_wave_source(op, directions) + (plane_wave(k=op.k_given, direction=given if as_given else directions)[0],)
+
+
 def _solver() -> str:
     solver = os.environ.get("BIEM_SOLVER", "ldlt")
     if solver not in ("ldlt", "lu"):
@@ -221,12 +233,12 @@ def _available_bytes(dev: torch.device) -> int:
     return free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
 
 
-def _single_ball_density(op: _Operator, g: torch.Tensor, tab: torch.Tensor, density_t: torch.Tensor, sp: int) -> None:
+def _single_ball_density(op: _Operator, g, tab: torch.Tensor, density_t: torch.Tensor, sp: int) -> None:
     """Single ball: density = f / (blc (alpha h + beta k h'))    (reference :648-691)."""
     lib, plan, nb, B = L.load(), op.plan, op.fl.nb, op.fl.B
     H, nrhs = plan.H, _nrhs(g)
     f = torch.empty((nb, nrhs, B * H), dtype=torch.complex128, device=op.dev)
-    _rhs_project(op, nb, g, 0, f, nrhs * B * H, 1, B * H, sp)
+    _rhs_project(op, nb, g, 0, f, nrhs * B * H, 1, B * H, sp, tab)
     L.check(lib.biem_density(plan.handle, nb, B, nrhs, _ptr(f), nrhs * B * H, 1, B * H, _ptr(tab), _ptr(density_t), sp), "biem_density")
 
 
@@ -290,7 +302,7 @@ def _resolve_with_lu(op: _Operator, e_lu, redo_h: torch.Tensor, g, density_t: to
     nr = int(redo.numel())
     pick = lambda t, batched: t[redo].contiguous() if batched else t
     k_r, eta_r = fl.k[redo].contiguous(), fl.eta[redo].contiguous()
-    g_r = g[redo].contiguous() if isinstance(g, torch.Tensor) else tuple(None if t is None else t[redo].contiguous() for t in g)
+    g_r = _pick_systems(g, redo)
     cen_r, rad_r = pick(fl.centers, fl.geom_batched), pick(fl.radii, fl.geom_batched)
     al_r, be_r = pick(fl.alpha, fl.ab_batched), pick(fl.beta, fl.ab_batched)
     dens_r = torch.empty((nr, nrhs, B, H), dtype=torch.complex128, device=dev)
@@ -305,7 +317,7 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
          uin: Callable[[Array], Array] | None = None, uin_grad: Callable[[Array], Array] | None = None, eta: Array | None = None,
          kind: Literal["inner", "outer"] = "outer", force_matrix: bool = False,
          translational_coefficients_method: Literal["gumerov", "plane_wave", "triplet"] | None = None, chunk: int = 0,
-         alpha_n: Array | None = None, beta_n: Array | None = None) -> BIEMResultCalculator:
+         alpha_n: Array | None = None, beta_n: Array | None = None, plane_wave_direction: Array | None = None) -> BIEMResultCalculator:
     r"""Boundary Integral Equation Method (BIEM) for the Helmholtz equation on MI355X.
 
     Same contract as the reference ``biem`` (``_biem.py:453-581``): solves, per leading batch element,
@@ -324,6 +336,12 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     symmetric inclusion the wave enters is such a condition: :func:`fluid_inclusion_bc`.  A ball that does not scatter some degree
     (gj_n = 0, e.g. a transparent sphere) has no symmetric form; its systems are solved by the pivoted LU.
 
+    ``plane_wave_direction`` (extension, shape ``(c_ndim, ...)`` like the direction of :func:`plane_wave`, normalised here; not together
+    with uin / uin_grad): the incident field is the plane wave ``e^{i k d.x}`` of the operator's own k, and its right-hand side is formed
+    in closed form, ``f = -C_d i^n gj_n conj(Y_h(d)) e^{i k d.c_b}`` - exact, where the projection of samples aliases (a plane wave has
+    content in every degree) - without sampling anything.  The result is that of ``biem(..., *plane_wave(k=k, direction=D))`` apart from
+    that: trailing axes of D on which the operator has size 1 are right-hand sides of one factorisation, ``.uin`` is plane_wave's callable.
+
     Solver: the reference passes every system to a general dense solve (``_biem.py:797``).  Here the system is first brought
     to its complex-symmetric form (real harmonics, symmetric scaling) and factored as U^T U (Cholesky-type, no conjugation)
     without interchanges - half the flops; a system in which a multiplier would exceed 100, or whose factor grew by more than
@@ -332,13 +350,14 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     """
     if translational_coefficients_method not in (None, "gumerov", "plane_wave", "triplet"):
         raise ValueError(f"Invalid translational_coefficients_method: {translational_coefficients_method}")
+    directions = None if plane_wave_direction is None else _check_plane_wave_direction(c, k, plane_wave_direction, uin, uin_grad)
     op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n, beta_n)
     lib = L.load()
     plan, fl, dev = op.plan, op.fl, op.dev
     B, nb, H = fl.B, fl.nb, plan.H
     sp = _stream_ptr(dev)
 
-    has_rhs = not (uin is None and uin_grad is None)
+    has_rhs = not (uin is None and uin_grad is None and directions is None)
     g = axes = None
     # A repeated call of the same shape takes its workspace FIRST, before the boundary samples: the block the previous call
     # returned to torch's caching allocator is then still whole.  Taken after them, one of their mid-size temporaries may have
@@ -346,8 +365,7 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     ws_key = (plan.tree, plan.chain, int(n_end), int(nb), int(B), int(chunk), os.environ.get("BIEM_MAX_RESIDENT_BYTES"))
     work_pre = _workspace(dev, ws_key) if has_rhs and nb > 0 and (B > 1 or force_matrix) else None
     if has_rhs:
-        _check_incident(op, uin, uin_grad)
-        g, axes = _boundary_samples(op, uin, uin_grad)
+        g, axes, uin = _incident_source(op, uin, uin_grad, directions, plane_wave_direction)
         nrhs = _nrhs(g)
 
     use_matrix = (not has_rhs) or B > 1 or force_matrix          # reference :643-645
@@ -361,7 +379,7 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
             _single_ball_density(op, g, _ball_tables(op, sp), density_t, sp)
         elif has_rhs:
             chunk = _choose_chunk(op, nrhs, int(chunk), work_pre)
-            wbytes = int(lib.biem_solve_workspace_bytes(plan.handle, nb, B, nrhs, chunk))
+            wbytes = int(lib.biem_solve_workspace_bytes(plan.handle, nb, B, nrhs, chunk)) + _source_workspace_bytes(op, g)
             if work_pre is not None and work_pre.numel() != wbytes:
                 work_pre = None                    # (another size after all: back to the allocator before the right one is taken)
             work = work_pre if work_pre is not None else _workspace(dev, ws_key, wbytes)
@@ -372,9 +390,10 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
             # (info < 0: close to a resonance of a sphere, or strongly coupled spheres) are solved again with the pivoted LU,
             # which is what the reference's linalg.solve does for every system (_biem.py:797).  BIEM_SOLVER=lu: LU only.
             solver = _solver()
-            # (degree-dependent coefficients: the *_n entries, alpha_n / beta_n for alpha / beta and the unmixed samples for g)
-            e_lu, what = _entry("biem_solve", op.per_degree, "biem_solve")
-            entry = _entry("biem_solve_ldlt", op.per_degree)[0] if solver == "ldlt" else e_lu
+            # (degree-dependent coefficients: the *_n entries, alpha_n / beta_n for alpha / beta and the unmixed samples for g; plane
+            # waves in closed form: the *_pw entries)
+            e_lu, what = _source_entry("biem_solve", op, g, "biem_solve")
+            entry = _source_entry("biem_solve_ldlt", op, g)[0] if solver == "ldlt" else e_lu
             L.check(entry(plan.handle, nb, B, nrhs, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
                           _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, *_sample_ptrs(g), _ptr(density_t), _ptr(info), chunk,
                           _ptr(work), wbytes, sp), what)
@@ -427,18 +446,20 @@ class BIEMFactorization:
         return (f"BIEMFactorization(c={self.c!r}, n_end={self.n_end}, kind={self.kind!r}, batch={self._op.batch}, "
                 f"n_symmetric={self.n_symmetric}, n_lu={self.n_lu}, nbytes={self.nbytes}{', closed' if self._closed else ''})")
 
-    def solve(self, *, uin: Callable[[Array], Array] | None = None, uin_grad: Callable[[Array], Array] | None = None) -> BIEMResultCalculator:
-        """Densities of the incident field (uin, uin_grad) against the stored factors: ``biem()``'s result for the same field."""
+    def solve(self, *, uin: Callable[[Array], Array] | None = None, uin_grad: Callable[[Array], Array] | None = None,
+              plane_wave_direction: Array | None = None) -> BIEMResultCalculator:
+        """Densities of the incident field (uin, uin_grad), or of plane waves along ``plane_wave_direction`` in closed form, against the
+        stored factors: ``biem()``'s result for the same field."""
         if self._closed:
             raise ValueError("BIEMFactorization is closed")
         op, lib = self._op, L.load()
+        directions = None if plane_wave_direction is None else _check_plane_wave_direction(op.c, op.k_given, plane_wave_direction, uin, uin_grad)
         plan, fl, dev = op.plan, op.fl, op.dev
         B, H, nb = fl.B, plan.H, fl.nb
-        has_rhs = not (uin is None and uin_grad is None)
+        has_rhs = not (uin is None and uin_grad is None and directions is None)
         density_t = axes = None
         if has_rhs:
-            _check_incident(op, uin, uin_grad)
-            g, axes = _boundary_samples(op, uin, uin_grad)
+            g, axes, uin = _incident_source(op, uin, uin_grad, directions, plane_wave_direction)
             nrhs = _nrhs(g)
             density_t = torch.empty((nb, nrhs, B, H), dtype=torch.complex128, device=dev)
             sp = _stream_ptr(dev)
@@ -449,11 +470,10 @@ class BIEMFactorization:
                     n_pad = int(self._factors.shape[-1])
                     sst = n_pad * n_pad
                     if self.n_symmetric > 0:
-                        wb = int(lib.biem_solve_factored_workspace_bytes(plan.handle, nb, B, nrhs))
+                        wb = int(lib.biem_solve_factored_workspace_bytes(plan.handle, nb, B, nrhs)) + _source_workspace_bytes(op, g)
                         work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
-                        entry, what = _entry("biem_solve_factored", op.per_degree)
-                        coef = (_ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched) if op.per_degree else ()
-                        L.check(entry(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab), *coef, *_sample_ptrs(g),
+                        entry, what = _source_entry("biem_solve_factored", op, g)
+                        L.check(entry(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab), *_factored_source_args(op, g), *_sample_ptrs(g),
                                       _ptr(density_t), _ptr(work), wb, sp), what)
                         del work
                     # LU-form systems (runs of consecutive systems): equilibrated right-hand sides in natural order, stored LU, density
@@ -462,7 +482,7 @@ class BIEMFactorization:
                         n = s1 - s0
                         x = torch.zeros((n, n_pad, ldx), dtype=torch.complex128, device=dev)
                         xs = n_pad * ldx
-                        _rhs_project(op, n, g, s0, x, xs, ldx, 1, sp)
+                        _rhs_project(op, n, g, s0, x, xs, ldx, 1, sp, self._tab[s0:s1])
                         L.check(lib.biem_lu_solve(n, n_pad, nrhs, _ptr(self._factors[s0]), n_pad, sst, _ptr(self._ipiv[s0]), _ptr(x), ldx, xs, sp),
                                 "biem_lu_solve")
                         L.check(lib.biem_density(plan.handle, n, B, nrhs, _ptr(x), xs, ldx, 1, _ptr(self._tab[s0]), _ptr(density_t[s0]), sp),

@@ -175,6 +175,7 @@ class _Operator:
     alpha_t: torch.Tensor
     beta_t: torch.Tensor
     per_degree: bool = False # alpha / beta are the degree-dependent alpha_n / beta_n of shape (..., B, n_end); fl.alpha / fl.beta likewise
+    k_given: Any = None      # k as the caller gave it (the wavenumber of a plane_wave_direction's callable)
 
 
 def _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n=None, beta_n=None) -> _Operator:
@@ -202,7 +203,7 @@ def _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n=None,
     fl = _flatten(batch, centers_t if list(perm) == list(range(len(perm))) else centers_t[..., list(perm)], radii_t, k_t, eta_t,
                   alpha_t, beta_t, int(n_end) if per_degree else 0)
     return _Operator(c, n_end, kind, origin, dev, tuple(batch), perm, plan, fl, centers_t, radii_t, k_t, eta_t, _is_complex(k),
-                     alpha, beta, alpha_t, beta_t, per_degree)
+                     alpha, beta, alpha_t, beta_t, per_degree, k)
 
 
 def _result_operator(res: Any, what: str, alpha, beta, alpha_n, beta_n, require=()) -> _Operator:
@@ -342,16 +343,79 @@ def _boundary_samples(op: _Operator, uin, uin_grad):
     return (tuple(parts) if op.per_degree else parts[0]), axes
 
 
+@dataclass(frozen=True)
+class _PlaneWaves:
+    """Plane waves as the source of the right-hand sides, in closed form (biem_rhs_plane_wave): unit directions in the plan's canonical
+    axes, [nb, nrhs, d] when they differ between the systems of the operator (batched), else [1, nrhs, d].  Stands where the samples of
+    _boundary_samples stand; _nrhs, _sample_ptrs, _pick_systems, _source_entry, _source_workspace_bytes and _rhs_project tell them apart."""
+
+    dirs: torch.Tensor
+    batched: int
+    per_degree: bool         # of the operator: the `_pw` entries take it as an argument, not as a second set of entries
+
+
+def _check_plane_wave_direction(c, k, direction, uin, uin_grad) -> np.ndarray:
+    """The checks of biem(plane_wave_direction=) that need no device; returns the directions on the host as float64, not yet normalised."""
+    if uin is not None or uin_grad is not None:
+        raise ValueError("plane_wave_direction replaces uin / uin_grad: give either the direction or the callables, not both")
+    D = _host_array(direction)
+    if D.dtype.kind not in "iuf":
+        raise ValueError(f"plane_wave_direction must be a real array, got dtype {D.dtype}")
+    D = D.astype(np.float64)
+    if D.ndim < 1 or D.shape[0] != c.c_ndim:
+        raise ValueError(f"The first dimension of plane_wave_direction must be c.c_ndim={c.c_ndim}, but got shape {tuple(D.shape)}")
+    if D.ndim != len(_shape(k)) + 1:
+        raise ValueError(f"plane_wave_direction.ndim={D.ndim} is not k.ndim + 1={len(_shape(k)) + 1}")
+    if not bool(np.all(np.isfinite(D))):
+        raise ValueError("plane_wave_direction has a non-finite entry")
+    if D.size and not bool(np.all(np.any(D != 0, axis=0))):
+        raise ValueError("plane_wave_direction has a zero vector: a plane wave needs a direction")
+    return D
+
+
+def _plane_wave_source(op: _Operator, D: np.ndarray):
+    """The source of the checked directions D (c_ndim, ...) and the _RhsAxes of its layout: the trailing axes of D broadcast against
+    the batch as the direction of plane_wave() does, and those on which the operator has size 1 become right-hand sides."""
+    batch = op.batch
+    try:
+        full = tuple(np.broadcast_shapes(batch, D.shape[1:]))
+    except ValueError as e:
+        raise ValueError("Shapes of the batch and plane_wave_direction[1:] are not broadcastable\n"
+                         f"batch shape={batch}\ntuple(plane_wave_direction.shape)={tuple(D.shape)}") from e
+    axes = _RhsAxes.of(batch, full)
+    D = D / np.linalg.norm(D, axis=0, keepdims=True)
+    D = D[list(op.perm)]                                              # canonical component i = the caller's perm[i], as the centres
+    batched = int(any(D.shape[1 + i] != 1 for i in axes.op_axes))
+    t = torch.as_tensor(np.moveaxis(np.broadcast_to(D, (D.shape[0],) + full), 0, -1).copy(), device=op.dev)
+    dirs = axes.lay_out(t)                                            # [nb, nrhs, d]
+    return _PlaneWaves(dirs if batched else dirs[:1].contiguous(), batched, op.per_degree), axes
+
+
 def _nrhs(g) -> int:
-    """Right-hand sides per system of the samples of _boundary_samples (a tensor, or the unmixed pair of the degree-dependent case)."""
+    """Right-hand sides per system of a source: the samples of _boundary_samples (a tensor, or the unmixed pair of the degree-dependent
+    case) or _PlaneWaves."""
+    if isinstance(g, _PlaneWaves):
+        return int(g.dirs.shape[1])
     return int((g if isinstance(g, torch.Tensor) else next(t for t in g if t is not None)).shape[1])
 
 
 def _sample_ptrs(g, s0: int = 0):
-    """The sample arguments of an entry point from system s0 on: (d_g,) or (d_gu, d_gdn), a missing set as the null pointer."""
+    """The source arguments of an entry point from system s0 on: (d_g,) or (d_gu, d_gdn), a missing set as the null pointer; plane
+    waves: (per_degree, d_dirs, dirs_batched)."""
+    if isinstance(g, _PlaneWaves):
+        return (int(g.per_degree), _ptr(g.dirs[s0:] if g.batched else g.dirs), g.batched)
     if isinstance(g, torch.Tensor):
         return (_ptr(g[s0:]),)
     return tuple(_ptr(None if t is None else t[s0:]) for t in g)
+
+
+def _pick_systems(g, idx: torch.Tensor):
+    """The source of the systems idx (a device index tensor) alone."""
+    if isinstance(g, _PlaneWaves):
+        return _PlaneWaves(g.dirs[idx].contiguous(), 1, g.per_degree) if g.batched else g
+    if isinstance(g, torch.Tensor):
+        return g[idx].contiguous()
+    return tuple(None if t is None else t[idx].contiguous() for t in g)
 
 
 def _entry(base: str, per_degree: bool, label: Optional[str] = None):
@@ -359,6 +423,30 @@ def _entry(base: str, per_degree: bool, label: Optional[str] = None):
     both forms)."""
     name = base + "_n" if per_degree else base
     return getattr(L.load(), name), label or name
+
+
+def _source_entry(base: str, op: _Operator, g, label: Optional[str] = None):
+    """The entry `base` for the source g: its `_pw` form for plane waves, else _entry's choice."""
+    if isinstance(g, _PlaneWaves):
+        return getattr(L.load(), base + "_pw"), label or base + "_pw"
+    return _entry(base, op.per_degree, label)
+
+
+def _source_workspace_bytes(op: _Operator, g) -> int:
+    """What the source adds at the tail of a path's workspace (plane waves: the harmonics of their directions)."""
+    if isinstance(g, _PlaneWaves):
+        return int(L.load().biem_rhs_plane_wave_workspace_bytes(op.plan.handle, op.fl.nb, _nrhs(g), g.batched))
+    return 0
+
+
+def _factored_source_args(op: _Operator, g) -> tuple:
+    """What biem_solve_factored* takes between the tables and the source arguments: nothing, the degree-dependent pair, or for plane
+    waves the wavenumbers, the centres and the coefficients."""
+    fl = op.fl
+    coef = (_ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched)
+    if isinstance(g, _PlaneWaves):
+        return (_ptr(fl.k), _ptr(fl.centers), fl.geom_batched) + coef
+    return coef if op.per_degree else ()
 
 
 def _ball_tables(op: _Operator, sp: int, fill: bool = True) -> torch.Tensor:
@@ -372,9 +460,20 @@ def _ball_tables(op: _Operator, sp: int, fill: bool = True) -> torch.Tensor:
     return tab
 
 
-def _rhs_project(op: _Operator, n: int, g, s0: int, f: torch.Tensor, sys_stride: int, elem_stride: int, rhs_stride: int, sp: int) -> None:
-    """biem_rhs_project / biem_rhs_project_n of the n systems from s0 on into f (natural order)."""
+def _rhs_project(op: _Operator, n: int, g, s0: int, f: torch.Tensor, sys_stride: int, elem_stride: int, rhs_stride: int, sp: int,
+                 tab: Optional[torch.Tensor] = None) -> None:
+    """The right-hand sides of the n systems from s0 on into f (natural order), by the source g: biem_rhs_project / biem_rhs_project_n
+    of samples, biem_rhs_plane_wave of plane waves (from `tab`, the ball tables of those n systems)."""
     fl, a0 = op.fl, s0 if op.fl.ab_batched else 0
+    if isinstance(g, _PlaneWaves):
+        lib = L.load()
+        wb = int(lib.biem_rhs_plane_wave_workspace_bytes(op.plan.handle, n, _nrhs(g), g.batched))
+        work = torch.empty(max(wb, 16), dtype=torch.uint8, device=op.dev)
+        _, d_dirs, batched = _sample_ptrs(g, s0)
+        L.check(lib.biem_rhs_plane_wave(op.plan.handle, n, fl.B, _nrhs(g), _ptr(fl.k[s0:]), _ptr(fl.centers[s0:] if fl.geom_batched else fl.centers),
+                                        fl.geom_batched, _ptr(tab), d_dirs, batched, _ptr(f), sys_stride, elem_stride, rhs_stride,
+                                        _ptr(work), wb, sp), "biem_rhs_plane_wave")
+        return
     entry, what = _entry("biem_rhs_project", op.per_degree)
     coef = (_ptr(fl.alpha[a0:]), _ptr(fl.beta[a0:]), fl.ab_batched) if op.per_degree else ()
     L.check(entry(op.plan.handle, n, fl.B, _nrhs(g), *_sample_ptrs(g, s0), *coef, _ptr(f), sys_stride, elem_stride, rhs_stride, sp), what)

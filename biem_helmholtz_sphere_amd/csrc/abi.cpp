@@ -490,6 +490,51 @@ int biem_solve_factored_n(const biem_plan* plan, int nb, int B, int nrhs, const 
                              {nullptr, d_gu, d_gdn}, d_density, d_work, work_bytes, (hipStream_t)stream);
 }
 
+// ---- plane-wave incidence in closed form (kernels_rhs_pw.hip): the third source of right-hand sides ----
+size_t biem_rhs_plane_wave_workspace_bytes(const biem_plan* plan, int nb, int nrhs, int dirs_batched) {
+  return plan ? rhs_plane_wave_workspace_bytes(plan, nb, nrhs, dirs_batched) : 0;
+}
+
+int biem_rhs_plane_wave(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
+                        const double* d_tab, const double* d_dirs, int dirs_batched, double* d_f, long long sys_stride,
+                        long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_centers, "d_centers"); NEED(d_tab, "d_tab"); NEED(d_dirs, "d_dirs"); NEED(d_f, "d_f"); NEED(d_work, "d_work");
+  const Samples src = {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched, d_work};
+  if (work_bytes < src.work_bytes(plan, nb, nrhs)) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, src.work_bytes(plan, nb, nrhs)); return BIEM_ERR_ARG; }
+  return rhs_project(plan, nb, B, nrhs, {nullptr, nullptr, 0, false}, src, d_f, sys_stride, elem_stride, rhs_stride, (hipStream_t)stream, false,
+                     SplitMap(), d_tab);
+}
+
+int biem_solve_pw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_dirs, int dirs_batched, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                  void* stream) {
+  NEED(d_dirs, "d_dirs");
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched}, d_density, d_info, chunk, d_work,
+                    work_bytes, (hipStream_t)stream, false);
+}
+
+int biem_solve_ldlt_pw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                       const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                       const double* d_dirs, int dirs_batched, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                       void* stream) {
+  NEED(d_dirs, "d_dirs");
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched}, d_density, d_info, chunk, d_work,
+                    work_bytes, (hipStream_t)stream, true);
+}
+
+int biem_solve_factored_pw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k, const double* d_centers, int geom_batched, const double* d_alpha,
+                           const double* d_beta, int ab_batched, int per_degree, const double* d_dirs, int dirs_batched,
+                           double* d_density, void* d_work, size_t work_bytes, void* stream) {
+  NEED(d_dirs, "d_dirs");
+  return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                             {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched}, d_density, d_work,
+                             work_bytes, (hipStream_t)stream);
+}
+
 // ---- extinction and absorbed power (kernels_power.hip), radiation force (kernels_force.hip) ----
 // both are defined for a lossless exterior: the wavenumbers come to the host for that test (one small copy, one wait)
 static int require_real_k(const char* who, const char* what, const double* d_k, int nb, hipStream_t st) {

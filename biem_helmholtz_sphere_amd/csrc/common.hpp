@@ -125,6 +125,13 @@ int launch_ball_tables_n(const biem_plan* p, int nb, int B, const double* d_k, c
 int launch_rhs_project_n(const biem_plan* p, int nb, int B, int nrhs, const double* d_gu, const double* d_gdn, const double* d_alpha_n,
                          const double* d_beta_n, int ab_batched, double* d_f, long long sys_stride, long long elem_stride,
                          long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap());
+// plane-wave incidence in closed form (kernels_rhs_pw.hip): f = -C_d i^n gj_n conj(Y_h(p^_r)) e^{i k p^_r.c_b} from the ball tables, written
+// where launch_rhs_project writes.  d_dirs: unit vectors in the plan's axes, [nrhs][d] or (dirs_batched) [nb][nrhs][d]; d_work:
+// rhs_plane_wave_workspace_bytes (the harmonics of the directions).  At most 65535 systems and right-hand sides.
+size_t rhs_plane_wave_workspace_bytes(const biem_plan* p, int nb, int nrhs, int dirs_batched);
+int launch_rhs_plane_wave(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
+                          const double* d_tab, const double* d_dirs, int dirs_batched, double* d_f, long long sys_stride,
+                          long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work);
 // d_info[s] = code for every system with a (ball, degree) whose symmetric scaling 1 / sqrt(gj gh) is not finite (gj = 0); others untouched
 // (biem_flag_unscalable exposes it for tests)
 int launch_flag_unscalable(const biem_plan* p, int nb, int B, const double* d_tab, int* d_info, int code, hipStream_t st);
@@ -233,8 +240,15 @@ struct BoundaryCoef {
   const char* alpha_name() const { return per_degree ? "d_alpha_n" : "d_alpha"; }
   const char* beta_name() const { return per_degree ? "d_beta_n" : "d_beta"; }
 };
-// boundary samples [nb][nrhs][B][Q] complex: g of plain coefficients; per degree the unmixed gu / gdn (either may be null: zero)
-struct Samples { const double* g; const double* gu; const double* gdn; };
+// the source of the right-hand sides.  Boundary samples [nb][nrhs][B][Q] complex: g of plain coefficients; per degree the unmixed gu / gdn
+// (either may be null: zero).  Or, with dirs set, plane waves along dirs in closed form (launch_rhs_plane_wave: no samples), which
+// reads the wavenumbers and centres of the call and keeps its harmonics in `work` (set by the path: the tail of its workspace).
+struct Samples {
+  const double* g; const double* gu; const double* gdn;
+  const double* dirs = nullptr; int dirs_batched = 0;
+  const double* k = nullptr; const double* centers = nullptr; int geom_batched = 0; void* work = nullptr;
+  size_t work_bytes(const biem_plan* p, int nb, int nrhs) const { return dirs ? rhs_plane_wave_workspace_bytes(p, nb, nrhs, dirs_batched) : 0; }
+};
 
 inline long long rhs_ld(long long nrhs) { return (nrhs + 7) / 8 * 8; }   // right-hand-side columns; rows stay 128-byte aligned (8 complex128)
 
@@ -244,11 +258,13 @@ inline int check_counts(const char* who, int nb, int nrhs, int B) {
   return BIEM_ERR_ARG;
 }
 
-// the one place that picks the per-degree launcher: ball tables, and the projection f of the samples (strides as launch_rhs_project)
+// the one place that picks the per-degree launcher: ball tables, and the projection f of the samples (strides as launch_rhs_project);
+// plane-wave sources take the closed form from d_tab, the ball tables of the nb systems
 int ball_tables(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii, int geom_batched,
                 const BoundaryCoef& bc, double* d_tab, hipStream_t st);
 int rhs_project(const biem_plan* p, int nb, int B, int nrhs, const BoundaryCoef& bc, const Samples& smp, double* d_f, long long sys_stride,
-                long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap());
+                long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap(),
+                const double* d_tab = nullptr);
 
 size_t solve_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int chunk);
 size_t factor_workspace_bytes(const biem_plan* p, int nb, int B, int chunk);

@@ -146,8 +146,11 @@ int rhs_load(const biem_plan* p, int s0, int c, int B, int nrhs, const BoundaryC
              const RhsView& v, bool symmetric, hipStream_t st) {
   const size_t g0 = (size_t)s0 * nrhs * B * p->Q * 2, ab0 = (bc.per_degree && bc.batched) ? (size_t)s0 * B * p->n_end * 2 : 0;
   const BoundaryCoef bcs = {bc.alpha + ab0, bc.beta + ab0, bc.batched, bc.per_degree};   // (read by the per-degree projection only)
-  const Samples ss = {smp.g ? smp.g + g0 : nullptr, smp.gu ? smp.gu + g0 : nullptr, smp.gdn ? smp.gdn + g0 : nullptr};
-  const int rc = rhs_project(p, c, B, nrhs, bcs, ss, v.f, v.sys_stride, v.ld, 1, st, symmetric, v.split);
+  const Samples ss = {smp.g ? smp.g + g0 : nullptr, smp.gu ? smp.gu + g0 : nullptr, smp.gdn ? smp.gdn + g0 : nullptr,
+                      smp.dirs ? smp.dirs + (smp.dirs_batched ? (size_t)s0 * nrhs * p->d : 0) : nullptr, smp.dirs_batched,
+                      smp.k ? smp.k + 2 * (size_t)s0 : nullptr, smp.centers ? smp.centers + (smp.geom_batched ? (size_t)s0 * B * p->d : 0) : nullptr,
+                      smp.geom_batched, smp.work};
+  const int rc = rhs_project(p, c, B, nrhs, bcs, ss, v.f, v.sys_stride, v.ld, 1, st, symmetric, v.split, tab);
   return (rc || !symmetric) ? rc : launch_sym_rhs(p, c, B, nrhs, v.n_pad, tab, v.f, v.ld, v.sys_stride, false, st, v.split);
 }
 int rhs_unload(const biem_plan* p, int c, int B, int nrhs, const double* tab, const RhsView& v, bool symmetric, double* density, hipStream_t st) {
@@ -163,7 +166,10 @@ int ball_tables(const biem_plan* p, int nb, int B, const double* d_k, const doub
 }
 
 int rhs_project(const biem_plan* p, int nb, int B, int nrhs, const BoundaryCoef& bc, const Samples& smp, double* d_f, long long sys_stride,
-                long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split) {
+                long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, const double* d_tab) {
+  if (smp.dirs)
+    return launch_rhs_plane_wave(p, nb, B, nrhs, smp.k, smp.centers, smp.geom_batched, d_tab, smp.dirs, smp.dirs_batched, d_f, sys_stride,
+                                 elem_stride, rhs_stride, st, slot_order, split, smp.work);
   return bc.per_degree ? launch_rhs_project_n(p, nb, B, nrhs, smp.gu, smp.gdn, bc.alpha, bc.beta, bc.batched, d_f, sys_stride, elem_stride,
                                               rhs_stride, st, slot_order, split)
                        : launch_rhs_project(p, nb, B, nrhs, smp.g, d_f, sys_stride, elem_stride, rhs_stride, st, slot_order, split);
@@ -180,14 +186,16 @@ void last_solve_split(int* npE, int* npO) {
 }
 
 int solve_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
-               const double* d_radii, int geom_batched, const BoundaryCoef& bc, const Samples& smp, double* d_density, int* d_info, int chunk,
+               const double* d_radii, int geom_batched, const BoundaryCoef& bc, const Samples& source, double* d_density, int* d_info, int chunk,
                void* d_work, size_t work_bytes, hipStream_t st, bool symmetric) {
+  Samples smp = source;
   NEED_DEV_AS(who, plan); NEED_AS(who, d_k, "d_k"); NEED_AS(who, d_eta, "d_eta"); NEED_AS(who, d_centers, "d_centers"); NEED_AS(who, d_radii, "d_radii");
   NEED_AS(who, bc.alpha, bc.alpha_name()); NEED_AS(who, bc.beta, bc.beta_name());
-  if (!bc.per_degree) NEED_AS(who, smp.g, "d_g");
+  if (!smp.dirs && !bc.per_degree) NEED_AS(who, smp.g, "d_g");
   NEED_AS(who, d_density, "d_density"); NEED_AS(who, d_info, "d_info"); NEED_AS(who, d_work, "d_work");
   if (nb <= 0 || B <= 0) return BIEM_OK;
   if (nrhs < 1) { set_error("%s: nrhs < 1", who); return BIEM_ERR_ARG; }
+  if (smp.dirs && (nb > 65535 || nrhs > 65535)) { set_error("%s: at most 65535 systems / right-hand sides per call (got nb=%d, nrhs=%d)", who, nb, nrhs); return BIEM_ERR_ARG; }
   const int H = plan->H;
   SplitMap sm = SplitMap();                // (off: the pivoted LU has no split form)
   if (symmetric) {
@@ -196,9 +204,11 @@ int solve_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, 
   }
   const bool split = sm.on();
   const SolveLayout L = make_layout(plan, nb, B, nrhs, chunk, split);
-  if (work_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, work_bytes, L.total); return BIEM_ERR_ARG; }
+  const size_t need = L.total + smp.work_bytes(plan, nb, nrhs);    // (a plane-wave source keeps its harmonics at the tail)
+  if (work_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", who, work_bytes, need); return BIEM_ERR_ARG; }
   if (split) { g_last_split[0] = sm.npE; g_last_split[1] = sm.npO; }
   char* w = (char*)d_work;
+  smp.work = w + L.total;
   double* tab = (double*)(w + L.off_tab);
   double* A = (double*)(w + L.off_A);
   void* T = w + L.off_T;
@@ -267,16 +277,19 @@ int factor_path(const char* who, const biem_plan* plan, int nb, int B, const dou
 }
 
 int solve_factored_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
-                        const double* d_tab, const BoundaryCoef& bc, const Samples& smp, double* d_density, void* d_work, size_t work_bytes,
+                        const double* d_tab, const BoundaryCoef& bc, const Samples& source, double* d_density, void* d_work, size_t work_bytes,
                         hipStream_t st) {
+  Samples smp = source;
   NEED_DEV_AS(who, plan); NEED_AS(who, d_F, "d_F"); NEED_AS(who, d_tab, "d_tab"); NEED_AS(who, d_density, "d_density"); NEED_AS(who, d_work, "d_work");
-  if (bc.per_degree) { NEED_AS(who, bc.alpha, bc.alpha_name()); NEED_AS(who, bc.beta, bc.beta_name()); }
+  if (smp.dirs) { NEED_AS(who, smp.k, "d_k"); NEED_AS(who, smp.centers, "d_centers"); }
+  else if (bc.per_degree) { NEED_AS(who, bc.alpha, bc.alpha_name()); NEED_AS(who, bc.beta, bc.beta_name()); }
   else NEED_AS(who, smp.g, "d_g");
   if (const int rc = check_counts(who, nb, nrhs, B)) return rc;
   if (nb == 0 || nrhs == 0 || B == 0) return BIEM_OK;
   const int n_pad = lu_npad(B * plan->H);
   const size_t need = solve_factored_workspace_bytes(plan, nb, B, nrhs);
-  if (const int rc = check_factor_room(who, lda, sys_stride, n_pad, work_bytes, need)) return rc;
+  if (const int rc = check_factor_room(who, lda, sys_stride, n_pad, work_bytes, need + smp.work_bytes(plan, nb, nrhs))) return rc;
+  smp.work = (char*)d_work + need;                                 // (a plane-wave source keeps its harmonics at the tail)
   // right-hand sides X[s][row][q] (row-major, ldx columns), rows in the slot order of the symmetric form; padding rows zero
   const long long ldx = rhs_ld(nrhs);
   const RhsView X = {(double*)d_work, (long long)n_pad * ldx, ldx, n_pad, SplitMap()};

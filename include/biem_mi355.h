@@ -408,6 +408,39 @@ int biem_solve_factored_n(const biem_plan* plan, int nb, int B, int nrhs, const 
                           const double* d_tab, const double* d_alpha_n, const double* d_beta_n, int ab_batched, const double* d_gu,
                           const double* d_gdn, double* d_density, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- plane-wave incidence in closed form: exact right-hand sides without samples.  With orthonormal harmonics and the
+ *      radial normalisation of biem_radial, u_in = e^{i k p^.x} has on the surface of ball b the projections
+ *        U_h = C_d i^n j_n(k rho) conj(Y_h(p^)) e^{i k p^.c_b},  V_h = C_d i^n k j_n'(k rho) conj(Y_h(p^)) e^{i k p^.c_b},
+ *        C_d = 2^{(d+1)/2} pi^{(d-1)/2}, so f(s, r, b, h) = -C_d i^{n(h)} gj_{n(h)}(s, b) conj(Y_h(p^_r)) e^{i k_s p^_r.c_b}
+ *      with gj row 0 of d_tab (biem_ball_tables or biem_ball_tables_n: degree-dependent coefficients need no form of their own); real
+ *      and complex k, every tree, the chains included.  d_dirs: UNIT vectors in the plan's axes, [nrhs][d] shared by all systems or
+ *      [nb][nrhs][d] with dirs_batched != 0 (a zero direction is the caller's error).  Every element is written by one lane, no
+ *      atomics: two calls give the same bits.  At most 65535 systems and right-hand sides per call (BIEM_ERR_ARG).
+ * biem_rhs_plane_wave writes f where biem_rhs_project does, d_f[s*sys_stride + (b*H + h)*elem_stride + r*rhs_stride].  Workspace:
+ * biem_rhs_plane_wave_workspace_bytes (the harmonics of the directions, twice).
+ * biem_solve_pw / biem_solve_ldlt_pw / biem_solve_factored_pw: biem_solve / biem_solve_ldlt / biem_solve_factored with that source in
+ * place of the samples.  per_degree != 0: d_alpha / d_beta are the [nb or 1][B][n_end] pair of the _n entries, which then run
+ * (biem_ball_tables_n, the pair-by-pair fill, the -(Npad+2) code).  biem_solve_factored_pw reads the stored tables (its coefficient
+ * arguments are not read and may be null) and takes the wavenumbers and centres the factored solve otherwise does not need.
+ * Workspace: the bytes of biem_solve_workspace_bytes (biem_solve_factored_workspace_bytes) PLUS biem_rhs_plane_wave_workspace_bytes,
+ * the harmonics at the tail. ---- */
+size_t biem_rhs_plane_wave_workspace_bytes(const biem_plan* plan, int nb, int nrhs, int dirs_batched);
+int biem_rhs_plane_wave(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_centers,
+                        int geom_batched, const double* d_tab, const double* d_dirs, int dirs_batched, double* d_f, long long sys_stride,
+                        long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream);
+int biem_solve_pw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_dirs, int dirs_batched, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                  void* stream);
+int biem_solve_ldlt_pw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta,
+                       const double* d_centers, const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta,
+                       int ab_batched, int per_degree, const double* d_dirs, int dirs_batched, double* d_density, int* d_info, int chunk,
+                       void* d_work, size_t work_bytes, void* stream);
+int biem_solve_factored_pw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k /*c128*/, const double* d_centers, int geom_batched,
+                           const double* d_alpha, const double* d_beta, int ab_batched, int per_degree, const double* d_dirs,
+                           int dirs_batched, double* d_density, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- cross sections: extinction and absorbed power per ball from what the solve already has (no second solve, no
  *      matrix, no workspace).  Real k only, in the far-field normalisation u_scat ~ F(x^) e^{ikr} / r^{(d-1)/2}: "power" is
  *      (1/k) Im oint conj(u) d_n u dS, for a unit plane wave the cross section.  With c_h = density_h blc_n(rho_b), U_h / V_h the
