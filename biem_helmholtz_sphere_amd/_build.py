@@ -178,6 +178,33 @@ def _chunk_loop(ins):
     return best, n_mfma
 
 
+def _vregs(tok: str) -> set:
+    m = re.fullmatch(r"v\[(\d+):(\d+)\]", tok)
+    if m:
+        return set(range(int(m.group(1)), int(m.group(2)) + 1))
+    m = re.fullmatch(r"v(\d+)", tok)
+    return {int(m.group(1))} if m else set()
+
+
+def _prefetch_hazards(ins) -> list:
+    """Instructions that touch the destination of a global_load_dwordx4 before the next `s_waitcnt vmcnt(0)`.  k_fill_red issues its table
+    prefetch from inline asm and waits for it much later (BIEM_TN_CLAIM), so the compiler does not know the registers are in flight: under
+    register pressure it has spilled them right behind the load and reused them as an address (k_fill_red<8, 2, false>), which stores
+    stale data and lets the load land in a live pointer."""
+    pending, bad = set(), []
+    for a, op, args in ins:
+        if op == "s_waitcnt" and "vmcnt(0)" in args:
+            pending = set()
+            continue
+        toks = [t.strip() for t in args.split(",")]
+        used = set().union(*[_vregs(t) for t in toks]) if toks else set()
+        if used & pending:
+            bad.append(f"{a:#x}: {op} {args}")
+        if op == "global_load_dwordx4":
+            pending |= _vregs(toks[0])
+    return bad
+
+
 def _label(kd) -> str:
     if isinstance(kd, tuple):
         return f"k_back_sweep<{kd[1]}>" if kd[0] == SWEEP else f"k_gemm3m_stack<{kd[1]}>"
@@ -218,9 +245,15 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = F
                     if rep["scratch_bytes"] != 0 or rep["vgpr_spills"] != 0:
                         raise IsaCheckError(f"k_back_sweep<{m.group(1)}>: scratch {rep['scratch_bytes']} B, {rep['vgpr_spills']} VGPR spills")
             gemm = [n for n in metas if "k_gemm3m_pipe" in n or "k_gemm3m_strip" in n or "k_gemm3m_stack" in n]
-            if not gemm:
+            red = [n for n in metas if "k_fill_red" in n]
+            if not gemm and not red:
                 continue
             dis = _disassemble(objdump, path)
+            # k_fill_red<KT, NC, SPLIT>: no prefetch register may be read, moved or spilled while its load is in flight
+            for name in red:
+                bad = _prefetch_hazards(dis[name])
+                if bad:
+                    raise IsaCheckError(f"{name}: {len(bad)} instructions touch a prefetch register before its wait, first {bad[0]}")
             for name in gemm:
                 stack = "k_gemm3m_stack" in name
                 kd = STRIP if "k_gemm3m_strip" in name else (STACK, int(re.search(r"k_gemm3m_stackILi(\d+)E", name).group(1))) if stack else \

@@ -40,6 +40,7 @@ SIGNATURES = {
     "biem_plan_quadrature": (_i, [_vp, _vp, _vp]),
     "biem_plan_projection": (_i, [_vp, _vp]),
     "biem_plan_terms": (_i, [_vp, _vp, _vp, _vp]),
+    "biem_plan_entry_terms": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), _vp, _vp]),
     "biem_plan_force_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "biem_radial": (_i, [_i, _i, _i, _dp, _dp, _vp]),
     "biem_radial_complex": (_i, [_i, _i, _i, _dp, _dp, _vp]),

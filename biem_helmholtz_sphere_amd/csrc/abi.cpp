@@ -199,6 +199,25 @@ int biem_plan_terms(const biem_plan* plan, long long* h_ptr, double* h_coef, int
   return BIEM_OK;
 }
 
+int biem_plan_entry_terms(int tree, int n_end, int h_col, int h_row, int capacity, int* n_terms, double* h_coef, int* h_tidx) {
+  NEED(n_terms, "n_terms");
+  std::vector<double> coef;
+  std::vector<int> tidx;
+  int rc = BIEM_OK;
+  try {
+    rc = plan_entry_terms(tree, n_end, h_col, h_row, coef, tidx);
+  } catch (const std::bad_alloc&) {
+    set_error("out of host memory building the integral tables for n_end=%d", n_end);
+    rc = BIEM_ERR_ALLOC;
+  }
+  if (rc != BIEM_OK) return rc;
+  *n_terms = (int)coef.size();
+  if ((int)coef.size() > capacity) { set_error("biem_plan_entry_terms: the entry has %d terms, capacity %d", (int)coef.size(), capacity); return BIEM_ERR_ARG; }
+  if (h_coef) memcpy(h_coef, coef.data(), coef.size() * sizeof(double));
+  if (h_tidx) memcpy(h_tidx, tidx.data(), tidx.size() * sizeof(int));
+  return BIEM_OK;
+}
+
 int biem_plan_force_terms(biem_plan* plan, long long* n_entries, long long* h_ptr, int* h_col, int* h_comp, double* h_val) {
   NEED(plan, "plan");
   int rc = BIEM_OK;

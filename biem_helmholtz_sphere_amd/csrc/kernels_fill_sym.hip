@@ -658,12 +658,19 @@ static int fill_sym_lanes(const SymFill& c, bool use_red, size_t shm, const Spli
                        p->d_deg, p->d_units, p->d_spos, p->d_rchunk, p->d_rcrow, p->d_rwrow, p->rchunk_rows_max, p->d_rcoef, p->d_ridx,   \
                        p->d_rphsel, c.T, c.A, c.lda, c.sys_stride, c.pc.classes, split.npE);                                              \
   }
-  // two combinations per iteration (the plan reserves LDS for two table rows) unless BIEM_FILL_NC=1 at plan build (A / B runs)
+  // two combinations per iteration (the plan reserves LDS for two table rows) unless BIEM_FILL_NC=1 at plan build (A / B runs).
+  // KT = 8 runs one combination per iteration whatever the plan says: with two, 16 prefetch registers of four VGPRs each are live under
+  // the 128-VGPR bound of a 1024-thread workgroup, and the register allocator spilled outputs of the inline-asm loads right behind the
+  // asm statement - BEFORE their wait in BIEM_TN_CLAIM - and reused the registers as the next load's address (k_fill_red<8, 2, false>:
+  // 101 spilled VGPRs; caa n_end 14 was the first plan the tests ran through it, and it ended in an illegal memory access).  The
+  // instantiation is not built any more; _build.check_isa refuses a library in which any k_fill_red reads a prefetch register before
+  // the wait.  (The kernel's LDS layout follows its own NC, so the second table row the plan reserved stays unused.)
 #define BIEM_LAUNCH_FILL_RED(KT)                                                                                                          \
   {                                                                                                                                       \
     if (p->red_nc == 2) { if (split.on()) BIEM_LAUNCH_FILL_RED_AS(KT, 2, true) else BIEM_LAUNCH_FILL_RED_AS(KT, 2, false) }               \
     else { if (split.on()) BIEM_LAUNCH_FILL_RED_AS(KT, 1, true) else BIEM_LAUNCH_FILL_RED_AS(KT, 1, false) }                              \
   }
+#define BIEM_LAUNCH_FILL_RED_ONE(KT) { if (split.on()) BIEM_LAUNCH_FILL_RED_AS(KT, 1, true) else BIEM_LAUNCH_FILL_RED_AS(KT, 1, false) }
 #define BIEM_LAUNCH_FILL_SYM(KT)                                                                                                          \
   {                                                                                                                                       \
     BIEM_HIPCHK(hipFuncSetAttribute((const void*)k_fill_sym<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));                  \
@@ -675,7 +682,7 @@ static int fill_sym_lanes(const SymFill& c, bool use_red, size_t shm, const Spli
     if (kt_need <= 1) BIEM_LAUNCH_FILL_RED(1)
     else if (kt_need <= 2) BIEM_LAUNCH_FILL_RED(2)
     else if (kt_need <= 4) BIEM_LAUNCH_FILL_RED(4)
-    else BIEM_LAUNCH_FILL_RED(8)
+    else BIEM_LAUNCH_FILL_RED_ONE(8)
   }
   else if (kt_need <= 1) BIEM_LAUNCH_FILL_SYM(1)
   else if (kt_need <= 2) BIEM_LAUNCH_FILL_SYM(2)
@@ -685,6 +692,7 @@ static int fill_sym_lanes(const SymFill& c, bool use_red, size_t shm, const Spli
   else BIEM_LAUNCH_FILL_SYM(8)
 #undef BIEM_LAUNCH_FILL_SYM
 #undef BIEM_LAUNCH_FILL_RED
+#undef BIEM_LAUNCH_FILL_RED_ONE
 #undef BIEM_LAUNCH_FILL_RED_AS
   BIEM_LAUNCHCHK();
   return BIEM_OK;

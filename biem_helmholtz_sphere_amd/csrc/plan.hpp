@@ -111,6 +111,8 @@ struct biem_plan {
 
 namespace biem {
 int plan_build_host(biem_plan* p, int tree, int n_end);   // returns BIEM_* status
+// the translation terms of entry (row h, column h') of bba / caa at order n_end, by the code the plan build runs, without a plan
+int plan_entry_terms(int tree, int n_end, int hp, int h, std::vector<double>& coef, std::vector<int>& tidx);
 int plan_build_chain_host(biem_plan* p, int d, int n_end);  // the standard chain tree "b" * (d - 2) + "a", 3 <= d <= kChainDimMax
 int plan_upload(biem_plan* p);
 int plan_build_force(biem_plan* p);         // the force coupling table, and its device mirror if the plan is uploaded; a no-op once built

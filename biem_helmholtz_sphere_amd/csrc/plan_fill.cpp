@@ -49,7 +49,7 @@ void build_entry_chunks(biem_plan* p) {
   for (size_t i = 0; i < p->tidx.size(); ++i) p->tidx16[i] = (uint16_t)p->tidx[i];
   const int max_ents = 1024;                                     // = FILL_THREADS of the fill kernel: one entry per thread
   long long budget = 150 * 1024 - (long long)(p->H2 + 2 * H) * 16 - (long long)(max_ents + 1) * 4 - 64;
-  // large orders (3-D n_end >= 40, 4-D >= 15): the pair table no longer leaves room for a useful slice of the term list - the
+  // large orders (3-D n_end >= 40, 4-D >= 14: H2 = 6930, H = 1015 leave 6 KB): the pair table no longer leaves room for a useful slice of the term list - the
   // kernel then reads the pair table from global memory (L2) and LDS holds only the column factors and the term slice
   p->fill_table_global = budget < 2048 * 10;
   if (p->fill_table_global) budget = 150 * 1024 - (long long)(2 * H) * 16 - (long long)(max_ents + 1) * 4 - 64;

@@ -5,7 +5,10 @@
 #include <algorithm>
 #include <cmath>
 #include <functional>
+#include <limits>
 #include <map>
+#include <memory>
+#include <mutex>
 #include <unordered_map>
 
 namespace biem {
@@ -353,81 +356,242 @@ static void terms_ba(biem_plan* p) {
     p->ptr[(size_t)h * H + hp + 1] = (uint32_t)p->coef.size();
   }
 }
-static void terms_caa(biem_plan* p) {
-  const int H = p->H, n = p->n_end;
-  // int Y' conj(Y) conj(Y'') = delta(m1'' = m1' - m1) delta(m2'' = m2' - m2) / (2 pi) * int cbar' cbar cbar'' sin cos dt;
-  // the polar integrand is a polynomial of degree <= 2 n_end - 2 in x = cos 2t: Gauss-Legendre with 2 n_end nodes is exact
-  const int nq = 2 * n;
-  std::vector<double> xg, wg; gauss_legendre(nq, xg, wg);
-  std::map<int, std::vector<double>> cb;      // key (n, a, b) -> values at the nodes
-  auto key = [](int q, int a, int b) { return (q * 256 + a) * 256 + b; };
-  for (size_t l = 0; l < p->deg2.size(); ++l) {
-    int q = p->labels2[3 * l], a = iabs(p->labels2[3 * l + 1]), b = iabs(p->labels2[3 * l + 2]);
-    auto& v = cb[key(q, a, b)];
-    if (!v.empty()) continue;
-    v.resize(nq);
-    for (int i = 0; i < nq; ++i) { double th = 0.5 * acos(xg[i]); v[i] = cbar_single(q, a, b, cos(th), sin(th)); }
-  }
-  std::map<int, int> pos2;                    // signed label -> index among degrees < n2
-  auto skey = [](int q, int m1, int m2) { return (q * 256 + (m1 + 128)) * 256 + (m2 + 128); };
-  for (size_t l = 0; l < p->deg2.size(); ++l) pos2[skey(p->labels2[3 * l], p->labels2[3 * l + 1], p->labels2[3 * l + 2])] = (int)l;
-  for (int h = 0; h < H; ++h) for (int hp = 0; hp < H; ++hp) {
-    int q = p->labels[3 * h], m1 = p->labels[3 * h + 1], m2 = p->labels[3 * h + 2];
-    int qp = p->labels[3 * hp], m1p = p->labels[3 * hp + 1], m2p = p->labels[3 * hp + 2];
-    int mu1 = m1p - m1, mu2 = m2p - m2;
-    const std::vector<double>& a = cb[key(qp, iabs(m1p), iabs(m2p))];
-    const std::vector<double>& b = cb[key(q, iabs(m1), iabs(m2))];
-    for (int q2 = iabs(q - qp); q2 <= q + qp; q2 += 2) {
-      if (q2 < iabs(mu1) + iabs(mu2)) continue;
-      const std::vector<double>& c = cb[key(q2, iabs(mu1), iabs(mu2))];
-      double acc = 0.0;
-      for (int i = 0; i < nq; ++i) acc += 0.25 * wg[i] * a[i] * b[i] * c[i];
-      if (fabs(acc) < 1e-14) continue;
-      p->coef.push_back(isign_even(q + q2 - qp) * acc / (2.0 * kPi));
-      p->tidx.push_back(pos2[skey(q2, mu1, mu2)]);
+// ---- the 4-D trees: term lists of bba and caa through one per-entry function ------------------------------------------------
+// Both trees keep, besides the label rules (triangle and parity in the degrees, the azimuthal deltas), polar triple integrals that
+// vanish with no rule behind them (zeros of the recoupling coefficient of SO(4)), and integrals that do not vanish fall with the
+// order without bound (3e-13 at bba n_end 24), so no constant separates the two.  The integrals are therefore taken in long double -
+// nodes, weights, node tables and the sum - and one counts as zero where it lies within the rounding bound of its own sum,
+// kZeroSlack nq eps sum |w a b c|; everything else is a term.  The double that the list carries is that sum rounded once.
+// The bound is 1.7e-16 of sum |w a b c| at n_end 24 (64-bit mantissa), and the smallest integrals that do not vanish fall by about 60
+// for every three orders (5e-14 at bba n_end 24), so they reach it near n_end 30: from there on real terms are taken for zeros again -
+// terms below 1e-15, far under what a double-precision contraction resolves, but that is the ceiling of this selection.
+typedef long double ldbl;
+static const ldbl kPiL = 3.14159265358979323846264338327950288L;
+static const ldbl kZeroSlack = 32.0L;
+
+static void gauss_legendre_l(int n, std::vector<ldbl>& t, std::vector<ldbl>& w) {
+  t.assign(n, 0.0L); w.assign(n, 0.0L);
+  for (int i = 0; i < n; ++i) {
+    ldbl x = cosl(kPiL * (i + 0.75L) / (n + 0.5L)), pp = 1.0L;
+    for (int it = 0; it < 100; ++it) {
+      ldbl p0 = 1.0L, p1 = x;
+      for (int k = 2; k <= n; ++k) { ldbl p2 = ((2.0L * k - 1.0L) * x * p1 - (k - 1.0L) * p0) / k; p0 = p1; p1 = p2; }
+      pp = n * (x * p1 - p0) / (x * x - 1.0L);
+      const ldbl dx = p1 / pp;
+      x -= dx;
+      if (it > 2 && fabsl(dx) < 4.0L * std::numeric_limits<ldbl>::epsilon()) break;
     }
-    p->ptr[(size_t)h * H + hp + 1] = (uint32_t)p->coef.size();
+    ldbl p0 = 1.0L, p1 = x;
+    for (int k = 2; k <= n; ++k) { ldbl p2 = ((2.0L * k - 1.0L) * x * p1 - (k - 1.0L) * p0) / k; p0 = p1; p1 = p2; }
+    pp = n * (x * p1 - p0) / (x * x - 1.0L);
+    t[n - 1 - i] = x;                         // ascending
+    w[n - 1 - i] = 2.0L / ((1.0L - x * x) * pp * pp);
   }
 }
-static void terms_bba(biem_plan* p) {
-  const int H = p->H, n = p->n_end, n2 = p->n2;
-  Gaunt3 G; G.init(n2, 2 * n);
-  // Abar[n][l][q] at Gauss-Chebyshev-2 nodes, degrees < n2
-  std::vector<double> tc, wc; gauss_cheb2(2 * n, tc, wc);
-  const int nq = 2 * n;
-  std::vector<double> Ab((size_t)n2 * n2 * nq, 0.0);
-  for (int qd = 0; qd < nq; ++qd) {
-    double x = tc[qd], s = sqrt(1.0 - x * x);
-    for (int l = 0; l < n2; ++l) {
-      double sl = 1.0; for (int i = 0; i < l; ++i) sl *= s;
-      for (int q = l; q < n2; ++q) Ab[((size_t)q * n2 + l) * nq + qd] = sl * gbar_single(q - l, l, x);
+// pbar_single, gbar_single, cbar_single (special.hpp) in long double
+static ldbl pbar_l(int n, int m, ldbl x, ldbl s) {
+  ldbl pmm = sqrtl(0.5L);
+  for (int i = 1; i <= m; ++i) pmm *= sqrtl((ldbl)(2 * i + 1) / (ldbl)(2 * i)) * s;
+  if (n == m) return pmm;
+  ldbl p1 = sqrtl((ldbl)(2 * m + 3)) * x * pmm, p0 = pmm;
+  for (int q = m + 2; q <= n; ++q) {
+    const ldbl a = sqrtl((ldbl)(4 * q * q - 1) / (ldbl)(q * q - m * m));
+    const ldbl b = sqrtl((ldbl)((q - 1) * (q - 1) - m * m) / (ldbl)(4 * (q - 1) * (q - 1) - 1));
+    const ldbl p2 = a * (x * p1 - b * p0);
+    p0 = p1; p1 = p2;
+  }
+  return p1;
+}
+static ldbl gbar_l(int k, int l, ldbl x) {
+  ldbl h0 = 0.5L * kPiL;
+  for (int i = 1; i <= l; ++i) h0 *= ((ldbl)i + 0.5L) / ((ldbl)i + 1.0L);
+  const ldbl lam = (ldbl)(l + 1);
+  ldbl p0 = 1.0L / sqrtl(h0);
+  if (k == 0) return p0;
+  const ldbl a1 = 0.5L * sqrtl((2.0L * lam) / (lam * (1.0L + lam)));
+  ldbl p1 = x * p0 / a1, aprev = a1;
+  for (int q = 2; q <= k; ++q) {
+    const ldbl aq = 0.5L * sqrtl((ldbl)q * ((ldbl)q + 2.0L * lam - 1.0L) / (((ldbl)q + lam - 1.0L) * ((ldbl)q + lam)));
+    const ldbl p2 = (x * p1 - aprev * p0) / aq;
+    p0 = p1; p1 = p2; aprev = aq;
+  }
+  return p1;
+}
+static ldbl cbar_l(int n, int a, int b, ldbl c, ldbl s) {
+  const int k = (n - a - b) / 2;
+  const ldbl x = c * c - s * s, al = (ldbl)b, be = (ldbl)a;
+  ldbl p0 = 1.0L, p1 = 1.0L;
+  if (k >= 1) {
+    p1 = (al + 1.0L) + 0.5L * (al + be + 2.0L) * (x - 1.0L);
+    for (int m = 1; m < k; ++m) {
+      const ldbl t = 2.0L * m + al + be;
+      const ldbl p2 = ((t + 1.0L) * ((t + 2.0L) * t * x + al * al - be * be) * p1 - 2.0L * (m + al) * (m + be) * (t + 2.0L) * p0) /
+                      (2.0L * (m + 1.0L) * (m + al + be + 1.0L) * t);
+      p0 = p1; p1 = p2;
     }
   }
-  auto off = [](int q) { return q * (q + 1) * (2 * q + 1) / 6; };
-  for (int h = 0; h < H; ++h) for (int hp = 0; hp < H; ++hp) {
-    int q = p->labels[3 * h], l = p->labels[3 * h + 1], m = p->labels[3 * h + 2];
-    int qp = p->labels[3 * hp], lp = p->labels[3 * hp + 1], mp = p->labels[3 * hp + 2], mu = mp - m;
-    const double* a = &Ab[((size_t)qp * n2 + lp) * nq];
-    const double* b = &Ab[((size_t)q * n2 + l) * nq];
-    for (int q2 = iabs(q - qp); q2 <= q + qp; q2 += 2) {
-      for (int l2 = iabs(l - lp); l2 <= l + lp && l2 <= q2; l2 += 2) {
-        if (l2 < iabs(mu)) continue;
-        double g3 = G(lp, mp, l, m, l2);
-        if (g3 == 0.0) continue;
-        const double* c = &Ab[((size_t)q2 * n2 + l2) * nq];
-        double a4 = 0.0;
-        for (int qd = 0; qd < nq; ++qd) a4 += wc[qd] * a[qd] * b[qd] * c[qd];
-        // (quadrature noise of a polar integral that vanishes by a selection rule reaches 3e-14 at n_end = 15; integrals that do not
-        // vanish are >= 1e-9 there: oracle/biem_oracle.py::_theta4)
-        if (fabs(a4) < 1e-12) continue;
-        double v = a4 * g3;
-        if (fabs(v) < 1e-14) continue;   // vanishes by a selection rule; only quadrature rounding is left
-        p->coef.push_back(isign_even(q + q2 - qp) * v);
-        p->tidx.push_back(off(q2) + l2 * l2 + l2 + mu);
+  ldbl r = 2.0L * (2.0L * k + a + b + 1.0L);
+  for (int i = 1; i <= a; ++i) r *= (ldbl)(k + b + i) / (ldbl)(k + i);
+  ldbl f = sqrtl(r);
+  for (int i = 0; i < a; ++i) f *= c;
+  for (int i = 0; i < b; ++i) f *= s;
+  return f * p1;
+}
+// sum_i w a b c, exactly 0.0 where the sum is within its own rounding bound
+static double resolved_sum(int nq, const ldbl* w, const ldbl* a, const ldbl* b, const ldbl* c, ldbl scale) {
+  ldbl acc = 0.0L, mag = 0.0L;
+  for (int i = 0; i < nq; ++i) { const ldbl t = w[i] * a[i] * b[i] * c[i]; acc += t; mag += fabsl(t); }
+  if (fabsl(acc) <= kZeroSlack * nq * std::numeric_limits<ldbl>::epsilon() * mag) return 0.0;
+  return (double)(acc * scale);
+}
+
+// One (tree, n_end) of bba / caa: labels, node tables, and the integral tables the entries share - one polar table per pair of
+// unsigned labels {(q'l'), (ql)} over its (q''l''), one S^2 table per {(l'|m'|), (l|m|)} and sign of m'm over its l'' - each filled
+// when an entry first asks for it.  The plan build walks every entry; biem_plan_entry_terms asks for one.
+struct Terms4 {
+  int tree = -1, n = 0, n2 = 0, nq = 0, H = 0;
+  std::vector<int> labels, deg, labels2, deg2;
+  std::vector<ldbl> wp, Tp;                     // polar rule and node table: bba Abar[(q n2 + l) nq + i]; caa cbar[row(q,a,b) nq + i]
+  std::vector<ldbl> wl, Pl;                     // bba: Gauss-Legendre rule and Pbar[(l n2 + m) nq + i]
+  std::vector<int> crow;                        // caa: (q n2 + a) n2 + b -> row of Tp
+  std::unordered_map<int, int> pos2;            // caa: signed label -> index among the degrees < n2
+  std::unordered_map<unsigned long long, std::vector<double>> polar, gaunt;
+
+  static int skey(int q, int m1, int m2) { return (q * 256 + (m1 + 128)) * 256 + (m2 + 128); }
+
+  void init(int tree_, int n_end) {
+    tree = tree_; n = n_end; n2 = 2 * n - 1; nq = 2 * n;
+    make_labels(tree, n, labels, deg);
+    make_labels(tree, n2, labels2, deg2);
+    H = (int)deg.size();
+    if (tree == TREE_BBA) {
+      // Gauss-Chebyshev-2: weight sqrt(1 - x^2) = one sin of sin^2 dtheta; the integrand is a polynomial of degree <= 4 n_end - 4
+      wp.resize(nq); Tp.assign((size_t)n2 * n2 * nq, 0.0L);
+      for (int i = 0; i < nq; ++i) {
+        const ldbl th = (i + 1) * kPiL / (nq + 1), x = cosl(th), s = sinl(th);
+        wp[i] = kPiL / (nq + 1) * s * s;
+        for (int l = 0; l < n2; ++l) {
+          ldbl sl = 1.0L; for (int j = 0; j < l; ++j) sl *= s;
+          for (int q = l; q < n2; ++q) Tp[((size_t)q * n2 + l) * nq + i] = sl * gbar_l(q - l, l, x);
+        }
+      }
+      std::vector<ldbl> t; gauss_legendre_l(nq, t, wl);
+      Pl.assign((size_t)n2 * n2 * nq, 0.0L);
+      for (int i = 0; i < nq; ++i) {
+        const ldbl x = t[i], s = sqrtl(1.0L - x * x);
+        for (int l = 0; l < n2; ++l) for (int m = 0; m <= l; ++m) Pl[((size_t)l * n2 + m) * nq + i] = pbar_l(l, m, x, s);
+      }
+    } else {
+      // sin t cos t dt = dx / 4 with x = cos 2t; the integrand is a polynomial of degree <= 2 n_end - 2 in x
+      std::vector<ldbl> xg; gauss_legendre_l(nq, xg, wp);
+      for (int i = 0; i < nq; ++i) wp[i] *= 0.25L;
+      crow.assign((size_t)n2 * n2 * n2, -1);
+      int rows = 0;
+      for (size_t l = 0; l < deg2.size(); ++l) {
+        int& r = crow[((size_t)labels2[3 * l] * n2 + iabs(labels2[3 * l + 1])) * n2 + iabs(labels2[3 * l + 2])];
+        if (r < 0) r = rows++;
+        pos2[skey(labels2[3 * l], labels2[3 * l + 1], labels2[3 * l + 2])] = (int)l;
+      }
+      Tp.assign((size_t)rows * nq, 0.0L);
+      for (int q = 0; q < n2; ++q) for (int a = 0; a <= q; ++a) for (int b = 0; a + b <= q; ++b) {
+        const int r = crow[((size_t)q * n2 + a) * n2 + b];
+        if (r < 0) continue;
+        for (int i = 0; i < nq; ++i) Tp[(size_t)r * nq + i] = cbar_l(q, a, b, sqrtl(0.5L * (1.0L + xg[i])), sqrtl(0.5L * (1.0L - xg[i])));
       }
     }
+  }
+
+  // bba: A4 over (q'' from |q - q'| in steps of 2, l'' from |l - l'| in steps of 2 while l'' <= min(l + l', q'')), the order of entry()
+  const std::vector<double>& polar_bba(int qp, int lp, int q, int l) {
+    int ka = qp * n2 + lp, kb = q * n2 + l;
+    if (ka > kb) std::swap(ka, kb);
+    std::vector<double>& v = polar[(unsigned long long)ka * n2 * n2 + kb];
+    if (!v.empty()) return v;
+    const ldbl* a = &Tp[(size_t)ka * nq]; const ldbl* b = &Tp[(size_t)kb * nq];
+    for (int q2 = iabs(q - qp); q2 <= q + qp; q2 += 2)
+      for (int l2 = iabs(l - lp); l2 <= l + lp && l2 <= q2; l2 += 2)
+        v.push_back(resolved_sum(nq, wp.data(), a, b, &Tp[((size_t)q2 * n2 + l2) * nq], 1.0L));
+    return v;
+  }
+  // bba: the real Gaunt-type integral over S^2 of Ybar' conj(Ybar) conj(Ybar''), m'' = m' - m, over l'' from |l - l'| in steps of 2
+  const std::vector<double>& gaunt_bba(int lp, int mp, int l, int m) {
+    const int mu = iabs(mp - m);
+    int ka = lp * n2 + iabs(mp), kb = l * n2 + iabs(m);
+    if (ka > kb) std::swap(ka, kb);
+    std::vector<double>& v = gaunt[((unsigned long long)ka * n2 * n2 + kb) * 2 + (mu == iabs(mp) + iabs(m) ? 1 : 0)];
+    if (!v.empty()) return v;
+    const ldbl* a = &Pl[(size_t)ka * nq]; const ldbl* b = &Pl[(size_t)kb * nq];
+    const ldbl inv_sqrt_2pi = 1.0L / sqrtl(2.0L * kPiL);
+    for (int l2 = iabs(l - lp); l2 <= l + lp; l2 += 2)
+      v.push_back(l2 < mu ? 0.0 : resolved_sum(nq, wl.data(), a, b, &Pl[((size_t)l2 * n2 + mu) * nq], inv_sqrt_2pi));
+    return v;
+  }
+  // caa: int cbar' cbar cbar'' sin cos dt over q'' from |q - q'| in steps of 2, (a'', b'') = (|m1' - m1|, |m2' - m2|)
+  const std::vector<double>& polar_caa(int qp, int m1p, int m2p, int q, int m1, int m2) {
+    const int a3 = iabs(m1p - m1), b3 = iabs(m2p - m2);
+    int ka = crow[((size_t)qp * n2 + iabs(m1p)) * n2 + iabs(m2p)], kb = crow[((size_t)q * n2 + iabs(m1)) * n2 + iabs(m2)];
+    if (ka > kb) std::swap(ka, kb);
+    const unsigned long long rows = Tp.size() / nq;
+    std::vector<double>& v = polar[(((unsigned long long)ka * rows + kb) * 2 + (a3 == iabs(m1p) + iabs(m1) ? 1 : 0)) * 2 + (b3 == iabs(m2p) + iabs(m2) ? 1 : 0)];
+    if (!v.empty()) return v;
+    const ldbl* a = &Tp[(size_t)ka * nq]; const ldbl* b = &Tp[(size_t)kb * nq];
+    for (int q2 = iabs(q - qp); q2 <= q + qp; q2 += 2)
+      v.push_back(q2 < a3 + b3 ? 0.0 : resolved_sum(nq, wp.data(), a, b, &Tp[(size_t)crow[((size_t)q2 * n2 + a3) * n2 + b3] * nq], 1.0L));
+    return v;
+  }
+
+  // appends the terms of entry (row h, column h') to coef, tidx
+  void entry(int h, int hp, std::vector<double>& coef, std::vector<int>& tidx) {
+    const int q = labels[3 * h], qp = labels[3 * hp];
+    if (tree == TREE_BBA) {
+      const int l = labels[3 * h + 1], m = labels[3 * h + 2], lp = labels[3 * hp + 1], mp = labels[3 * hp + 2], mu = mp - m;
+      const std::vector<double>& A4 = polar_bba(qp, lp, q, l);
+      const std::vector<double>& G3 = gaunt_bba(lp, mp, l, m);
+      size_t k = 0;
+      for (int q2 = iabs(q - qp); q2 <= q + qp; q2 += 2)
+        for (int l2 = iabs(l - lp), j = 0; l2 <= l + lp && l2 <= q2; l2 += 2, ++j, ++k) {
+          const double v = A4[k] * G3[j];
+          if (v == 0.0) continue;               // a rule (l'' < |m''|) or a resolved zero of either integral
+          coef.push_back(isign_even(q + q2 - qp) * v);
+          tidx.push_back(q2 * (q2 + 1) * (2 * q2 + 1) / 6 + l2 * l2 + l2 + mu);
+        }
+    } else {
+      // int Y' conj(Y) conj(Y'') = delta(m1'' = m1' - m1) delta(m2'' = m2' - m2) / (2 pi) * the polar integral
+      const int m1 = labels[3 * h + 1], m2 = labels[3 * h + 2], m1p = labels[3 * hp + 1], m2p = labels[3 * hp + 2];
+      const std::vector<double>& I3 = polar_caa(qp, m1p, m2p, q, m1, m2);
+      size_t k = 0;
+      for (int q2 = iabs(q - qp); q2 <= q + qp; q2 += 2, ++k) {
+        if (I3[k] == 0.0) continue;             // the rule q'' < |m1''| + |m2''| or a resolved zero
+        coef.push_back(isign_even(q + q2 - qp) * I3[k] / (2.0 * kPi));
+        tidx.push_back(pos2.at(skey(q2, m1p - m1, m2p - m2)));
+      }
+    }
+  }
+};
+
+static int terms_4d(biem_plan* p) {
+  Terms4 t; t.init(p->tree, p->n_end);
+  const int H = p->H;
+  for (int h = 0; h < H; ++h) for (int hp = 0; hp < H; ++hp) {
+    t.entry(h, hp, p->coef, p->tidx);
+    if (p->coef.size() > 0xffffffffULL) { set_error("n_end=%d: more than 2^32 translation terms", p->n_end); return BIEM_ERR_UNSUPPORTED; }
     p->ptr[(size_t)h * H + hp + 1] = (uint32_t)p->coef.size();
   }
+  return BIEM_OK;
+}
+
+// the term list of one entry of bba / caa without a plan; the tables of the last (tree, n_end) asked for are kept between calls
+int plan_entry_terms(int tree, int n_end, int hp, int h, std::vector<double>& coef, std::vector<int>& tidx) {
+  static std::mutex mu;
+  static std::unique_ptr<Terms4> kept;
+  if (tree != TREE_BBA && tree != TREE_CAA) { set_error("biem_plan_entry_terms: tree id %d (built: bba, caa)", tree); return BIEM_ERR_UNSUPPORTED; }
+  if (n_end < 1 || n_end > 64) { set_error("biem_plan_entry_terms: n_end=%d out of range (1 .. 64)", n_end); return BIEM_ERR_ARG; }
+  std::lock_guard<std::mutex> lock(mu);
+  if (!kept || kept->tree != tree || kept->n != n_end) { kept.reset(new Terms4()); kept->init(tree, n_end); }
+  if (h < 0 || h >= kept->H || hp < 0 || hp >= kept->H) { set_error("biem_plan_entry_terms: entry (%d, %d) outside the %d harmonics of n_end=%d", hp, h, kept->H, n_end); return BIEM_ERR_ARG; }
+  coef.clear(); tidx.clear();
+  kept->entry(h, hp, coef, tidx);
+  return BIEM_OK;
 }
 
 // int Y' conj(Y) conj(Y'') = delta(m'' = m' - m) / sqrt(2 pi) * prod_j I_j, I_j = int (1-x^2)^{(d-j-3)/2} f'_j f_j f''_j dx over
@@ -501,8 +665,7 @@ static int build_terms(biem_plan* p) {
   switch (p->tree) {
     case TREE_A: terms_a(p); break;
     case TREE_BA: terms_ba(p); break;
-    case TREE_BBA: terms_bba(p); break;
-    case TREE_CAA: terms_caa(p); break;
+    case TREE_BBA: case TREE_CAA: return terms_4d(p);
     default: return terms_chain(p);
   }
   return BIEM_OK;

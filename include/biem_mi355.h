@@ -113,6 +113,11 @@ int biem_plan_projection(const biem_plan* plan, double* h_W);
 /* translation terms in CSR over entries e = h*H + h' (row h = test index, column h' = unknown):
  * (S|R)_{h'->h}(t) = sum_{p in [ptr[e],ptr[e+1])} coef[p] * T[tidx[p]],  T[l] = C_d h_{n''}(k|t|) Y_l(t^), l over labels of degree < 2 n_end - 1 */
 int biem_plan_terms(const biem_plan* plan, long long* h_ptr /*[H*H+1]*/, double* h_coef, int* h_tidx);
+/* the term list of ONE entry (row h_row, column h_col: the slice [ptr[e], ptr[e+1]) of biem_plan_terms at e = h_row*H + h_col) of
+ * tree bba (2) or caa (3) at order n_end (1 .. 64), by the code the plan build runs but without building a plan (host only; a plan at
+ * n_end 22 holds hundreds of millions of terms).  *n_terms = terms of the entry; they are written while n_terms <= capacity, otherwise
+ * BIEM_ERR_ARG and nothing is written.  The integral tables of the last (tree, n_end) are kept between calls. */
+int biem_plan_entry_terms(int tree, int n_end, int h_col, int h_row, int capacity, int* n_terms, double* h_coef, int* h_tidx);
 /* coupling table of the radiation force, T^i_{h'h} = int y_i Y_h conj(Y_h') dOmega, in CSR over the rows h': entry p in
  * [ptr[h'], ptr[h'+1]) is T^{comp[p]}_{h', col[p]} = val[p] (complex128), ordered by (component, column) within a row.  Hermitian in
  * (h', h), entries only where |n - n'| = 1.  Built on the first request (this call or biem_force; host work only unless the plan is

@@ -372,7 +372,7 @@ def _gaunt3(n_end: int):
 def _theta4(n_end: int):
     """A4[(n'l'), (n l), n'', l''] = int Abar_{n'l'} Abar_{nl} Abar_{n''l''} sin^2 dtheta (type-b root of bba)."""
     n2 = 2 * n_end - 1
-    t, w = _gauss_cheb2(2 * n_end)                                  # weight sqrt(1-t^2) = one sin of sin^2 dtheta
+    t, w = _gauss_cheb2(3 * n_end + 3)                              # weight sqrt(1-t^2) = one sin of sin^2 dtheta
     s = np.sqrt(1 - t * t)
     Ab = np.zeros((n2, n2, len(t)))                                 # [n, l, q]
     for l in range(n2):
@@ -382,10 +382,12 @@ def _theta4(n_end: int):
     nl = [(n, l) for n in range(n_end) for l in range(n + 1)]
     An = np.array([Ab[n, l] for (n, l) in nl])                      # [NL, q]
     A4 = np.einsum("aq,bq,nlq,q->abnl", An, An, Ab, w, optimize=True)
-    # quadrature noise on entries that vanish by the selection rules.  The noise grows with the order (3e-14 at n_end = 15, where a
-    # 1e-14 cut let some of it through: 1.6e-10 in u_scat of two close spheres against the same table from a 3 n_end-node rule);
-    # entries that do not vanish are >= 1e-9 up to n_end = 15, so 1e-12 separates the two
-    A4[np.abs(A4) < 1e-12] = 0.0
+    # Entries that vanish (by the selection rules, or with no rule behind them) come out as quadrature rounding, and rounding let through
+    # as a coefficient cost 1.6e-10 in u_scat of two close spheres at n_end = 15.  An entry is zero where it lies within 1024 roundings
+    # of the sum of its own moduli, sum |w a b c|.  Entries that do not vanish fall with the order without bound (1e-8 at n_end 15,
+    # 2e-10 at 18) and reach that bound near n_end 21: beyond it float64 cannot tell them from rounding and this table is no reference.
+    mag = np.einsum("aq,bq,nlq,q->abnl", np.abs(An), np.abs(An), np.abs(Ab), w, optimize=True)
+    A4[np.abs(A4) <= 1024 * np.finfo(np.float64).eps * mag] = 0.0
     return A4, nl, Ab
 
 

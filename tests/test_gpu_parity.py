@@ -1120,9 +1120,15 @@ def test_sharded_solve_on_rccl_world_size_one(amd):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("form", ["default", "red", "entry", "sys"])
-@pytest.mark.parametrize("tree,n_end,B,robin", [("a", 9, 3, False), ("a", 40, 4, True), ("ba", 6, 3, True), ("ba", 12, 2, False), ("bba", 4, 3, True), ("caa", 4, 2, False),
-                                                ("bbba", 4, 3, True), ("bbbbbba", 3, 2, False)])
+@pytest.mark.parametrize("tree,n_end,B,robin,form", [
+    case + (form,) for form in ["default", "red", "entry", "sys"]
+    for case in [("a", 9, 3, False), ("a", 40, 4, True), ("ba", 6, 3, True), ("ba", 12, 2, False), ("bba", 4, 3, True), ("caa", 4, 2, False),
+                 ("bbba", 4, 3, True), ("bbbbbba", 3, 2, False)]] + [
+    # the 4-D trees on either side of the general fill's pair-table switch (tests/test_gpu_fill_4d_ceiling.py), in the form the product
+    # runs and in the form without an order ceiling (the lane forms "red" / "entry" are refused where their tables do not fit LDS).
+    # caa n_end 14 is the plan whose reduced table needs eight prefetch registers per lane (k_fill_red<8, ..>: DESIGN.md 7c)
+    case + (form,) for form in ["default", "sys"]
+    for case in [("bba", 14, 2, True), ("bba", 15, 2, False), ("caa", 13, 2, False), ("caa", 14, 2, True)]])
 def test_symmetric_fill_vs_transformed_general_fill(amd, lib, tree, n_end, B, robin, form, monkeypatch):
     """BIEM_FILL_SYMMETRIC (what the L D L^T path factors, written once by the fused kernel) against R W^H M W R^-1 formed in
     NumPy from the general BIEM_FILL_EQUILIBRATED matrix, on everything the factorisation reads (upper triangle + diagonal
