@@ -88,6 +88,13 @@ EXPECTED_LDS_DMA_KLONG = 32
 # read back in front of the MFMA block) inside the loop.  The build before it had 15 and ran the bulk update measurably slower
 # (DESIGN.md section 5), so a compiler that brings them back is reported, not taken silently.
 MAX_LANE_SPILL_OPS_KLONG = 0
+# k_gemm3m_narrow<NF>, the K-long instance for the last tile column of a left-looking band (NF of the tile's four 16-column groups are
+# multiplied, the rest is identity padding): the text of the K-long kernel with shorter MFMA nests, so its pins hold - no scratch, no
+# spills, 32 LDS-DMA, 48 stores, no lane spills in the chunk loop - with 24 NF MFMAs per chunk, all in one loop, and no tile-map load.
+# Keys (NARROW, NF), handed out by check_isa_narrow().
+NARROW = "narrow"
+NARROW_NF = (1, 2, 3)
+MFMA_PER_FRAG = 24
 # k_gemm3m_strip, the product form of the K = 64 kernel (symmetric strip pass: no C slots, four DMAs per group): the same pins, under
 # the key STRIP, handed out by check_isa_strip().  In its chunk loop the vector-memory instructions are the ring's LDS-DMA alone: the
 # product form adds none.  24 = six groups of four (prologue, fused, unfused interior and clamped edge
@@ -207,7 +214,7 @@ def _prefetch_hazards(ins) -> list:
 
 def _label(kd) -> str:
     if isinstance(kd, tuple):
-        return f"k_back_sweep<{kd[1]}>" if kd[0] == SWEEP else f"k_gemm3m_stack<{kd[1]}>"
+        return f"k_back_sweep<{kd[1]}>" if kd[0] == SWEEP else f"k_gemm3m_narrow<{kd[1]}>" if kd[0] == NARROW else f"k_gemm3m_stack<{kd[1]}>"
     return "k_gemm3m_strip" if kd == STRIP else "k_sym_slab" if kd == SLAB else f"k_gemm3m_pipe<{kd}>"
 
 
@@ -244,7 +251,7 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = F
                     report[(SWEEP, int(m.group(1)))] = rep
                     if rep["scratch_bytes"] != 0 or rep["vgpr_spills"] != 0:
                         raise IsaCheckError(f"k_back_sweep<{m.group(1)}>: scratch {rep['scratch_bytes']} B, {rep['vgpr_spills']} VGPR spills")
-            gemm = [n for n in metas if "k_gemm3m_pipe" in n or "k_gemm3m_strip" in n or "k_gemm3m_stack" in n]
+            gemm = [n for n in metas if "k_gemm3m_pipe" in n or "k_gemm3m_strip" in n or "k_gemm3m_stack" in n or "k_gemm3m_narrow" in n]
             red = [n for n in metas if "k_fill_red" in n]
             if not gemm and not red:
                 continue
@@ -255,9 +262,11 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = F
                 if bad:
                     raise IsaCheckError(f"{name}: {len(bad)} instructions touch a prefetch register before its wait, first {bad[0]}")
             for name in gemm:
-                stack = "k_gemm3m_stack" in name
+                stack, narrow = "k_gemm3m_stack" in name, "k_gemm3m_narrow" in name
                 kd = STRIP if "k_gemm3m_strip" in name else (STACK, int(re.search(r"k_gemm3m_stackILi(\d+)E", name).group(1))) if stack else \
+                    (NARROW, int(re.search(r"k_gemm3m_narrowILi(\d+)E", name).group(1))) if narrow else \
                     int(re.search(r"k_gemm3m_pipeILi(\d+)E", name).group(1))
+                want_mfma = MFMA_PER_FRAG * kd[1] if narrow else MFMA_PER_CHUNK
                 label = _label(kd)
                 meta, ins = metas[name], dis[name]
                 loop, n_mfma = _chunk_loop(ins)
@@ -276,32 +285,33 @@ def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = F
                     bad.append(f"scratch {rep['scratch_bytes']} B")
                 if rep["vgpr_spills"] != 0:
                     bad.append(f"{rep['vgpr_spills']} VGPR spills")
-                if rep["mfma_in_chunk_loop"] != MFMA_PER_CHUNK or n_mfma != MFMA_PER_CHUNK:
-                    bad.append(f"{rep['mfma_in_chunk_loop']} MFMAs in the chunk loop, {n_mfma} in the kernel (expected {MFMA_PER_CHUNK})")
+                if rep["mfma_in_chunk_loop"] != want_mfma or n_mfma != want_mfma:
+                    bad.append(f"{rep['mfma_in_chunk_loop']} MFMAs in the chunk loop, {n_mfma} in the kernel (expected {want_mfma})")
                 extra = {op: c for op, c in vm.items() if op not in ("global_load_lds_dwordx4", "global_load_dword", "global_store_dwordx4")}
                 if (kd == STRIP or stack) and extra.get("global_load_dwordx4") == (EXPECTED_LOADS_STACK if stack else EXPECTED_LOADS_STRIP) and \
                         not any(op == "global_load_dwordx4" for _, op, _ in loop):
                     del extra["global_load_dwordx4"]
                 if extra:
                     bad.append(f"unexpected vector-memory instructions: {extra}")
-                want_dma = EXPECTED_LDS_DMA_STACK if stack else EXPECTED_LDS_DMA_STRIP if kd == STRIP else EXPECTED_LDS_DMA_KLONG if kd == KLONG else \
+                want_dma = EXPECTED_LDS_DMA_STACK if stack else EXPECTED_LDS_DMA_STRIP if kd == STRIP else EXPECTED_LDS_DMA_KLONG if kd == KLONG or narrow else \
                     EXPECTED_LDS_DMA.get(kd)
                 if vm.get("global_load_lds_dwordx4", 0) != want_dma:
                     bad.append(f"{vm.get('global_load_lds_dwordx4', 0)} LDS-DMA instructions (reviewed build: {want_dma})")
                 want_stores = EXPECTED_STORES_STACK if stack else EXPECTED_STORES_STRIP if kd == STRIP else EXPECTED_STORES
                 if vm.get("global_store_dwordx4", 0) != want_stores:
                     bad.append(f"{vm.get('global_store_dwordx4', 0)} result stores (reviewed build: {want_stores})")
-                if kd == KLONG and rep["lane_spill_ops_in_chunk_loop"] > MAX_LANE_SPILL_OPS_KLONG:
+                if (kd == KLONG or narrow) and rep["lane_spill_ops_in_chunk_loop"] > MAX_LANE_SPILL_OPS_KLONG:
                     bad.append(f"{rep['lane_spill_ops_in_chunk_loop']} lane-spill instructions in the chunk loop (reviewed build: {MAX_LANE_SPILL_OPS_KLONG})")
                 if stack and rep["lane_spill_ops_in_chunk_loop"] > MAX_LANE_SPILL_OPS_STACK:
                     bad.append(f"{rep['lane_spill_ops_in_chunk_loop']} lane-spill instructions in the chunk loop (reviewed build: {MAX_LANE_SPILL_OPS_STACK})")
-                if stack and vm.get("global_load_dword", 0) != 0:
-                    bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (the stacked pass reads no tile map)")
+                if (stack or narrow) and vm.get("global_load_dword", 0) != 0:
+                    bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (this launch reads no tile map)")
                 if vm.get("global_load_dword", 0) > MAX_TILE_MAP_LOADS:
                     bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (expected <= {MAX_TILE_MAP_LOADS})")
                 if bad:
                     raise IsaCheckError(f"{label}: the hand-counted vmcnt scheme is not safe with this code object: " + "; ".join(bad))
-    want = set(EXPECTED_LDS_DMA) | {KLONG, STRIP, SLAB} | {(STACK, k) for k in STACK_KD} | {(SWEEP, q) for q in SWEEP_NQ}
+    want = set(EXPECTED_LDS_DMA) | {KLONG, STRIP, SLAB} | {(STACK, k) for k in STACK_KD} | {(SWEEP, q) for q in SWEEP_NQ} | \
+        {(NARROW, f) for f in NARROW_NF}
     if set(report) != want:
         raise IsaCheckError(f"update kernels found: {sorted(report, key=str)}, expected {sorted(want, key=str)}")
     if verbose:
@@ -326,6 +336,12 @@ def check_isa_stack(lib_path: str = LIB) -> dict:
     """The reports of k_gemm3m_stack<KD>, keyed by KD, and of k_sym_slab under SLAB (same checks as check_isa, which raises for them as well)."""
     rep = check_isa(lib_path, _all_kernels=True)
     return {**{k: rep[(STACK, k)] for k in STACK_KD}, SLAB: rep[SLAB]}
+
+
+def check_isa_narrow(lib_path: str = LIB) -> dict:
+    """The reports of k_gemm3m_narrow<NF>, keyed by NF (same checks as check_isa, which raises for them as well)."""
+    rep = check_isa(lib_path, _all_kernels=True)
+    return {f: rep[(NARROW, f)] for f in NARROW_NF}
 
 
 def check_isa_sweep(lib_path: str = LIB) -> dict:

@@ -73,6 +73,7 @@ SIGNATURES = {
     "biem_sym_factor_solve_n": (_i, [_i, _i, _i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
     "biem_sym_update_form": (_i, [_i, _i, _i]),
     "biem_sym_form": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_sz)]),
+    "biem_gemm_narrow_frags": (_i, [_i, _i, _i, _i]),
     "biem_last_solve_split": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "biem_sym_factor": (_i, [_i, _i, _dp, _ll, _ll, _ip, _vp, _sz, _vp]),
     "biem_sym_solve": (_i, [_i, _i, _i, _dp, _ll, _ll, _dp, _ll, _ll, _vp]),

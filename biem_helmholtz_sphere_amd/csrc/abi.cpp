@@ -344,6 +344,7 @@ int biem_sym_factor_solve_n(int nb, int n_pad, int n_active, int nrhs, double* d
 
 int biem_sym_update_form(int nb, int n_pad, int nrhs) { return sym_update_left(nb, n_pad, nrhs); }
 int biem_sym_form(int nb, int n_pad, int n_active, int nrhs, int* form, size_t* work) { return sym_form_query(nb, n_pad, n_active, nrhs, form, work); }
+int biem_gemm_narrow_frags(int nb, int n_pad, int n_active, int J) { return sym_gemm_narrow(nb, n_pad, n_active, J); }
 
 int biem_density(const biem_plan* plan, int nb, int B, int nrhs, const double* d_x, long long sys_stride, long long elem_stride,
                  long long rhs_stride, const double* d_tab, double* d_density, void* stream) {

@@ -211,6 +211,7 @@ int launch_lu_factor_solve(int nb, int n_pad, int nrhs, double* d_A, long long l
 // (the form of a call is decided in one place, sym_form in kernels_sym.hip; these read single decisions of it)
 int sym_update_left(int nb, int n_pad, int nrhs);  // form of the bulk update launch_sym_factor_solve runs for this call: 1 left-looking, 0 right-looking
 bool sym_small_path(int n_active, int nrhs);      // whether launch_sym_factor_solve takes its one-launch LDS-resident path
+int sym_gemm_narrow(int nb, int n_pad, int n_active, int J);   // column groups the left-looking band at row J multiplies in its last tile column (4: all)
 // the whole form and the workspace layout of a call as numbers (biem_sym_form); host only
 __attribute__((visibility("hidden"))) int sym_form_query(int nb, int n_pad, int n_active, int nrhs, int* form, size_t* work);
 // (n_active: rows n_active .. n_pad-1 are identity padding; systems of at most 128 active rows run in one LDS-resident launch)

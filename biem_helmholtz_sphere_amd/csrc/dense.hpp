@@ -131,7 +131,10 @@ int launch_gemm_stream(hipStream_t st, int nb, cplx* A, long long lda, long long
                        int prof_class = PK_GEMM, double prof_work = -1.0, cplx* pout = nullptr, long long pout_ld = 0,
                        long long pout_stride = 0, int pcol_tx = 0, const int* tri_map = nullptr, bool upper = false);
 // the K-long left-looking update of the row form: A[J:row_end, J:col_end] -= U[0:J, J:row_end]^T U[0:J, J:col_end]
-int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, int J, int row_end, int col_end);
+// nf < 4: col_end ends the last matrix tile column, of which only the column groups 0 .. nf-1 are multiplied (gemm_narrow_frags)
+int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, int J, int row_end, int col_end, int nf = 4);
+// the rule of that split for the band at row J: the column groups to multiply, 4 = the launch stays whole (mode: BIEM_GEMM_NARROW, -1 unset)
+int gemm_narrow_frags(int nb, int n_pad, int n_active, int J, int mode);
 // the strip of panel j of the symmetric factorisation as a pure product: A[j:j+64, j+64:col_end] = -V^T A[j:j+64, j+64:col_end] (pass V - j);
 // with Y (compact Y[s][q][row], y_ld rows per right-hand side, nrhs <= 8) also Y[.., c] -= U[j:j+64, c]^T Y[.., j:j+64] for the strip's columns
 int launch_gemm_strip(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, const cplx* V, long long v_stride, int j, int col_end,

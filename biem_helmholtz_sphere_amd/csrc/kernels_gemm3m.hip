@@ -103,9 +103,15 @@ __device__ __host__ inline void band_decode(int r, int h, int& ty, int& tx) {
   }
 }
 // ROW1: a launch of ONE tile row without a tile map (the stacked pass): tile r of a system is tile column r
-template <int KD, bool ROW1 = false>
+// COL1: a launch of ONE tile column without a tile map (the narrow launch of the left-looking update): tile r of a system is tile row r
+template <int KD, bool ROW1 = false, bool COL1 = false>
 __device__ inline void tile_decode_of(const TileGrid& tg, int t, int& s, int& ty, int& tx) {
-  if constexpr (ROW1) {
+  if constexpr (COL1) {
+    s = (int)(((unsigned long long)(unsigned)t * tg.per_sys_magic) >> 40);
+    ty = t - s * tg.per_sys;
+    if (ty >= tg.per_sys) { ty -= tg.per_sys; ++s; }
+    tx = 0;
+  } else if constexpr (ROW1) {
     s = (int)(((unsigned long long)(unsigned)t * tg.per_sys_magic) >> 40);
     tx = t - s * tg.per_sys;
     if (tx >= tg.per_sys) { tx -= tg.per_sys; ++s; }
@@ -211,9 +217,16 @@ __device__ unsigned long long g_gemm_trace[16][64][8];
 // Exactly one workgroup per (panel, tile column, system) touches those 64 entries: no atomics, two solves agree bit for bit.  Its
 // loads and stores are unknown to the ring's vmcnt counts: such a tile ends with stores_pending = 2 (vmcnt(0) at the next first chunk).
 struct StripRhs { cplx* Y; int nrhs; int ld; };   // Y == nullptr: none; ld = rows per right-hand side (n_pad)
-template <int KD, bool PROD, bool ROW1 = false>
+//
+// NF < 4 is the narrow K-long form (k_gemm3m_narrow<NF>): the tiles of the LAST tile column of a left-looking band whose column groups
+// n >= NF lie in the identity padding, where U is zero off the diagonal and the update a sum of exact zeros.  Only the 3M operand sums
+// and the MFMA nests run over n < NF (24 NF MFMAs per chunk); ring, fragment reads, C units, stores and every vmcnt count are those of
+// k_gemm3m_pipe<0>: the accumulators n >= NF carry their C unit and store it back.  Its launch is one tile column (COL1 decode).
+template <int KD, bool PROD, bool ROW1 = false, int NF = 4>
 __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda, long long sys_stride, const cplx* __restrict__ Pw,
                                             long long ldp, long long p_stride, const TileGrid& tg, const StripRhs& yr) {
+  static_assert(NF == 4 || (NF >= 1 && NF < 4 && KD == 0 && !PROD && !ROW1), "the narrow form exists for the K-long update only");
+  constexpr bool COL1 = NF < 4;
   static_assert(!PROD || KD == 64 || KD == 128 || KD == 192 || KD == 256, "the product form exists for K = 64 (strip) and K = 128 / 192 / 256 (stacked pass)");
   const int n_pad = tg.row_end, n_cols = tg.col_end;
   // KD = 0 is the K-long form of the left-looking update: the chunk count is a run-time value (TileGrid.nch = kd / 8 >= 16), the
@@ -259,7 +272,7 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   typedef const __attribute__((address_space(1))) void* glb_ptr_t;
   int cs, cty, ctx;
-  tile_decode_of<KD, ROW1>(tg, t, cs, cty, ctx);
+  tile_decode_of<KD, ROW1, COL1>(tg, t, cs, cty, ctx);
 
   const unsigned offA0 = (unsigned)(((size_t)(wave) * ldp + lane) * sizeof(cplx));
   const unsigned offA1 = (unsigned)(((size_t)(wave + 4) * ldp + lane) * sizeof(cplx));
@@ -336,7 +349,7 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
     pA += strideA; pB += strideB;
     if (++p_ch == NCH) {                                   // producer moves on to the next tile of this workgroup
       int tn = next_tile();
-      if (tn >= 0) { tile_decode_of<KD, ROW1>(tg, tn, p_s, p_ty, p_tx); producer_tile(); }
+      if (tn >= 0) { tile_decode_of<KD, ROW1, COL1>(tg, tn, p_s, p_ty, p_tx); producer_tile(); }
       else p_valid = false;
     }
   };
@@ -577,7 +590,7 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
         for (int g = 0; g < 4; ++g) fas[k4][g] = fa[k4][g].x;
 #else
 #pragma unroll
-        for (int n = 0; n < 4; ++n) fbs[k4][n] = fb[k4][n].x + fb[k4][n].y;
+        for (int n = 0; n < NF; ++n) fbs[k4][n] = fb[k4][n].x + fb[k4][n].y;
 #pragma unroll
         for (int g = 0; g < 4; ++g) fas[k4][g] = fa[k4][g].x + fa[k4][g].y;
 #endif
@@ -621,15 +634,15 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
 #pragma unroll
       for (int k4 = 0; k4 < 2; ++k4) {
 #pragma unroll
-        for (int n = 0; n < 4; ++n)
+        for (int n = 0; n < NF; ++n)
 #pragma unroll
           for (int g = 0; g < 4; ++g) mfma_acc_neg(N1[n][g], fa[k4][g].x, fb[k4][n].x);
 #pragma unroll
-        for (int n = 0; n < 4; ++n)
+        for (int n = 0; n < NF; ++n)
 #pragma unroll
           for (int g = 0; g < 4; ++g) mfma_acc(P2[n][g], fa[k4][g].y, fb[k4][n].y);
 #pragma unroll
-        for (int n = 0; n < 4; ++n)
+        for (int n = 0; n < NF; ++n)
 #pragma unroll
           for (int g = 0; g < 4; ++g) mfma_acc_neg(N3[n][g], fas[k4][g], fbs[k4][n]);
       }
@@ -771,6 +784,13 @@ __global__ void __launch_bounds__(256, 2) k_gemm3m_pipe(cplx* __restrict__ A, lo
                                                          TileGrid tg) {
   gemm3m_body<KD, false>(A, lda, sys_stride, Pw, ldp, p_stride, tg, StripRhs{nullptr, 0, 0});
 }
+// the narrow K-long form: the last tile column of a left-looking band, column groups n < NF only (gemm3m_body; launch_gemm_left)
+template <int NF>
+__global__ void __launch_bounds__(256, 2) k_gemm3m_narrow(cplx* __restrict__ A, long long lda, long long sys_stride,
+                                                           const cplx* __restrict__ Pw, long long ldp, long long p_stride,
+                                                           TileGrid tg) {
+  gemm3m_body<0, false, false, NF>(A, lda, sys_stride, Pw, ldp, p_stride, tg, StripRhs{nullptr, 0, 0});
+}
 // the strip pass of the symmetric factorisation, U12 = U11^{-T} C as the pure product -V^T C with V = -U11^{-T} (64 x 64 per system, K = 64)
 __global__ void __launch_bounds__(256, 2) k_gemm3m_strip(cplx* __restrict__ A, long long lda, long long sys_stride,
                                                           const cplx* __restrict__ Pw, long long ldp, long long p_stride,
@@ -886,17 +906,64 @@ int launch_gemm_stack(hipStream_t st, int nb, cplx* A, long long lda, long long 
 // of the finished rows 0 .. J-1 in one K-long pass,
 //   A[J:row_end, J:col_end] -= U[0:J, J:row_end]^T U[0:J, J:col_end]      (tiles with tx >= ty only)
 // Both operands are rows of the matrix itself (Pw = A, brow = 0, kd = J); every tile reads and writes its C once.
-int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, int J, int row_end, int col_end) {
+//
+// nf < 4 (gemm_narrow_frags below): col_end is the end of the last matrix tile column, whose column groups nf .. 3 are identity padding.
+// The launch then splits in two that write disjoint tiles and read finished rows only: the band without its last tile column
+// (k_gemm3m_pipe<0>; nothing where that column is the whole band), and the last column's min(h, w) tiles per system, which multiply
+// nf of their four column groups (k_gemm3m_narrow<nf>, one tile column starting at col_begin).  Both count in PK_GEMM; the narrow
+// launch's work is that of its active column groups, so the class's flops stay executed flops.
+static int launch_gemm_narrow_col(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, int J, int row_end, int col_end,
+                                  int h_last, int nf);
+int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, int J, int row_end, int col_end, int nf) {
   if (J <= 0 || row_end <= J || col_end < row_end) return BIEM_OK;
+  if (nf < 1 || nf > 4 || (nf < 4 && (col_end - J) % BN3 != 0)) { set_error("biem_sym: narrow bulk update over a partial tile column"); return BIEM_ERR_ARG; }
   TileGrid tg;
   tg.pout = nullptr; tg.pout_ld = 0; tg.pout_stride = 0; tg.pcol_tx = 0; tg.tri = 0; tg.tri_map = nullptr; tg.full_bands = 0;
-  tg.ty_n = (row_end - J) / BM3; tg.tx_n = (col_end - J + BN3 - 1) / BN3;
-  const int grid = finish_tile_grid(tg, band_tiles(tg.ty_n, tg.tx_n), nb);
+  tg.ty_n = (row_end - J) / BM3; tg.tx_n = (col_end - J + BN3 - 1) / BN3 - (nf < 4 ? 1 : 0);
+  tg.row_begin = J; tg.row_end = row_end; tg.col_begin = J; tg.col_end = col_end - (nf < 4 ? BN3 : 0); tg.brow = 0;
+  if (tg.tx_n > 0) {
+    const int grid = finish_tile_grid(tg, band_tiles(tg.ty_n, tg.tx_n), nb);
+    if (grid == 0) return BIEM_ERR_ARG;
+    tg.nch = J / KC;                                  // (shares tri_full's word: set after the tile map's fields)
+    ProfScope ps(PK_GEMM, st, 8.0 * (double)nb * (double)tg.per_sys * BM3 * BN3 * (double)J);
+    hipLaunchKernelGGL(k_gemm3m_pipe<0>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, A, lda, sys_stride, tg);
+  }
+  if (nf == 4) return BIEM_OK;
+  return launch_gemm_narrow_col(st, nb, A, lda, sys_stride, J, row_end, col_end, tg.ty_n < tg.tx_n + 1 ? tg.ty_n : tg.tx_n + 1, nf);
+}
+// the narrow launch: the tile rows 0 .. h_last-1 of the band at row J in the tile column that ends at col_end - tile row r of a system
+// at tile column 0 of a region that starts at that column
+static int launch_gemm_narrow_col(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, int J, int row_end, int col_end,
+                                  int h_last, int nf) {
+  TileGrid tg;
+  tg.pout = nullptr; tg.pout_ld = 0; tg.pout_stride = 0; tg.pcol_tx = 0; tg.tri = 0; tg.tri_map = nullptr; tg.full_bands = 0;
+  tg.ty_n = (row_end - J) / BM3; tg.tx_n = 1;
+  tg.row_begin = J; tg.row_end = row_end; tg.col_begin = col_end - BN3; tg.col_end = col_end; tg.brow = 0;
+  const int grid = finish_tile_grid(tg, h_last, nb);
   if (grid == 0) return BIEM_ERR_ARG;
-  tg.row_begin = J; tg.row_end = row_end; tg.col_begin = J; tg.col_end = col_end; tg.brow = 0; tg.nch = J / KC;
-  ProfScope ps(PK_GEMM, st, 8.0 * (double)nb * (double)tg.per_sys * BM3 * BN3 * (double)J);
-  hipLaunchKernelGGL(k_gemm3m_pipe<0>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, A, lda, sys_stride, tg);
+  tg.nch = J / KC;
+  ProfScope ps(PK_GEMM, st, 8.0 * (double)nb * (double)tg.per_sys * BM3 * 16.0 * nf * (double)J);
+  if (nf == 1) hipLaunchKernelGGL(k_gemm3m_narrow<1>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, A, lda, sys_stride, tg);
+  else if (nf == 2) hipLaunchKernelGGL(k_gemm3m_narrow<2>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, A, lda, sys_stride, tg);
+  else hipLaunchKernelGGL(k_gemm3m_narrow<3>, dim3(grid), dim3(256), 0, st, A, lda, sys_stride, A, lda, sys_stride, tg);
   return BIEM_OK;
+}
+
+// Whether launch_gemm_left splits the last tile column off the band at row J of an n_pad system with n_active active rows and columns
+// (the factorisation ending at column n_pad): the column groups of that tile column to multiply, NF = ceil((64 - padding) / 16), or 4
+// where the launch stays whole - padding below 16 columns, or too few narrow tiles.  The narrow launch holds min(h, w) tiles per system
+// (h = min(4, w) tile rows, w = T - J / 64 tile columns): below GEMM_GRID_CAP tiles a few K = J tiles would run on part of the chip
+// while the rest of the band has finished, so the launch splits only from one tile per workgroup of the persistent grid - or where the
+// last column is the whole band and nothing is split at all.  (512 is reasoned, not measured: DESIGN.md section 5.)
+// mode: BIEM_GEMM_NARROW - 0 never, 1 without the size rule, anything else the rule.
+int gemm_narrow_frags(int nb, int n_pad, int n_active, int J, int mode) {
+  if (mode == 0 || J <= 0 || J >= n_pad || n_active > n_pad || n_active <= n_pad - BN3) return 4;
+  const int nf = (BN3 - (n_pad - n_active) + 15) / 16;
+  if (nf >= 4) return 4;
+  const int w = (n_pad - J) / NB, h = w < 4 ? w : 4;      // (h <= w: the narrow launch has h tiles per system)
+  const bool whole_band = w == 1;
+  if (mode != 1 && !whole_band && (long long)h * nb < GEMM_GRID_CAP) return 4;
+  return nf;
 }
 
 // Which form of the bulk update launch_sym_factor_solve runs by default (sym_form, kernels_sym.hip: SymForm.left): left-looking
@@ -1008,6 +1075,30 @@ extern "C" int biem_debug_gemm_left(int nb, int n, int kd, int reps, float* ms_o
   *tiles_out = nb * band_tiles(4, n / 64);
   hipFree(A);
   return hipGetLastError() != hipSuccess;
+}
+// the narrow launch alone: the four tiles per system of the last tile column of a four-row band at J = kd (k_gemm3m_narrow<nf>); nf = 4:
+// four full K-long tiles per system for comparison (k_gemm3m_pipe<0> on a one-row band of four tile columns).  Either way nb * 4
+// tiles of K = kd; up to 128 systems every tile has a workgroup of its own, from 64 systems every CU holds two
+extern "C" int biem_debug_gemm_narrow(int nb, int kd, int nf, int reps, float* ms_out, int* tiles_out) {
+  const long long lda = kd + 256 + 8, rows = kd + 256;
+  cplx* A = nullptr;
+  const size_t na = (size_t)nb * rows * lda;
+  if (nf < 1 || nf > 4 || kd < 128 || kd % 8 || hipMalloc((void**)&A, na * sizeof(cplx)) != hipSuccess) return 1;
+  hipLaunchKernelGGL(k_trace_fill, dim3(2048), dim3(256), 0, 0, (double*)A, na * 2);
+  hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+  auto launch = [&]() {
+    return nf == 4 ? launch_gemm_left(0, nb, A, lda, rows * lda, kd, kd + 64, kd + 256)
+                   : launch_gemm_narrow_col(0, nb, A, lda, rows * lda, kd, kd + 256, kd + 256, 4, nf);
+  };
+  int rc = launch();
+  hipDeviceSynchronize();
+  hipEventRecord(e0, 0);
+  for (int r = 0; r < reps && rc == 0; ++r) rc = launch();
+  hipEventRecord(e1, 0); hipEventSynchronize(e1);
+  float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_out = ms / reps;
+  *tiles_out = nb * 4;
+  hipFree(A);
+  return rc != 0 || hipGetLastError() != hipSuccess;
 }
 // one small update launch, as a single system sees it: C[r0 : r0 + rows, 0 : n] -= P^T M[brow ..], `reps` launches back to back; cold = 1:
 // every launch takes another row strip (the matrix is far larger than the caches), cold = 0: the same one

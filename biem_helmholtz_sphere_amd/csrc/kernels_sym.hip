@@ -890,11 +890,14 @@ __global__ void __launch_bounds__(256, 2) k_sym_slab(const cplx* __restrict__ A,
 // the rule in place for BIEM_SYM_UPDATE, BIEM_SYM_GROUP and BIEM_DIAG_FORM; for BIEM_BACK_FORM it selects the row form (any value
 // that starts with neither c nor s does); BIEM_NO_SMALL_PATH counts as soon as it is set, whatever its value.
 // A sixth, BIEM_BACK_ROW=blocks, picks no form: inside the row form it runs the per-block launches (k_back_row) instead of the sweep.
-struct SymEnv { int update, group, back, diag; bool no_small; int back_row; };
+// A seventh, BIEM_GEMM_NARROW=0|1, picks no form either: under the left-looking update it turns the narrow launch of the last tile column
+// off, or drops its size rule (gemm_narrow_frags, kernels_gemm3m.hip).
+struct SymEnv { int update, group, back, diag; bool no_small; int back_row; int narrow; };
 static SymEnv sym_env() {
   auto first = [](const char* name) { const char* e = getenv(name); return e ? (int)(unsigned char)e[0] : -1; };
+  const int nw = first("BIEM_GEMM_NARROW");
   return {first("BIEM_SYM_UPDATE"), first("BIEM_SYM_GROUP"), first("BIEM_BACK_FORM"), first("BIEM_DIAG_FORM"), getenv("BIEM_NO_SMALL_PATH") != nullptr,
-          first("BIEM_BACK_ROW")};
+          first("BIEM_BACK_ROW"), nw == '0' ? 0 : nw == '1' ? 1 : -1};
 }
 
 // the whole system fits LDS: one launch does everything (k_small_utu)
@@ -959,6 +962,7 @@ SymForm sym_form(int nb, int n_pad, int n_active, int nrhs) {
 int sym_update_left(int nb, int n_pad, int nrhs) { return left_rule(sym_env(), nb, n_pad, nrhs) ? 1 : 0; }
 bool sym_group_stacked(bool left, int nb) { return stacked_rule(sym_env(), left, nb); }
 bool sym_small_path(int n_active, int nrhs) { return small_rule(sym_env(), n_active, nrhs); }
+int sym_gemm_narrow(int nb, int n_pad, int n_active, int J) { return gemm_narrow_frags(nb, n_pad, n_active, J, sym_env().narrow); }
 
 int sym_aliases(const SymForm& f, const DenseWork& w, void* d_work, int nb, int n_pad, int nrhs, SymAliases& a) {
   a = SymAliases{nullptr, nullptr, nullptr, 0, 0, 0, 0};
@@ -1079,13 +1083,17 @@ static int sym_factor(const SymForm& f, const SymCall& c) {
   // the strip became a pure product and the right-hand sides left the matrix; this form runs only where the launches are large.
   // DESIGN.md section 5 has both measurements.)
   cplx* const slab = f.stacked ? c.slab : nullptr;
+  const int narrow_mode = sym_env().narrow;
   for (int J = 0; J < n_pad; J += 4 * NB) {
     const cplx* strip = A + (size_t)J * lda;        // both operands of this group's updates: rows J .. of the matrix itself
     if (f.left && J > 0) {
       // left-looking: the group's rows take every pending update of the finished rows 0 .. J-1 now, in one K = J pass (many right-hand
       // sides: tile columns of the same launch; few: not in the matrix at all)
       const int row_end = J + 4 * NB < n_pad ? J + 4 * NB : n_pad;
-      keep(launch_gemm_left(st, nb, A, lda, sys_stride, J, row_end, f_cols));
+      // (the last tile column's identity padding is not multiplied where that pays: a narrow launch of its own, gemm_narrow_frags;
+      // right-hand sides as tile columns behind it: the launch stays whole)
+      const int nf = f_cols > n_pad ? 4 : gemm_narrow_frags(nb, n_pad, c.n_active, J, narrow_mode);
+      keep(launch_gemm_left(st, nb, A, lda, sys_stride, J, row_end, f_cols, nf));
     }
     panel(J);
     for (int q = 1; q < 4; ++q) {

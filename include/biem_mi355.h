@@ -234,6 +234,15 @@ int biem_sym_update_form(int nb, int n_pad, int nrhs);
 #define BIEM_SYM_FORM_LEN 9
 #define BIEM_SYM_WORK_LEN 11
 int biem_sym_form(int nb, int n_pad, int n_active, int nrhs, int* form, size_t* work);
+/* The left-looking bulk update of the band at row J (a multiple of 256, 0 < J < n_pad) and the identity padding (host only, no GPU
+ * work).  The last tile column of an n_pad system holds n_pad - n_active padding columns, where U is zero off the diagonal; of its
+ * four 16-column groups only NF = ceil((64 - padding) / 16) need multiplying.  Returns NF in 1 .. 3 where the band's launch splits
+ * that tile column off into a narrow launch (min(h, w) tiles per system: h = min(4, w) tile rows, w = n_pad / 64 - J / 64 tile
+ * columns), and 4 where the launch stays whole: padding below 16 columns, or fewer than 512 narrow tiles over the nb systems unless
+ * the last tile column is the whole band (w = 1).  It describes calls whose right-hand sides are not tile columns of the update
+ * (nrhs <= 8); others stay whole.  BIEM_GEMM_NARROW=0 in the environment turns the split off, =1 drops the size rule only; read
+ * per call. */
+int biem_gemm_narrow_frags(int nb, int n_pad, int n_active, int J);
 /* How the last biem_solve_ldlt / biem_solve_ldlt_n call of this thread ran: npE = npO = 0 unsplit, otherwise the padded orders of the
  * two blocks it factored one after the other (biem_plan_split_order).  The split form runs for shared geometry (geom_batched = 0) of a
  * chain tree whose centres all have the same last coordinate (compared bit for bit on the host, -0.0 as 0.0: one small copy and one

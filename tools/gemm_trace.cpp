@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <vector>
 extern "C" int biem_debug_gemm_left(int nb, int n, int kd, int reps, float* ms_out, int* tiles_out);
+extern "C" int biem_debug_gemm_narrow(int nb, int kd, int nf, int reps, float* ms_out, int* tiles_out);
 extern "C" int biem_debug_gemm(int nb, int n, int kd, int reps, unsigned long long* trace_out, float* ms_out);
 int main(int argc, char** argv) {
   int nb = argc > 1 ? atoi(argv[1]) : 8, n = argc > 2 ? atoi(argv[2]) : 6272, kd = argc > 3 ? atoi(argv[3]) : 128;
@@ -14,6 +15,14 @@ int main(int argc, char** argv) {
     const double units = (double)tiles * kd / 256.0;
     printf("left nb=%d n=%d kd=%d  tiles=%d  %.3f ms  %.2f TFLOP/s (algorithmic)  %.4f us per tile and K-256 unit\n", nb, n, kd, tiles, ms,
            8.0 * tiles * 64.0 * 64.0 * kd / (ms * 1e-3) / 1e12, ms * 1e3 / units);
+    return 0;
+  }
+  if (argc > 4 && argv[4][0] == 'n') {   // gemm_trace nb nf kd narrow: the narrow launch alone, 4 tiles per system of nf column groups (nf = 4: full tiles)
+    float ms = 0; int tiles = 0;
+    if (biem_debug_gemm_narrow(nb, kd, n, 5, &ms, &tiles)) { printf("failed\n"); return 1; }
+    const double units = (double)tiles * kd / 256.0, rounds = (tiles + 511) / 512;
+    printf("narrow nb=%d nf=%d kd=%d  tiles=%d  %.4f ms  %.4f us per tile and K-256 unit  %.3f us per round and K-256 unit\n", nb, n, kd, tiles, ms,
+           ms * 1e3 / units, ms * 1e3 / (rounds * kd / 256.0));
     return 0;
   }
   std::vector<unsigned long long> tr(16 * 64 * 8);
