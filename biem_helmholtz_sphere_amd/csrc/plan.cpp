@@ -81,7 +81,10 @@ int plan_build_force(biem_plan* p) {
         for (size_t c = 0; c < cand[hp].size(); ++c) {
           const double vr = acc[((first[hp] + c) * d + i) * 2], vi = acc[((first[hp] + c) * d + i) * 2 + 1];
           const double mag = hypot(vr, vi);
-          // the values are O(1) algebraic numbers or exact zeros: anything between is a rule that was not exact
+          // the values are algebraic numbers or exact zeros.  They are not O(1): the smallest shrinks with order and dimension
+          // (7.2e-3 at ba 50, 1.15e-3 at bba 16, 3.0e-4 at bbba 10), but at the order ceilings of the field kernels and two orders
+          // above them it stays six decades above this band, and an independent rule leaves at most 3e-16 where an entry was dropped
+          // (tests/test_force_table_full_order_host.py asserts both margins).  Anything between is a rule that was not exact
           if (mag > 1e-14 && mag < 1e-10) {
             set_error("internal: force coupling entry (%d, %d) component %d of tree %d n_end %d has the size %.3e of neither a value nor rounding",
                       hp, cand[hp][c], i, p->tree, p->n_end, mag);

@@ -41,6 +41,56 @@ def density(w: np.ndarray, t: np.ndarray, deg: np.ndarray) -> np.ndarray:
     return (w.real * s) + 1j * (w.imag * s)
 
 
+HESS_FORCE_PATH = os.path.join(os.path.dirname(PATH), "full_order_hess_force.npz")
+
+
+def load_hess_force(path: str = HESS_FORCE_PATH) -> dict:
+    """{case id: record} of ``tests/golden/full_order_hess_force.npz`` (``tools/make_full_order_hess_force_fixtures.py``).
+
+    A force record has tree, n_end, regime, bc ("robin": the scalar pair alpha, beta; "fluid" / "transparent-top": alpha_n, beta_n
+    [B, n_end]), k, eta, radii [B], density [B, H], phi [B, d] (NaN for a ball whose expected output is NaN), cond [B], oracle_err [B].
+    A Hessian record (family "hess") has tree, kind, regime, n_end, k, eta, centers [B, d], radii [B], density [B, H], x [P, d],
+    valid [P], hess [d, d, P] (stored as its upper triangle), cond [P] (of the value series) and oracle_err [P] (the fp64 twin).
+    The launch-shape record (regime "batch") has k [S], radii [S, B], density [S, R, B, H] (right-hand side r is the table w rolled by
+    r harmonics) and phi [S, R, B, d], cond and oracle_err [S, R, B]."""
+    out = {}
+    with np.load(path, allow_pickle=False) as z:
+        for cid in json.loads(str(z["cases"])):
+            meta = json.loads(str(z[cid + "/meta"]))
+            rec = types.SimpleNamespace(id=cid, **meta)
+            for key in z.files:
+                if key.startswith(cid + "/") and key != cid + "/meta":
+                    setattr(rec, key[len(cid) + 1:], z[key])
+            rec.radii = np.array(meta["radii"])
+            rec.cond, rec.oracle_err = rec.caps.astype(np.float64)          # (the two admission figures, in single precision)
+            if "centers" in meta:
+                rec.centers = np.array(meta["centers"])
+            if "k_interior" in meta:
+                rec.density_ratio = np.array(meta["density_ratio"])
+                rec.k_interior = np.array([[complex(*v) for v in row] for row in meta["k_interior"]])
+                rec.k_interior = rec.k_interior[0] if rec.radii.ndim == 1 else rec.k_interior
+            deg = O.tree(rec.tree).degrees(rec.n_end)
+            w = z["w/" + rec.w].astype(np.complex128)          # (stored in single precision: exact fp64 numbers at half the size)
+            if rec.family == "hess":
+                rec.k = complex(*meta["k"]) if meta["k"][1] != 0.0 else float(meta["k"][0])
+                d = rec.x.shape[1]
+                iu = np.triu_indices(d)
+                rec.hess = np.empty((d, d, len(rec.x)), dtype=np.complex128)
+                rec.hess[iu] = rec.hess_upper
+                rec.hess[(iu[1], iu[0])] = rec.hess_upper
+                rec.density = density(w[:len(rec.radii)], rec.t, deg)
+                out[cid] = rec
+                continue
+            rec.alpha, rec.beta = complex(*meta["alpha"]), complex(*meta["beta"])
+            if rec.regime == "batch":
+                rec.k = np.array(meta["k"])
+                rec.density = np.stack([np.stack([density(np.roll(w, r, axis=1), t, deg) for r in range(rec.phi.shape[1])]) for t in rec.t])
+            else:
+                rec.density = density(w[:len(rec.radii)], rec.t, deg)
+            out[cid] = rec
+    return out
+
+
 def load(path: str = PATH) -> dict:
     """{case id: record}.  A record has tree, kind ("outer", "inner", "interior"), regime, n_end, k, eta, centers [B, d], radii [B],
     density [B, H], x [P, d], valid [P], value [P], cond [P], oracle_err [P] and, where the case has them, grad [d, P],

@@ -186,6 +186,29 @@ def _mp(v):
     return mp.mpf(v.real) if v.imag == 0.0 else mp.mpc(v.real, v.imag)
 
 
+HESS_STEPS = ("1e-10", "2e-10")
+STEP_AGREE = 1e-14
+
+
+def hessian_by_differences(F, x, step, mode: str = "near"):
+    """[d][d] mpc at one point (mpf list): second central differences of the sum over the balls of the 40-digit series of F."""
+    d = F.d
+    h = mp.mpf(step)
+    balls = F.balls(mode, x)
+
+    def f(shift):
+        y = [x[i] + shift.get(i, 0) * h for i in range(d)]
+        return mp.fsum(F.ball_sum(mode, b, y) for b in balls)
+
+    f0 = f({})
+    H = [[None] * d for _ in range(d)]
+    for i in range(d):
+        H[i][i] = (f({i: 1}) - 2 * f0 + f({i: -1})) / (h * h)
+        for j in range(i + 1, d):
+            H[i][j] = H[j][i] = (f({i: 1, j: 1}) - f({i: 1, j: -1}) - f({i: -1, j: 1}) + f({i: -1, j: -1})) / (4 * h * h)
+    return H
+
+
 # --------------------------------------------------------------------------------------
 # the evaluator
 # --------------------------------------------------------------------------------------
@@ -327,6 +350,19 @@ class MPField:
                 xm[i] -= step
                 g.append(mp.fsum(self.ball_sum(mode, b, xp) - self.ball_sum(mode, b, xm) for b in balls) / (2 * step))
             return g
+
+    def hessian(self, mode: str, x):
+        """Cartesian Hessian [d][d] of the sum over balls at one point: second central differences (diagonal) and four-point cross
+        differences of the high-precision field with the step HESS_STEPS[0], accepted only if the step HESS_STEPS[1] agrees within
+        STEP_AGREE of the largest component (truncation (step^2 / 12) f'''' and rounding 10^-DPS / step^2 are both near 1e-20)."""
+        with mp.workdps(DPS):
+            x = self._x(x)
+            one, two = (hessian_by_differences(self, x, s, mode) for s in HESS_STEPS)
+            scale = max(abs(v) for row in one for v in row)
+            worst = max(abs(one[i][j] - two[i][j]) for i in range(self.d) for j in range(self.d))
+            if worst > STEP_AGREE * scale:
+                raise ArithmeticError(f"second differences of steps {HESS_STEPS} differ by {float(worst / scale):.1e} of max |H|")
+            return one
 
     # ---- NumPy faces with the oracle's conventions -----------------------------------------------
     def _mode(self, far_field: bool, interior: bool) -> str:

@@ -12,13 +12,14 @@ import ctypes as C
 import math
 
 import numpy as np
+from scipy import sparse
 
 from biem_helmholtz_sphere_amd import _lib
 from oracle import biem_oracle as O
 
 from test_chain_trees_host import chain
 
-_TABLES = {}
+_TERMS, _SPARSE, _TABLES = {}, {}, {}
 
 
 def oracle_tree(name):
@@ -26,12 +27,12 @@ def oracle_tree(name):
     return O.tree(name) if name in O._TREES else chain(len(name) + 1)
 
 
-def plan_table(tree, n_end):
-    """(d, labels [H, lw], deg [H], T [d, H, H] dense) of the plan of a canonical tree (a, ba, bba, caa or a chain) at n_end;
-    computed once per (tree, n_end) and never modified."""
+def plan_terms(tree, n_end):
+    """(d, labels [H, lw], deg [H], ptr [H + 1], col, comp, val) of the plan of a canonical tree (a, ba, bba, caa or a chain) at n_end:
+    the coupling table as the plan lists it, rows h' in CSR order.  Computed once per (tree, n_end) and never modified."""
     key = (tree, n_end)
-    if key in _TABLES:
-        return _TABLES[key]
+    if key in _TERMS:
+        return _TERMS[key]
     lib = _lib.load()
     p = C.c_void_p()
     if tree in _lib.TREE_IDS:
@@ -53,17 +54,45 @@ def plan_table(tree, n_end):
         _lib.check(lib.biem_plan_force_terms(p, None, ptr.ctypes.data, col.ctypes.data, comp.ctypes.data, val.ctypes.data), "biem_plan_force_terms")
     finally:
         lib.biem_plan_destroy(p)
-    T = np.zeros((d, H, H), dtype=np.complex128)
-    T[comp, np.repeat(np.arange(H), np.diff(ptr)), col] = val
     assert (deg == oracle_tree(tree).degrees(n_end)).all()          # the plan lists its harmonics in the oracle's order
-    _TABLES[key] = (d, lab, deg, T)
+    for a in (lab, deg, ptr, col, comp, val):
+        a.setflags(write=False)
+    _TERMS[key] = (d, lab, deg, ptr, col, comp, val)
+    return _TERMS[key]
+
+
+def csr_tables(d, H, ptr, col, comp, val):
+    """[T^0 .. T^{d-1}] as SciPy CSR [H, H] (rows h', columns h) from the listing of biem_plan_force_terms."""
+    rows = np.repeat(np.arange(H), np.diff(ptr))
+    return [sparse.csr_matrix((val[comp == i], (rows[comp == i], col[comp == i])), shape=(H, H)) for i in range(d)]
+
+
+def plan_table_sparse(tree, n_end):
+    """(d, labels [H, lw], deg [H], [T^i as CSR [H, H]]) of the plan: what the orders need whose dense table is gigabytes."""
+    key = (tree, n_end)
+    if key not in _SPARSE:
+        d, lab, deg, ptr, col, comp, val = plan_terms(tree, n_end)
+        _SPARSE[key] = (d, lab, deg, csr_tables(d, len(deg), ptr, col, comp, val))
+    return _SPARSE[key]
+
+
+def plan_table(tree, n_end):
+    """(d, labels [H, lw], deg [H], T [d, H, H] dense) of the plan; computed once per (tree, n_end) and never modified."""
+    key = (tree, n_end)
+    if key not in _TABLES:
+        d, lab, deg, ptr, col, comp, val = plan_terms(tree, n_end)
+        H = len(deg)
+        T = np.zeros((d, H, H), dtype=np.complex128)
+        T[comp, np.repeat(np.arange(H), np.diff(ptr)), col] = val
+        T.setflags(write=False)
+        _TABLES[key] = (d, lab, deg, T)
     return _TABLES[key]
 
 
 def embed(tree, n_end):
     """Position of every harmonic of the order-n_end plan in the plan of order n_end + 2, matched by label and degree."""
-    _, lab, deg, _ = plan_table(tree, n_end)
-    _, lab2, deg2, _ = plan_table(tree, n_end + 2)
+    _, lab, deg = plan_terms(tree, n_end)[:3]
+    _, lab2, deg2 = plan_terms(tree, n_end + 2)[:3]
     where = {tuple(l) + (int(n),): i for i, (l, n) in enumerate(zip(lab2.tolist(), deg2.tolist()))}
     idx = np.array([where[tuple(l) + (int(n),)] for l, n in zip(lab.tolist(), deg.tolist())])
     assert len(set(idx.tolist())) == len(idx)
@@ -71,7 +100,16 @@ def embed(tree, n_end):
 
 
 def ladder(T, deg, k, c, i, n_src=None):
-    """D_i c along canonical axis i; c[..., H] in the layout of the table.  Columns of degree >= n_src are skipped."""
+    """D_i c along canonical axis i; c[..., H] in the layout of the table.  Columns of degree >= n_src are skipped.  T is the dense
+    [d, H, H] table or the list of CSR matrices of plan_table_sparse (the same sums over the stored entries alone)."""
+    if sparse.issparse(T[i]):
+        M = T[i].tocoo()
+        w = M.data * np.sign(deg[M.col] - deg[M.row])
+        if n_src is not None:
+            w = w * (deg[M.col] < n_src)
+        M = sparse.csr_matrix((w, (M.row, M.col)), shape=M.shape)
+        flat = np.asarray(c, dtype=np.complex128).reshape(-1, M.shape[1])
+        return k * (M @ flat.T).T.reshape(np.shape(c)[:-1] + (M.shape[0],))
     sgn = np.sign(deg[None, :] - deg[:, None]).astype(np.float64)        # [h', h]
     M = T[i] * sgn
     if n_src is not None:
@@ -79,9 +117,9 @@ def ladder(T, deg, k, c, i, n_src=None):
     return k * np.einsum("gh,...h->...g", M, c)
 
 
-def hessian_coefs(tree, n_end, k, c):
+def hessian_coefs(tree, n_end, k, c, sparse_table=False):
     """D_j D_i c [d, d, ..., H2] in the layout of the plan of order n_end + 2 from c[..., H] in the order-n_end layout."""
-    d, _, deg2, T = plan_table(tree, n_end + 2)
+    d, _, deg2, T = (plan_table_sparse if sparse_table else plan_table)(tree, n_end + 2)
     idx = embed(tree, n_end)
     c2 = np.zeros(c.shape[:-1] + (len(deg2),), dtype=np.complex128)
     c2[..., idx] = c
@@ -124,13 +162,13 @@ def series(tree, n_end, k, kind, centers, coefs, x):
     return out
 
 
-def hessian(name, n_end, k, eta, kind, centers, radii, density, x):
+def hessian(name, n_end, k, eta, kind, centers, radii, density, x, sparse_table=False):
     """The twin's Hessian [d, d, P] of the near field of a record at x[P, d], in the caller's axes of tree `name`, unmasked."""
     tr = oracle_tree(name)
     canon = tr.base or name
     perm = list(tr.perm) if tr.base else list(range(tr.d))            # canonical y_i = x_{perm[i]}
     c = near_coefs(name, n_end, k, eta, radii, density, kind)
-    _, hc = hessian_coefs(canon, n_end, k, c)
+    _, hc = hessian_coefs(canon, n_end, k, c, sparse_table)
     Hc = series(canon, n_end + 2, k, kind, np.asarray(centers)[:, perm], hc, np.asarray(x)[:, perm])
     out = np.empty_like(Hc)
     for i in range(tr.d):

@@ -103,23 +103,10 @@ def case_list():
 
 
 def mp_hessian(F, x, step):
-    """[d, d] mpc at one point: second central differences of the sum over the balls of the 40-digit series."""
-    import mpmath as mp
+    """[d, d] mpc at one point: the rule of oracle.mp_field (MPField.hessian applies it with both steps and the same acceptance)."""
+    from oracle import mp_field as M
 
-    d = F.d
-    h = mp.mpf(step)
-
-    def f(shift):
-        y = [x[i] + shift.get(i, 0) * h for i in range(d)]
-        return mp.fsum(F.ball_sum("near", b, y) for b in range(F.B))
-
-    f0 = f({})
-    H = [[None] * d for _ in range(d)]
-    for i in range(d):
-        H[i][i] = (f({i: 1}) - 2 * f0 + f({i: -1})) / (h * h)
-        for j in range(i + 1, d):
-            H[i][j] = H[j][i] = (f({i: 1, j: 1}) - f({i: 1, j: -1}) - f({i: -1, j: 1}) + f({i: -1, j: -1})) / (4 * h * h)
-    return H
+    return M.hessian_by_differences(F, x, step)
 
 
 def build_case(case):
