@@ -7,6 +7,7 @@ ring counts vector-memory instructions by hand (`s_waitcnt vmcnt(N)`), which is 
 """
 from __future__ import annotations
 
+import copy
 import hashlib
 import os
 import re
@@ -14,6 +15,7 @@ import shutil
 import subprocess
 import tempfile
 from collections import Counter
+from dataclasses import dataclass
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -69,66 +71,102 @@ def is_stale() -> bool:
 # ------------------------------------------------------------------------------------------------
 # ISA check of the trailing-update kernels (CPU side: llvm-objdump / llvm-readelf on the built library)
 # ------------------------------------------------------------------------------------------------
-# What the check pins for every k_gemm3m_pipe<KD> (whole kernel; the compiler places cold paths of the chunk loop outside its
-# address range, so per-loop counts are not stable):
-#   * no scratch, no VGPR spills (either would add vector-memory instructions the vmcnt waits do not count);
-#   * exactly 96 MFMAs, all inside one loop (3 real products x 2 k4-steps x 16 accumulators per chunk);
-#   * the only vector-memory instructions are global_load_lds_dwordx4 (the ring), global_store_dwordx4 (48 = three epilogue
-#     forms x 16 result stores, outside the chunk loop) and at most 2 global_load_dword (the triangular tile map, read when the
-#     producer moves to its next tile; hipcc waits vmcnt(0) for it, which only drains the ring early);
-#   * the static number of LDS-DMA instructions equals the count of the reviewed build (prologue + fused groups with / without a
-#     C unit + the clamped edge-tile group).  A different count means the compiler restructured the groups: re-derive the
-#     vmcnt(N) constants of kernels_gemm3m.hip against the new disassembly before changing the numbers here.
-EXPECTED_LDS_DMA = {64: 34, 128: 28, 192: 32, 256: 32}
-# k_gemm3m_pipe<0>, the K-long instance of the left-looking update (run-time chunk count, no tile map): the same pins, reported by
-# check_isa_klong(); check_isa() checks it too and returns the reports of the fixed-K instances
+# Three steps: _isa_facts() reads what the library holds (once per file), _violations() compares one kernel's facts with its record in
+# PINS and nothing else, check_isa() raises on the first kernel with violations.
+#
+# Keys of PINS and of the report: KD (64 / 128 / 192 / 256) for k_gemm3m_pipe<KD> and KLONG for k_gemm3m_pipe<0>, (NARROW, NF), STRIP,
+# (STACK, KD), SLAB, (SWEEP, NQ).
 KLONG = 0
-EXPECTED_LDS_DMA_KLONG = 32
-# The reviewed K-long build keeps every scalar of its chunk loop in SGPRs: no v_readlane / v_writelane (scalars spilled to VGPR lanes and
-# read back in front of the MFMA block) inside the loop.  The build before it had 15 and ran the bulk update measurably slower
-# (DESIGN.md section 5), so a compiler that brings them back is reported, not taken silently.
-MAX_LANE_SPILL_OPS_KLONG = 0
-# k_gemm3m_narrow<NF>, the K-long instance for the last tile column of a left-looking band (NF of the tile's four 16-column groups are
-# multiplied, the rest is identity padding): the text of the K-long kernel with shorter MFMA nests, so its pins hold - no scratch, no
-# spills, 32 LDS-DMA, 48 stores, no lane spills in the chunk loop - with 24 NF MFMAs per chunk, all in one loop, and no tile-map load.
-# Keys (NARROW, NF), handed out by check_isa_narrow().
+PIPE_KD = (64, 128, 192, 256)
 NARROW = "narrow"
 NARROW_NF = (1, 2, 3)
-MFMA_PER_FRAG = 24
-# k_gemm3m_strip, the product form of the K = 64 kernel (symmetric strip pass: no C slots, four DMAs per group): the same pins, under
-# the key STRIP, handed out by check_isa_strip().  In its chunk loop the vector-memory instructions are the ring's LDS-DMA alone: the
-# product form adds none.  24 = six groups of four (prologue, fused, unfused interior and clamped edge
-# forms), every wait is vmcnt(4), vmcnt(4 + 16) behind a full tile's stores, or vmcnt(0).
-# The epilogue that carries the right-hand sides adds, outside the chunk loop, exactly 5 global_load_dwordx4 (z_j of the lane's four
-# rows, the 64 entries of Y) and 17 stores (a fourth form of the 16 result stores, Y); tiles that run it end with vmcnt(0).
 STRIP = "strip"
-EXPECTED_LDS_DMA_STRIP = 24
-EXPECTED_STORES_STRIP = 65
-EXPECTED_LOADS_STRIP = 5
-# k_gemm3m_stack<KD>, the product form at K = 128 / 192 / 256 (the stacked pass of the panels b, c, d of a group): the text of the strip
-# kernel with a longer chunk loop and the tile decode of a single tile row, so the strip's pins hold for every instance - 24 LDS-DMA,
-# 65 stores, 5 loads of the right-hand-side epilogue outside the chunk loop - with no tile-map load at all and, as for the K-long
-# kernel, no v_readlane / v_writelane in the chunk loop (the strip kernel has 5, on the path that decodes the producer's next tile).
-# Keys (STACK, KD), handed out by check_isa_stack().
 STACK = "stack"
+STACK_KD = (128, 192, 256)
 SLAB = "slab"
-# k_back_sweep<NQ>, the row-form back substitution in one launch per group of right-hand sides: one 1024-thread workgroup per system,
-# so 128 VGPRs per lane is all there is - a spill puts scratch traffic into the stream over U.  No scratch and no VGPR spills are pinned
-# for every instance.  Keys (SWEEP, NQ), handed out by check_isa_sweep().
 SWEEP = "sweep"
 SWEEP_NQ = (1, 2, 4, 8)
-STACK_KD = (128, 192, 256)
-EXPECTED_LDS_DMA_STACK = 24
-EXPECTED_STORES_STACK = 65
-EXPECTED_LOADS_STACK = 5
-MAX_LANE_SPILL_OPS_STACK = 0
-EXPECTED_STORES = 48
-MFMA_PER_CHUNK = 96
-MAX_TILE_MAP_LOADS = 2
+
+
+@dataclass(frozen=True)
+class Pins:
+    """What is pinned for one kernel.  Every kernel: no scratch and no VGPR spills (either would add vector-memory instructions the vmcnt
+    waits do not count).  With `mfma` set, the kernel is an update kernel and the counts below hold for the whole kernel (the compiler
+    places cold paths of the chunk loop outside its address range, so per-loop counts are not stable); its only vector-memory instructions
+    are then global_load_lds_dwordx4 (the ring), global_store_dwordx4, global_load_dword and the `loads` global_load_dwordx4."""
+    scratch_bytes: int = 0
+    vgpr_spills: int = 0
+    mfma: int | None = None            # MFMAs of the kernel, all inside one loop, the chunk loop (None: not an update kernel, no count below applies)
+    lds_dma: int | None = None         # static global_load_lds_dwordx4 count of the reviewed build
+    stores: int | None = None          # global_store_dwordx4, all outside the chunk loop
+    loads: int = 0                     # global_load_dwordx4: exactly this many, none of them in the chunk loop (0: none allowed anywhere)
+    tile_map_loads: int = 0            # global_load_dword at most (the triangular tile map; 0: this launch reads no tile map)
+    lane_spill_ops: int | None = None  # v_readlane / v_writelane in the chunk loop at most (None: not pinned)
+
+
+PINS = {
+    # k_gemm3m_pipe<KD>: 96 MFMAs, all inside one loop (3 real products x 2 k4-steps x 16 accumulators per chunk); 48 stores = three epilogue
+    # forms x 16 result stores, outside the chunk loop; at most 2 global_load_dword (the triangular tile map, read when the producer
+    # moves to its next tile; hipcc waits vmcnt(0) for it, which only drains the ring early).  The static number of LDS-DMA instructions
+    # equals the count of the reviewed build (prologue + fused groups with / without a C unit + the clamped edge-tile group).  A
+    # different count means the compiler restructured the groups: re-derive the vmcnt(N) constants of kernels_gemm3m.hip against the
+    # new disassembly before changing the numbers here.
+    **{kd: Pins(mfma=96, lds_dma=dma, stores=48, tile_map_loads=2) for kd, dma in zip(PIPE_KD, (34, 28, 32, 32))},
+    # k_gemm3m_pipe<0>, the K-long instance of the left-looking update (run-time chunk count, no tile map): the same pins, reported by
+    # check_isa_klong(); check_isa() checks it too and returns the reports of the fixed-K instances.
+    # The reviewed K-long build keeps every scalar of its chunk loop in SGPRs: no v_readlane / v_writelane (scalars spilled to VGPR lanes
+    # and read back in front of the MFMA block) inside the loop.  The build before it had 15 and ran the bulk update measurably slower
+    # (DESIGN.md section 5), so a compiler that brings them back is reported, not taken silently.
+    KLONG: Pins(mfma=96, lds_dma=32, stores=48, tile_map_loads=2, lane_spill_ops=0),
+    # k_gemm3m_narrow<NF>, the K-long instance for the last tile column of a left-looking band (NF of the tile's four 16-column groups
+    # are multiplied, the rest is identity padding): the text of the K-long kernel with shorter MFMA nests, so its pins hold - no
+    # scratch, no spills, 32 LDS-DMA, 48 stores, no lane spills in the chunk loop - with 24 NF MFMAs per chunk, all in one loop, and no
+    # tile-map load.  Handed out by check_isa_narrow().
+    **{(NARROW, nf): Pins(mfma=24 * nf, lds_dma=32, stores=48, tile_map_loads=0, lane_spill_ops=0) for nf in NARROW_NF},
+    # k_gemm3m_strip, the product form of the K = 64 kernel (symmetric strip pass: no C slots, four DMAs per group): the same pins,
+    # handed out by check_isa_strip().  In its chunk loop the vector-memory instructions are the ring's LDS-DMA alone: the product form
+    # adds none.  24 = six groups of four (prologue, fused, unfused interior and clamped edge forms), every wait is vmcnt(4),
+    # vmcnt(4 + 16) behind a full tile's stores, or vmcnt(0).  The epilogue that carries the right-hand sides adds, outside the chunk
+    # loop, exactly 5 global_load_dwordx4 (z_j of the lane's four rows, the 64 entries of Y) and 17 stores (a fourth form of the 16
+    # result stores, Y): 65 in all; tiles that run it end with vmcnt(0).
+    STRIP: Pins(mfma=96, lds_dma=24, stores=65, loads=5, tile_map_loads=2),
+    # k_gemm3m_stack<KD>, the product form at K = 128 / 192 / 256 (the stacked pass of the panels b, c, d of a group): the text of the
+    # strip kernel with a longer chunk loop and the tile decode of a single tile row, so the strip's pins hold for every instance - 24
+    # LDS-DMA, 65 stores, 5 loads of the right-hand-side epilogue outside the chunk loop - with no tile-map load at all and, as for the
+    # K-long kernel, no v_readlane / v_writelane in the chunk loop (the strip kernel has 5, on the path that decodes the producer's
+    # next tile).  Handed out by check_isa_stack().
+    **{(STACK, kd): Pins(mfma=96, lds_dma=24, stores=65, loads=5, tile_map_loads=0, lane_spill_ops=0) for kd in STACK_KD},
+    # k_sym_slab, the small VALU kernel in front of every stacked pass: a build of it with its loops unrolled spilled 1164 registers to
+    # scratch and cost the stage a third of its time, so no scratch and no spills are pinned for it too (check_isa_stack()[SLAB])
+    SLAB: Pins(),
+    # k_back_sweep<NQ>, the row-form back substitution in one launch per group of right-hand sides: one 1024-thread workgroup per
+    # system, so 128 VGPRs per lane is all there is - a spill puts scratch traffic into the stream over U.  No scratch and no VGPR
+    # spills are pinned for every instance.  Handed out by check_isa_sweep().
+    **{(SWEEP, nq): Pins() for nq in SWEEP_NQ},
+}
+# the names tests read: aliases into the table
+EXPECTED_LDS_DMA = {kd: PINS[kd].lds_dma for kd in PIPE_KD}
+EXPECTED_LDS_DMA_KLONG = PINS[KLONG].lds_dma
+EXPECTED_STORES = PINS[KLONG].stores
+MAX_LANE_SPILL_OPS_KLONG = PINS[KLONG].lane_spill_ops
 
 
 class IsaCheckError(RuntimeError):
     pass
+
+
+def _code_objects(lib_path: str, tmp: str) -> list:
+    """Unpack the gfx950 code objects of `lib_path` into the directory `tmp`; their paths."""
+    objdump = _llvm_tool("llvm-objdump")
+    if not objdump:
+        raise IsaCheckError("llvm-objdump not found: cannot unpack the code object")
+    local = os.path.join(tmp, "lib.so")
+    shutil.copy(lib_path, local)
+    subprocess.run([objdump, "--offloading", local], check=True, capture_output=True, cwd=tmp)
+    objs = sorted(os.path.join(tmp, f) for f in os.listdir(tmp) if "gfx950" in f)
+    if not objs:
+        raise IsaCheckError("no gfx950 code object found in " + lib_path)
+    return objs
 
 
 def _kernel_meta(readelf: str, obj: str) -> dict:
@@ -218,108 +256,130 @@ def _label(kd) -> str:
     return "k_gemm3m_strip" if kd == STRIP else "k_sym_slab" if kd == SLAB else f"k_gemm3m_pipe<{kd}>"
 
 
-def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = False) -> dict:
-    """Disassemble the gfx950 code objects of `lib_path`; raise IsaCheckError unless every k_gemm3m_pipe<*> has no scratch,
-    no VGPR spills, 96 MFMAs in its chunk loop and only the expected vector-memory instructions there.  Returns the report."""
+def _key_of(name: str):
+    """The key of a checked kernel from its mangled name, or None"""
+    if "k_sym_slab" in name:
+        return SLAB
+    if "k_gemm3m_strip" in name:
+        return STRIP
+    for stem, family in (("k_back_sweep", SWEEP), ("k_gemm3m_stack", STACK), ("k_gemm3m_narrow", NARROW), ("k_gemm3m_pipe", None)):
+        m = re.search(stem + r"ILi(\d+)E", name)
+        if m:
+            return int(m.group(1)) if family is None else (family, int(m.group(1)))
+    return None
+
+
+_FACTS = {}     # (path, size, mtime) -> what _isa_facts read from that file
+
+
+def _isa_facts(lib_path: str = LIB) -> dict:
+    """What the checks need to know of the library, read once per file (keyed on path, size and modification time; callers do not change
+    the result): {"kernels": {key: facts}, "prefetch_hazards": {k_fill_red instance: [instructions]}}.  The facts of a kernel are its
+    report as check_isa returns it - metadata, instruction counts of the kernel and of its chunk loop - plus, under names that start
+    with an underscore, what only the check reads."""
+    st = os.stat(lib_path)
+    cache_key = (os.path.abspath(lib_path), st.st_size, st.st_mtime_ns)
+    if cache_key in _FACTS:
+        return _FACTS[cache_key]
     objdump, readelf = _llvm_tool("llvm-objdump"), _llvm_tool("llvm-readelf")
     if not objdump or not readelf:
         raise IsaCheckError("llvm-objdump / llvm-readelf not found: cannot check the code object")
-    report = {}
+    kernels, hazards = {}, {}
     with tempfile.TemporaryDirectory(prefix="biem_isa_") as tmp:
-        local = os.path.join(tmp, "lib.so")
-        shutil.copy(lib_path, local)
-        subprocess.run([objdump, "--offloading", local], check=True, capture_output=True, cwd=tmp)
-        objs = sorted(f for f in os.listdir(tmp) if "gfx950" in f)
-        if not objs:
-            raise IsaCheckError("no gfx950 code object found in " + lib_path)
-        for o in objs:
-            path = os.path.join(tmp, o)
+        for path in _code_objects(lib_path, tmp):
             metas = _kernel_meta(readelf, path)
-            for n in metas:
-                # k_sym_slab, the small VALU kernel in front of every stacked pass: a build of it with its loops unrolled spilled 1164
-                # registers to scratch and cost the stage a third of its time, so no scratch and no spills are pinned for it too
-                if "k_sym_slab" in n:
-                    rep = {"scratch_bytes": int(metas[n].get("private_segment_fixed_size", -1)), "vgpr_spills": int(metas[n].get("vgpr_spill_count", -1)),
-                           "vgprs": int(metas[n].get("vgpr_count", -1))}
-                    report[SLAB] = rep
-                    if rep["scratch_bytes"] != 0 or rep["vgpr_spills"] != 0:
-                        raise IsaCheckError(f"k_sym_slab: scratch {rep['scratch_bytes']} B, {rep['vgpr_spills']} VGPR spills")
-                m = re.search(r"k_back_sweepILi(\d+)E", n)
-                if m:
-                    rep = {"scratch_bytes": int(metas[n].get("private_segment_fixed_size", -1)), "vgpr_spills": int(metas[n].get("vgpr_spill_count", -1)),
-                           "vgprs": int(metas[n].get("vgpr_count", -1))}
-                    report[(SWEEP, int(m.group(1)))] = rep
-                    if rep["scratch_bytes"] != 0 or rep["vgpr_spills"] != 0:
-                        raise IsaCheckError(f"k_back_sweep<{m.group(1)}>: scratch {rep['scratch_bytes']} B, {rep['vgpr_spills']} VGPR spills")
-            gemm = [n for n in metas if "k_gemm3m_pipe" in n or "k_gemm3m_strip" in n or "k_gemm3m_stack" in n or "k_gemm3m_narrow" in n]
+            keys = {n: _key_of(n) for n in metas}
             red = [n for n in metas if "k_fill_red" in n]
-            if not gemm and not red:
-                continue
-            dis = _disassemble(objdump, path)
-            # k_fill_red<KT, NC, SPLIT>: no prefetch register may be read, moved or spilled while its load is in flight
+            dis = _disassemble(objdump, path) if red or any(k is not None and PINS[k].mfma is not None for k in keys.values()) else {}
             for name in red:
-                bad = _prefetch_hazards(dis[name])
-                if bad:
-                    raise IsaCheckError(f"{name}: {len(bad)} instructions touch a prefetch register before its wait, first {bad[0]}")
-            for name in gemm:
-                stack, narrow = "k_gemm3m_stack" in name, "k_gemm3m_narrow" in name
-                kd = STRIP if "k_gemm3m_strip" in name else (STACK, int(re.search(r"k_gemm3m_stackILi(\d+)E", name).group(1))) if stack else \
-                    (NARROW, int(re.search(r"k_gemm3m_narrowILi(\d+)E", name).group(1))) if narrow else \
-                    int(re.search(r"k_gemm3m_pipeILi(\d+)E", name).group(1))
-                want_mfma = MFMA_PER_FRAG * kd[1] if narrow else MFMA_PER_CHUNK
-                label = _label(kd)
-                meta, ins = metas[name], dis[name]
-                loop, n_mfma = _chunk_loop(ins)
-                if loop is None:
-                    raise IsaCheckError(f"{label}: no loop holds the kernel's MFMAs")
-                ops = Counter(op for _, op, _ in ins)
-                lops = Counter(op for _, op, _ in loop)
-                vm = {op: c for op, c in ops.items() if op.startswith(("global_", "buffer_", "flat_", "scratch_"))}
-                rep = {"scratch_bytes": int(meta.get("private_segment_fixed_size", -1)), "vgpr_spills": int(meta.get("vgpr_spill_count", -1)),
-                       "sgpr_spills": int(meta.get("sgpr_spill_count", -1)), "vgprs": int(meta.get("vgpr_count", -1)),
-                       "mfma_in_chunk_loop": sum(c for op, c in lops.items() if op.startswith("v_mfma")), "mfma_total": n_mfma,
-                       "vm": vm, "lane_spill_ops_in_chunk_loop": lops.get("v_readlane_b32", 0) + lops.get("v_writelane_b32", 0)}
-                report[kd] = rep
-                bad = []
-                if rep["scratch_bytes"] != 0:
-                    bad.append(f"scratch {rep['scratch_bytes']} B")
-                if rep["vgpr_spills"] != 0:
-                    bad.append(f"{rep['vgpr_spills']} VGPR spills")
-                if rep["mfma_in_chunk_loop"] != want_mfma or n_mfma != want_mfma:
-                    bad.append(f"{rep['mfma_in_chunk_loop']} MFMAs in the chunk loop, {n_mfma} in the kernel (expected {want_mfma})")
-                extra = {op: c for op, c in vm.items() if op not in ("global_load_lds_dwordx4", "global_load_dword", "global_store_dwordx4")}
-                if (kd == STRIP or stack) and extra.get("global_load_dwordx4") == (EXPECTED_LOADS_STACK if stack else EXPECTED_LOADS_STRIP) and \
-                        not any(op == "global_load_dwordx4" for _, op, _ in loop):
-                    del extra["global_load_dwordx4"]
-                if extra:
-                    bad.append(f"unexpected vector-memory instructions: {extra}")
-                want_dma = EXPECTED_LDS_DMA_STACK if stack else EXPECTED_LDS_DMA_STRIP if kd == STRIP else EXPECTED_LDS_DMA_KLONG if kd == KLONG or narrow else \
-                    EXPECTED_LDS_DMA.get(kd)
-                if vm.get("global_load_lds_dwordx4", 0) != want_dma:
-                    bad.append(f"{vm.get('global_load_lds_dwordx4', 0)} LDS-DMA instructions (reviewed build: {want_dma})")
-                want_stores = EXPECTED_STORES_STACK if stack else EXPECTED_STORES_STRIP if kd == STRIP else EXPECTED_STORES
-                if vm.get("global_store_dwordx4", 0) != want_stores:
-                    bad.append(f"{vm.get('global_store_dwordx4', 0)} result stores (reviewed build: {want_stores})")
-                if (kd == KLONG or narrow) and rep["lane_spill_ops_in_chunk_loop"] > MAX_LANE_SPILL_OPS_KLONG:
-                    bad.append(f"{rep['lane_spill_ops_in_chunk_loop']} lane-spill instructions in the chunk loop (reviewed build: {MAX_LANE_SPILL_OPS_KLONG})")
-                if stack and rep["lane_spill_ops_in_chunk_loop"] > MAX_LANE_SPILL_OPS_STACK:
-                    bad.append(f"{rep['lane_spill_ops_in_chunk_loop']} lane-spill instructions in the chunk loop (reviewed build: {MAX_LANE_SPILL_OPS_STACK})")
-                if (stack or narrow) and vm.get("global_load_dword", 0) != 0:
-                    bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (this launch reads no tile map)")
-                if vm.get("global_load_dword", 0) > MAX_TILE_MAP_LOADS:
-                    bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword (expected <= {MAX_TILE_MAP_LOADS})")
-                if bad:
-                    raise IsaCheckError(f"{label}: the hand-counted vmcnt scheme is not safe with this code object: " + "; ".join(bad))
-    want = set(EXPECTED_LDS_DMA) | {KLONG, STRIP, SLAB} | {(STACK, k) for k in STACK_KD} | {(SWEEP, q) for q in SWEEP_NQ} | \
-        {(NARROW, f) for f in NARROW_NF}
-    if set(report) != want:
-        raise IsaCheckError(f"update kernels found: {sorted(report, key=str)}, expected {sorted(want, key=str)}")
+                hazards[name] = _prefetch_hazards(dis[name])
+            for name, key in keys.items():
+                if key is None:
+                    continue
+                meta = metas[name]
+                facts = {"scratch_bytes": int(meta.get("private_segment_fixed_size", -1)), "vgpr_spills": int(meta.get("vgpr_spill_count", -1)),
+                         "vgprs": int(meta.get("vgpr_count", -1))}
+                if PINS[key].mfma is not None:
+                    ins = dis[name]
+                    loop, n_mfma = _chunk_loop(ins)
+                    ops = Counter(op for _, op, _ in ins)
+                    lops = Counter(op for _, op, _ in loop or [])
+                    facts.update({"sgpr_spills": int(meta.get("sgpr_spill_count", -1)),
+                                  "mfma_in_chunk_loop": sum(c for op, c in lops.items() if op.startswith("v_mfma")), "mfma_total": n_mfma,
+                                  "vm": {op: c for op, c in ops.items() if op.startswith(("global_", "buffer_", "flat_", "scratch_"))},
+                                  "lane_spill_ops_in_chunk_loop": lops.get("v_readlane_b32", 0) + lops.get("v_writelane_b32", 0),
+                                  "_has_chunk_loop": loop is not None, "_loads_in_chunk_loop": lops.get("global_load_dwordx4", 0)})
+                kernels[key] = facts
+    _FACTS[cache_key] = {"kernels": kernels, "prefetch_hazards": hazards}
+    return _FACTS[cache_key]
+
+
+def _violations(key, facts: dict) -> list:
+    """What the facts of kernel `key` break of its record PINS[key]: one phrase per pin, none if the kernel is as reviewed"""
+    pins, bad = PINS[key], []
+    if pins.mfma is None:
+        if facts["scratch_bytes"] != pins.scratch_bytes or facts["vgpr_spills"] != pins.vgpr_spills:
+            bad.append(f"scratch {facts['scratch_bytes']} B, {facts['vgpr_spills']} VGPR spills")
+        return bad
+    if not facts["_has_chunk_loop"]:
+        return ["no loop holds the kernel's MFMAs"]
+    vm = facts["vm"]
+    if facts["scratch_bytes"] != pins.scratch_bytes:
+        bad.append(f"scratch {facts['scratch_bytes']} B")
+    if facts["vgpr_spills"] != pins.vgpr_spills:
+        bad.append(f"{facts['vgpr_spills']} VGPR spills")
+    if facts["mfma_in_chunk_loop"] != pins.mfma or facts["mfma_total"] != pins.mfma:
+        bad.append(f"{facts['mfma_in_chunk_loop']} MFMAs in the chunk loop, {facts['mfma_total']} in the kernel (expected {pins.mfma})")
+    extra = {op: c for op, c in vm.items() if op not in ("global_load_lds_dwordx4", "global_load_dword", "global_store_dwordx4")}
+    if pins.loads and extra.get("global_load_dwordx4") == pins.loads and facts["_loads_in_chunk_loop"] == 0:
+        del extra["global_load_dwordx4"]
+    if extra:
+        bad.append(f"unexpected vector-memory instructions: {extra}")
+    if vm.get("global_load_lds_dwordx4", 0) != pins.lds_dma:
+        bad.append(f"{vm.get('global_load_lds_dwordx4', 0)} LDS-DMA instructions (reviewed build: {pins.lds_dma})")
+    if vm.get("global_store_dwordx4", 0) != pins.stores:
+        bad.append(f"{vm.get('global_store_dwordx4', 0)} result stores (reviewed build: {pins.stores})")
+    if pins.lane_spill_ops is not None and facts["lane_spill_ops_in_chunk_loop"] > pins.lane_spill_ops:
+        bad.append(f"{facts['lane_spill_ops_in_chunk_loop']} lane-spill instructions in the chunk loop (reviewed build: {pins.lane_spill_ops})")
+    if vm.get("global_load_dword", 0) > pins.tile_map_loads:
+        bad.append(f"{vm.get('global_load_dword', 0)} global_load_dword " +
+                   (f"(expected <= {pins.tile_map_loads})" if pins.tile_map_loads else "(this launch reads no tile map)"))
+    return bad
+
+
+def _complaint(key, bad: list) -> str:
+    """The message of IsaCheckError for the violations `bad` of kernel `key`"""
+    counted = PINS[key].mfma is not None and bad != ["no loop holds the kernel's MFMAs"]
+    return f"{_label(key)}: " + ("the hand-counted vmcnt scheme is not safe with this code object: " if counted else "") + "; ".join(bad)
+
+
+def _check_facts(facts: dict) -> None:
+    """Raise IsaCheckError for the first kernel of `facts` (as _isa_facts returns them) that breaks a pin, or if a kernel of PINS is missing"""
+    for name, bad in facts["prefetch_hazards"].items():
+        # k_fill_red<KT, NC, SPLIT>: no prefetch register may be read, moved or spilled while its load is in flight
+        if bad:
+            raise IsaCheckError(f"{name}: {len(bad)} instructions touch a prefetch register before its wait, first {bad[0]}")
+    for key, f in facts["kernels"].items():
+        bad = _violations(key, f)
+        if bad:
+            raise IsaCheckError(_complaint(key, bad))
+    if set(facts["kernels"]) != set(PINS):
+        raise IsaCheckError(f"update kernels found: {sorted(facts['kernels'], key=str)}, expected {sorted(PINS, key=str)}")
+
+
+def check_isa(lib_path: str = LIB, verbose: bool = False, _all_kernels: bool = False) -> dict:
+    """Disassemble the gfx950 code objects of `lib_path` (once per file); raise IsaCheckError unless every kernel of PINS is there and keeps
+    its pins: for every k_gemm3m_* no scratch, no VGPR spills, its MFMAs in its chunk loop and only the expected vector-memory
+    instructions.  Returns the report of the fixed-K instances k_gemm3m_pipe<64 / 128 / 192 / 256>."""
+    facts = _isa_facts(lib_path)
+    _check_facts(facts)
+    report = {key: copy.deepcopy({k: v for k, v in f.items() if not k.startswith("_")}) for key, f in facts["kernels"].items()}
     if verbose:
         for kd in sorted(report, key=str):
             print(f"isa check {_label(kd)}: {report[kd]}")
-    # (tests/test_host_logic.py pins the key set of this report to the fixed-K instances [64, 128, 192, 256]: the K-long instance and the
-    # strip kernel are checked above like the others and handed out by check_isa_klong / check_isa_strip)
-    return report if _all_kernels else {kd: r for kd, r in report.items() if kd in EXPECTED_LDS_DMA}
+    # (tests/test_host_logic.py pins the key set of this report to the fixed-K instances [64, 128, 192, 256]: the other kernels are
+    # checked above like them and handed out by the accessors below)
+    return report if _all_kernels else {kd: r for kd, r in report.items() if kd in PIPE_KD}
 
 
 def check_isa_klong(lib_path: str = LIB) -> dict:

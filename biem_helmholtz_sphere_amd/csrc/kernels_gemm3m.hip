@@ -1,6 +1,9 @@
-// kernels_gemm3m.hip -- trailing update of the dense factorisations: persistent 3M zgemm on v_mfma_f64_4x4x4_4b_f64 (k_gemm3m_pipe<KD>,
-// K = 64 / 128 / 192 / 256 and the K-long form of the left-looking update), its tile grids and launchers, the MFMA micro-benchmark
-// and the BIEM_GEMM_TRACE debug entries.
+// kernels_gemm3m.hip -- trailing update of the dense factorisations: persistent 3M zgemm on v_mfma_f64_4x4x4_4b_f64.  One body,
+// gemm3m_body, for four kernels: k_gemm3m_pipe<KD> (K = 64 / 128 / 192 / 256, and KD = 0, the K-long form of the left-looking update),
+// k_gemm3m_narrow<NF> (its last tile column), and the pure products k_gemm3m_strip (K = 64) and k_gemm3m_stack<KD> (K = 128 / 192 /
+// 256).  The asm statement of the chunk loop is composed from one set of pieces (BIEM_FRAG_READS16 ... BIEM_DMA_INS, above the body),
+// where the timing ablations that cut into it are defined too.  Also here: the tile grids and launchers, the MFMA micro-benchmark and
+// the BIEM_GEMM_TRACE debug entries.
 //
 // MFMA form.  Measured on MI355X (tools/mfma_probe*.hip, profiles/r01_mfma_f64_*probe*.txt): the 16x16x4 f64 MFMA
 // saturates at ~47-49 TFLOP/s (one per ~100 cycles per SIMD) at any occupancy, the 4-block 4x4x4 form issues every
@@ -24,19 +27,20 @@
 
 namespace biem {
 
+// (every member has its "off" value as default: a launcher sets what its launch uses)
 struct TileGrid {
-  int ty_n, tx_n, per_sys, full_bands, ntiles;
-  int row_begin, row_end, col_begin, col_end;   // C region updated by this launch
-  int brow;                                     // first row of the B operand (U12 rows brow .. brow + K)
+  int ty_n = 0, tx_n = 0, per_sys = 0, full_bands = 0, ntiles = 0;
+  int row_begin = 0, row_end = 0, col_begin = 0, col_end = 0;   // C region updated by this launch
+  int brow = 0;                                 // first row of the B operand (U12 rows brow .. brow + K)
   // tiles of tile column `pcol_tx` deliver their result transposed into the panel workspace (the next panel to factor:
   // column-major P[c][row]) instead of the matrix, which saves that panel's transposing load; pout == nullptr: off
-  cplx* pout; long long pout_ld, pout_stride; int pcol_tx;
-  int tri;                                      // 1: only tiles with tx <= ty (square region, symmetric update); 2: only tx >= ty
+  cplx* pout = nullptr; long long pout_ld = 0, pout_stride = 0; int pcol_tx = 0;
+  int tri = 0;                                  // 1: only tiles with tx <= ty (square region, symmetric update); 2: only tx >= ty
   // (ty << 16 | tx) of the first tri_full tiles of that order (the full bands); the K-long launch (k_gemm3m_pipe<0>, band order
   // below, no tile map) keeps its K-chunks per tile, kd / 8, in the same word: the argument layout of the other launches is unchanged
-  const int* tri_map; union { int tri_full; int nch; };
-  int blk_sh;                                   // log2 of the tiles per XCD block of the workgroup -> tile map: 6, or 3 for small launches
-  unsigned long long per_sys_magic;             // ceil(2^40 / per_sys): t / per_sys = (t * magic) >> 40 for t < 2^25 (scalar multiply, no VALU division)
+  const int* tri_map = nullptr; union { int tri_full = 0; int nch; };
+  int blk_sh = 0;                               // log2 of the tiles per XCD block of the workgroup -> tile map: 6, or 3 for small launches
+  unsigned long long per_sys_magic = 0;         // ceil(2^40 / per_sys): t / per_sys = (t * magic) >> 40 for t < 2^25 (scalar multiply, no VALU division)
 };
 // nch shares tri_full's word: only k_gemm3m_pipe<0> reads nch, and it never calls tile_decode (the one reader of tri_full); its
 // launch (launch_gemm_left) sets tri = 0 and no tile map.  The layout the fixed-K instances were compiled against is pinned:
@@ -141,14 +145,6 @@ constexpr int KC = 8;               // K rows per LDS stage (chunk)
 // Stage = A[8][64] + B[8][64] + C slice (UPC x 256 lanes) = 20 (K=128) or 24 KiB (K=64); 3 stages; 2 workgroups per CU.
 // ---------------------------------------------------------------------------------------------
 template <int N> __device__ inline void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// LDS fragment read outside the compiler's memory model: hipcc orders every ds_read it can see behind ALL pending LDS-DMA
-// (s_waitcnt vmcnt(0)), which would drain the ring's prefetches; the consumer issues lds_wait() + sched_barrier itself.
-__device__ inline cplx lds_read16(const cplx* p) {
-  cplx v;
-  unsigned addr = (unsigned)(size_t)(const __attribute__((address_space(3))) cplx*)p;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
 // acc += a*b / acc -= a*b on the 4-block f64 MFMA (the f64 NEG bit, blgp bit 0, negates A).
 // (An inline-asm form with the accumulator tied "+v" was tried to stop hipcc from rotating accumulators through the
 // register file; it produced wrong results on gfx950 even with hazard padding, and the rolled chunk loop made it
@@ -157,10 +153,6 @@ __device__ inline void mfma_acc(double& acc, double a, double b) { acc = __built
 __device__ inline void mfma_acc_neg(double& acc, double a, double b) { acc = __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, acc, 0, 0, 1); }
 // keeps hipcc from moving VALU work into the MFMA block (and the MFMAs out of it)
 __device__ inline void mfma_fence() { __builtin_amdgcn_sched_barrier(0); }
-__device__ inline void lds_wait() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);   // keep MFMAs behind the wait (hipcc moves register-only instructions across asm)
-}
 
 // What the ISA of earlier attempts taught (all measured):
 //  * hipcc puts s_waitcnt vmcnt(0) in front of every ds_read it can see while an LDS-DMA is pending (even with one
@@ -187,24 +179,69 @@ __device__ unsigned long long g_gemm_trace[16][64][8];
 #define BIEM_TR(i)
 #define BIEM_TR_NEXT()
 #endif
-// the 16 fragment reads of a chunk and the four operand DMAs of a fused group, as the statements below spell them out: the text of
-// the product form's groups, which carry no C unit
+// The pieces of the chunk statement.  All seven asm statements of the chunk loop of gemm3m_body - fused (with the next DMA group
+// between the fragment reads and their wait) and unfused, product form, one C unit, none, two - are composed from them, so every
+// instruction's text and every slot offset stands here once; the vmcnt counts rest on this text.  A fused statement reads
+//   reads [C reads] | M0 save | operand DMAs [C DMAs] | M0 restore | lgkmcnt wait
+// (M0 is compiler-reserved, hence save and restore; the C DMAs sit in front of the restore), an unfused one the reads and the wait.
+// Byte offsets inside a stage: k4 * 4352 + g * 64 (A fragments, from aA), k4 * 4096 + n * 256 (B, from aB), u * 4096 (C units, from
+// aC); DMA slots: mA and mA + 4352 (A rows w, w + 4), mB and mB + 4096 (B rows), mB + 8192 / 12288 (C units 0 / 1).
+//
+// The timing ablations that cut into this text (tools/build_trace.sh; results wrong by construction) are alternative definitions of
+// the piece they remove or redirect, beside the count they imply - so they hold for EVERY instance that uses the piece:
+//   BIEM_ABL_NOLDS    no fragment and no C reads                BIEM_ABL_NOCDMA  no C-unit DMA (BIEM_NDMA_PER_CUNIT = 0)
+//   BIEM_ABL_ONLYCDMA no operand DMAs (BIEM_NDMA_OPERAND = 0)   BIEM_ABL_CHOT    the C units come from an L2-resident address
+// NDMA in gemm3m_body is BIEM_NDMA_OPERAND + C units x BIEM_NDMA_PER_CUNIT: it follows the text.  (The groups that issue_dma builds
+// from builtins - prologue and edge tiles - keep their full count under these flags.)
+#ifdef BIEM_ABL_NOLDS
+#define BIEM_FRAG_READS16 ""
+#define BIEM_C_READ1 ""
+#define BIEM_C_READ2 ""
+#else
 #define BIEM_FRAG_READS16                                                                                                                  \
   "ds_read_b128 %[b0], %[aB]\n\tds_read_b128 %[b1], %[aB] offset:256\n\tds_read_b128 %[b2], %[aB] offset:512\n\tds_read_b128 %[b3], %[aB] offset:768\n\t" \
   "ds_read_b128 %[b4], %[aB] offset:4096\n\tds_read_b128 %[b5], %[aB] offset:4352\n\tds_read_b128 %[b6], %[aB] offset:4608\n\tds_read_b128 %[b7], %[aB] offset:4864\n\t" \
   "ds_read_b128 %[a0], %[aA]\n\tds_read_b128 %[a1], %[aA] offset:64\n\tds_read_b128 %[a2], %[aA] offset:128\n\tds_read_b128 %[a3], %[aA] offset:192\n\t" \
   "ds_read_b128 %[a4], %[aA] offset:4352\n\tds_read_b128 %[a5], %[aA] offset:4416\n\tds_read_b128 %[a6], %[aA] offset:4480\n\tds_read_b128 %[a7], %[aA] offset:4544\n\t"
+#define BIEM_C_READ1 "ds_read_b128 %[c0], %[aC]\n\t"
+#define BIEM_C_READ2 BIEM_C_READ1 "ds_read_b128 %[c1], %[aC] offset:4096\n\t"
+#endif
+#define BIEM_M0_SAVE "s_mov_b32 %[keep], m0\n\t"
+#define BIEM_M0_RESTORE "s_mov_b32 m0, %[keep]\n\t"
+#ifdef BIEM_ABL_ONLYCDMA
+#define BIEM_OPERAND_DMA4 ""
+#define BIEM_NDMA_OPERAND 0
+#else
 #define BIEM_OPERAND_DMA4                                                                     \
-  "s_mov_b32 %[keep], m0\n\t"                                                                 \
   "s_mov_b32 m0, %[mA]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA0], %[pA]\n\t"               \
   "s_add_u32 m0, %[mA], 4352\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA1], %[pA]\n\t"         \
   "s_mov_b32 m0, %[mB]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB0], %[pB]\n\t"               \
-  "s_add_u32 m0, %[mB], 4096\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB1], %[pB]\n\t"         \
-  "s_mov_b32 m0, %[keep]\n\t"
+  "s_add_u32 m0, %[mB], 4096\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB1], %[pB]\n\t"
+#define BIEM_NDMA_OPERAND 4
+#endif
+#ifdef BIEM_ABL_NOCDMA
+#define BIEM_C_DMA(slot, ptr) ""
+#define BIEM_NDMA_PER_CUNIT 0
+#else
+#define BIEM_C_DMA(slot, ptr) "s_add_u32 m0, %[mB], " #slot "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oC], %[" #ptr "]\n\t"
+#define BIEM_NDMA_PER_CUNIT 1
+#endif
+#ifdef BIEM_ABL_CHOT
+#define BIEM_C_SRC(d) ((const char*)Pw + ((d) & 0xfffff))   // (the panel workspace)
+#else
+#define BIEM_C_SRC(d) (pC + (d))                            // source of the C unit at byte offset d of the producer's tile
+#endif
+#define BIEM_LGKM_WAIT "s_waitcnt lgkmcnt(0)"
+// operand lists: outputs (a fused statement puts [keep] in front), inputs (a statement with C DMAs adds [oC] and its C pointers)
 #define BIEM_FRAG_OUTS                                                                                                                     \
   [a0] "=&v"(fa[0][0]), [a1] "=&v"(fa[0][1]), [a2] "=&v"(fa[0][2]), [a3] "=&v"(fa[0][3]), [a4] "=&v"(fa[1][0]), [a5] "=&v"(fa[1][1]),       \
   [a6] "=&v"(fa[1][2]), [a7] "=&v"(fa[1][3]), [b0] "=&v"(fb[0][0]), [b1] "=&v"(fb[0][1]), [b2] "=&v"(fb[0][2]), [b3] "=&v"(fb[0][3]),       \
   [b4] "=&v"(fb[1][0]), [b5] "=&v"(fb[1][1]), [b6] "=&v"(fb[1][2]), [b7] "=&v"(fb[1][3])
+#define BIEM_C_OUTS1 [c0] "=&v"(cv[0])
+#define BIEM_C_OUTS2 BIEM_C_OUTS1, [c1] "=&v"(cv[UPC - 1])
+#define BIEM_FRAG_INS [aA] "v"(aA), [aB] "v"(aB)
+#define BIEM_C_IN [aC] "v"(aC)
+#define BIEM_DMA_INS [mA] "s"(mA), [mB] "s"(mB), [oA0] "v"(offA0), [oA1] "v"(offA1), [oB0] "v"(offB0), [oB1] "v"(offB1), [pA] "s"(pA), [pB] "s"(pB)
 
 // One text of the tile loop for three kernels (as fast_layout.hpp does for the field kernels): k_gemm3m_pipe<KD> is the body with
 // PROD = false.  PROD = true is the pure product of the symmetric strip pass (k_gemm3m_strip, K = 64) and of the stacked pass of a
@@ -236,13 +273,8 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
   constexpr int UPC = KD == 0 || NCHC >= 16 ? 1 : 16 / NCHC;   // C units (one complex per lane) per chunk that carries C: 1 or 2
   constexpr int NCC = 16 / UPC;              // chunks that carry C units: the first NCC of a tile (all of them for K <= 128)
   constexpr bool ALLC = KD != 0 && NCC == NCHC;   // every chunk of a tile carries C units
-#if defined(BIEM_ABL_NOCDMA)                  // timing ablation: no C-slice DMA in the fused (interior, K = 128) path
-  constexpr int NDMA = 4;
-#elif defined(BIEM_ABL_ONLYCDMA)              // timing ablation: only the C-slice DMA
-  constexpr int NDMA = 1;
-#else
-  constexpr int NDMA = PROD ? 4 : 4 + UPC;   // LDS-DMA instructions per wave per chunk
-#endif
+  constexpr int NCD = UPC * BIEM_NDMA_PER_CUNIT;                           // C-unit DMAs of a group that carries C: UPC
+  constexpr int NDMA = PROD ? BIEM_NDMA_OPERAND : BIEM_NDMA_OPERAND + NCD;   // LDS-DMA instructions per wave per chunk: 4, or 4 + UPC
   constexpr int AST = 68;                    // A row stride in LDS: +4 elements (64 B) so the broadcast A-fragment reads of
                                              // two k-rows in one ds_read_b128 lane group hit different banks
   constexpr int BOF = KC * AST;              // B block offset inside a stage
@@ -343,7 +375,7 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
         }
       }
     }
-    n_new = (PROD || ALLC || p_ch < NCC) ? NDMA : NDMA - UPC;      // VM instructions of the group just issued
+    n_new = (PROD || ALLC || p_ch < NCC) ? NDMA : NDMA - NCD;      // VM instructions of the group just issued
   };
   auto advance = [&]() {
     pA += strideA; pB += strideB;
@@ -389,18 +421,18 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
       // retire this chunk's DMA group (mine), then meet the other waves: their groups have landed too and nobody still
       // reads the stage the next group is about to overwrite
       BIEM_TR(0)
-      // (the newest group holds n_new instructions: NDMA, or NDMA - UPC for the chunks of a K = 256 tile without a C unit)
+      // (the newest group holds n_new instructions: NDMA, or NDMA - NCD for the chunks of a K = 256 tile without a C unit)
       const bool small_grp = !ALLC && n_new != NDMA;
       if (__builtin_expect(stores_pending == 0 && p_valid, 1)) {
-        if (small_grp) wait_vmcnt<NDMA - UPC>(); else wait_vmcnt<NDMA>();
+        if (small_grp) wait_vmcnt<NDMA - NCD>(); else wait_vmcnt<NDMA>();
       } else if (!p_valid) {
         wait_vmcnt<0>();                                   // tail of this workgroup's work: no further groups are issued
       } else if (stores_pending == 2 && c == 0) {
         wait_vmcnt<0>();
       } else if (stores_pending == 1 && c < 2) {
-        if (small_grp) wait_vmcnt<NDMA - UPC + 16>(); else wait_vmcnt<NDMA + 16>();
+        if (small_grp) wait_vmcnt<NDMA - NCD + 16>(); else wait_vmcnt<NDMA + 16>();
       } else {
-        if (small_grp) wait_vmcnt<NDMA - UPC>(); else wait_vmcnt<NDMA>();
+        if (small_grp) wait_vmcnt<NDMA - NCD>(); else wait_vmcnt<NDMA>();
       }
       BIEM_TR(1)
 #ifndef BIEM_ABL_NOBARRIER
@@ -420,9 +452,9 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
 #endif
       __builtin_amdgcn_sched_barrier(0);
       BIEM_TR(3)
-      // fragments of both k4-steps and the C units of this chunk: 20 + UPC ds_read_b128 and their lgkmcnt wait in ONE asm
+      // fragments of both k4-steps and the C units of this chunk: 16 + UPC ds_read_b128 and their lgkmcnt wait in ONE asm
       // statement - hipcc may copy an asm output right after the statement, i.e. before a separate wait (that was the
-      // cause of percent-level errors in an earlier build); byte offsets: k4*4352 + g*64 (A), k4*4096 + n*256 (B)
+      // cause of percent-level errors in an earlier build).  Seven statements, one per group form, all from the pieces above
       cplx fb[2][4], fa[2][4], cv[UPC];   // [k4][column group of 16], [k4][row quad]
       unsigned m0_keep;                    // M0 is compiler-reserved: the fused statements save and restore it
       {
@@ -431,53 +463,25 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
           typedef __attribute__((address_space(3))) cplx* lds_cplx_t;
           cplx* S2 = ring + st2 * STG;
           const unsigned mA = (unsigned)(size_t)(lds_cplx_t)(S2 + wave * AST), mB = (unsigned)(size_t)(lds_cplx_t)(S2 + BOF + wave * 64);
-          asm volatile(BIEM_FRAG_READS16 BIEM_OPERAND_DMA4 "s_waitcnt lgkmcnt(0)"
+          asm volatile(BIEM_FRAG_READS16 BIEM_M0_SAVE BIEM_OPERAND_DMA4 BIEM_M0_RESTORE BIEM_LGKM_WAIT
                        : [keep] "=&s"(m0_keep), BIEM_FRAG_OUTS
-                       : [aA] "v"(aA), [aB] "v"(aB), [mA] "s"(mA), [mB] "s"(mB), [oA0] "v"(offA0), [oA1] "v"(offA1), [oB0] "v"(offB0),
-                         [oB1] "v"(offB1), [pA] "s"(pA), [pB] "s"(pB)
+                       : BIEM_FRAG_INS, BIEM_DMA_INS
                        : "memory", "scc");
           __builtin_amdgcn_sched_barrier(0);
           n_new = NDMA;
           advance();
         } else if constexpr (PROD) {
-          asm volatile(BIEM_FRAG_READS16 "s_waitcnt lgkmcnt(0)" : BIEM_FRAG_OUTS : [aA] "v"(aA), [aB] "v"(aB) : "memory");
+          asm volatile(BIEM_FRAG_READS16 BIEM_LGKM_WAIT : BIEM_FRAG_OUTS : BIEM_FRAG_INS : "memory");
         } else if (UPC == 1 && fused && (ALLC || p_ch < NCC)) {
           typedef __attribute__((address_space(3))) cplx* lds_cplx_t;
           cplx* S2 = ring + st2 * STG;
           const unsigned mA = (unsigned)(size_t)(lds_cplx_t)(S2 + wave * AST), mB = (unsigned)(size_t)(lds_cplx_t)(S2 + BOF + wave * 64);
           const long long dC = ((long long)(4 * (p_ch & 3)) * lda + (p_ch >> 2) * 16) * (long long)sizeof(cplx);
-#ifdef BIEM_ABL_CHOT      // timing ablation: the C slice comes from an L2-resident address (the panel workspace)
-          const char* pCc = (const char*)Pw + (dC & 0xfffff);
-#else
-          const char* pCc = pC + dC;
-#endif
-          asm volatile(
-#ifndef BIEM_ABL_NOLDS
-              "ds_read_b128 %[b0], %[aB]\n\tds_read_b128 %[b1], %[aB] offset:256\n\tds_read_b128 %[b2], %[aB] offset:512\n\tds_read_b128 %[b3], %[aB] offset:768\n\t"
-              "ds_read_b128 %[b4], %[aB] offset:4096\n\tds_read_b128 %[b5], %[aB] offset:4352\n\tds_read_b128 %[b6], %[aB] offset:4608\n\tds_read_b128 %[b7], %[aB] offset:4864\n\t"
-              "ds_read_b128 %[a0], %[aA]\n\tds_read_b128 %[a1], %[aA] offset:64\n\tds_read_b128 %[a2], %[aA] offset:128\n\tds_read_b128 %[a3], %[aA] offset:192\n\t"
-              "ds_read_b128 %[a4], %[aA] offset:4352\n\tds_read_b128 %[a5], %[aA] offset:4416\n\tds_read_b128 %[a6], %[aA] offset:4480\n\tds_read_b128 %[a7], %[aA] offset:4544\n\t"
-              "ds_read_b128 %[c0], %[aC]\n\t"
-#endif
-#ifndef BIEM_ABL_ONLYCDMA
-              "s_mov_b32 %[keep], m0\n\t"
-              "s_mov_b32 m0, %[mA]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA0], %[pA]\n\t"
-              "s_add_u32 m0, %[mA], 4352\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA1], %[pA]\n\t"
-              "s_mov_b32 m0, %[mB]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB0], %[pB]\n\t"
-              "s_add_u32 m0, %[mB], 4096\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB1], %[pB]\n\t"
-#endif
-#ifndef BIEM_ABL_NOCDMA
-              "s_add_u32 m0, %[mB], 8192\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oC], %[pC]\n\t"
-#endif
-              "s_mov_b32 m0, %[keep]\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : [keep] "=&s"(m0_keep), [a0] "=&v"(fa[0][0]), [a1] "=&v"(fa[0][1]), [a2] "=&v"(fa[0][2]), [a3] "=&v"(fa[0][3]), [a4] "=&v"(fa[1][0]),
-                [a5] "=&v"(fa[1][1]), [a6] "=&v"(fa[1][2]), [a7] "=&v"(fa[1][3]), [b0] "=&v"(fb[0][0]), [b1] "=&v"(fb[0][1]),
-                [b2] "=&v"(fb[0][2]), [b3] "=&v"(fb[0][3]), [b4] "=&v"(fb[1][0]), [b5] "=&v"(fb[1][1]), [b6] "=&v"(fb[1][2]),
-                [b7] "=&v"(fb[1][3]), [c0] "=&v"(cv[0])
-              : [aA] "v"(aA), [aB] "v"(aB), [aC] "v"(aC), [mA] "s"(mA), [mB] "s"(mB), [oA0] "v"(offA0), [oA1] "v"(offA1), [oB0] "v"(offB0),
-                [oB1] "v"(offB1), [oC] "v"(offC), [pA] "s"(pA), [pB] "s"(pB), [pC] "s"(pCc)
-              : "memory", "scc");
+          const char* pCc = BIEM_C_SRC(dC);
+          asm volatile(BIEM_FRAG_READS16 BIEM_C_READ1 BIEM_M0_SAVE BIEM_OPERAND_DMA4 BIEM_C_DMA(8192, pC) BIEM_M0_RESTORE BIEM_LGKM_WAIT
+                       : [keep] "=&s"(m0_keep), BIEM_FRAG_OUTS, BIEM_C_OUTS1
+                       : BIEM_FRAG_INS, BIEM_C_IN, BIEM_DMA_INS, [oC] "v"(offC), [pC] "s"(pCc)
+                       : "memory", "scc");
           __builtin_amdgcn_sched_barrier(0);
           n_new = NDMA;
           advance();
@@ -485,32 +489,13 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
           typedef __attribute__((address_space(3))) cplx* lds_cplx_t;
           cplx* S2 = ring + st2 * STG;
           const unsigned mA = (unsigned)(size_t)(lds_cplx_t)(S2 + wave * AST), mB = (unsigned)(size_t)(lds_cplx_t)(S2 + BOF + wave * 64);
-          asm volatile(
-#ifndef BIEM_ABL_NOLDS
-              "ds_read_b128 %[b0], %[aB]\n\tds_read_b128 %[b1], %[aB] offset:256\n\tds_read_b128 %[b2], %[aB] offset:512\n\tds_read_b128 %[b3], %[aB] offset:768\n\t"
-              "ds_read_b128 %[b4], %[aB] offset:4096\n\tds_read_b128 %[b5], %[aB] offset:4352\n\tds_read_b128 %[b6], %[aB] offset:4608\n\tds_read_b128 %[b7], %[aB] offset:4864\n\t"
-              "ds_read_b128 %[a0], %[aA]\n\tds_read_b128 %[a1], %[aA] offset:64\n\tds_read_b128 %[a2], %[aA] offset:128\n\tds_read_b128 %[a3], %[aA] offset:192\n\t"
-              "ds_read_b128 %[a4], %[aA] offset:4352\n\tds_read_b128 %[a5], %[aA] offset:4416\n\tds_read_b128 %[a6], %[aA] offset:4480\n\tds_read_b128 %[a7], %[aA] offset:4544\n\t"
-              "ds_read_b128 %[c0], %[aC]\n\t"
-#endif
-#ifndef BIEM_ABL_ONLYCDMA
-              "s_mov_b32 %[keep], m0\n\t"
-              "s_mov_b32 m0, %[mA]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA0], %[pA]\n\t"
-              "s_add_u32 m0, %[mA], 4352\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA1], %[pA]\n\t"
-              "s_mov_b32 m0, %[mB]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB0], %[pB]\n\t"
-              "s_add_u32 m0, %[mB], 4096\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB1], %[pB]\n\t"
-#endif
-              "s_mov_b32 m0, %[keep]\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : [keep] "=&s"(m0_keep), [a0] "=&v"(fa[0][0]), [a1] "=&v"(fa[0][1]), [a2] "=&v"(fa[0][2]), [a3] "=&v"(fa[0][3]), [a4] "=&v"(fa[1][0]),
-                [a5] "=&v"(fa[1][1]), [a6] "=&v"(fa[1][2]), [a7] "=&v"(fa[1][3]), [b0] "=&v"(fb[0][0]), [b1] "=&v"(fb[0][1]),
-                [b2] "=&v"(fb[0][2]), [b3] "=&v"(fb[0][3]), [b4] "=&v"(fb[1][0]), [b5] "=&v"(fb[1][1]), [b6] "=&v"(fb[1][2]),
-                [b7] "=&v"(fb[1][3]), [c0] "=&v"(cv[0])
-              : [aA] "v"(aA), [aB] "v"(aB), [aC] "v"(aC), [mA] "s"(mA), [mB] "s"(mB), [oA0] "v"(offA0), [oA1] "v"(offA1), [oB0] "v"(offB0),
-                [oB1] "v"(offB1), [pA] "s"(pA), [pB] "s"(pB)
-              : "memory", "scc");
+          // (the consumer may still be inside the NCC chunks that carry C: the C read stays)
+          asm volatile(BIEM_FRAG_READS16 BIEM_C_READ1 BIEM_M0_SAVE BIEM_OPERAND_DMA4 BIEM_M0_RESTORE BIEM_LGKM_WAIT
+                       : [keep] "=&s"(m0_keep), BIEM_FRAG_OUTS, BIEM_C_OUTS1
+                       : BIEM_FRAG_INS, BIEM_C_IN, BIEM_DMA_INS
+                       : "memory", "scc");
           __builtin_amdgcn_sched_barrier(0);
-          n_new = NDMA - UPC;
+          n_new = NDMA - NCD;
           advance();
         } else if (UPC == 2 && fused) {
           // the K = 64 form: two C units per chunk (slots mB + 8192 and mB + 12288)
@@ -518,61 +503,20 @@ __device__ __forceinline__ void gemm3m_body(cplx* __restrict__ A, long long lda,
           cplx* S2 = ring + st2 * STG;
           const unsigned mA = (unsigned)(size_t)(lds_cplx_t)(S2 + wave * AST), mB = (unsigned)(size_t)(lds_cplx_t)(S2 + BOF + wave * 64);
           const int u0 = p_ch * 2, u1 = u0 + 1;
-          const char* pC0 = pC + ((long long)(4 * (u0 & 3)) * lda + (u0 >> 2) * 16) * (long long)sizeof(cplx);
-          const char* pC1 = pC + ((long long)(4 * (u1 & 3)) * lda + (u1 >> 2) * 16) * (long long)sizeof(cplx);
-          asm volatile(
-              "ds_read_b128 %[b0], %[aB]\n\tds_read_b128 %[b1], %[aB] offset:256\n\tds_read_b128 %[b2], %[aB] offset:512\n\tds_read_b128 %[b3], %[aB] offset:768\n\t"
-              "ds_read_b128 %[b4], %[aB] offset:4096\n\tds_read_b128 %[b5], %[aB] offset:4352\n\tds_read_b128 %[b6], %[aB] offset:4608\n\tds_read_b128 %[b7], %[aB] offset:4864\n\t"
-              "ds_read_b128 %[a0], %[aA]\n\tds_read_b128 %[a1], %[aA] offset:64\n\tds_read_b128 %[a2], %[aA] offset:128\n\tds_read_b128 %[a3], %[aA] offset:192\n\t"
-              "ds_read_b128 %[a4], %[aA] offset:4352\n\tds_read_b128 %[a5], %[aA] offset:4416\n\tds_read_b128 %[a6], %[aA] offset:4480\n\tds_read_b128 %[a7], %[aA] offset:4544\n\t"
-              "ds_read_b128 %[c0], %[aC]\n\tds_read_b128 %[c1], %[aC] offset:4096\n\t"
-              "s_mov_b32 %[keep], m0\n\t"
-              "s_mov_b32 m0, %[mA]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA0], %[pA]\n\t"
-              "s_add_u32 m0, %[mA], 4352\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oA1], %[pA]\n\t"
-              "s_mov_b32 m0, %[mB]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB0], %[pB]\n\t"
-              "s_add_u32 m0, %[mB], 4096\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oB1], %[pB]\n\t"
-              "s_add_u32 m0, %[mB], 8192\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oC], %[pC0]\n\t"
-              "s_add_u32 m0, %[mB], 12288\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[oC], %[pC1]\n\t"
-              "s_mov_b32 m0, %[keep]\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : [keep] "=&s"(m0_keep), [a0] "=&v"(fa[0][0]), [a1] "=&v"(fa[0][1]), [a2] "=&v"(fa[0][2]), [a3] "=&v"(fa[0][3]), [a4] "=&v"(fa[1][0]),
-                [a5] "=&v"(fa[1][1]), [a6] "=&v"(fa[1][2]), [a7] "=&v"(fa[1][3]), [b0] "=&v"(fb[0][0]), [b1] "=&v"(fb[0][1]),
-                [b2] "=&v"(fb[0][2]), [b3] "=&v"(fb[0][3]), [b4] "=&v"(fb[1][0]), [b5] "=&v"(fb[1][1]), [b6] "=&v"(fb[1][2]),
-                [b7] "=&v"(fb[1][3]), [c0] "=&v"(cv[0]), [c1] "=&v"(cv[UPC - 1])
-              : [aA] "v"(aA), [aB] "v"(aB), [aC] "v"(aC), [mA] "s"(mA), [mB] "s"(mB), [oA0] "v"(offA0), [oA1] "v"(offA1), [oB0] "v"(offB0),
-                [oB1] "v"(offB1), [oC] "v"(offC), [pA] "s"(pA), [pB] "s"(pB), [pC0] "s"(pC0), [pC1] "s"(pC1)
-              : "memory", "scc");
+          const char* pC0 = BIEM_C_SRC(((long long)(4 * (u0 & 3)) * lda + (u0 >> 2) * 16) * (long long)sizeof(cplx));
+          const char* pC1 = BIEM_C_SRC(((long long)(4 * (u1 & 3)) * lda + (u1 >> 2) * 16) * (long long)sizeof(cplx));
+          asm volatile(BIEM_FRAG_READS16 BIEM_C_READ2 BIEM_M0_SAVE BIEM_OPERAND_DMA4 BIEM_C_DMA(8192, pC0) BIEM_C_DMA(12288, pC1)
+                       BIEM_M0_RESTORE BIEM_LGKM_WAIT
+                       : [keep] "=&s"(m0_keep), BIEM_FRAG_OUTS, BIEM_C_OUTS2
+                       : BIEM_FRAG_INS, BIEM_C_IN, BIEM_DMA_INS, [oC] "v"(offC), [pC0] "s"(pC0), [pC1] "s"(pC1)
+                       : "memory", "scc");
           __builtin_amdgcn_sched_barrier(0);
           n_new = NDMA;
           advance();
         } else if constexpr (UPC == 1) {
-          asm volatile(
-              "ds_read_b128 %[b0], %[aB]\n\tds_read_b128 %[b1], %[aB] offset:256\n\tds_read_b128 %[b2], %[aB] offset:512\n\tds_read_b128 %[b3], %[aB] offset:768\n\t"
-              "ds_read_b128 %[b4], %[aB] offset:4096\n\tds_read_b128 %[b5], %[aB] offset:4352\n\tds_read_b128 %[b6], %[aB] offset:4608\n\tds_read_b128 %[b7], %[aB] offset:4864\n\t"
-              "ds_read_b128 %[a0], %[aA]\n\tds_read_b128 %[a1], %[aA] offset:64\n\tds_read_b128 %[a2], %[aA] offset:128\n\tds_read_b128 %[a3], %[aA] offset:192\n\t"
-              "ds_read_b128 %[a4], %[aA] offset:4352\n\tds_read_b128 %[a5], %[aA] offset:4416\n\tds_read_b128 %[a6], %[aA] offset:4480\n\tds_read_b128 %[a7], %[aA] offset:4544\n\t"
-              "ds_read_b128 %[c0], %[aC]\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : [a0] "=&v"(fa[0][0]), [a1] "=&v"(fa[0][1]), [a2] "=&v"(fa[0][2]), [a3] "=&v"(fa[0][3]), [a4] "=&v"(fa[1][0]),
-                [a5] "=&v"(fa[1][1]), [a6] "=&v"(fa[1][2]), [a7] "=&v"(fa[1][3]), [b0] "=&v"(fb[0][0]), [b1] "=&v"(fb[0][1]),
-                [b2] "=&v"(fb[0][2]), [b3] "=&v"(fb[0][3]), [b4] "=&v"(fb[1][0]), [b5] "=&v"(fb[1][1]), [b6] "=&v"(fb[1][2]),
-                [b7] "=&v"(fb[1][3]), [c0] "=&v"(cv[0])
-              : [aA] "v"(aA), [aB] "v"(aB), [aC] "v"(aC)
-              : "memory");
+          asm volatile(BIEM_FRAG_READS16 BIEM_C_READ1 BIEM_LGKM_WAIT : BIEM_FRAG_OUTS, BIEM_C_OUTS1 : BIEM_FRAG_INS, BIEM_C_IN : "memory");
         } else {
-          asm volatile(
-              "ds_read_b128 %[b0], %[aB]\n\tds_read_b128 %[b1], %[aB] offset:256\n\tds_read_b128 %[b2], %[aB] offset:512\n\tds_read_b128 %[b3], %[aB] offset:768\n\t"
-              "ds_read_b128 %[b4], %[aB] offset:4096\n\tds_read_b128 %[b5], %[aB] offset:4352\n\tds_read_b128 %[b6], %[aB] offset:4608\n\tds_read_b128 %[b7], %[aB] offset:4864\n\t"
-              "ds_read_b128 %[a0], %[aA]\n\tds_read_b128 %[a1], %[aA] offset:64\n\tds_read_b128 %[a2], %[aA] offset:128\n\tds_read_b128 %[a3], %[aA] offset:192\n\t"
-              "ds_read_b128 %[a4], %[aA] offset:4352\n\tds_read_b128 %[a5], %[aA] offset:4416\n\tds_read_b128 %[a6], %[aA] offset:4480\n\tds_read_b128 %[a7], %[aA] offset:4544\n\t"
-              "ds_read_b128 %[c0], %[aC]\n\tds_read_b128 %[c1], %[aC] offset:4096\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : [a0] "=&v"(fa[0][0]), [a1] "=&v"(fa[0][1]), [a2] "=&v"(fa[0][2]), [a3] "=&v"(fa[0][3]), [a4] "=&v"(fa[1][0]),
-                [a5] "=&v"(fa[1][1]), [a6] "=&v"(fa[1][2]), [a7] "=&v"(fa[1][3]), [b0] "=&v"(fb[0][0]), [b1] "=&v"(fb[0][1]),
-                [b2] "=&v"(fb[0][2]), [b3] "=&v"(fb[0][3]), [b4] "=&v"(fb[1][0]), [b5] "=&v"(fb[1][1]), [b6] "=&v"(fb[1][2]),
-                [b7] "=&v"(fb[1][3]), [c0] "=&v"(cv[0]), [c1] "=&v"(cv[UPC - 1])
-              : [aA] "v"(aA), [aB] "v"(aB), [aC] "v"(aC)
-              : "memory");
+          asm volatile(BIEM_FRAG_READS16 BIEM_C_READ2 BIEM_LGKM_WAIT : BIEM_FRAG_OUTS, BIEM_C_OUTS2 : BIEM_FRAG_INS, BIEM_C_IN : "memory");
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -867,7 +811,6 @@ int launch_gemm_strip(hipStream_t st, int nb, cplx* A, long long lda, long long 
   if (col_end <= j + NB) return BIEM_OK;
   if (Y != nullptr && ((col_end - j) % BN3 != 0 || nrhs < 1 || nrhs > 8)) { set_error("biem_sym: strip with right-hand sides over a partial tile column"); return BIEM_ERR_ARG; }
   TileGrid tg;
-  tg.pout = nullptr; tg.pout_ld = 0; tg.pout_stride = 0; tg.pcol_tx = 0; tg.tri = 0; tg.tri_map = nullptr; tg.tri_full = 0; tg.full_bands = 0;
   tg.ty_n = 1; tg.tx_n = (col_end - j - NB + BN3 - 1) / BN3;
   tg.row_begin = j; tg.row_end = j + NB; tg.col_begin = j + NB; tg.col_end = col_end; tg.brow = j;
   const int grid = finish_tile_grid(tg, tg.tx_n, nb);
@@ -888,7 +831,6 @@ int launch_gemm_stack(hipStream_t st, int nb, cplx* A, long long lda, long long 
   if (p <= J || (p - J) % NB != 0 || kd > 4 * NB) { set_error("biem_sym: stacked pass outside its group"); return BIEM_ERR_ARG; }
   if (Y != nullptr && ((col_end - p) % BN3 != 0 || nrhs < 1 || nrhs > 8)) { set_error("biem_sym: stacked pass with right-hand sides over a partial tile column"); return BIEM_ERR_ARG; }
   TileGrid tg;
-  tg.pout = nullptr; tg.pout_ld = 0; tg.pout_stride = 0; tg.pcol_tx = 0; tg.tri = 0; tg.tri_map = nullptr; tg.tri_full = 0; tg.full_bands = 0;
   tg.ty_n = 1; tg.tx_n = (col_end - p - NB + BN3 - 1) / BN3;
   tg.row_begin = p; tg.row_end = p + NB; tg.col_begin = p + NB; tg.col_end = col_end; tg.brow = J;
   const int grid = finish_tile_grid(tg, tg.tx_n, nb);
@@ -918,7 +860,6 @@ int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long s
   if (J <= 0 || row_end <= J || col_end < row_end) return BIEM_OK;
   if (nf < 1 || nf > 4 || (nf < 4 && (col_end - J) % BN3 != 0)) { set_error("biem_sym: narrow bulk update over a partial tile column"); return BIEM_ERR_ARG; }
   TileGrid tg;
-  tg.pout = nullptr; tg.pout_ld = 0; tg.pout_stride = 0; tg.pcol_tx = 0; tg.tri = 0; tg.tri_map = nullptr; tg.full_bands = 0;
   tg.ty_n = (row_end - J) / BM3; tg.tx_n = (col_end - J + BN3 - 1) / BN3 - (nf < 4 ? 1 : 0);
   tg.row_begin = J; tg.row_end = row_end; tg.col_begin = J; tg.col_end = col_end - (nf < 4 ? BN3 : 0); tg.brow = 0;
   if (tg.tx_n > 0) {
@@ -936,7 +877,6 @@ int launch_gemm_left(hipStream_t st, int nb, cplx* A, long long lda, long long s
 static int launch_gemm_narrow_col(hipStream_t st, int nb, cplx* A, long long lda, long long sys_stride, int J, int row_end, int col_end,
                                   int h_last, int nf) {
   TileGrid tg;
-  tg.pout = nullptr; tg.pout_ld = 0; tg.pout_stride = 0; tg.pcol_tx = 0; tg.tri = 0; tg.tri_map = nullptr; tg.full_bands = 0;
   tg.ty_n = (row_end - J) / BM3; tg.tx_n = 1;
   tg.row_begin = J; tg.row_end = row_end; tg.col_begin = col_end - BN3; tg.col_end = col_end; tg.brow = 0;
   const int grid = finish_tile_grid(tg, h_last, nb);

@@ -3,7 +3,7 @@
 
     python tools/diff_kernels.py OLD.so NEW.so
 
-The code objects are extracted the way `_build.check_isa` does (llvm-objdump --offloading).  Compared per kernel: that both builds
+The code objects are extracted by `_build._code_objects`, as for `_build.check_isa` (llvm-objdump --offloading).  Compared per kernel: that both builds
 have it, its disassembly with addresses and encodings stripped and cut at the symbol's size (what follows is alignment padding), and
 its metadata (VGPRs, SGPRs, static LDS, scratch, spills ...).  Which translation unit a kernel sits in does not matter.  Prints the kernels that differ; exit status 1 if any.
 """
@@ -11,26 +11,15 @@ from __future__ import annotations
 
 import os
 import re
-import shutil
 import subprocess
 import sys
 import tempfile
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from biem_helmholtz_sphere_amd._build import _llvm_tool  # noqa: E402
+from biem_helmholtz_sphere_amd._build import IsaCheckError, _code_objects, _llvm_tool  # noqa: E402
 
 META_KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count",
              "sgpr_spill_count", "kernarg_segment_size", "max_flat_workgroup_size", "wavefront_size", "uses_dynamic_stack")
-
-
-def _code_objects(objdump: str, lib: str, tmp: str) -> list:
-    local = os.path.join(tmp, "lib.so")
-    shutil.copy(lib, local)
-    subprocess.run([objdump, "--offloading", local], check=True, capture_output=True, cwd=tmp)
-    objs = sorted(os.path.join(tmp, f) for f in os.listdir(tmp) if "gfx950" in f)
-    if not objs:
-        raise SystemExit(f"no gfx950 code object found in {lib}")
-    return objs
 
 
 def _metadata(readelf: str, obj: str) -> dict:
@@ -78,7 +67,11 @@ def kernels_of(lib: str) -> dict:
         raise SystemExit("llvm-objdump / llvm-readelf not found")
     kernels = {}
     with tempfile.TemporaryDirectory(prefix="biem_diffk_") as tmp:
-        for obj in _code_objects(objdump, lib, tmp):
+        try:
+            objs = _code_objects(lib, tmp)
+        except IsaCheckError as e:
+            raise SystemExit(str(e))
+        for obj in objs:
             metas, dis = _metadata(readelf, obj), _disassembly(objdump, readelf, obj)
             for sym, meta in metas.items():
                 if sym in kernels:
