@@ -28,9 +28,9 @@ from ._fields import (USCAT_GRAD_N_END_MAX, biem_far_pattern, biem_u, biem_u_gra
                       biem_u_total, biem_u_total_grad)
 from ._incident import fluid_inclusion_bc, max_memory, max_n_end, plane_wave, point_source
 from ._observables import BIEMPower, biem_force, biem_power
-from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_incident, _check_plane_wave_direction, _entry,
-                        _factored_source_args, _nrhs, _operator, _pick_systems, _plane_wave_source, _rhs_project, _sample_ptrs,
-                        _source_entry, _source_workspace_bytes, _validate_biem_inputs, _warn_biem_inputs)
+from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_closed_form, _check_incident, _check_plane_wave_direction,
+                        _check_point_source_position, _entry, _factored_source_args, _nrhs, _operator, _pick_systems, _plane_wave_source,
+                        _point_source_source, _rhs_project, _sample_ptrs, _source_entry, _source_workspace_bytes, _validate_biem_inputs, _warn_biem_inputs)
 from ._plans import _chain_plan_dim, _plan
 
 try:  # numpy >= 1.25
@@ -209,15 +209,29 @@ def _result(op: _Operator, uin, density_t: Optional[torch.Tensor], axes: Optiona
 # --------------------------------------------------------------------------------------
 # the solver (reference :453-819)
 # --------------------------------------------------------------------------------------
-def _incident_source(op: _Operator, uin, uin_grad, directions, given=None):
+def _closed_form_request(c, k, uin, uin_grad, plane_wave_direction, point_source_position):
+    """The checks of plane_wave_direction / point_source_position that need no device.  None without either, else (argument name, the
+    checked array on the host, the argument as the caller passed it)."""
+    if point_source_position is not None:
+        checked = _check_point_source_position(c, k, point_source_position, uin, uin_grad, plane_wave_direction)
+        return "point_source_position", checked, point_source_position
+    if plane_wave_direction is not None:
+        return "plane_wave_direction", _check_plane_wave_direction(c, k, plane_wave_direction, uin, uin_grad), plane_wave_direction
+    return None
+
+
+def _incident_source(op: _Operator, uin, uin_grad, closed=None):
     """The source of the right-hand sides, the _RhsAxes of its layout and the callable the result keeps as `.uin`: the samples of
-    (uin, uin_grad), or - `directions`: the checked plane_wave_direction, `given`: as the caller passed it - plane waves in closed form,
-    whose `.uin` is plane_wave's for the caller's k and direction (a floating tensor as it is, anything else as float64)."""
-    if directions is None:
+    (uin, uin_grad), or - `closed`: what _closed_form_request returned - plane waves or point sources in closed form, whose `.uin` is
+    plane_wave's / point_source's (n = 0) for the caller's k and argument (a floating tensor as it is, anything else as float64)."""
+    if closed is None:
         _check_incident(op, uin, uin_grad)
         return _boundary_samples(op, uin, uin_grad) + (uin,)
-    as_given = isinstance(given, torch.Tensor) and given.is_floating_point()
-    return _plane_wave_source(op, directions) + (plane_wave(k=op.k_given, direction=given if as_given else directions)[0],)
+    name, checked, given = closed
+    arg = given if isinstance(given, torch.Tensor) and given.is_floating_point() else checked
+    if name == "point_source_position":
+        return _point_source_source(op, checked) + (point_source(k=op.k_given, source=arg, n=0)[0],)
+    return _plane_wave_source(op, checked) + (plane_wave(k=op.k_given, direction=arg)[0],)
 
 
 def _solver() -> str:
@@ -317,7 +331,8 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
          uin: Callable[[Array], Array] | None = None, uin_grad: Callable[[Array], Array] | None = None, eta: Array | None = None,
          kind: Literal["inner", "outer"] = "outer", force_matrix: bool = False,
          translational_coefficients_method: Literal["gumerov", "plane_wave", "triplet"] | None = None, chunk: int = 0,
-         alpha_n: Array | None = None, beta_n: Array | None = None, plane_wave_direction: Array | None = None) -> BIEMResultCalculator:
+         alpha_n: Array | None = None, beta_n: Array | None = None, plane_wave_direction: Array | None = None,
+         point_source_position: Array | None = None) -> BIEMResultCalculator:
     r"""Boundary Integral Equation Method (BIEM) for the Helmholtz equation on MI355X.
 
     Same contract as the reference ``biem`` (``_biem.py:453-581``): solves, per leading batch element,
@@ -342,6 +357,16 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     content in every degree) - without sampling anything.  The result is that of ``biem(..., *plane_wave(k=k, direction=D))`` apart from
     that: trailing axes of D on which the operator has size 1 are right-hand sides of one factorisation, ``.uin`` is plane_wave's callable.
 
+    ``point_source_position`` (extension, shape ``(c_ndim, ...)`` like the source of :func:`point_source`; not together with uin /
+    uin_grad / plane_wave_direction): the incident field is the monopole ``h_0(k |x - s|)`` of the operator's own k,
+    ``point_source(k=k, source=S, n=0)``, and its right-hand side is formed in closed form,
+    ``f = -C_d gj_n h_n(k |s - c_b|) conj(Y_h((s - c_b)^))`` - exact, where the projection of samples aliases badly for a source close
+    to a sphere (content of degree n decays only like ``(rho_b / |s - c_b|)^n``), and the transpose of the evaluation of the scattered
+    field at s, so that reciprocity holds to rounding at every order.  Every source must lie strictly outside every ball, for kind
+    "inner" and "outer" alike (``ValueError`` naming the first source and ball otherwise; tested on the device, one synchronisation per
+    call).  The axes of S behave as those of plane_wave_direction, ``.uin`` is point_source's callable.  Orders n >= 1 of
+    :func:`point_source` have no such expansion and stay with uin / uin_grad.  ``NotImplementedError`` for n_end > 320 (2-D only).
+
     Solver: the reference passes every system to a general dense solve (``_biem.py:797``).  Here the system is first brought
     to its complex-symmetric form (real harmonics, symmetric scaling) and factored as U^T U (Cholesky-type, no conjugation)
     without interchanges - half the flops; a system in which a multiplier would exceed 100, or whose factor grew by more than
@@ -350,14 +375,14 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     """
     if translational_coefficients_method not in (None, "gumerov", "plane_wave", "triplet"):
         raise ValueError(f"Invalid translational_coefficients_method: {translational_coefficients_method}")
-    directions = None if plane_wave_direction is None else _check_plane_wave_direction(c, k, plane_wave_direction, uin, uin_grad)
+    closed = _closed_form_request(c, k, uin, uin_grad, plane_wave_direction, point_source_position)
     op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n, beta_n)
     lib = L.load()
     plan, fl, dev = op.plan, op.fl, op.dev
     B, nb, H = fl.B, fl.nb, plan.H
     sp = _stream_ptr(dev)
 
-    has_rhs = not (uin is None and uin_grad is None and directions is None)
+    has_rhs = not (uin is None and uin_grad is None and closed is None)
     g = axes = None
     # A repeated call of the same shape takes its workspace FIRST, before the boundary samples: the block the previous call
     # returned to torch's caching allocator is then still whole.  Taken after them, one of their mid-size temporaries may have
@@ -365,7 +390,7 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     ws_key = (plan.tree, plan.chain, int(n_end), int(nb), int(B), int(chunk), os.environ.get("BIEM_MAX_RESIDENT_BYTES"))
     work_pre = _workspace(dev, ws_key) if has_rhs and nb > 0 and (B > 1 or force_matrix) else None
     if has_rhs:
-        g, axes, uin = _incident_source(op, uin, uin_grad, directions, plane_wave_direction)
+        g, axes, uin = _incident_source(op, uin, uin_grad, closed)
         nrhs = _nrhs(g)
 
     use_matrix = (not has_rhs) or B > 1 or force_matrix          # reference :643-645
@@ -391,12 +416,12 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
             # which is what the reference's linalg.solve does for every system (_biem.py:797).  BIEM_SOLVER=lu: LU only.
             solver = _solver()
             # (degree-dependent coefficients: the *_n entries, alpha_n / beta_n for alpha / beta and the unmixed samples for g; plane
-            # waves in closed form: the *_pw entries)
+            # waves and point sources in closed form: the *_pw and *_ps entries)
             e_lu, what = _source_entry("biem_solve", op, g, "biem_solve")
             entry = _source_entry("biem_solve_ldlt", op, g)[0] if solver == "ldlt" else e_lu
-            L.check(entry(plan.handle, nb, B, nrhs, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
-                          _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, *_sample_ptrs(g), _ptr(density_t), _ptr(info), chunk,
-                          _ptr(work), wbytes, sp), what)
+            _check_closed_form(g, entry(plan.handle, nb, B, nrhs, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii), fl.geom_batched,
+                                        _ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched, *_sample_ptrs(g), _ptr(density_t), _ptr(info), chunk,
+                                        _ptr(work), wbytes, sp), what)
             lu_h, codes = _lu_systems(info, solver)
             if solver == "ldlt" and lu_h.numel() > 0:
                 _resolve_with_lu(op, e_lu, lu_h, g, density_t, chunk, work, sp)
@@ -447,19 +472,21 @@ class BIEMFactorization:
                 f"n_symmetric={self.n_symmetric}, n_lu={self.n_lu}, nbytes={self.nbytes}{', closed' if self._closed else ''})")
 
     def solve(self, *, uin: Callable[[Array], Array] | None = None, uin_grad: Callable[[Array], Array] | None = None,
-              plane_wave_direction: Array | None = None) -> BIEMResultCalculator:
-        """Densities of the incident field (uin, uin_grad), or of plane waves along ``plane_wave_direction`` in closed form, against the
-        stored factors: ``biem()``'s result for the same field."""
+              plane_wave_direction: Array | None = None, point_source_position: Array | None = None) -> BIEMResultCalculator:
+        """Densities of the incident field (uin, uin_grad), or of plane waves along ``plane_wave_direction`` or of point sources at
+        ``point_source_position`` (the monopoles ``h_0(k |x - s|)``, strictly outside every ball) in closed form, against the stored
+        factors: ``biem()``'s result for the same field.  Many source positions against one factorisation are right-hand sides of one
+        call: a trailing axis of the argument on which the operator has size 1."""
         if self._closed:
             raise ValueError("BIEMFactorization is closed")
         op, lib = self._op, L.load()
-        directions = None if plane_wave_direction is None else _check_plane_wave_direction(op.c, op.k_given, plane_wave_direction, uin, uin_grad)
+        closed = _closed_form_request(op.c, op.k_given, uin, uin_grad, plane_wave_direction, point_source_position)
         plan, fl, dev = op.plan, op.fl, op.dev
         B, H, nb = fl.B, plan.H, fl.nb
-        has_rhs = not (uin is None and uin_grad is None and directions is None)
+        has_rhs = not (uin is None and uin_grad is None and closed is None)
         density_t = axes = None
         if has_rhs:
-            g, axes, uin = _incident_source(op, uin, uin_grad, directions, plane_wave_direction)
+            g, axes, uin = _incident_source(op, uin, uin_grad, closed)
             nrhs = _nrhs(g)
             density_t = torch.empty((nb, nrhs, B, H), dtype=torch.complex128, device=dev)
             sp = _stream_ptr(dev)
@@ -473,8 +500,8 @@ class BIEMFactorization:
                         wb = int(lib.biem_solve_factored_workspace_bytes(plan.handle, nb, B, nrhs)) + _source_workspace_bytes(op, g)
                         work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
                         entry, what = _source_entry("biem_solve_factored", op, g)
-                        L.check(entry(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab), *_factored_source_args(op, g), *_sample_ptrs(g),
-                                      _ptr(density_t), _ptr(work), wb, sp), what)
+                        _check_closed_form(g, entry(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab), *_factored_source_args(op, g),
+                                                    *_sample_ptrs(g), _ptr(density_t), _ptr(work), wb, sp), what)
                         del work
                     # LU-form systems (runs of consecutive systems): equilibrated right-hand sides in natural order, stored LU, density
                     ldx = nrhs

@@ -127,7 +127,7 @@ def point_source(*, k: Array, source: Array, n: int) -> Tuple[Callable[[Array], 
 
     def inner(x: Array, /) -> Array:
         was_np, dev, rel, r, kt = _prep(x)
-        h, _ = _radial(int(rel.shape[0]), (kt * r).expand(r.shape) if kt.ndim else kt * r)
+        h, _ = _radial(int(rel.shape[0]), kt * r)      # (k and the source may each have batch axes the other has at size 1)
         return _back(h, was_np, dev)
 
     def inner_grad(x: Array, /) -> Array:

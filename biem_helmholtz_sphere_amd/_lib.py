@@ -93,6 +93,11 @@ SIGNATURES = {
     "biem_solve_pw": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_ldlt_pw": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_factored_pw": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _dp, _vp, _sz, _vp]),
+    "biem_rhs_point_source_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "biem_rhs_point_source": (_i, [_vp, _i, _i, _i, _dp, _dp, _i, _dp, _dp, _i, _dp, _ll, _ll, _ll, _vp, _sz, _vp]),
+    "biem_solve_ps": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_solve_ldlt_ps": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_solve_factored_ps": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _dp, _vp, _sz, _vp]),
     "biem_power": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, _vp]),
     "biem_power_n": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, _vp]),
     "biem_force": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _vp]),

@@ -352,6 +352,47 @@ class _PlaneWaves:
     dirs: torch.Tensor
     batched: int
     per_degree: bool         # of the operator: the `_pw` entries take it as an argument, not as a second set of entries
+    suffix = "_pw"           # of the whole-path entries
+    rhs_entry = "biem_rhs_plane_wave"
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.dirs
+
+    def workspace_bytes(self, op: "_Operator", n: int) -> int:
+        return int(L.load().biem_rhs_plane_wave_workspace_bytes(op.plan.handle, n, int(self.dirs.shape[1]), self.batched))
+
+
+@dataclass(frozen=True)
+class _PointSources:
+    """Point sources h_0(k |x - s|) as the source of the right-hand sides, in closed form (biem_rhs_point_source): positions in the plan's
+    canonical axes, [nb, nrhs, d] when they differ between the systems of the operator (batched), else [1, nrhs, d].  Stands where
+    _PlaneWaves stands, with the same fields."""
+
+    pts: torch.Tensor
+    batched: int
+    per_degree: bool
+    suffix = "_ps"
+    rhs_entry = "biem_rhs_point_source"
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.pts
+
+    def workspace_bytes(self, op: "_Operator", n: int) -> int:
+        return int(L.load().biem_rhs_point_source_workspace_bytes(op.plan.handle, n, op.fl.B, int(self.pts.shape[1]), self.batched,
+                                                                  op.fl.geom_batched))
+
+
+_CLOSED_FORM = (_PlaneWaves, _PointSources)
+
+
+def _check_closed_form(g, rc: int, what: str) -> None:
+    """L.check; for point sources BIEM_ERR_UNSUPPORTED (the order limit of their radial table, 2-D only) as NotImplementedError."""
+    if isinstance(g, _PointSources) and rc == L.BIEM_ERR_UNSUPPORTED:
+        msg = L.load().biem_last_error()
+        raise NotImplementedError(msg.decode() if msg else f"{what}: not built for this order")
+    L.check(rc, what)
 
 
 def _check_plane_wave_direction(c, k, direction, uin, uin_grad) -> np.ndarray:
@@ -391,19 +432,70 @@ def _plane_wave_source(op: _Operator, D: np.ndarray):
     return _PlaneWaves(dirs if batched else dirs[:1].contiguous(), batched, op.per_degree), axes
 
 
+def _check_point_source_position(c, k, position, uin, uin_grad, plane_wave_direction) -> np.ndarray:
+    """The checks of biem(point_source_position=) that need no device; returns the positions on the host as float64."""
+    if uin is not None or uin_grad is not None or plane_wave_direction is not None:
+        raise ValueError("point_source_position replaces uin / uin_grad / plane_wave_direction: give one source of the incident field, not several")
+    S = _host_array(position)
+    if S.dtype.kind not in "iuf":
+        raise ValueError(f"point_source_position must be a real array, got dtype {S.dtype}")
+    S = S.astype(np.float64)
+    if S.ndim < 1 or S.shape[0] != c.c_ndim:
+        raise ValueError(f"The first dimension of point_source_position must be c.c_ndim={c.c_ndim}, but got shape {tuple(S.shape)}")
+    if S.ndim != len(_shape(k)) + 1:
+        raise ValueError(f"point_source_position.ndim={S.ndim} is not k.ndim + 1={len(_shape(k)) + 1}")
+    if not bool(np.all(np.isfinite(S))):
+        raise ValueError("point_source_position has a non-finite entry")
+    return S
+
+
+def _check_sources_outside(op: _Operator, pts: torch.Tensor) -> None:
+    """ValueError unless |s - c_b| > rho_b for every (system, source, ball) of pts [nb or 1, nrhs, d] (canonical axes), naming the first
+    that fails.  On the device; the test of the result is one synchronisation."""
+    fl = op.fl
+    if not pts.numel() or not fl.B:
+        return
+    dist = torch.linalg.vector_norm(pts[:, :, None, :] - fl.centers[:, None, :, :], dim=-1)      # [nb or 1, nrhs, B]
+    bad = ~(dist > fl.radii[:, None, :])
+    if bool(bad.any()):
+        s, r, b = (int(v) for v in torch.nonzero(bad)[0])
+        raise ValueError(f"point_source_position: source {r} (system {s}) lies on or inside ball {b}: |s - c| = {float(dist[s, r, b]):.17g} "
+                         f"<= radius {float(fl.radii[s if fl.geom_batched else 0, b]):.17g}; a point source must lie strictly outside every ball")
+
+
+def _point_source_source(op: _Operator, S: np.ndarray):
+    """The source of the checked positions S (c_ndim, ...) and the _RhsAxes of its layout, as _plane_wave_source.  Every source must lie
+    strictly outside every ball (the expansion about a ball's centre converges only there, for kind "inner" and "outer" alike):
+    _check_sources_outside, before any library call."""
+    batch = op.batch
+    try:
+        full = tuple(np.broadcast_shapes(batch, S.shape[1:]))
+    except ValueError as e:
+        raise ValueError("Shapes of the batch and point_source_position[1:] are not broadcastable\n"
+                         f"batch shape={batch}\ntuple(point_source_position.shape)={tuple(S.shape)}") from e
+    axes = _RhsAxes.of(batch, full)
+    S = S[list(op.perm)]                                              # canonical component i = the caller's perm[i], as the centres
+    batched = int(any(S.shape[1 + i] != 1 for i in axes.op_axes))
+    t = torch.as_tensor(np.moveaxis(np.broadcast_to(S, (S.shape[0],) + full), 0, -1).copy(), device=op.dev)
+    pts = axes.lay_out(t)                                             # [nb, nrhs, d]
+    pts = pts if batched else pts[:1].contiguous()
+    _check_sources_outside(op, pts)
+    return _PointSources(pts, batched, op.per_degree), axes
+
+
 def _nrhs(g) -> int:
     """Right-hand sides per system of a source: the samples of _boundary_samples (a tensor, or the unmixed pair of the degree-dependent
-    case) or _PlaneWaves."""
-    if isinstance(g, _PlaneWaves):
-        return int(g.dirs.shape[1])
+    case), _PlaneWaves or _PointSources."""
+    if isinstance(g, _CLOSED_FORM):
+        return int(g.vectors.shape[1])
     return int((g if isinstance(g, torch.Tensor) else next(t for t in g if t is not None)).shape[1])
 
 
 def _sample_ptrs(g, s0: int = 0):
     """The source arguments of an entry point from system s0 on: (d_g,) or (d_gu, d_gdn), a missing set as the null pointer; plane
-    waves: (per_degree, d_dirs, dirs_batched)."""
-    if isinstance(g, _PlaneWaves):
-        return (int(g.per_degree), _ptr(g.dirs[s0:] if g.batched else g.dirs), g.batched)
+    waves and point sources: (per_degree, d_dirs or d_src, batched)."""
+    if isinstance(g, _CLOSED_FORM):
+        return (int(g.per_degree), _ptr(g.vectors[s0:] if g.batched else g.vectors), g.batched)
     if isinstance(g, torch.Tensor):
         return (_ptr(g[s0:]),)
     return tuple(_ptr(None if t is None else t[s0:]) for t in g)
@@ -411,8 +503,8 @@ def _sample_ptrs(g, s0: int = 0):
 
 def _pick_systems(g, idx: torch.Tensor):
     """The source of the systems idx (a device index tensor) alone."""
-    if isinstance(g, _PlaneWaves):
-        return _PlaneWaves(g.dirs[idx].contiguous(), 1, g.per_degree) if g.batched else g
+    if isinstance(g, _CLOSED_FORM):
+        return type(g)(g.vectors[idx].contiguous(), 1, g.per_degree) if g.batched else g
     if isinstance(g, torch.Tensor):
         return g[idx].contiguous()
     return tuple(None if t is None else t[idx].contiguous() for t in g)
@@ -426,25 +518,24 @@ def _entry(base: str, per_degree: bool, label: Optional[str] = None):
 
 
 def _source_entry(base: str, op: _Operator, g, label: Optional[str] = None):
-    """The entry `base` for the source g: its `_pw` form for plane waves, else _entry's choice."""
-    if isinstance(g, _PlaneWaves):
-        return getattr(L.load(), base + "_pw"), label or base + "_pw"
+    """The entry `base` for the source g: its `_pw` form for plane waves, its `_ps` form for point sources, else _entry's choice."""
+    if isinstance(g, _CLOSED_FORM):
+        return getattr(L.load(), base + g.suffix), label or base + g.suffix
     return _entry(base, op.per_degree, label)
 
 
 def _source_workspace_bytes(op: _Operator, g) -> int:
-    """What the source adds at the tail of a path's workspace (plane waves: the harmonics of their directions)."""
-    if isinstance(g, _PlaneWaves):
-        return int(L.load().biem_rhs_plane_wave_workspace_bytes(op.plan.handle, op.fl.nb, _nrhs(g), g.batched))
-    return 0
+    """What the source adds at the tail of a path's workspace (plane waves: the harmonics of their directions; point sources: those
+    of the unit vectors from every ball, and the radial table)."""
+    return g.workspace_bytes(op, op.fl.nb) if isinstance(g, _CLOSED_FORM) else 0
 
 
 def _factored_source_args(op: _Operator, g) -> tuple:
     """What biem_solve_factored* takes between the tables and the source arguments: nothing, the degree-dependent pair, or for plane
-    waves the wavenumbers, the centres and the coefficients."""
+    waves and point sources the wavenumbers, the centres and the coefficients."""
     fl = op.fl
     coef = (_ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched)
-    if isinstance(g, _PlaneWaves):
+    if isinstance(g, _CLOSED_FORM):
         return (_ptr(fl.k), _ptr(fl.centers), fl.geom_batched) + coef
     return coef if op.per_degree else ()
 
@@ -463,16 +554,17 @@ def _ball_tables(op: _Operator, sp: int, fill: bool = True) -> torch.Tensor:
 def _rhs_project(op: _Operator, n: int, g, s0: int, f: torch.Tensor, sys_stride: int, elem_stride: int, rhs_stride: int, sp: int,
                  tab: Optional[torch.Tensor] = None) -> None:
     """The right-hand sides of the n systems from s0 on into f (natural order), by the source g: biem_rhs_project / biem_rhs_project_n
-    of samples, biem_rhs_plane_wave of plane waves (from `tab`, the ball tables of those n systems)."""
+    of samples, biem_rhs_plane_wave of plane waves and biem_rhs_point_source of point sources (from `tab`, the ball tables of those n
+    systems)."""
     fl, a0 = op.fl, s0 if op.fl.ab_batched else 0
-    if isinstance(g, _PlaneWaves):
-        lib = L.load()
-        wb = int(lib.biem_rhs_plane_wave_workspace_bytes(op.plan.handle, n, _nrhs(g), g.batched))
+    if isinstance(g, _CLOSED_FORM):
+        wb = g.workspace_bytes(op, n)
         work = torch.empty(max(wb, 16), dtype=torch.uint8, device=op.dev)
-        _, d_dirs, batched = _sample_ptrs(g, s0)
-        L.check(lib.biem_rhs_plane_wave(op.plan.handle, n, fl.B, _nrhs(g), _ptr(fl.k[s0:]), _ptr(fl.centers[s0:] if fl.geom_batched else fl.centers),
-                                        fl.geom_batched, _ptr(tab), d_dirs, batched, _ptr(f), sys_stride, elem_stride, rhs_stride,
-                                        _ptr(work), wb, sp), "biem_rhs_plane_wave")
+        _, d_vec, batched = _sample_ptrs(g, s0)
+        rc = getattr(L.load(), g.rhs_entry)(op.plan.handle, n, fl.B, _nrhs(g), _ptr(fl.k[s0:]), _ptr(fl.centers[s0:] if fl.geom_batched else fl.centers),
+                                            fl.geom_batched, _ptr(tab), d_vec, batched, _ptr(f), sys_stride, elem_stride, rhs_stride,
+                                            _ptr(work), wb, sp)
+        _check_closed_form(g, rc, g.rhs_entry)
         return
     entry, what = _entry("biem_rhs_project", op.per_degree)
     coef = (_ptr(fl.alpha[a0:]), _ptr(fl.beta[a0:]), fl.ab_batched) if op.per_degree else ()

@@ -520,7 +520,7 @@ int biem_rhs_plane_wave(const biem_plan* plan, int nb, int B, int nrhs, const do
                         long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream) {
   NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_centers, "d_centers"); NEED(d_tab, "d_tab"); NEED(d_dirs, "d_dirs"); NEED(d_f, "d_f"); NEED(d_work, "d_work");
   const Samples src = {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched, d_work};
-  if (work_bytes < src.work_bytes(plan, nb, nrhs)) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, src.work_bytes(plan, nb, nrhs)); return BIEM_ERR_ARG; }
+  if (work_bytes < src.work_bytes(plan, nb, B, nrhs)) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, src.work_bytes(plan, nb, B, nrhs)); return BIEM_ERR_ARG; }
   return rhs_project(plan, nb, B, nrhs, {nullptr, nullptr, 0, false}, src, d_f, sys_stride, elem_stride, rhs_stride, (hipStream_t)stream, false,
                      SplitMap(), d_tab);
 }
@@ -553,6 +553,55 @@ int biem_solve_factored_pw(const biem_plan* plan, int nb, int B, int nrhs, const
   return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {d_alpha, d_beta, ab_batched, per_degree != 0},
                              {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched}, d_density, d_work,
                              work_bytes, (hipStream_t)stream);
+}
+
+// ---- point-source incidence in closed form (kernels_rhs_ps.hip): the fourth source of right-hand sides ----
+static Samples point_sources(const double* d_src, int src_batched, const double* d_k, const double* d_centers, int geom_batched, void* d_work = nullptr) {
+  return {nullptr, nullptr, nullptr, nullptr, 0, d_k, d_centers, geom_batched, d_work, d_src, src_batched};
+}
+
+size_t biem_rhs_point_source_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs, int src_batched, int geom_batched) {
+  return plan ? rhs_point_source_workspace_bytes(plan, nb, B, nrhs, src_batched, geom_batched) : 0;
+}
+
+int biem_rhs_point_source(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
+                          const double* d_tab, const double* d_src, int src_batched, double* d_f, long long sys_stride,
+                          long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_centers, "d_centers"); NEED(d_tab, "d_tab"); NEED(d_src, "d_src"); NEED(d_f, "d_f"); NEED(d_work, "d_work");
+  const Samples src = point_sources(d_src, src_batched, d_k, d_centers, geom_batched, d_work);
+  if (work_bytes < src.work_bytes(plan, nb, B, nrhs)) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, src.work_bytes(plan, nb, B, nrhs)); return BIEM_ERR_ARG; }
+  return rhs_project(plan, nb, B, nrhs, {nullptr, nullptr, 0, false}, src, d_f, sys_stride, elem_stride, rhs_stride, (hipStream_t)stream, false,
+                     SplitMap(), d_tab);
+}
+
+int biem_solve_ps(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_src, int src_batched, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                  void* stream) {
+  NEED(d_src, "d_src");
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    point_sources(d_src, src_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work, work_bytes,
+                    (hipStream_t)stream, false);
+}
+
+int biem_solve_ldlt_ps(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                       const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                       const double* d_src, int src_batched, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                       void* stream) {
+  NEED(d_src, "d_src");
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    point_sources(d_src, src_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work, work_bytes,
+                    (hipStream_t)stream, true);
+}
+
+int biem_solve_factored_ps(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k, const double* d_centers, int geom_batched, const double* d_alpha,
+                           const double* d_beta, int ab_batched, int per_degree, const double* d_src, int src_batched,
+                           double* d_density, void* d_work, size_t work_bytes, void* stream) {
+  NEED(d_src, "d_src");
+  return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                             point_sources(d_src, src_batched, d_k, d_centers, geom_batched), d_density, d_work, work_bytes,
+                             (hipStream_t)stream);
 }
 
 // ---- extinction and absorbed power (kernels_power.hip), radiation force (kernels_force.hip) ----

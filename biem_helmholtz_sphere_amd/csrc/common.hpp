@@ -132,6 +132,17 @@ size_t rhs_plane_wave_workspace_bytes(const biem_plan* p, int nb, int nrhs, int 
 int launch_rhs_plane_wave(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
                           const double* d_tab, const double* d_dirs, int dirs_batched, double* d_f, long long sys_stride,
                           long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work);
+// complex [batch][rows][cols] -> [batch][cols][rows], 32 x 32 tiles through LDS (kernels_rhs_pw.hip); batches <= 65535, rows <= 32 x 65535
+int launch_transpose_rows(int cols, int rows, int batches, const double* d_in, double* d_out, hipStream_t st);
+// point-source incidence in closed form (kernels_rhs_ps.hip): the monopole h_0(k |x - s_r|), f = -C_d gj_n h_n(k |t|) conj(Y_h(t^)),
+// t = s_r - c_b, from the ball tables, written where launch_rhs_project writes.  d_src: source positions in the plan's axes, [nrhs][d] or
+// (src_batched) [nb][nrhs][d]; d_work: rhs_point_source_workspace_bytes.  |t| > rho_b is the caller's to ensure (not tested: finite
+// nonsense on or inside a sphere, non-finite values at t = 0).  At most 65535 systems and right-hand sides; n_end <= kMaxRad, else
+// BIEM_ERR_UNSUPPORTED and nothing launched.
+size_t rhs_point_source_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int src_batched, int geom_batched);
+int launch_rhs_point_source(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
+                            const double* d_tab, const double* d_src, int src_batched, double* d_f, long long sys_stride,
+                            long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work);
 // d_info[s] = code for every system with a (ball, degree) whose symmetric scaling 1 / sqrt(gj gh) is not finite (gj = 0); others untouched
 // (biem_flag_unscalable exposes it for tests)
 int launch_flag_unscalable(const biem_plan* p, int nb, int B, const double* d_tab, int* d_info, int code, hipStream_t st);
@@ -243,12 +254,18 @@ struct BoundaryCoef {
 };
 // the source of the right-hand sides.  Boundary samples [nb][nrhs][B][Q] complex: g of plain coefficients; per degree the unmixed gu / gdn
 // (either may be null: zero).  Or, with dirs set, plane waves along dirs in closed form (launch_rhs_plane_wave: no samples), which
-// reads the wavenumbers and centres of the call and keeps its harmonics in `work` (set by the path: the tail of its workspace).
+// reads the wavenumbers and centres of the call and keeps its harmonics in `work` (set by the path: the tail of its workspace).  Or, with
+// src set, point sources at src in closed form (launch_rhs_point_source), which reads and keeps the same.
 struct Samples {
   const double* g; const double* gu; const double* gdn;
   const double* dirs = nullptr; int dirs_batched = 0;
   const double* k = nullptr; const double* centers = nullptr; int geom_batched = 0; void* work = nullptr;
-  size_t work_bytes(const biem_plan* p, int nb, int nrhs) const { return dirs ? rhs_plane_wave_workspace_bytes(p, nb, nrhs, dirs_batched) : 0; }
+  const double* src = nullptr; int src_batched = 0;
+  bool closed_form() const { return dirs || src; }
+  size_t work_bytes(const biem_plan* p, int nb, int B, int nrhs) const {
+    return dirs ? rhs_plane_wave_workspace_bytes(p, nb, nrhs, dirs_batched)
+         : src ? rhs_point_source_workspace_bytes(p, nb, B, nrhs, src_batched, geom_batched) : 0;
+  }
 };
 
 inline long long rhs_ld(long long nrhs) { return (nrhs + 7) / 8 * 8; }   // right-hand-side columns; rows stay 128-byte aligned (8 complex128)

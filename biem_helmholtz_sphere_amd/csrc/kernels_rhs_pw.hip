@@ -93,6 +93,12 @@ __global__ void __launch_bounds__(256) k_rhs_pw_r(int d, int H, int n_end, int B
 }
 }  // namespace
 
+int launch_transpose_rows(int cols, int rows, int batches, const double* d_in, double* d_out, hipStream_t st) {
+  hipLaunchKernelGGL(k_pw_transpose, dim3((cols + 31) / 32, (rows + 31) / 32, batches), dim3(256), 0, st, cols, rows, (const cplx*)d_in, (cplx*)d_out);
+  BIEM_LAUNCHCHK();
+  return BIEM_OK;
+}
+
 size_t rhs_plane_wave_workspace_bytes(const biem_plan* p, int nb, int nrhs, int dirs_batched) {
   if (nb <= 0 || nrhs <= 0) return 0;
   // the harmonics of the directions [dir][H], and their copy [h][r] per system of directions for the form with r along the lanes
@@ -113,8 +119,7 @@ int launch_rhs_plane_wave(const biem_plan* p, int nb, int B, int nrhs, const dou
   const int* hpos = slot_order ? p->d_hpos : nullptr;
   // consecutive right-hand sides of a row contiguous and at least a wave of them: r along the lanes; else h along the lanes
   if (rhs_stride == 1 && nrhs >= 64) {
-    hipLaunchKernelGGL(k_pw_transpose, dim3((H + 31) / 32, (nrhs + 31) / 32, dsys), dim3(256), 0, st, H, nrhs, Y, Yt);
-    BIEM_LAUNCHCHK();
+    if (const int rc = launch_transpose_rows(H, nrhs, dsys, (const double*)Y, (double*)Yt, st)) return rc;
     hipLaunchKernelGGL(k_rhs_pw_r, dim3((nrhs + 63) / 64 * B, nb), dim3(256), 0, st, p->d, H, p->n_end, B, nrhs, p->Cd, (const cplx*)d_k,
                        d_centers, geom_batched, (const cplx*)d_tab, d_dirs, dirs_batched, Yt, p->d_deg, (cplx*)d_f, sys_stride,
                        elem_stride, hpos, split);

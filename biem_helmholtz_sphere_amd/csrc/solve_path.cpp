@@ -138,6 +138,13 @@ int flag_unscalable(const biem_plan* p, int c, int B, const BoundaryCoef& bc, co
   return bc.per_degree ? launch_flag_unscalable(p, c, B, tab, info, -(n_pad + 2), st) : BIEM_OK;
 }
 
+// point sources: the radial table of a (source, ball) pair is a thread-local array (before anything is launched)
+int point_source_order(const char* who, const biem_plan* p, const Samples& smp) {
+  if (!smp.src || p->n_end <= kMaxRad) return BIEM_OK;
+  set_error("%s: n_end=%d exceeds the built table size %d of the point-source right-hand side", who, p->n_end, kMaxRad);
+  return BIEM_ERR_UNSUPPORTED;
+}
+
 // Where the right-hand sides of c systems live: f is the first entry of the first system, row r of system s at f + 2 (s sys_stride + r ld)
 // (complex128); the columns n_pad .. of an augmented matrix, or an array of their own.  Rows in the slot order of the symmetric form.
 struct RhsView { double* f; long long sys_stride, ld; int n_pad; SplitMap split; };
@@ -149,7 +156,7 @@ int rhs_load(const biem_plan* p, int s0, int c, int B, int nrhs, const BoundaryC
   const Samples ss = {smp.g ? smp.g + g0 : nullptr, smp.gu ? smp.gu + g0 : nullptr, smp.gdn ? smp.gdn + g0 : nullptr,
                       smp.dirs ? smp.dirs + (smp.dirs_batched ? (size_t)s0 * nrhs * p->d : 0) : nullptr, smp.dirs_batched,
                       smp.k ? smp.k + 2 * (size_t)s0 : nullptr, smp.centers ? smp.centers + (smp.geom_batched ? (size_t)s0 * B * p->d : 0) : nullptr,
-                      smp.geom_batched, smp.work};
+                      smp.geom_batched, smp.work, smp.src ? smp.src + (smp.src_batched ? (size_t)s0 * nrhs * p->d : 0) : nullptr, smp.src_batched};
   const int rc = rhs_project(p, c, B, nrhs, bcs, ss, v.f, v.sys_stride, v.ld, 1, st, symmetric, v.split, tab);
   return (rc || !symmetric) ? rc : launch_sym_rhs(p, c, B, nrhs, v.n_pad, tab, v.f, v.ld, v.sys_stride, false, st, v.split);
 }
@@ -167,6 +174,9 @@ int ball_tables(const biem_plan* p, int nb, int B, const double* d_k, const doub
 
 int rhs_project(const biem_plan* p, int nb, int B, int nrhs, const BoundaryCoef& bc, const Samples& smp, double* d_f, long long sys_stride,
                 long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, const double* d_tab) {
+  if (smp.src)
+    return launch_rhs_point_source(p, nb, B, nrhs, smp.k, smp.centers, smp.geom_batched, d_tab, smp.src, smp.src_batched, d_f, sys_stride,
+                                   elem_stride, rhs_stride, st, slot_order, split, smp.work);
   if (smp.dirs)
     return launch_rhs_plane_wave(p, nb, B, nrhs, smp.k, smp.centers, smp.geom_batched, d_tab, smp.dirs, smp.dirs_batched, d_f, sys_stride,
                                  elem_stride, rhs_stride, st, slot_order, split, smp.work);
@@ -191,11 +201,12 @@ int solve_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, 
   Samples smp = source;
   NEED_DEV_AS(who, plan); NEED_AS(who, d_k, "d_k"); NEED_AS(who, d_eta, "d_eta"); NEED_AS(who, d_centers, "d_centers"); NEED_AS(who, d_radii, "d_radii");
   NEED_AS(who, bc.alpha, bc.alpha_name()); NEED_AS(who, bc.beta, bc.beta_name());
-  if (!smp.dirs && !bc.per_degree) NEED_AS(who, smp.g, "d_g");
+  if (!smp.closed_form() && !bc.per_degree) NEED_AS(who, smp.g, "d_g");
   NEED_AS(who, d_density, "d_density"); NEED_AS(who, d_info, "d_info"); NEED_AS(who, d_work, "d_work");
   if (nb <= 0 || B <= 0) return BIEM_OK;
   if (nrhs < 1) { set_error("%s: nrhs < 1", who); return BIEM_ERR_ARG; }
-  if (smp.dirs && (nb > 65535 || nrhs > 65535)) { set_error("%s: at most 65535 systems / right-hand sides per call (got nb=%d, nrhs=%d)", who, nb, nrhs); return BIEM_ERR_ARG; }
+  if (smp.closed_form() && (nb > 65535 || nrhs > 65535)) { set_error("%s: at most 65535 systems / right-hand sides per call (got nb=%d, nrhs=%d)", who, nb, nrhs); return BIEM_ERR_ARG; }
+  if (const int rc = point_source_order(who, plan, smp)) return rc;
   const int H = plan->H;
   SplitMap sm = SplitMap();                // (off: the pivoted LU has no split form)
   if (symmetric) {
@@ -204,7 +215,7 @@ int solve_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, 
   }
   const bool split = sm.on();
   const SolveLayout L = make_layout(plan, nb, B, nrhs, chunk, split);
-  const size_t need = L.total + smp.work_bytes(plan, nb, nrhs);    // (a plane-wave source keeps its harmonics at the tail)
+  const size_t need = L.total + smp.work_bytes(plan, nb, B, nrhs);    // (a source in closed form keeps its harmonics at the tail)
   if (work_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", who, work_bytes, need); return BIEM_ERR_ARG; }
   if (split) { g_last_split[0] = sm.npE; g_last_split[1] = sm.npO; }
   char* w = (char*)d_work;
@@ -281,15 +292,16 @@ int solve_factored_path(const char* who, const biem_plan* plan, int nb, int B, i
                         hipStream_t st) {
   Samples smp = source;
   NEED_DEV_AS(who, plan); NEED_AS(who, d_F, "d_F"); NEED_AS(who, d_tab, "d_tab"); NEED_AS(who, d_density, "d_density"); NEED_AS(who, d_work, "d_work");
-  if (smp.dirs) { NEED_AS(who, smp.k, "d_k"); NEED_AS(who, smp.centers, "d_centers"); }
+  if (smp.closed_form()) { NEED_AS(who, smp.k, "d_k"); NEED_AS(who, smp.centers, "d_centers"); }
   else if (bc.per_degree) { NEED_AS(who, bc.alpha, bc.alpha_name()); NEED_AS(who, bc.beta, bc.beta_name()); }
   else NEED_AS(who, smp.g, "d_g");
   if (const int rc = check_counts(who, nb, nrhs, B)) return rc;
   if (nb == 0 || nrhs == 0 || B == 0) return BIEM_OK;
+  if (const int rc = point_source_order(who, plan, smp)) return rc;
   const int n_pad = lu_npad(B * plan->H);
   const size_t need = solve_factored_workspace_bytes(plan, nb, B, nrhs);
-  if (const int rc = check_factor_room(who, lda, sys_stride, n_pad, work_bytes, need + smp.work_bytes(plan, nb, nrhs))) return rc;
-  smp.work = (char*)d_work + need;                                 // (a plane-wave source keeps its harmonics at the tail)
+  if (const int rc = check_factor_room(who, lda, sys_stride, n_pad, work_bytes, need + smp.work_bytes(plan, nb, B, nrhs))) return rc;
+  smp.work = (char*)d_work + need;                                 // (a source in closed form keeps its harmonics at the tail)
   // right-hand sides X[s][row][q] (row-major, ldx columns), rows in the slot order of the symmetric form; padding rows zero
   const long long ldx = rhs_ld(nrhs);
   const RhsView X = {(double*)d_work, (long long)n_pad * ldx, ldx, n_pad, SplitMap()};

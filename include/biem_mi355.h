@@ -455,6 +455,37 @@ int biem_solve_factored_pw(const biem_plan* plan, int nb, int B, int nrhs, const
                            const double* d_alpha, const double* d_beta, int ab_batched, int per_degree, const double* d_dirs,
                            int dirs_batched, double* d_density, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- point-source incidence in closed form: exact right-hand sides without samples.  The monopole
+ *      u_in(x) = h_0(k |x - s|) (point_source with n = 0) has on the surface of ball b, with t = s - c_b and |t| > rho_b, the projections
+ *        U_h = C_d j_n(k rho) h_n(k |t|) conj(Y_h(t^)),  V_h = C_d k j_n'(k rho) h_n(k |t|) conj(Y_h(t^)),
+ *      so f(s, r, b, h) = -C_d gj_{n(h)}(s, b) h_{n(h)}(k_s |t_{r,b}|) conj(Y_h(t^_{r,b})) with gj row 0 of d_tab (biem_ball_tables or
+ *      biem_ball_tables_n); real and complex k, every tree, the chains included, kind inner and outer alike.  d_src: source positions
+ *      in the plan's axes, [nrhs][d] shared by all systems or [nb][nrhs][d] with src_batched != 0.  NOT TESTED HERE: every source
+ *      must lie strictly outside every ball.  A source on or inside a sphere gives finite values that mean nothing, a source at a
+ *      centre (t = 0) non-finite ones.  Every element is written by one lane, no atomics: two calls give the same bits.  At most
+ *      65535 systems and right-hand sides per call (BIEM_ERR_ARG); n_end above 320 (2-D only) is BIEM_ERR_UNSUPPORTED, nothing launched.
+ * biem_rhs_point_source writes f where biem_rhs_project does, d_f[s*sys_stride + (b*H + h)*elem_stride + r*rhs_stride].  Workspace:
+ * biem_rhs_point_source_workspace_bytes (unit vectors and distances, their harmonics twice, the radial table nb x nrhs x B x n_end).
+ * biem_solve_ps / biem_solve_ldlt_ps / biem_solve_factored_ps: the _pw entries with d_src, src_batched in place of d_dirs,
+ * dirs_batched.  Workspace: the bytes of biem_solve_workspace_bytes (biem_solve_factored_workspace_bytes) PLUS
+ * biem_rhs_point_source_workspace_bytes, at the tail. ---- */
+size_t biem_rhs_point_source_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs, int src_batched, int geom_batched);
+int biem_rhs_point_source(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_centers,
+                          int geom_batched, const double* d_tab, const double* d_src, int src_batched, double* d_f, long long sys_stride,
+                          long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream);
+int biem_solve_ps(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_src, int src_batched, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                  void* stream);
+int biem_solve_ldlt_ps(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta,
+                       const double* d_centers, const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta,
+                       int ab_batched, int per_degree, const double* d_src, int src_batched, double* d_density, int* d_info, int chunk,
+                       void* d_work, size_t work_bytes, void* stream);
+int biem_solve_factored_ps(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k /*c128*/, const double* d_centers, int geom_batched,
+                           const double* d_alpha, const double* d_beta, int ab_batched, int per_degree, const double* d_src,
+                           int src_batched, double* d_density, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- cross sections: extinction and absorbed power per ball from what the solve already has (no second solve, no
  *      matrix, no workspace).  Real k only, in the far-field normalisation u_scat ~ F(x^) e^{ikr} / r^{(d-1)/2}: "power" is
  *      (1/k) Im oint conj(u) d_n u dS, for a unit plane wave the cross section.  With c_h = density_h blc_n(rho_b), U_h / V_h the
