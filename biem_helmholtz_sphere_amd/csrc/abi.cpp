@@ -260,7 +260,8 @@ int biem_ball_tables(const biem_plan* plan, int nb, int B, const double* d_k, co
 int biem_rhs_project(const biem_plan* plan, int nb, int B, int nrhs, const double* d_g, double* d_f, long long sys_stride,
                      long long elem_stride, long long rhs_stride, void* stream) {
   NEED_DEV(plan); NEED(d_g, "d_g"); NEED(d_f, "d_f");
-  return rhs_project(plan, nb, B, nrhs, {nullptr, nullptr, 0, false}, {d_g, nullptr, nullptr}, d_f, sys_stride, elem_stride, rhs_stride, (hipStream_t)stream);
+  return RhsSource::samples(d_g).launch(plan, nb, B, nrhs, {nullptr, nullptr, 0, false}, nullptr, d_f, sys_stride, elem_stride, rhs_stride,
+                                        (hipStream_t)stream);
 }
 
 int biem_ball_tables_n(const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
@@ -273,8 +274,8 @@ int biem_rhs_project_n(const biem_plan* plan, int nb, int B, int nrhs, const dou
                        const double* d_beta_n, int ab_batched, double* d_f, long long sys_stride, long long elem_stride,
                        long long rhs_stride, void* stream) {
   NEED_DEV(plan); NEED(d_alpha_n, "d_alpha_n"); NEED(d_beta_n, "d_beta_n"); NEED(d_f, "d_f");
-  return rhs_project(plan, nb, B, nrhs, {d_alpha_n, d_beta_n, ab_batched, true}, {nullptr, d_gu, d_gdn}, d_f, sys_stride, elem_stride, rhs_stride,
-                     (hipStream_t)stream);
+  return RhsSource::samples_n(d_gu, d_gdn).launch(plan, nb, B, nrhs, {d_alpha_n, d_beta_n, ab_batched, true}, nullptr, d_f, sys_stride,
+                                                  elem_stride, rhs_stride, (hipStream_t)stream);
 }
 
 int biem_flag_unscalable(const biem_plan* plan, int nb, int B, const double* d_tab, int* d_info, int code, void* stream) {
@@ -432,14 +433,14 @@ int biem_solve(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k
                const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched,
                const double* d_g, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes, void* stream) {
   return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, false},
-                    {d_g, nullptr, nullptr}, d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, false);
+                    RhsSource::samples(d_g), d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, false);
 }
 
 int biem_solve_ldlt(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
                     const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched,
                     const double* d_g, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes, void* stream) {
   return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, false},
-                    {d_g, nullptr, nullptr}, d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, true);
+                    RhsSource::samples(d_g), d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, true);
 }
 
 int biem_last_solve_split(int* npE, int* npO) { last_solve_split(npE, npO); return BIEM_OK; }
@@ -449,7 +450,7 @@ int biem_solve_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d
                  const double* d_gu, const double* d_gdn, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
                  void* stream) {
   return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha_n, d_beta_n, ab_batched, true},
-                    {nullptr, d_gu, d_gdn}, d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, false);
+                    RhsSource::samples_n(d_gu, d_gdn), d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, false);
 }
 
 int biem_solve_ldlt_n(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
@@ -457,7 +458,7 @@ int biem_solve_ldlt_n(const biem_plan* plan, int nb, int B, int nrhs, const doub
                       const double* d_gu, const double* d_gdn, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
                       void* stream) {
   return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha_n, d_beta_n, ab_batched, true},
-                    {nullptr, d_gu, d_gdn}, d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, true);
+                    RhsSource::samples_n(d_gu, d_gdn), d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, true);
 }
 
 // ---- factor now, solve later: the symmetric path split at the factorisation -------------------------------------------------
@@ -499,7 +500,7 @@ size_t biem_solve_factored_workspace_bytes(const biem_plan* plan, int nb, int B,
 
 int biem_solve_factored(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
                         const double* d_tab, const double* d_g, double* d_density, void* d_work, size_t work_bytes, void* stream) {
-  return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {nullptr, nullptr, 0, false}, {d_g, nullptr, nullptr},
+  return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {nullptr, nullptr, 0, false}, RhsSource::samples(d_g),
                              d_density, d_work, work_bytes, (hipStream_t)stream);
 }
 
@@ -507,7 +508,17 @@ int biem_solve_factored_n(const biem_plan* plan, int nb, int B, int nrhs, const 
                           const double* d_tab, const double* d_alpha_n, const double* d_beta_n, int ab_batched, const double* d_gu,
                           const double* d_gdn, double* d_density, void* d_work, size_t work_bytes, void* stream) {
   return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {d_alpha_n, d_beta_n, ab_batched, true},
-                             {nullptr, d_gu, d_gdn}, d_density, d_work, work_bytes, (hipStream_t)stream);
+                             RhsSource::samples_n(d_gu, d_gdn), d_density, d_work, work_bytes, (hipStream_t)stream);
+}
+
+// ---- right-hand sides in closed form on their own: the source's limits, its workspace, then its launcher (natural order, unsplit) ----
+static int closed_form_rhs(const char* who, RhsSource src, const biem_plan* plan, int nb, int B, int nrhs, const double* d_tab, double* d_f,
+                           long long sys_stride, long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, hipStream_t st) {
+  if (const int rc = src.check(who, plan, nb, nrhs)) return rc;
+  const size_t need = src.work_bytes(plan, nb, B, nrhs);
+  if (work_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", who, work_bytes, need); return BIEM_ERR_ARG; }
+  src.work = d_work;
+  return src.launch(plan, nb, B, nrhs, {nullptr, nullptr, 0, false}, d_tab, d_f, sys_stride, elem_stride, rhs_stride, st);
 }
 
 // ---- plane-wave incidence in closed form (kernels_rhs_pw.hip): the third source of right-hand sides ----
@@ -519,10 +530,8 @@ int biem_rhs_plane_wave(const biem_plan* plan, int nb, int B, int nrhs, const do
                         const double* d_tab, const double* d_dirs, int dirs_batched, double* d_f, long long sys_stride,
                         long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream) {
   NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_centers, "d_centers"); NEED(d_tab, "d_tab"); NEED(d_dirs, "d_dirs"); NEED(d_f, "d_f"); NEED(d_work, "d_work");
-  const Samples src = {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched, d_work};
-  if (work_bytes < src.work_bytes(plan, nb, B, nrhs)) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, src.work_bytes(plan, nb, B, nrhs)); return BIEM_ERR_ARG; }
-  return rhs_project(plan, nb, B, nrhs, {nullptr, nullptr, 0, false}, src, d_f, sys_stride, elem_stride, rhs_stride, (hipStream_t)stream, false,
-                     SplitMap(), d_tab);
+  return closed_form_rhs(__func__, RhsSource::plane_waves(d_dirs, dirs_batched, d_k, d_centers, geom_batched), plan, nb, B, nrhs, d_tab, d_f,
+                         sys_stride, elem_stride, rhs_stride, d_work, work_bytes, (hipStream_t)stream);
 }
 
 int biem_solve_pw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
@@ -531,7 +540,7 @@ int biem_solve_pw(const biem_plan* plan, int nb, int B, int nrhs, const double* 
                   void* stream) {
   NEED(d_dirs, "d_dirs");
   return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
-                    {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched}, d_density, d_info, chunk, d_work,
+                    RhsSource::plane_waves(d_dirs, dirs_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work,
                     work_bytes, (hipStream_t)stream, false);
 }
 
@@ -541,7 +550,7 @@ int biem_solve_ldlt_pw(const biem_plan* plan, int nb, int B, int nrhs, const dou
                        void* stream) {
   NEED(d_dirs, "d_dirs");
   return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
-                    {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched}, d_density, d_info, chunk, d_work,
+                    RhsSource::plane_waves(d_dirs, dirs_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work,
                     work_bytes, (hipStream_t)stream, true);
 }
 
@@ -551,15 +560,11 @@ int biem_solve_factored_pw(const biem_plan* plan, int nb, int B, int nrhs, const
                            double* d_density, void* d_work, size_t work_bytes, void* stream) {
   NEED(d_dirs, "d_dirs");
   return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {d_alpha, d_beta, ab_batched, per_degree != 0},
-                             {nullptr, nullptr, nullptr, d_dirs, dirs_batched, d_k, d_centers, geom_batched}, d_density, d_work,
+                             RhsSource::plane_waves(d_dirs, dirs_batched, d_k, d_centers, geom_batched), d_density, d_work,
                              work_bytes, (hipStream_t)stream);
 }
 
 // ---- point-source incidence in closed form (kernels_rhs_ps.hip): the fourth source of right-hand sides ----
-static Samples point_sources(const double* d_src, int src_batched, const double* d_k, const double* d_centers, int geom_batched, void* d_work = nullptr) {
-  return {nullptr, nullptr, nullptr, nullptr, 0, d_k, d_centers, geom_batched, d_work, d_src, src_batched};
-}
-
 size_t biem_rhs_point_source_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs, int src_batched, int geom_batched) {
   return plan ? rhs_point_source_workspace_bytes(plan, nb, B, nrhs, src_batched, geom_batched) : 0;
 }
@@ -568,10 +573,8 @@ int biem_rhs_point_source(const biem_plan* plan, int nb, int B, int nrhs, const 
                           const double* d_tab, const double* d_src, int src_batched, double* d_f, long long sys_stride,
                           long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream) {
   NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_centers, "d_centers"); NEED(d_tab, "d_tab"); NEED(d_src, "d_src"); NEED(d_f, "d_f"); NEED(d_work, "d_work");
-  const Samples src = point_sources(d_src, src_batched, d_k, d_centers, geom_batched, d_work);
-  if (work_bytes < src.work_bytes(plan, nb, B, nrhs)) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, src.work_bytes(plan, nb, B, nrhs)); return BIEM_ERR_ARG; }
-  return rhs_project(plan, nb, B, nrhs, {nullptr, nullptr, 0, false}, src, d_f, sys_stride, elem_stride, rhs_stride, (hipStream_t)stream, false,
-                     SplitMap(), d_tab);
+  return closed_form_rhs(__func__, RhsSource::point_sources(d_src, src_batched, d_k, d_centers, geom_batched), plan, nb, B, nrhs, d_tab, d_f,
+                         sys_stride, elem_stride, rhs_stride, d_work, work_bytes, (hipStream_t)stream);
 }
 
 int biem_solve_ps(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
@@ -580,7 +583,7 @@ int biem_solve_ps(const biem_plan* plan, int nb, int B, int nrhs, const double* 
                   void* stream) {
   NEED(d_src, "d_src");
   return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
-                    point_sources(d_src, src_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work, work_bytes,
+                    RhsSource::point_sources(d_src, src_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work, work_bytes,
                     (hipStream_t)stream, false);
 }
 
@@ -590,7 +593,7 @@ int biem_solve_ldlt_ps(const biem_plan* plan, int nb, int B, int nrhs, const dou
                        void* stream) {
   NEED(d_src, "d_src");
   return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
-                    point_sources(d_src, src_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work, work_bytes,
+                    RhsSource::point_sources(d_src, src_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work, work_bytes,
                     (hipStream_t)stream, true);
 }
 
@@ -600,7 +603,7 @@ int biem_solve_factored_ps(const biem_plan* plan, int nb, int B, int nrhs, const
                            double* d_density, void* d_work, size_t work_bytes, void* stream) {
   NEED(d_src, "d_src");
   return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {d_alpha, d_beta, ab_batched, per_degree != 0},
-                             point_sources(d_src, src_batched, d_k, d_centers, geom_batched), d_density, d_work, work_bytes,
+                             RhsSource::point_sources(d_src, src_batched, d_k, d_centers, geom_batched), d_density, d_work, work_bytes,
                              (hipStream_t)stream);
 }
 

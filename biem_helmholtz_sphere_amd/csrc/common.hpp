@@ -106,6 +106,7 @@ struct SplitMap {
   }
 };
 inline int roundup64(int v) { return (v + 63) / 64 * 64; }
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }   // regions of a workspace start on 256-byte boundaries
 inline SplitMap make_split_map(int B, int H, int U) { SplitMap m; m.U = U; m.npE = roundup64(B * U); m.npO = roundup64(B * (H - U)); return m; }
 
 // launch wrappers implemented in the .hip files (all stream-ordered, no syncs)
@@ -114,11 +115,12 @@ int launch_radial_c(int d, int nmax, int count, const double* d_z, double* d_out
 int launch_harmonics(const biem_plan* p, int count, const double* d_u, double* d_Y, hipStream_t st);
 int launch_ball_tables(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
                        int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, double* d_tab, hipStream_t st);
+// projection of boundary samples (kernels_rhs.hip), any number of rows nb nrhs B an int counts.
 // slot_order: harmonic h of a ball goes to / comes from the plan's internal slot hpos[h] (symmetric path) instead of position h
 int launch_rhs_project(const biem_plan* p, int nb, int B, int nrhs, const double* d_g, double* d_f, long long sys_stride,
                        long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap());
-// degree-dependent boundary coefficients (kernels_degree_bc.hip): alpha_n / beta_n [nb or 1][B][n_end] complex; the tables are laid out
-// as launch_ball_tables' and feed the same fill / solve / density launches
+// degree-dependent boundary coefficients: alpha_n / beta_n [nb or 1][B][n_end] complex; the tables are laid out as
+// launch_ball_tables' (the same kernel text) and feed the same fill / solve / density launches
 int launch_ball_tables_n(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
                          int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched, double* d_tab, hipStream_t st);
 // f = -(alpha_n P[gu] + beta_n P[gdn]); a null sample set is zero; strides and slot order as launch_rhs_project
@@ -127,7 +129,7 @@ int launch_rhs_project_n(const biem_plan* p, int nb, int B, int nrhs, const doub
                          long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap());
 // plane-wave incidence in closed form (kernels_rhs_pw.hip): f = -C_d i^n gj_n conj(Y_h(p^_r)) e^{i k p^_r.c_b} from the ball tables, written
 // where launch_rhs_project writes.  d_dirs: unit vectors in the plan's axes, [nrhs][d] or (dirs_batched) [nb][nrhs][d]; d_work:
-// rhs_plane_wave_workspace_bytes (the harmonics of the directions).  At most 65535 systems and right-hand sides.
+// rhs_plane_wave_workspace_bytes (the harmonics of the directions).  At most 65535 systems and right-hand sides (RhsSource::check).
 size_t rhs_plane_wave_workspace_bytes(const biem_plan* p, int nb, int nrhs, int dirs_batched);
 int launch_rhs_plane_wave(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
                           const double* d_tab, const double* d_dirs, int dirs_batched, double* d_f, long long sys_stride,
@@ -137,8 +139,8 @@ int launch_transpose_rows(int cols, int rows, int batches, const double* d_in, d
 // point-source incidence in closed form (kernels_rhs_ps.hip): the monopole h_0(k |x - s_r|), f = -C_d gj_n h_n(k |t|) conj(Y_h(t^)),
 // t = s_r - c_b, from the ball tables, written where launch_rhs_project writes.  d_src: source positions in the plan's axes, [nrhs][d] or
 // (src_batched) [nb][nrhs][d]; d_work: rhs_point_source_workspace_bytes.  |t| > rho_b is the caller's to ensure (not tested: finite
-// nonsense on or inside a sphere, non-finite values at t = 0).  At most 65535 systems and right-hand sides; n_end <= kMaxRad, else
-// BIEM_ERR_UNSUPPORTED and nothing launched.
+// nonsense on or inside a sphere, non-finite values at t = 0).  At most 65535 systems and right-hand sides and n_end <= kMaxRad: both
+// are RhsSource::check's to refuse before anything is launched.
 size_t rhs_point_source_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int src_batched, int geom_batched);
 int launch_rhs_point_source(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
                             const double* d_tab, const double* d_src, int src_batched, double* d_f, long long sys_stride,
@@ -252,20 +254,57 @@ struct BoundaryCoef {
   const char* alpha_name() const { return per_degree ? "d_alpha_n" : "d_alpha"; }
   const char* beta_name() const { return per_degree ? "d_beta_n" : "d_beta"; }
 };
-// the source of the right-hand sides.  Boundary samples [nb][nrhs][B][Q] complex: g of plain coefficients; per degree the unmixed gu / gdn
-// (either may be null: zero).  Or, with dirs set, plane waves along dirs in closed form (launch_rhs_plane_wave: no samples), which
-// reads the wavenumbers and centres of the call and keeps its harmonics in `work` (set by the path: the tail of its workspace).  Or, with
-// src set, point sources at src in closed form (launch_rhs_point_source), which reads and keeps the same.
-struct Samples {
-  const double* g; const double* gu; const double* gdn;
-  const double* dirs = nullptr; int dirs_batched = 0;
-  const double* k = nullptr; const double* centers = nullptr; int geom_batched = 0; void* work = nullptr;
-  const double* src = nullptr; int src_batched = 0;
-  bool closed_form() const { return dirs || src; }
-  size_t work_bytes(const biem_plan* p, int nb, int B, int nrhs) const {
-    return dirs ? rhs_plane_wave_workspace_bytes(p, nb, nrhs, dirs_batched)
-         : src ? rhs_point_source_workspace_bytes(p, nb, B, nrhs, src_batched, geom_batched) : 0;
+// The source of the right-hand sides of a call, made by its named constructors only.  A new incident field is one more kind, one more
+// constructor and one more case in work_bytes / check / launch (solve_path.cpp).
+//   SAMPLES        boundary samples g [nb][nrhs][B][Q] complex of plain coefficients, projected by launch_rhs_project
+//   SAMPLES_N      the unmixed samples gu / gdn of per-degree coefficients (either may be null: zero), launch_rhs_project_n
+//   PLANE_WAVES    plane waves along pts = dirs in closed form (launch_rhs_plane_wave: no samples)
+//   POINT_SOURCES  point sources at pts = src in closed form (launch_rhs_point_source)
+// The closed forms read the wavenumbers, centres and ball tables of the call and keep their harmonics in `work`, work_bytes() of them:
+// the caller's workspace, or (set by the whole path) the tail of its own.
+struct RhsSource {
+  enum Kind { SAMPLES, SAMPLES_N, PLANE_WAVES, POINT_SOURCES };
+  Kind kind;
+  const double* g[2] = {nullptr, nullptr};                 // samples: g, or gu and gdn
+  const double* pts = nullptr; int pts_batched = 0;        // closed forms: [nrhs][d], or (pts_batched) [nb][nrhs][d], in the plan's axes
+  const double* k = nullptr; const double* centers = nullptr; int geom_batched = 0;
+  void* work = nullptr;
+
+  static RhsSource samples(const double* g) { RhsSource s(SAMPLES); s.g[0] = g; return s; }
+  static RhsSource samples_n(const double* gu, const double* gdn) { RhsSource s(SAMPLES_N); s.g[0] = gu; s.g[1] = gdn; return s; }
+  static RhsSource plane_waves(const double* dirs, int batched, const double* k, const double* centers, int geom_batched) {
+    return RhsSource(PLANE_WAVES, dirs, batched, k, centers, geom_batched);
   }
+  static RhsSource point_sources(const double* src, int batched, const double* k, const double* centers, int geom_batched) {
+    return RhsSource(POINT_SOURCES, src, batched, k, centers, geom_batched);
+  }
+
+  bool closed_form() const { return kind == PLANE_WAVES || kind == POINT_SOURCES; }
+  // the same source for the systems s0 .. of the call
+  RhsSource at(const biem_plan* p, int s0, int nrhs, int B) const {
+    RhsSource s = *this;
+    for (const double*& x : s.g) if (x) x += (size_t)s0 * nrhs * B * p->Q * 2;
+    if (pts && pts_batched) s.pts += (size_t)s0 * nrhs * p->d;
+    if (k) s.k += 2 * (size_t)s0;
+    if (centers && geom_batched) s.centers += (size_t)s0 * B * p->d;
+    return s;
+  }
+  size_t work_bytes(const biem_plan* p, int nb, int B, int nrhs) const {
+    return kind == PLANE_WAVES ? rhs_plane_wave_workspace_bytes(p, nb, nrhs, pts_batched)
+         : kind == POINT_SOURCES ? rhs_point_source_workspace_bytes(p, nb, B, nrhs, pts_batched, geom_batched) : 0;
+  }
+  // what the closed forms cannot take (grid dimensions; the thread-local radial table of a (source, ball) pair): refused under the
+  // caller's name `who` before anything is launched
+  int check(const char* who, const biem_plan* p, int nb, int nrhs) const;
+  // f of the nb systems this source starts at: strides, slot order and split as launch_rhs_project; bc is read by SAMPLES_N, the ball
+  // tables d_tab of the nb systems by the closed forms
+  int launch(const biem_plan* p, int nb, int B, int nrhs, const BoundaryCoef& bc, const double* d_tab, double* d_f, long long sys_stride,
+             long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap()) const;
+
+ private:
+  explicit RhsSource(Kind kd, const double* pts_ = nullptr, int batched = 0, const double* k_ = nullptr, const double* centers_ = nullptr,
+                     int geom_batched_ = 0)
+      : kind(kd), pts(pts_), pts_batched(batched), k(k_), centers(centers_), geom_batched(geom_batched_) {}
 };
 
 inline long long rhs_ld(long long nrhs) { return (nrhs + 7) / 8 * 8; }   // right-hand-side columns; rows stay 128-byte aligned (8 complex128)
@@ -276,13 +315,9 @@ inline int check_counts(const char* who, int nb, int nrhs, int B) {
   return BIEM_ERR_ARG;
 }
 
-// the one place that picks the per-degree launcher: ball tables, and the projection f of the samples (strides as launch_rhs_project);
-// plane-wave sources take the closed form from d_tab, the ball tables of the nb systems
+// the one place that picks the per-degree launcher of the ball tables
 int ball_tables(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii, int geom_batched,
                 const BoundaryCoef& bc, double* d_tab, hipStream_t st);
-int rhs_project(const biem_plan* p, int nb, int B, int nrhs, const BoundaryCoef& bc, const Samples& smp, double* d_f, long long sys_stride,
-                long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order = false, const SplitMap& split = SplitMap(),
-                const double* d_tab = nullptr);
 
 size_t solve_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int chunk);
 size_t factor_workspace_bytes(const biem_plan* p, int nb, int B, int chunk);
@@ -291,14 +326,14 @@ void last_solve_split(int* npE, int* npO);
 
 // tables -> fill -> right-hand side -> factor and solve -> density; symmetric: U^T U (LDL^T entries), else the pivoted LU
 int solve_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
-               const double* d_radii, int geom_batched, const BoundaryCoef& bc, const Samples& smp, double* d_density, int* d_info, int chunk,
+               const double* d_radii, int geom_batched, const BoundaryCoef& bc, const RhsSource& src, double* d_density, int* d_info, int chunk,
                void* d_work, size_t work_bytes, hipStream_t st, bool symmetric);
 // the same path cut at the factorisation: factors and tables stay with the caller, right-hand sides come later
 int factor_path(const char* who, const biem_plan* plan, int nb, int B, const double* d_k, const double* d_eta, const double* d_centers,
                 const double* d_radii, int geom_batched, const BoundaryCoef& bc, double* d_F, long long lda, long long sys_stride,
                 double* d_tab, int* d_info, int chunk, void* d_work, size_t work_bytes, hipStream_t st);
 int solve_factored_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
-                        const double* d_tab, const BoundaryCoef& bc, const Samples& smp, double* d_density, void* d_work, size_t work_bytes,
+                        const double* d_tab, const BoundaryCoef& bc, const RhsSource& src, double* d_density, void* d_work, size_t work_bytes,
                         hipStream_t st);
 
 }  // namespace biem

@@ -19,7 +19,6 @@
 
 namespace biem {
 namespace {
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 constexpr long long kGridMax = 1 << 20;      // workgroups of a strided launch (256 CUs: thousands per CU are plenty)
 inline unsigned strided_grid(long long groups) { return (unsigned)(groups < kGridMax ? groups : kGridMax); }
 
@@ -131,8 +130,7 @@ int launch_rhs_point_source(const biem_plan* p, int nb, int B, int nrhs, const d
                             const double* d_tab, const double* d_src, int src_batched, double* d_f, long long sys_stride,
                             long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work) {
   if (nrhs < 1) { set_error("biem_rhs_point_source: nrhs < 1"); return BIEM_ERR_ARG; }
-  if (nb > 65535 || nrhs > 65535) { set_error("biem_rhs_point_source: at most 65535 systems / right-hand sides per call (got nb=%d, nrhs=%d)", nb, nrhs); return BIEM_ERR_ARG; }
-  if (p->n_end > kMaxRad) { set_error("biem_rhs_point_source: n_end=%d exceeds the built table size %d", p->n_end, kMaxRad); return BIEM_ERR_UNSUPPORTED; }
+  // (nb, nrhs <= 65535: grid dimensions, n_end <= kMaxRad: the arrays of k_ps_radial - RhsSource::check has refused the rest)
   if (nb <= 0 || B <= 0) return BIEM_OK;
   const int H = p->H, n_end = p->n_end, batched = (src_batched || geom_batched) ? 1 : 0, dsys = batched ? nb : 1;
   const long long pts = (long long)dsys * nrhs * B, triples = (long long)nb * nrhs * B;

@@ -10,8 +10,6 @@
 
 namespace biem {
 namespace {
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // e^{i k t} for complex k: exp(-Im k t) (cos(Re k t) + i sin(Re k t)); scaled by -C_d once per (s, r, b)
 __device__ inline cplx pw_phase(cplx k, const double* __restrict__ p, const double* __restrict__ c, int d, double scale) {
   double t = 0.0;
@@ -109,7 +107,7 @@ int launch_rhs_plane_wave(const biem_plan* p, int nb, int B, int nrhs, const dou
                           const double* d_tab, const double* d_dirs, int dirs_batched, double* d_f, long long sys_stride,
                           long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work) {
   if (nrhs < 1) { set_error("biem_rhs_plane_wave: nrhs < 1"); return BIEM_ERR_ARG; }
-  if (nb > 65535 || nrhs > 65535) { set_error("biem_rhs_plane_wave: at most 65535 systems / right-hand sides per call (got nb=%d, nrhs=%d)", nb, nrhs); return BIEM_ERR_ARG; }
+  // (nb, nrhs <= 65535: grid dimensions - RhsSource::check has refused the rest)
   if (nb <= 0 || B <= 0) return BIEM_OK;
   const int H = p->H, dsys = dirs_batched ? nb : 1;
   ProfScope ps(PK_RHS, st, 0.0);

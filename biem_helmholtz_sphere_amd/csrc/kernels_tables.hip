@@ -101,10 +101,13 @@ int launch_harmonics(const biem_plan* p, int count, const double* d_u, double* d
 }
 
 // ---------------------------------------------------------------------------------------------
-// K0a: per-ball tables  gj = alpha j + beta k j',  gh = alpha h + beta k h',  blc = dlc - i eta slc
+// K0a: per-ball tables  gj_n = alpha j_n + beta k j_n',  gh_n = alpha h_n + beta k h_n',  blc = dlc - i eta slc
 //   (ush.harmonics_regular_singular_component x4 + potential_coef S/D, _biem.py:723-789)
 // one thread per (system, ball); outputs tab[s][b][3][n_end] complex.
+// PER_DEGREE: alpha / beta [nb or 1][B][n_end], one pair per degree, else [nb or 1][B].  The arithmetic per degree is
+// the same text, so degree-constant coefficients give the scalar table.
 // ---------------------------------------------------------------------------------------------
+template <bool PER_DEGREE>
 __global__ void k_ball_tables(int d, int n_end, int nb, int B, const cplx* __restrict__ k, const double* __restrict__ eta,
                               const double* __restrict__ radii, int geom_batched, const cplx* __restrict__ alpha,
                               const cplx* __restrict__ beta, int ab_batched, cplx* __restrict__ tab, cplx* __restrict__ scratch) {
@@ -114,8 +117,10 @@ __global__ void k_ball_tables(int d, int n_end, int nb, int B, const cplx* __res
   const cplx kk = k[s];
   const double et = eta[s];
   double rho = radii[(geom_batched ? (size_t)s * B : 0) + b];
-  cplx al = alpha[(ab_batched ? (size_t)s * B : 0) + b];
-  cplx be = beta[(ab_batched ? (size_t)s * B : 0) + b];
+  const cplx* al = alpha + ((ab_batched ? (size_t)s * B : 0) + b) * (PER_DEGREE ? n_end : 1);
+  const cplx* be = beta + ((ab_batched ? (size_t)s * B : 0) + b) * (PER_DEGREE ? n_end : 1);
+  cplx a0 = make_double2(0.0, 0.0), b0 = a0;       // one pair per ball: read here, in front of the radial functions, as it always was
+  if (!PER_DEGREE) { a0 = al[0]; b0 = be[0]; }
   // orders up to kMaxRad: thread-local arrays; beyond (2-D only): 2 (n_end + 3) complex of global scratch per (system, ball)
   cplx Jl[kMaxRad + 3], Hl[kMaxRad + 3];
   cplx* J = scratch ? scratch + (size_t)i * 2 * (n_end + 3) : Jl;
@@ -134,8 +139,9 @@ __global__ void k_ball_tables(int d, int n_end, int nb, int B, const cplx* __res
     const cplx hp = csub(cscale(cmul(ix, h), (double)n), Hh[n + 1]);
     const cplx kjp = cmul(kk, jp), khp = cmul(kk, hp);
     // gj = alpha j + beta k j',  gh = alpha h + beta k h'
-    cplx gj = cadd(cmul(al, j), cmul(be, kjp));
-    cplx gh = cadd(cmul(al, h), cmul(be, khp));
+    const cplx a = PER_DEGREE ? al[n] : a0, bt = PER_DEGREE ? be[n] : b0;
+    cplx gj = cadd(cmul(a, j), cmul(bt, kjp));
+    cplx gh = cadd(cmul(a, h), cmul(bt, khp));
     // blc = i k^{d-1} rho^{d-1} j' - i eta * i k^{d-2} rho^{d-1} j = k^{d-2} rho^{d-1} (eta j + i k j')
     cplx blc = cscale(cmul(kd2, make_double2(et * j.x - kjp.y, et * j.y + kjp.x)), rp);
     out[n] = gj;
@@ -144,19 +150,30 @@ __global__ void k_ball_tables(int d, int n_end, int nb, int B, const cplx* __res
   }
 }
 
-int launch_ball_tables(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
-                       int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, double* d_tab, hipStream_t st) {
+template <bool PER_DEGREE>
+static int launch_tables(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii, int geom_batched,
+                         const double* d_alpha, const double* d_beta, int ab_batched, double* d_tab, hipStream_t st) {
   if (p->n_end > kMaxRad && p->tree != TREE_A) { set_error("n_end=%d exceeds the built table size %d", p->n_end, kMaxRad); return BIEM_ERR_UNSUPPORTED; }
   int total = nb * B;
   if (total <= 0) return BIEM_OK;
   ProfScope ps(PK_TABLES, st);
   cplx* scratch = nullptr;
   if (p->n_end > kMaxRad) BIEM_HIPCHK(hipMallocAsync((void**)&scratch, (size_t)total * 2 * (p->n_end + 3) * sizeof(cplx), st));   // (2-D, large orders: stream-ordered)
-  hipLaunchKernelGGL(k_ball_tables, dim3((total + 63) / 64), dim3(64), 0, st, p->d, p->n_end, nb, B, (const cplx*)d_k, d_eta, d_radii,
+  hipLaunchKernelGGL(k_ball_tables<PER_DEGREE>, dim3((total + 63) / 64), dim3(64), 0, st, p->d, p->n_end, nb, B, (const cplx*)d_k, d_eta, d_radii,
                      geom_batched, (const cplx*)d_alpha, (const cplx*)d_beta, ab_batched, (cplx*)d_tab, scratch);
   BIEM_LAUNCHCHK();
   if (scratch) BIEM_HIPCHK(hipFreeAsync(scratch, st));
   return BIEM_OK;
+}
+
+int launch_ball_tables(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
+                       int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, double* d_tab, hipStream_t st) {
+  return launch_tables<false>(p, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha, d_beta, ab_batched, d_tab, st);
+}
+
+int launch_ball_tables_n(const biem_plan* p, int nb, int B, const double* d_k, const double* d_eta, const double* d_radii,
+                         int geom_batched, const double* d_alpha_n, const double* d_beta_n, int ab_batched, double* d_tab, hipStream_t st) {
+  return launch_tables<true>(p, nb, B, d_k, d_eta, d_radii, geom_batched, d_alpha_n, d_beta_n, ab_batched, d_tab, st);
 }
 
 // ---------------------------------------------------------------------------------------------

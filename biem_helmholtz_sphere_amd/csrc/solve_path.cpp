@@ -10,7 +10,6 @@ namespace {
 // does not fall.  (Not 392 or below: rejection codes of small flat systems are pinned in unsplit row numbers by the tests.)
 constexpr int SYM_SPLIT_MIN_N = 1024;
 thread_local int g_last_split[2] = {0, 0};   // npE, npO of the last symmetric solve on this thread; 0, 0: unsplit
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // systems resident per chunk: the number asked for, or (chunk <= 0) as many as fit the budget; at most nb and cap, at least 1
 int resident_chunk(int chunk, size_t budget_bytes, size_t per_system_bytes, int nb, int cap) {
@@ -138,26 +137,15 @@ int flag_unscalable(const biem_plan* p, int c, int B, const BoundaryCoef& bc, co
   return bc.per_degree ? launch_flag_unscalable(p, c, B, tab, info, -(n_pad + 2), st) : BIEM_OK;
 }
 
-// point sources: the radial table of a (source, ball) pair is a thread-local array (before anything is launched)
-int point_source_order(const char* who, const biem_plan* p, const Samples& smp) {
-  if (!smp.src || p->n_end <= kMaxRad) return BIEM_OK;
-  set_error("%s: n_end=%d exceeds the built table size %d of the point-source right-hand side", who, p->n_end, kMaxRad);
-  return BIEM_ERR_UNSUPPORTED;
-}
-
 // Where the right-hand sides of c systems live: f is the first entry of the first system, row r of system s at f + 2 (s sys_stride + r ld)
 // (complex128); the columns n_pad .. of an augmented matrix, or an array of their own.  Rows in the slot order of the symmetric form.
 struct RhsView { double* f; long long sys_stride, ld; int n_pad; SplitMap split; };
-// load: project the samples of the systems s0 .. s0 + c, then f~ = R W^H f; unload: x = W R^-1 x~, then the density
-int rhs_load(const biem_plan* p, int s0, int c, int B, int nrhs, const BoundaryCoef& bc, const Samples& smp, const double* tab,
+// load: the right-hand sides of the systems s0 .. s0 + c from their source, then f~ = R W^H f; unload: x = W R^-1 x~, then the density
+int rhs_load(const biem_plan* p, int s0, int c, int B, int nrhs, const BoundaryCoef& bc, const RhsSource& src, const double* tab,
              const RhsView& v, bool symmetric, hipStream_t st) {
-  const size_t g0 = (size_t)s0 * nrhs * B * p->Q * 2, ab0 = (bc.per_degree && bc.batched) ? (size_t)s0 * B * p->n_end * 2 : 0;
+  const size_t ab0 = (bc.per_degree && bc.batched) ? (size_t)s0 * B * p->n_end * 2 : 0;
   const BoundaryCoef bcs = {bc.alpha + ab0, bc.beta + ab0, bc.batched, bc.per_degree};   // (read by the per-degree projection only)
-  const Samples ss = {smp.g ? smp.g + g0 : nullptr, smp.gu ? smp.gu + g0 : nullptr, smp.gdn ? smp.gdn + g0 : nullptr,
-                      smp.dirs ? smp.dirs + (smp.dirs_batched ? (size_t)s0 * nrhs * p->d : 0) : nullptr, smp.dirs_batched,
-                      smp.k ? smp.k + 2 * (size_t)s0 : nullptr, smp.centers ? smp.centers + (smp.geom_batched ? (size_t)s0 * B * p->d : 0) : nullptr,
-                      smp.geom_batched, smp.work, smp.src ? smp.src + (smp.src_batched ? (size_t)s0 * nrhs * p->d : 0) : nullptr, smp.src_batched};
-  const int rc = rhs_project(p, c, B, nrhs, bcs, ss, v.f, v.sys_stride, v.ld, 1, st, symmetric, v.split, tab);
+  const int rc = src.at(p, s0, nrhs, B).launch(p, c, B, nrhs, bcs, tab, v.f, v.sys_stride, v.ld, 1, st, symmetric, v.split);
   return (rc || !symmetric) ? rc : launch_sym_rhs(p, c, B, nrhs, v.n_pad, tab, v.f, v.ld, v.sys_stride, false, st, v.split);
 }
 int rhs_unload(const biem_plan* p, int c, int B, int nrhs, const double* tab, const RhsView& v, bool symmetric, double* density, hipStream_t st) {
@@ -172,17 +160,32 @@ int ball_tables(const biem_plan* p, int nb, int B, const double* d_k, const doub
                        : launch_ball_tables(p, nb, B, d_k, d_eta, d_radii, geom_batched, bc.alpha, bc.beta, bc.batched, d_tab, st);
 }
 
-int rhs_project(const biem_plan* p, int nb, int B, int nrhs, const BoundaryCoef& bc, const Samples& smp, double* d_f, long long sys_stride,
-                long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, const double* d_tab) {
-  if (smp.src)
-    return launch_rhs_point_source(p, nb, B, nrhs, smp.k, smp.centers, smp.geom_batched, d_tab, smp.src, smp.src_batched, d_f, sys_stride,
-                                   elem_stride, rhs_stride, st, slot_order, split, smp.work);
-  if (smp.dirs)
-    return launch_rhs_plane_wave(p, nb, B, nrhs, smp.k, smp.centers, smp.geom_batched, d_tab, smp.dirs, smp.dirs_batched, d_f, sys_stride,
-                                 elem_stride, rhs_stride, st, slot_order, split, smp.work);
-  return bc.per_degree ? launch_rhs_project_n(p, nb, B, nrhs, smp.gu, smp.gdn, bc.alpha, bc.beta, bc.batched, d_f, sys_stride, elem_stride,
-                                              rhs_stride, st, slot_order, split)
-                       : launch_rhs_project(p, nb, B, nrhs, smp.g, d_f, sys_stride, elem_stride, rhs_stride, st, slot_order, split);
+int RhsSource::check(const char* who, const biem_plan* p, int nb, int nrhs) const {
+  if (!closed_form()) return BIEM_OK;
+  if (nb > 65535 || nrhs > 65535) { set_error("%s: at most 65535 systems / right-hand sides per call (got nb=%d, nrhs=%d)", who, nb, nrhs); return BIEM_ERR_ARG; }
+  if (kind == POINT_SOURCES && p->n_end > kMaxRad) {
+    set_error("%s: n_end=%d exceeds the built table size %d of the point-source right-hand side", who, p->n_end, kMaxRad);
+    return BIEM_ERR_UNSUPPORTED;
+  }
+  return BIEM_OK;
+}
+
+int RhsSource::launch(const biem_plan* p, int nb, int B, int nrhs, const BoundaryCoef& bc, const double* d_tab, double* d_f, long long sys_stride,
+                      long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split) const {
+  switch (kind) {
+    case SAMPLES:
+      return launch_rhs_project(p, nb, B, nrhs, g[0], d_f, sys_stride, elem_stride, rhs_stride, st, slot_order, split);
+    case SAMPLES_N:
+      return launch_rhs_project_n(p, nb, B, nrhs, g[0], g[1], bc.alpha, bc.beta, bc.batched, d_f, sys_stride, elem_stride, rhs_stride, st,
+                                  slot_order, split);
+    case PLANE_WAVES:
+      return launch_rhs_plane_wave(p, nb, B, nrhs, k, centers, geom_batched, d_tab, pts, pts_batched, d_f, sys_stride, elem_stride,
+                                   rhs_stride, st, slot_order, split, work);
+    case POINT_SOURCES:
+      return launch_rhs_point_source(p, nb, B, nrhs, k, centers, geom_batched, d_tab, pts, pts_batched, d_f, sys_stride, elem_stride,
+                                     rhs_stride, st, slot_order, split, work);
+  }
+  return BIEM_ERR_ARG;
 }
 
 size_t solve_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int chunk) { return make_layout(p, nb, B, nrhs, chunk).total; }
@@ -196,17 +199,16 @@ void last_solve_split(int* npE, int* npO) {
 }
 
 int solve_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
-               const double* d_radii, int geom_batched, const BoundaryCoef& bc, const Samples& source, double* d_density, int* d_info, int chunk,
+               const double* d_radii, int geom_batched, const BoundaryCoef& bc, const RhsSource& source, double* d_density, int* d_info, int chunk,
                void* d_work, size_t work_bytes, hipStream_t st, bool symmetric) {
-  Samples smp = source;
+  RhsSource src = source;
   NEED_DEV_AS(who, plan); NEED_AS(who, d_k, "d_k"); NEED_AS(who, d_eta, "d_eta"); NEED_AS(who, d_centers, "d_centers"); NEED_AS(who, d_radii, "d_radii");
   NEED_AS(who, bc.alpha, bc.alpha_name()); NEED_AS(who, bc.beta, bc.beta_name());
-  if (!smp.closed_form() && !bc.per_degree) NEED_AS(who, smp.g, "d_g");
+  if (src.kind == RhsSource::SAMPLES) NEED_AS(who, src.g[0], "d_g");
   NEED_AS(who, d_density, "d_density"); NEED_AS(who, d_info, "d_info"); NEED_AS(who, d_work, "d_work");
   if (nb <= 0 || B <= 0) return BIEM_OK;
   if (nrhs < 1) { set_error("%s: nrhs < 1", who); return BIEM_ERR_ARG; }
-  if (smp.closed_form() && (nb > 65535 || nrhs > 65535)) { set_error("%s: at most 65535 systems / right-hand sides per call (got nb=%d, nrhs=%d)", who, nb, nrhs); return BIEM_ERR_ARG; }
-  if (const int rc = point_source_order(who, plan, smp)) return rc;
+  if (const int rc = src.check(who, plan, nb, nrhs)) return rc;
   const int H = plan->H;
   SplitMap sm = SplitMap();                // (off: the pivoted LU has no split form)
   if (symmetric) {
@@ -215,11 +217,11 @@ int solve_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, 
   }
   const bool split = sm.on();
   const SolveLayout L = make_layout(plan, nb, B, nrhs, chunk, split);
-  const size_t need = L.total + smp.work_bytes(plan, nb, B, nrhs);    // (a source in closed form keeps its harmonics at the tail)
+  const size_t need = L.total + src.work_bytes(plan, nb, B, nrhs);    // (a source in closed form keeps its harmonics at the tail)
   if (work_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", who, work_bytes, need); return BIEM_ERR_ARG; }
   if (split) { g_last_split[0] = sm.npE; g_last_split[1] = sm.npO; }
   char* w = (char*)d_work;
-  smp.work = w + L.total;
+  src.work = w + L.total;
   double* tab = (double*)(w + L.off_tab);
   double* A = (double*)(w + L.off_A);
   void* T = w + L.off_T;
@@ -246,7 +248,7 @@ int solve_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, 
                        fill_workspace_bytes(plan, c, B), st);
     if (rc) return rc;
     if (!small) launch_clear_cols(st, rhs.f, L.lda, L.lda - L.n_pad, (long long)L.n_pad * c);
-    if ((rc = rhs_load(plan, ch.s0, c, B, nrhs, bc, smp, ch.tab, rhs, symmetric, st))) return rc;
+    if ((rc = rhs_load(plan, ch.s0, c, B, nrhs, bc, src, ch.tab, rhs, symmetric, st))) return rc;
     if (symmetric) {
       // the existing factorisation on the whole matrix, or on two views of the one allocation, E then O
       const SymBlock whole[1] = {{0, L.n_pad, L.N, info}};
@@ -288,25 +290,25 @@ int factor_path(const char* who, const biem_plan* plan, int nb, int B, const dou
 }
 
 int solve_factored_path(const char* who, const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
-                        const double* d_tab, const BoundaryCoef& bc, const Samples& source, double* d_density, void* d_work, size_t work_bytes,
+                        const double* d_tab, const BoundaryCoef& bc, const RhsSource& source, double* d_density, void* d_work, size_t work_bytes,
                         hipStream_t st) {
-  Samples smp = source;
+  RhsSource src = source;
   NEED_DEV_AS(who, plan); NEED_AS(who, d_F, "d_F"); NEED_AS(who, d_tab, "d_tab"); NEED_AS(who, d_density, "d_density"); NEED_AS(who, d_work, "d_work");
-  if (smp.closed_form()) { NEED_AS(who, smp.k, "d_k"); NEED_AS(who, smp.centers, "d_centers"); }
-  else if (bc.per_degree) { NEED_AS(who, bc.alpha, bc.alpha_name()); NEED_AS(who, bc.beta, bc.beta_name()); }
-  else NEED_AS(who, smp.g, "d_g");
+  if (src.closed_form()) { NEED_AS(who, src.k, "d_k"); NEED_AS(who, src.centers, "d_centers"); }
+  else if (src.kind == RhsSource::SAMPLES_N) { NEED_AS(who, bc.alpha, bc.alpha_name()); NEED_AS(who, bc.beta, bc.beta_name()); }
+  else NEED_AS(who, src.g[0], "d_g");
   if (const int rc = check_counts(who, nb, nrhs, B)) return rc;
   if (nb == 0 || nrhs == 0 || B == 0) return BIEM_OK;
-  if (const int rc = point_source_order(who, plan, smp)) return rc;
+  if (const int rc = src.check(who, plan, nb, nrhs)) return rc;
   const int n_pad = lu_npad(B * plan->H);
   const size_t need = solve_factored_workspace_bytes(plan, nb, B, nrhs);
-  if (const int rc = check_factor_room(who, lda, sys_stride, n_pad, work_bytes, need + smp.work_bytes(plan, nb, B, nrhs))) return rc;
-  smp.work = (char*)d_work + need;                                 // (a source in closed form keeps its harmonics at the tail)
+  if (const int rc = check_factor_room(who, lda, sys_stride, n_pad, work_bytes, need + src.work_bytes(plan, nb, B, nrhs))) return rc;
+  src.work = (char*)d_work + need;                                 // (a source in closed form keeps its harmonics at the tail)
   // right-hand sides X[s][row][q] (row-major, ldx columns), rows in the slot order of the symmetric form; padding rows zero
   const long long ldx = rhs_ld(nrhs);
   const RhsView X = {(double*)d_work, (long long)n_pad * ldx, ldx, n_pad, SplitMap()};
   BIEM_HIPCHK(hipMemsetAsync(X.f, 0, need, st));
-  int rc = rhs_load(plan, 0, nb, B, nrhs, bc, smp, d_tab, X, true, st);
+  int rc = rhs_load(plan, 0, nb, B, nrhs, bc, src, d_tab, X, true, st);
   if (rc) return rc;
   rc = launch_sym_solve(nb, n_pad, nrhs, d_F, lda, sys_stride, X.f, X.ld, X.sys_stride, st);
   return rc ? rc : rhs_unload(plan, nb, B, nrhs, d_tab, X, true, d_density, st);

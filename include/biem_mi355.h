@@ -147,7 +147,8 @@ int biem_ball_tables(const biem_plan* plan, int nb, int B, const double* d_k /*c
 /* ---- right-hand side (ush.expand, _biem.py:627-639): the incident field stays a Python callable; only its samples
  *      g[s][r][b][q] = (-alpha u_in - beta d_n u_in)(c_b + rho_b y_q) cross the ABI; r = 0..nrhs-1 are right-hand sides that
  *      share system s (incidences on which k, eta, the geometry and alpha/beta do not depend: factor once, solve many).
- *      f element (s, r, b, h) is written to d_f[s*sys_stride + (b*H + h)*elem_stride + r*rhs_stride]  (complex128 units) ---- */
+ *      f element (s, r, b, h) is written to d_f[s*sys_stride + (b*H + h)*elem_stride + r*rhs_stride]  (complex128 units).
+ *      The nb*nrhs*B rows run in blocks of 8 on one flat grid dimension (biem_rhs_project_n: blocks of 4), not on a dimension of 65535. ---- */
 int biem_rhs_project(const biem_plan* plan, int nb, int B, int nrhs, const double* d_g /*[nb][nrhs][B][Q] c128*/, double* d_f,
                      long long sys_stride, long long elem_stride, long long rhs_stride, void* stream);
 

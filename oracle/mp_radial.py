@@ -1,6 +1,6 @@
 """High-precision radial functions, per-ball tables and the 2-D translation entry  --  TEST INFRASTRUCTURE ONLY, CPU only (mpmath).
 
-The layer below ``oracle/mp_field.py``: what ``radial_jh`` (csrc/special.hpp), ``k_ball_tables`` / ``k_ball_tables_n`` and the 2-D pair
+The layer below ``oracle/mp_field.py``: what ``radial_jh`` (csrc/special.hpp), ``k_ball_tables`` (csrc/kernels_tables.hip, scalar and per-degree coefficients) and the 2-D pair
 tables compute, restated in mpmath.  Inputs enter as the exact values of their fp64 numbers.
 
 * radial functions  z_n^{(d)}(z) = sqrt(pi/2) J_{n+d/2-1}(z) / z^{d/2-1}  and  h_n^{(d)}  likewise with hankel1, d = 2 .. 10;

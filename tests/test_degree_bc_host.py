@@ -94,7 +94,8 @@ def test_new_entries_are_declared_bound_and_built():
         decl = re.search(r"\bint " + nm + r"\(([^;]*)\);", header)
         assert decl, nm
         assert len(decl.group(1).split(",")) == len(_lib.SIGNATURES[nm][1]), nm          # one ctypes type per declared argument
-    assert "kernels_degree_bc.hip" in _build.SOURCES
+    # the per-degree kernels are instantiations of the scalar ones' templates: no translation unit of their own
+    assert "kernels_tables.hip" in _build.SOURCES and "kernels_rhs.hip" in _build.SOURCES
     # the scalar entries keep their declarations: the per-degree ones are additions
     for nm in ("biem_ball_tables", "biem_rhs_project", "biem_solve", "biem_solve_ldlt", "biem_factor_ldlt", "biem_solve_factored"):
         assert re.search(r"\bint " + nm + r"\(", header), nm

@@ -344,7 +344,8 @@ def test_flag_marks_exactly_the_systems_with_a_zero_gj(amd):
 
 def test_degree_constant_tables_are_the_scalar_tables(amd):
     """biem_ball_tables_n with coefficients that do not vary with the degree against biem_ball_tables: to two units in the last place of
-    each entry's modulus (the same arithmetic per degree, compiled in another translation unit)."""
+    each entry's modulus (the same text per degree in another instantiation of the kernel, which reads its coefficients inside the loop
+    over the degrees: the compiler contracts the multiply-adds around that load differently)."""
     from biem_helmholtz_sphere_amd import _biem, _lib as L
     B, n_end, nb = 3, 9, 2
     lib = L.load()
