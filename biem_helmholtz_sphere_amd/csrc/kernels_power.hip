@@ -10,9 +10,11 @@
 namespace biem {
 
 // One wave per (ball, right-hand side, system) = (blockIdx.x, .y, .z).  Lane 0 runs the radial recurrences at k rho into LDS, the
-// lanes then form the per-degree factors (k h_n' = k ((n / x) h_n - h_{n+1}); the absorption weight Im(alpha_n conj beta_n) / |gj_n|^2,
-// exactly 0 where the pair is lossless - no division there, so gj_n = 0 of a lossless ball is harmless - and NaN where a lossy degree
-// has gj_n zero or not finite) and stride over the harmonics.  wave_sum adds in a fixed order: no atomics, two calls agree bit for bit.
+// lanes then form the per-degree factors (k h_n' = k ((n / x) h_n - h_{n+1}); the absorption weight Im(alpha_n conj beta_n), exactly 0
+// where the pair is lossless - no division there, so gj_n = 0 of a lossless ball is harmless - and NaN where a lossy degree has gj_n
+// zero or not finite; 1 / gj_n by a scaled division) and stride over the harmonics.  The absorbed term is w |c_h / gj_n|^2, the quotient
+// first: c_h and gj_n both fall like j_n(k rho), and their squares leave the fp64 range (|gj_n| < 1e-154: tree a from degree 283 at
+// k rho = 60) long before they do.  wave_sum adds in a fixed order: no atomics, two calls agree bit for bit.
 // alpha / beta: [nb or 1][B] (per_degree = 0) or [nb or 1][B][n_end]; tab [nb][B][3][n_end] (gj, gh, blc); density, pu, pv
 // [nb][nrhs][B][H]; out [nb][nrhs][B][2] = (P_ext, P_abs).
 __global__ void __launch_bounds__(64) k_power(int d, int H, int n_end, const int* __restrict__ deg, int B, int nrhs,
@@ -22,7 +24,8 @@ __global__ void __launch_bounds__(64) k_power(int d, int H, int n_end, const int
                                                const cplx* __restrict__ pv, double* __restrict__ out) {
   __shared__ cplx sJ[kMaxRad + 3], sH[kMaxRad + 3];     // radial_jh: n_end + 1 entries (+ its order shift for d >= 4)
   __shared__ cplx sHp[kMaxRad];                         // k h_n'(k rho)
-  __shared__ double sA[kMaxRad];                        // Im(alpha_n conj beta_n) / |gj_n|^2
+  __shared__ double sA[kMaxRad];                        // Im(alpha_n conj beta_n)
+  __shared__ cplx sIg[kMaxRad];                         // 1 / gj_n of a lossy degree
   const int b = blockIdx.x, r = blockIdx.y, s = blockIdx.z, lane = threadIdx.x;
   const double kr = k[s].x;
   const double rho = radii[(geom_batched ? (size_t)s * B : 0) + b];
@@ -37,12 +40,19 @@ __global__ void __launch_bounds__(64) k_power(int d, int H, int n_end, const int
     const cplx be = per_degree ? beta[ab0 * n_end + n] : beta[ab0];
     const double w = a.y * be.x - a.x * be.y;           // Im(alpha conj beta)
     double v = 0.0;
+    cplx ig = make_double2(0.0, 0.0);
     if (w != 0.0) {
       const cplx gj = t[n];
-      const double g2 = gj.x * gj.x + gj.y * gj.y;
-      v = (isfinite(g2) && g2 > 0.0) ? w / g2 : nan("");
+      const double m = fmax(fabs(gj.x), fabs(gj.y));
+      v = nan("");
+      if (isfinite(m) && m > 0.0) {                     // (scaled by the larger component: no underflow of the squares)
+        const double xs = gj.x / m, ys = gj.y / m, den = (xs * xs + ys * ys) * m;
+        ig = make_double2(xs / den, -ys / den);
+        v = w;
+      }
     }
     sA[n] = v;
+    sIg[n] = ig;
   }
   __syncthreads();
   const size_t row = (((size_t)s * nrhs + r) * B + b) * H;
@@ -54,7 +64,10 @@ __global__ void __launch_bounds__(64) k_power(int d, int H, int n_end, const int
     const cplx dc = cmul(c, sHp[n]), vc = cmul(c, sH[n]);          // k c h_n', c h_n
     pe += (U.x * dc.y - U.y * dc.x) + (vc.x * V.y - vc.y * V.x);   // Im[conj(U) k c h_n'] + Im[conj(c h_n) V]
     const double w = sA[n];
-    if (w != 0.0) pa += w * (c.x * c.x + c.y * c.y);
+    if (w != 0.0) {
+      const cplx q = cmul(c, sIg[n]);
+      pa += w * (q.x * q.x + q.y * q.y);
+    }
   }
   pe = wave_sum(pe);
   pa = wave_sum(pa);
