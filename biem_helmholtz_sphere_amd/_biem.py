@@ -26,9 +26,10 @@ from . import _lib as L
 from ._arrays import Array, _ptr, _stream_ptr
 from ._fields import (USCAT_GRAD_N_END_MAX, biem_far_pattern, biem_u, biem_u_grad, biem_u_hess, biem_u_interior, biem_u_interior_grad,
                       biem_u_total, biem_u_total_grad)
-from ._incident import fluid_inclusion_bc, max_memory, max_n_end, plane_wave, point_source
+from ._incident import fluid_inclusion_bc, harmonic_labels, max_memory, max_n_end, multipole_source, plane_wave, point_source
 from ._observables import BIEMPower, biem_force, biem_power
-from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_closed_form, _check_incident, _check_plane_wave_direction,
+from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_closed_form, _check_incident, _check_multipole_source,
+                        _check_plane_wave_direction, _multipole_source_source,
                         _check_point_source_position, _entry, _factored_source_args, _nrhs, _operator, _pick_systems, _plane_wave_source,
                         _point_source_source, _rhs_project, _sample_ptrs, _source_entry, _source_workspace_bytes, _validate_biem_inputs, _warn_biem_inputs)
 from ._plans import _chain_plan_dim, _plan
@@ -46,7 +47,8 @@ warnings.filterwarnings("error", category=ComplexWarning)
 __all__ = [
     "BIEMFactorization", "BIEMKwargs", "BIEMPower", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
     "biem_factorize", "biem_far_pattern", "biem_force", "biem_power", "biem_u", "biem_u_grad", "biem_u_hess", "biem_u_interior",
-    "biem_u_interior_grad", "biem_u_total", "biem_u_total_grad", "fluid_inclusion_bc", "max_memory", "max_n_end", "plane_wave", "point_source",
+    "biem_u_interior_grad", "biem_u_total", "biem_u_total_grad", "fluid_inclusion_bc", "harmonic_labels", "max_memory", "max_n_end",
+    "multipole_source", "plane_wave", "point_source",
 ]
 
 _last_solve_stats: dict = {}   # how the last biem() call solved its systems (tests / bench)
@@ -209,9 +211,15 @@ def _result(op: _Operator, uin, density_t: Optional[torch.Tensor], axes: Optiona
 # --------------------------------------------------------------------------------------
 # the solver (reference :453-819)
 # --------------------------------------------------------------------------------------
-def _closed_form_request(c, k, uin, uin_grad, plane_wave_direction, point_source_position):
-    """The checks of plane_wave_direction / point_source_position that need no device.  None without either, else (argument name, the
-    checked array on the host, the argument as the caller passed it)."""
+def _closed_form_request(c, k, n_end, uin, uin_grad, plane_wave_direction, point_source_position, multipole_source_position=None,
+                         multipole_source_index=None):
+    """The checks of plane_wave_direction / point_source_position / the multipole_source pair that need no device.  None without any,
+    else (argument name, the checked array on the host - multipoles: the pair (positions, indices) -, the argument as the caller passed
+    it)."""
+    if multipole_source_position is not None or multipole_source_index is not None:
+        checked = _check_multipole_source(c, k, n_end, multipole_source_position, multipole_source_index, uin, uin_grad, plane_wave_direction,
+                                          point_source_position)
+        return "multipole_source_position", checked, multipole_source_position
     if point_source_position is not None:
         checked = _check_point_source_position(c, k, point_source_position, uin, uin_grad, plane_wave_direction)
         return "point_source_position", checked, point_source_position
@@ -223,11 +231,15 @@ def _closed_form_request(c, k, uin, uin_grad, plane_wave_direction, point_source
 def _incident_source(op: _Operator, uin, uin_grad, closed=None):
     """The source of the right-hand sides, the _RhsAxes of its layout and the callable the result keeps as `.uin`: the samples of
     (uin, uin_grad), or - `closed`: what _closed_form_request returned - plane waves or point sources in closed form, whose `.uin` is
-    plane_wave's / point_source's (n = 0) for the caller's k and argument (a floating tensor as it is, anything else as float64)."""
+    plane_wave's / point_source's (n = 0) / multipole_source's for the caller's k and argument (a floating tensor as it is, anything
+    else as float64)."""
     if closed is None:
         _check_incident(op, uin, uin_grad)
         return _boundary_samples(op, uin, uin_grad) + (uin,)
     name, checked, given = closed
+    if name == "multipole_source_position":
+        arg = given if isinstance(given, torch.Tensor) and given.is_floating_point() else checked[0]
+        return _multipole_source_source(op, checked) + (multipole_source(op.c, k=op.k_given, source=arg, index=checked[1], n_end=op.n_end)[0],)
     arg = given if isinstance(given, torch.Tensor) and given.is_floating_point() else checked
     if name == "point_source_position":
         return _point_source_source(op, checked) + (point_source(k=op.k_given, source=arg, n=0)[0],)
@@ -332,7 +344,8 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
          kind: Literal["inner", "outer"] = "outer", force_matrix: bool = False,
          translational_coefficients_method: Literal["gumerov", "plane_wave", "triplet"] | None = None, chunk: int = 0,
          alpha_n: Array | None = None, beta_n: Array | None = None, plane_wave_direction: Array | None = None,
-         point_source_position: Array | None = None) -> BIEMResultCalculator:
+         point_source_position: Array | None = None, multipole_source_position: Array | None = None,
+         multipole_source_index: Array | int | None = None) -> BIEMResultCalculator:
     r"""Boundary Integral Equation Method (BIEM) for the Helmholtz equation on MI355X.
 
     Same contract as the reference ``biem`` (``_biem.py:453-581``): solves, per leading batch element,
@@ -367,6 +380,18 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     call).  The axes of S behave as those of plane_wave_direction, ``.uin`` is point_source's callable.  Orders n >= 1 of
     :func:`point_source` have no such expansion and stay with uin / uin_grad.  ``NotImplementedError`` for n_end > 320 (2-D only).
 
+    ``multipole_source_position`` / ``multipole_source_index`` (extension, given together; positions of shape ``(c_ndim, ...)`` like
+    point_source_position, the index an integer or an integer array broadcastable to the positions' trailing axes; not together with uin /
+    uin_grad / plane_wave_direction / point_source_position): the incident field is the outgoing multipole
+    ``h_n'(k |x - s|) Y_h'((x - s)^)`` of the operator's own k, h' a position on the harmonic axis (:func:`harmonic_labels`: the axis of
+    ``density[..., H]``, in the canonical tree's labels), :func:`multipole_source`.  Normalisation: orthonormal Y_h and the project's
+    radial functions; an index of degree 0 gives ``Y_0 h_0(k |x - s|)``, point_source_position's problem times the constant
+    ``Y_0 = |S^{d-1}|^{-1/2}``.  The right-hand side is exact, ``f = -gj_n (S|R)_{h'->h}(c_b - s)``: a column of the translation operator
+    the matrix is filled with, where the projection of samples aliases as for a point source, worse with every degree.  The axes behave
+    as those of point_source_position, every source must lie strictly outside every ball (``ValueError``), ``.uin`` is
+    multipole_source's callable.  A general multipole (a dipole along an arbitrary axis) is a linear combination: pass its harmonics as
+    right-hand sides and combine the densities.  ``NotImplementedError`` for n_end > 320 in 2-D and n_end > 160 elsewhere.
+
     Solver: the reference passes every system to a general dense solve (``_biem.py:797``).  Here the system is first brought
     to its complex-symmetric form (real harmonics, symmetric scaling) and factored as U^T U (Cholesky-type, no conjugation)
     without interchanges - half the flops; a system in which a multiplier would exceed 100, or whose factor grew by more than
@@ -375,7 +400,8 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     """
     if translational_coefficients_method not in (None, "gumerov", "plane_wave", "triplet"):
         raise ValueError(f"Invalid translational_coefficients_method: {translational_coefficients_method}")
-    closed = _closed_form_request(c, k, uin, uin_grad, plane_wave_direction, point_source_position)
+    closed = _closed_form_request(c, k, n_end, uin, uin_grad, plane_wave_direction, point_source_position, multipole_source_position,
+                                  multipole_source_index)
     op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n, beta_n)
     lib = L.load()
     plan, fl, dev = op.plan, op.fl, op.dev
@@ -472,15 +498,19 @@ class BIEMFactorization:
                 f"n_symmetric={self.n_symmetric}, n_lu={self.n_lu}, nbytes={self.nbytes}{', closed' if self._closed else ''})")
 
     def solve(self, *, uin: Callable[[Array], Array] | None = None, uin_grad: Callable[[Array], Array] | None = None,
-              plane_wave_direction: Array | None = None, point_source_position: Array | None = None) -> BIEMResultCalculator:
+              plane_wave_direction: Array | None = None, point_source_position: Array | None = None,
+              multipole_source_position: Array | None = None, multipole_source_index: Array | int | None = None) -> BIEMResultCalculator:
         """Densities of the incident field (uin, uin_grad), or of plane waves along ``plane_wave_direction`` or of point sources at
         ``point_source_position`` (the monopoles ``h_0(k |x - s|)``, strictly outside every ball) in closed form, against the stored
         factors: ``biem()``'s result for the same field.  Many source positions against one factorisation are right-hand sides of one
-        call: a trailing axis of the argument on which the operator has size 1."""
+        call: a trailing axis of the argument on which the operator has size 1.  ``multipole_source_position`` with
+        ``multipole_source_index`` (given together): the outgoing multipoles ``h_n'(k |x - s|) Y_h'((x - s)^)`` in closed form, as in
+        :func:`biem`."""
         if self._closed:
             raise ValueError("BIEMFactorization is closed")
         op, lib = self._op, L.load()
-        closed = _closed_form_request(op.c, op.k_given, uin, uin_grad, plane_wave_direction, point_source_position)
+        closed = _closed_form_request(op.c, op.k_given, op.n_end, uin, uin_grad, plane_wave_direction, point_source_position,
+                                      multipole_source_position, multipole_source_index)
         plan, fl, dev = op.plan, op.fl, op.dev
         B, H, nb = fl.B, plan.H, fl.nb
         has_rhs = not (uin is None and uin_grad is None and closed is None)

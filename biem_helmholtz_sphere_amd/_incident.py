@@ -8,7 +8,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._arrays import Array, _bshape_ok, _compute_device, _is_complex, _like, _ptr, _stream_ptr, _to_dev
+from ._arrays import Array, _bshape_ok, _compute_device, _host_array, _inverse_perm, _is_complex, _like, _ptr, _stream_ptr, _to_dev
+from ._coords import canonical_tree
+from ._plans import _plan
 
 
 # --------------------------------------------------------------------------------------
@@ -135,6 +137,101 @@ def point_source(*, k: Array, source: Array, n: int) -> Tuple[Callable[[Array], 
         _, hp = _radial(int(rel.shape[0]), kt * r)
         coeff = kt * hp / r
         return _back(coeff[None, ...] * rel, was_np, dev)
+
+    return inner, inner_grad
+
+
+def harmonic_labels(c, /, n_end: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``(labels [H, width], degrees [H])`` of the harmonic axis at order ``n_end``, NumPy: the axis of ``density[..., H]`` and the axis
+    ``multipole_source_index`` counts along, in the labels of the canonical tree (a tree with primed nodes runs as its canonical tree in
+    permuted axes).  Labels: (m, -, -) for a, (n, m, -) for ba, (n, l, m) for bba, (n, m1, m2) for caa, (l_0 .. l_{d-3}, m) for the chains.
+    The axis at a larger n_end does not begin with this one for every tree: look an index up by its label, not by its position."""
+    tree, _ = canonical_tree(c.branching_types_expression_str)
+    plan = _plan(tree, int(n_end), _compute_device(None))
+    return plan.labels.copy(), plan.degrees.copy()
+
+
+def multipole_source(c, /, *, k: Array, source: Array, index, n_end: int) -> Tuple[Callable[[Array], Array], Callable[[Array], Array]]:
+    r"""Outgoing multipole :math:`u(x) = h_{n'}(k\|x - source\|) Y_{h'}((x - source)/\|x - source\|)`, h' = ``index`` a position on the
+    harmonic axis of order ``n_end`` (:func:`harmonic_labels`), n' its degree: a solution of the Helmholtz equation for every degree, which
+    ``point_source(n=)`` with n > 0 is not.  Normalisation: orthonormal harmonics Y_h of the tree c and the project's radial functions
+    h_n = sqrt(pi/2) H_{n+d/2-1}(z) / z^{d/2-1}; an index of degree 0 gives ``Y_0 h_0(k |x - s|)``, point_source's n = 0 field times the
+    constant ``Y_0 = |S^{d-1}|^{-1/2}``.
+
+    k has shape (...), source (c_ndim, ...), index is an integer or an integer array broadcastable to source.shape[1:].  Returns
+    (u, grad u) with point_source's shapes: x of shape (c_ndim, ...(any), ...) gives (...(any), ...) and (c_ndim, ...(any), ...).  Both
+    evaluate on the device through ``biem_multipole_field`` (the value kernels of the scattered field on one coefficient; the gradient by
+    one step of the coefficient ladder in the plan of order n_end + 1)."""
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    perm = list(perm)
+    n_end = int(n_end)
+    k_ = k if isinstance(k, torch.Tensor) else np.asarray(k)
+    s_ = source if isinstance(source, torch.Tensor) else np.asarray(source, dtype=np.float64)
+    i_ = np.asarray(index) if isinstance(index, (int, np.integer)) else _host_array(index)
+    if i_.dtype.kind not in "iu":
+        raise ValueError(f"index must be an integer or an integer array, got dtype {i_.dtype}")
+    H = _harm_n_ndim_le(n_end, c.c_ndim)
+    if i_.size and (int(i_.min()) < 0 or int(i_.max()) >= H):
+        raise ValueError(f"index must lie in [0, H) with H={H} harmonics of degree < n_end={n_end}, got values from {int(i_.min())} to {int(i_.max())}")
+    if s_.ndim < 1 or s_.shape[0] != c.c_ndim:
+        raise ValueError(f"The first dimension of source must be c.c_ndim={c.c_ndim}, but got shape {tuple(s_.shape)}")
+    if not _bshape_ok(tuple(k_.shape), tuple(s_.shape[1:])) or not _bshape_ok(tuple(i_.shape), tuple(s_.shape[1:])):
+        raise ValueError(f"Shapes of k, index and source[1:] are not broadcastable\n{tuple(k_.shape)=}\n{tuple(i_.shape)=}\n{tuple(s_.shape)=}")
+    if s_.ndim != k_.ndim + 1:
+        raise ValueError(f"source.ndim={s_.ndim} is not k.ndim + 1={k_.ndim + 1}")
+    nd = k_.ndim
+    raised: dict = {}                          # device index -> the indices on the axis of order n_end + 1 (the gradient's plan)
+
+    def _raised_index(dev) -> np.ndarray:
+        key = dev.index
+        if key not in raised:
+            small, big = _plan(tree, n_end, dev), _plan(tree, n_end + 1, dev)
+            where = {tuple(lab) + (int(n),): j for j, (lab, n) in enumerate(zip(big.labels.tolist(), big.degrees.tolist()))}
+            raised[key] = np.array([where[tuple(lab) + (int(n),)] for lab, n in zip(small.labels.tolist(), small.degrees.tolist())], dtype=np.int64)
+        return raised[key][i_]
+
+    def _field(x, grad: bool):
+        was_np = not isinstance(x, torch.Tensor)
+        back = None if was_np else x.device
+        dev = _compute_device(back)
+        xt = _to_dev(x, dev, torch.float64)
+        d = int(xt.shape[0])
+        if xt.ndim - 1 < nd:                                                       # (broadcasting against the batch prepends axes)
+            xt = xt.reshape((d,) + (1,) * (nd - xt.ndim + 1) + tuple(xt.shape[1:]))
+        lead, xb = tuple(xt.shape[1:xt.ndim - nd]), tuple(xt.shape[xt.ndim - nd:])
+        st = _to_dev(s_, dev, torch.float64)
+        kt = _to_dev(k_, dev, torch.complex128)
+        batch = tuple(np.broadcast_shapes(tuple(kt.shape), tuple(st.shape[1:]), xb))
+        nb, P = math.prod(batch), math.prod(lead)
+        out_shape = ((d,) if grad else ()) + lead + batch
+        if nb == 0 or P == 0:
+            res = torch.empty(out_shape, dtype=torch.complex128, device=dev)
+            return res.cpu().numpy() if was_np else res.to(back)
+        plan = _plan(tree, n_end + 1 if grad else n_end, dev)
+        idx = _raised_index(dev) if grad else i_
+        kf = kt.expand(batch).reshape(nb).contiguous()
+        sf = torch.movedim(st[perm], 0, -1).expand(batch + (d,)).reshape(nb, d).contiguous()
+        jf = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(idx, batch)).reshape(nb).astype(np.int32), device=dev)
+        xp = xt[perm]
+        batched = any(n != 1 for n in xb)
+        pts = (xp.expand((d,) + lead + batch).reshape(d, P, nb) if batched else xp.reshape(d, P)).contiguous()
+        out = torch.empty(((d,) if grad else ()) + (P, nb), dtype=torch.complex128, device=dev)
+        lib = L.load()
+        with torch.cuda.device(dev):
+            wb = int(lib.biem_multipole_field_workspace_bytes(plan.handle, nb))
+            work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+            L.check(lib.biem_multipole_field(plan.handle, nb, P, _ptr(kf), _ptr(sf), _ptr(jf), _ptr(pts), L.USCAT_POINTS_BATCHED if batched else 0,
+                                             int(grad), _ptr(out), _ptr(work), wb, _stream_ptr(dev)), "biem_multipole_field")
+        res = out.reshape(out_shape)
+        if grad:
+            res = res[_inverse_perm(perm)]                                          # canonical component i is the caller's perm[i]
+        return res.cpu().numpy() if was_np else res.to(back)
+
+    def inner(x: Array, /) -> Array:
+        return _field(x, False)
+
+    def inner_grad(x: Array, /) -> Array:
+        return _field(x, True)
 
     return inner, inner_grad
 

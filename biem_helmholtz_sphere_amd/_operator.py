@@ -13,6 +13,7 @@ import torch
 from . import _lib as L
 from ._arrays import _Origin, _host_array, _inverse_perm, _is_complex, _origin_of, _ptr, _shape, _to_dev
 from ._coords import canonical_tree
+from ._incident import _harm_n_ndim_le
 from ._plans import _Plan, _plan
 
 
@@ -384,12 +385,34 @@ class _PointSources:
                                                                   op.fl.geom_batched))
 
 
-_CLOSED_FORM = (_PlaneWaves, _PointSources)
+@dataclass(frozen=True)
+class _MultipoleSources:
+    """Outgoing multipoles h_n'(k |x - s|) Y_h'((x - s)^) as the source of the right-hand sides, in closed form (biem_rhs_multipole):
+    positions as _PointSources', and the harmonic h' of every source, an index into the plan's harmonic axis, int32 [nb, nrhs] or
+    [1, nrhs] with the positions."""
+
+    pts: torch.Tensor
+    batched: int
+    per_degree: bool
+    index: torch.Tensor
+    suffix = "_ms"
+    rhs_entry = "biem_rhs_multipole"
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.pts
+
+    def workspace_bytes(self, op: "_Operator", n: int) -> int:
+        return int(L.load().biem_rhs_multipole_workspace_bytes(op.plan.handle, n, op.fl.B, int(self.pts.shape[1]), self.batched,
+                                                               op.fl.geom_batched))
+
+
+_CLOSED_FORM = (_PlaneWaves, _PointSources, _MultipoleSources)
 
 
 def _check_closed_form(g, rc: int, what: str) -> None:
-    """L.check; for point sources BIEM_ERR_UNSUPPORTED (the order limit of their radial table, 2-D only) as NotImplementedError."""
-    if isinstance(g, _PointSources) and rc == L.BIEM_ERR_UNSUPPORTED:
+    """L.check; for point and multipole sources BIEM_ERR_UNSUPPORTED (the order limits of their tables) as NotImplementedError."""
+    if isinstance(g, (_PointSources, _MultipoleSources)) and rc == L.BIEM_ERR_UNSUPPORTED:
         msg = L.load().biem_last_error()
         raise NotImplementedError(msg.decode() if msg else f"{what}: not built for this order")
     L.check(rc, what)
@@ -436,20 +459,25 @@ def _check_point_source_position(c, k, position, uin, uin_grad, plane_wave_direc
     """The checks of biem(point_source_position=) that need no device; returns the positions on the host as float64."""
     if uin is not None or uin_grad is not None or plane_wave_direction is not None:
         raise ValueError("point_source_position replaces uin / uin_grad / plane_wave_direction: give one source of the incident field, not several")
+    return _check_source_position("point_source_position", c, k, position)
+
+
+def _check_source_position(name: str, c, k, position) -> np.ndarray:
+    """The checks of the positions of point or multipole sources (the argument `name`) that need no device; returns them as float64."""
     S = _host_array(position)
     if S.dtype.kind not in "iuf":
-        raise ValueError(f"point_source_position must be a real array, got dtype {S.dtype}")
+        raise ValueError(f"{name} must be a real array, got dtype {S.dtype}")
     S = S.astype(np.float64)
     if S.ndim < 1 or S.shape[0] != c.c_ndim:
-        raise ValueError(f"The first dimension of point_source_position must be c.c_ndim={c.c_ndim}, but got shape {tuple(S.shape)}")
+        raise ValueError(f"The first dimension of {name} must be c.c_ndim={c.c_ndim}, but got shape {tuple(S.shape)}")
     if S.ndim != len(_shape(k)) + 1:
-        raise ValueError(f"point_source_position.ndim={S.ndim} is not k.ndim + 1={len(_shape(k)) + 1}")
+        raise ValueError(f"{name}.ndim={S.ndim} is not k.ndim + 1={len(_shape(k)) + 1}")
     if not bool(np.all(np.isfinite(S))):
-        raise ValueError("point_source_position has a non-finite entry")
+        raise ValueError(f"{name} has a non-finite entry")
     return S
 
 
-def _check_sources_outside(op: _Operator, pts: torch.Tensor) -> None:
+def _check_sources_outside(op: _Operator, pts: torch.Tensor, name: str = "point_source_position") -> None:
     """ValueError unless |s - c_b| > rho_b for every (system, source, ball) of pts [nb or 1, nrhs, d] (canonical axes), naming the first
     that fails.  On the device; the test of the result is one synchronisation."""
     fl = op.fl
@@ -459,28 +487,70 @@ def _check_sources_outside(op: _Operator, pts: torch.Tensor) -> None:
     bad = ~(dist > fl.radii[:, None, :])
     if bool(bad.any()):
         s, r, b = (int(v) for v in torch.nonzero(bad)[0])
-        raise ValueError(f"point_source_position: source {r} (system {s}) lies on or inside ball {b}: |s - c| = {float(dist[s, r, b]):.17g} "
-                         f"<= radius {float(fl.radii[s if fl.geom_batched else 0, b]):.17g}; a point source must lie strictly outside every ball")
+        what = "a point source" if name == "point_source_position" else "a multipole source"
+        raise ValueError(f"{name}: source {r} (system {s}) lies on or inside ball {b}: |s - c| = {float(dist[s, r, b]):.17g} "
+                         f"<= radius {float(fl.radii[s if fl.geom_batched else 0, b]):.17g}; {what} must lie strictly outside every ball")
 
 
-def _point_source_source(op: _Operator, S: np.ndarray):
-    """The source of the checked positions S (c_ndim, ...) and the _RhsAxes of its layout, as _plane_wave_source.  Every source must lie
-    strictly outside every ball (the expansion about a ball's centre converges only there, for kind "inner" and "outer" alike):
+def _source_positions(op: _Operator, S: np.ndarray, name: str = "point_source_position"):
+    """The checked positions S (c_ndim, ...) of the argument `name` laid out as [nb or 1, nrhs, d] in canonical axes, whether they differ
+    between the systems, the _RhsAxes of the layout and the full batch shape, as _plane_wave_source.  Every source must lie strictly
+    outside every ball (the expansion about a ball's centre converges only there, for kind "inner" and "outer" alike):
     _check_sources_outside, before any library call."""
     batch = op.batch
     try:
         full = tuple(np.broadcast_shapes(batch, S.shape[1:]))
     except ValueError as e:
-        raise ValueError("Shapes of the batch and point_source_position[1:] are not broadcastable\n"
-                         f"batch shape={batch}\ntuple(point_source_position.shape)={tuple(S.shape)}") from e
+        raise ValueError(f"Shapes of the batch and {name}[1:] are not broadcastable\n"
+                         f"batch shape={batch}\ntuple({name}.shape)={tuple(S.shape)}") from e
     axes = _RhsAxes.of(batch, full)
     S = S[list(op.perm)]                                              # canonical component i = the caller's perm[i], as the centres
     batched = int(any(S.shape[1 + i] != 1 for i in axes.op_axes))
     t = torch.as_tensor(np.moveaxis(np.broadcast_to(S, (S.shape[0],) + full), 0, -1).copy(), device=op.dev)
     pts = axes.lay_out(t)                                             # [nb, nrhs, d]
     pts = pts if batched else pts[:1].contiguous()
-    _check_sources_outside(op, pts)
+    _check_sources_outside(op, pts, name)
+    return pts, batched, axes, full
+
+
+def _point_source_source(op: _Operator, S: np.ndarray):
+    """The source of the checked positions S and the _RhsAxes of its layout."""
+    pts, batched, axes, _ = _source_positions(op, S)
     return _PointSources(pts, batched, op.per_degree), axes
+
+
+def _check_multipole_source(c, k, n_end, position, index, uin, uin_grad, plane_wave_direction, point_source_position):
+    """The checks of biem(multipole_source_position=, multipole_source_index=) that need no device; returns the positions (float64) and
+    the indices (int32, broadcast to the positions' trailing axes) on the host."""
+    if position is None or index is None:
+        raise ValueError("multipole_source_position and multipole_source_index must be given together")
+    if uin is not None or uin_grad is not None or plane_wave_direction is not None or point_source_position is not None:
+        raise ValueError("multipole_source_position replaces uin / uin_grad / plane_wave_direction / point_source_position: give one source "
+                         "of the incident field, not several")
+    S = _check_source_position("multipole_source_position", c, k, position)
+    I = np.asarray(index) if isinstance(index, (int, np.integer)) and not isinstance(index, bool) else _host_array(index)
+    if I.dtype.kind not in "iu":
+        raise ValueError(f"multipole_source_index must be an integer or an integer array, got dtype {I.dtype}")
+    H = _harm_n_ndim_le(int(n_end), c.c_ndim)
+    if I.size and (int(I.min()) < 0 or int(I.max()) >= H):
+        raise ValueError(f"multipole_source_index must lie in [0, H) with H={H} harmonics of degree < n_end={int(n_end)}, "
+                         f"got values from {int(I.min())} to {int(I.max())}")
+    try:
+        I = np.broadcast_to(I, S.shape[1:])
+    except ValueError as e:
+        raise ValueError("multipole_source_index is not broadcastable to multipole_source_position.shape[1:]\n"
+                         f"tuple(multipole_source_index.shape)={tuple(I.shape)}\ntuple(multipole_source_position.shape)={tuple(S.shape)}") from e
+    return S, I.astype(np.int32)
+
+
+def _multipole_source_source(op: _Operator, checked):
+    """The source of the checked (positions S (c_ndim, ...), indices I S.shape[1:]) and the _RhsAxes of its layout, as
+    _point_source_source; the indices are laid out with the positions."""
+    S, I = checked
+    pts, batched, axes, full = _source_positions(op, S, "multipole_source_position")
+    idx = axes.lay_out(torch.as_tensor(np.broadcast_to(I, full)[..., None].copy(), device=op.dev))[..., 0]      # [nb, nrhs]
+    idx = (idx if batched else idx[:1]).to(torch.int32).contiguous()
+    return _MultipoleSources(pts, batched, op.per_degree, idx), axes
 
 
 def _nrhs(g) -> int:
@@ -493,9 +563,10 @@ def _nrhs(g) -> int:
 
 def _sample_ptrs(g, s0: int = 0):
     """The source arguments of an entry point from system s0 on: (d_g,) or (d_gu, d_gdn), a missing set as the null pointer; plane
-    waves and point sources: (per_degree, d_dirs or d_src, batched)."""
+    waves and point sources: (per_degree, d_dirs or d_src, batched); multipoles: d_idx after them."""
     if isinstance(g, _CLOSED_FORM):
-        return (int(g.per_degree), _ptr(g.vectors[s0:] if g.batched else g.vectors), g.batched)
+        args = (int(g.per_degree), _ptr(g.vectors[s0:] if g.batched else g.vectors), g.batched)
+        return args + (_ptr(g.index[s0:] if g.batched else g.index),) if isinstance(g, _MultipoleSources) else args
     if isinstance(g, torch.Tensor):
         return (_ptr(g[s0:]),)
     return tuple(_ptr(None if t is None else t[s0:]) for t in g)
@@ -504,7 +575,10 @@ def _sample_ptrs(g, s0: int = 0):
 def _pick_systems(g, idx: torch.Tensor):
     """The source of the systems idx (a device index tensor) alone."""
     if isinstance(g, _CLOSED_FORM):
-        return type(g)(g.vectors[idx].contiguous(), 1, g.per_degree) if g.batched else g
+        if not g.batched:
+            return g
+        more = (g.index[idx].contiguous(),) if isinstance(g, _MultipoleSources) else ()
+        return type(g)(g.vectors[idx].contiguous(), 1, g.per_degree, *more)
     if isinstance(g, torch.Tensor):
         return g[idx].contiguous()
     return tuple(None if t is None else t[idx].contiguous() for t in g)
@@ -518,7 +592,8 @@ def _entry(base: str, per_degree: bool, label: Optional[str] = None):
 
 
 def _source_entry(base: str, op: _Operator, g, label: Optional[str] = None):
-    """The entry `base` for the source g: its `_pw` form for plane waves, its `_ps` form for point sources, else _entry's choice."""
+    """The entry `base` for the source g: its `_pw` form for plane waves, `_ps` for point sources, `_ms` for multipoles, else _entry's
+    choice."""
     if isinstance(g, _CLOSED_FORM):
         return getattr(L.load(), base + g.suffix), label or base + g.suffix
     return _entry(base, op.per_degree, label)
@@ -526,13 +601,13 @@ def _source_entry(base: str, op: _Operator, g, label: Optional[str] = None):
 
 def _source_workspace_bytes(op: _Operator, g) -> int:
     """What the source adds at the tail of a path's workspace (plane waves: the harmonics of their directions; point sources: those
-    of the unit vectors from every ball, and the radial table)."""
+    of the unit vectors from every ball, and the radial table; multipoles: the table rows of one slice)."""
     return g.workspace_bytes(op, op.fl.nb) if isinstance(g, _CLOSED_FORM) else 0
 
 
 def _factored_source_args(op: _Operator, g) -> tuple:
     """What biem_solve_factored* takes between the tables and the source arguments: nothing, the degree-dependent pair, or for plane
-    waves and point sources the wavenumbers, the centres and the coefficients."""
+    waves, point sources and multipoles the wavenumbers, the centres and the coefficients."""
     fl = op.fl
     coef = (_ptr(fl.alpha), _ptr(fl.beta), fl.ab_batched)
     if isinstance(g, _CLOSED_FORM):
@@ -560,9 +635,8 @@ def _rhs_project(op: _Operator, n: int, g, s0: int, f: torch.Tensor, sys_stride:
     if isinstance(g, _CLOSED_FORM):
         wb = g.workspace_bytes(op, n)
         work = torch.empty(max(wb, 16), dtype=torch.uint8, device=op.dev)
-        _, d_vec, batched = _sample_ptrs(g, s0)
         rc = getattr(L.load(), g.rhs_entry)(op.plan.handle, n, fl.B, _nrhs(g), _ptr(fl.k[s0:]), _ptr(fl.centers[s0:] if fl.geom_batched else fl.centers),
-                                            fl.geom_batched, _ptr(tab), d_vec, batched, _ptr(f), sys_stride, elem_stride, rhs_stride,
+                                            fl.geom_batched, _ptr(tab), *_sample_ptrs(g, s0)[1:], _ptr(f), sys_stride, elem_stride, rhs_stride,
                                             _ptr(work), wb, sp)
         _check_closed_form(g, rc, g.rhs_entry)
         return

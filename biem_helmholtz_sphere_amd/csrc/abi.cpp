@@ -607,6 +607,59 @@ int biem_solve_factored_ps(const biem_plan* plan, int nb, int B, int nrhs, const
                              (hipStream_t)stream);
 }
 
+// ---- multipole incidence in closed form (kernels_rhs_ms.hip): the fifth source; the _ps entries with d_idx after src_batched ----
+size_t biem_rhs_multipole_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs, int src_batched, int geom_batched) {
+  return plan ? rhs_multipole_workspace_bytes(plan, nb, B, nrhs, src_batched, geom_batched) : 0;
+}
+
+int biem_rhs_multipole(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
+                          const double* d_tab, const double* d_src, int src_batched, const int* d_idx, double* d_f, long long sys_stride,
+                          long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_centers, "d_centers"); NEED(d_tab, "d_tab"); NEED(d_src, "d_src"); NEED(d_idx, "d_idx"); NEED(d_f, "d_f"); NEED(d_work, "d_work");
+  return closed_form_rhs(__func__, RhsSource::multipole_sources(d_src, d_idx, src_batched, d_k, d_centers, geom_batched), plan, nb, B, nrhs, d_tab, d_f,
+                         sys_stride, elem_stride, rhs_stride, d_work, work_bytes, (hipStream_t)stream);
+}
+
+int biem_solve_ms(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_src, int src_batched, const int* d_idx, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                  void* stream) {
+  NEED(d_src, "d_src"); NEED(d_idx, "d_idx");
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    RhsSource::multipole_sources(d_src, d_idx, src_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work, work_bytes,
+                    (hipStream_t)stream, false);
+}
+
+int biem_solve_ldlt_ms(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                       const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                       const double* d_src, int src_batched, const int* d_idx, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                       void* stream) {
+  NEED(d_src, "d_src"); NEED(d_idx, "d_idx");
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    RhsSource::multipole_sources(d_src, d_idx, src_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work, work_bytes,
+                    (hipStream_t)stream, true);
+}
+
+int biem_solve_factored_ms(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k, const double* d_centers, int geom_batched, const double* d_alpha,
+                           const double* d_beta, int ab_batched, int per_degree, const double* d_src, int src_batched, const int* d_idx,
+                           double* d_density, void* d_work, size_t work_bytes, void* stream) {
+  NEED(d_src, "d_src"); NEED(d_idx, "d_idx");
+  return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                             RhsSource::multipole_sources(d_src, d_idx, src_batched, d_k, d_centers, geom_batched), d_density, d_work, work_bytes,
+                             (hipStream_t)stream);
+}
+
+// the field of the source itself (kernels_ladder.hip): what .uin, utotal and the powers of a closed-form call evaluate
+size_t biem_multipole_field_workspace_bytes(const biem_plan* plan, int nb) { return plan ? multipole_field_workspace_bytes(plan, nb) : 0; }
+
+int biem_multipole_field(biem_plan* plan, int nb, int P, const double* d_k, const double* d_src, const int* d_idx, const double* d_points,
+                         int flags, int grad, double* d_out, void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_src, "d_src"); NEED(d_idx, "d_idx"); NEED(d_points, "d_points"); NEED(d_out, "d_out"); NEED(d_work, "d_work");
+  if (grad) { if (const int rc = build_force_table(__func__, plan)) return rc; }
+  return launch_multipole_field(plan, nb, P, d_k, d_src, d_idx, d_points, flags, grad, d_out, d_work, work_bytes, (hipStream_t)stream);
+}
+
 // ---- extinction and absorbed power (kernels_power.hip), radiation force (kernels_force.hip) ----
 // both are defined for a lossless exterior: the wavenumbers come to the host for that test (one small copy, one wait)
 static int require_real_k(const char* who, const char* what, const double* d_k, int nb, hipStream_t st) {

@@ -145,6 +145,15 @@ size_t rhs_point_source_workspace_bytes(const biem_plan* p, int nb, int B, int n
 int launch_rhs_point_source(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
                             const double* d_tab, const double* d_src, int src_batched, double* d_f, long long sys_stride,
                             long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work);
+// multipole incidence in closed form (kernels_rhs_ms.hip): the outgoing multipole h_n'(k |x - s_r|) Y_h'((x - s_r)^), h' = d_idx[r] an index
+// into the plan's harmonic axis; f = -gj_n (S|R)_{h'->h}(c_b - s_r) from the ball tables and the plan's term lists (tree a: Graf's one term),
+// written where launch_rhs_project writes.  d_src as launch_rhs_point_source's, d_idx [nrhs] or (src_batched) [nb][nrhs]; d_work:
+// rhs_multipole_workspace_bytes, the table rows of one slice of (systems x right-hand sides).  |t| > rho_b and 0 <= h' < H are the caller's
+// to ensure (an index outside gives NaN); the count and order limits and a plan without term lists are RhsSource::check's to refuse.
+size_t rhs_multipole_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int src_batched, int geom_batched);
+int launch_rhs_multipole(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
+                         const double* d_tab, const double* d_src, int src_batched, const int* d_idx, double* d_f, long long sys_stride,
+                         long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work);
 // d_info[s] = code for every system with a (ball, degree) whose symmetric scaling 1 / sqrt(gj gh) is not finite (gj = 0); others untouched
 // (biem_flag_unscalable exposes it for tests)
 int launch_flag_unscalable(const biem_plan* p, int nb, int B, const double* d_tab, int* d_info, int code, hipStream_t st);
@@ -199,6 +208,12 @@ size_t uscat_hess_workspace_bytes(const biem_plan* p, int nb, int B);
 int launch_uscat_hess(const biem_plan* p, int nb, int B, int P, const double* d_k, const double* d_eta, const double* d_centers,
                       const double* d_radii, int geom_batched, const double* d_density, const double* d_points, int flags,
                       double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
+// the field of the outgoing multipole h_n'(k |x - s|) Y_h'((x - s)^) at the points (kernels_ladder.hip): d_src [nb][d], d_idx [nb] into the
+// plan's harmonic axis; out [P][nb], or (grad) its Cartesian gradient [d][P][nb] - p is then a plan of order n' + 2 or more with its force
+// coupling table uploaded.  flags: BIEM_USCAT_POINTS_BATCHED only
+size_t multipole_field_workspace_bytes(const biem_plan* p, int nb);
+int launch_multipole_field(const biem_plan* p, int nb, int P, const double* d_k, const double* d_src, const int* d_idx, const double* d_points,
+                           int flags, int grad, double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
 // per-lane order ceiling of a tree (kernels_uscat.hip: kFastNendMax*; 0 for the chain trees)
 int uscat_fast_nend_max(int tree);
 // total field inside penetrable fluid balls (kernels_uinterior.hip).  d_kint / d_delta [nb or 1][B] complex; the coefficient step
@@ -260,13 +275,15 @@ struct BoundaryCoef {
 //   SAMPLES_N      the unmixed samples gu / gdn of per-degree coefficients (either may be null: zero), launch_rhs_project_n
 //   PLANE_WAVES    plane waves along pts = dirs in closed form (launch_rhs_plane_wave: no samples)
 //   POINT_SOURCES  point sources at pts = src in closed form (launch_rhs_point_source)
+//   MULTIPOLE_SOURCES  outgoing multipoles at pts = src of the harmonics idx in closed form (launch_rhs_multipole)
 // The closed forms read the wavenumbers, centres and ball tables of the call and keep their harmonics in `work`, work_bytes() of them:
 // the caller's workspace, or (set by the whole path) the tail of its own.
 struct RhsSource {
-  enum Kind { SAMPLES, SAMPLES_N, PLANE_WAVES, POINT_SOURCES };
+  enum Kind { SAMPLES, SAMPLES_N, PLANE_WAVES, POINT_SOURCES, MULTIPOLE_SOURCES };
   Kind kind;
   const double* g[2] = {nullptr, nullptr};                 // samples: g, or gu and gdn
   const double* pts = nullptr; int pts_batched = 0;        // closed forms: [nrhs][d], or (pts_batched) [nb][nrhs][d], in the plan's axes
+  const int* idx = nullptr;                                // multipoles: the harmonic of every source, [nrhs] or (pts_batched) [nb][nrhs]
   const double* k = nullptr; const double* centers = nullptr; int geom_batched = 0;
   void* work = nullptr;
 
@@ -279,19 +296,27 @@ struct RhsSource {
     return RhsSource(POINT_SOURCES, src, batched, k, centers, geom_batched);
   }
 
-  bool closed_form() const { return kind == PLANE_WAVES || kind == POINT_SOURCES; }
+  static RhsSource multipole_sources(const double* src, const int* idx, int batched, const double* k, const double* centers, int geom_batched) {
+    RhsSource s(MULTIPOLE_SOURCES, src, batched, k, centers, geom_batched);
+    s.idx = idx;
+    return s;
+  }
+
+  bool closed_form() const { return kind == PLANE_WAVES || kind == POINT_SOURCES || kind == MULTIPOLE_SOURCES; }
   // the same source for the systems s0 .. of the call
   RhsSource at(const biem_plan* p, int s0, int nrhs, int B) const {
     RhsSource s = *this;
     for (const double*& x : s.g) if (x) x += (size_t)s0 * nrhs * B * p->Q * 2;
     if (pts && pts_batched) s.pts += (size_t)s0 * nrhs * p->d;
+    if (idx && pts_batched) s.idx += (size_t)s0 * nrhs;
     if (k) s.k += 2 * (size_t)s0;
     if (centers && geom_batched) s.centers += (size_t)s0 * B * p->d;
     return s;
   }
   size_t work_bytes(const biem_plan* p, int nb, int B, int nrhs) const {
     return kind == PLANE_WAVES ? rhs_plane_wave_workspace_bytes(p, nb, nrhs, pts_batched)
-         : kind == POINT_SOURCES ? rhs_point_source_workspace_bytes(p, nb, B, nrhs, pts_batched, geom_batched) : 0;
+         : kind == POINT_SOURCES ? rhs_point_source_workspace_bytes(p, nb, B, nrhs, pts_batched, geom_batched)
+         : kind == MULTIPOLE_SOURCES ? rhs_multipole_workspace_bytes(p, nb, B, nrhs, pts_batched, geom_batched) : 0;
   }
   // what the closed forms cannot take (grid dimensions; the thread-local radial table of a (source, ball) pair): refused under the
   // caller's name `who` before anything is launched

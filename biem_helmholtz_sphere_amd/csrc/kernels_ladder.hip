@@ -1,4 +1,5 @@
-// kernels_ladder.hip -- Hessian of the scattered field by a coefficient ladder (gfx950).
+// kernels_ladder.hip -- Hessian of the scattered field by a coefficient ladder (gfx950), and the field and gradient of a
+// multipole source by the same ladder.
 //
 // For z = h (outer) or z = j (kind inner) in every dimension, with T^i_{h'h} = int y_i Y_h conj(Y_h') dOmega (the plan's force
 // coupling table, plan_build_force):
@@ -75,6 +76,56 @@ int launch_uscat_hess(const biem_plan* p, int nb, int B, int P, const double* d_
       BIEM_LAUNCHCHK();
       if ((rc = uscat_eval_coef(p, nb, B, P, d_k, d_centers, d_radii, geom_batched, pair, d_points, flags, d_out + (size_t)q * per, st)) != BIEM_OK) return rc;
     }
+  return BIEM_OK;
+}
+
+// ---- the field of an outgoing multipole h_n'(k |x - s|) Y_h'((x - s)^) itself: the scattered field of one fictitious ball per system at
+// s, radius 0, with the unit coefficient set delta_{h, idx}; its gradient: one ladder step per component, then the value kernels
+// (launch_uscat_hess's route taken once).  c[s][h] = delta_{h, idx[s]}; an index outside [0, H) leaves the set zero
+__global__ void __launch_bounds__(256) k_unit_coef(int H, long long count, const int* __restrict__ idx, cplx* __restrict__ c, double* __restrict__ zero_radii) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+    const long long s = i / H;
+    const int h = (int)(i - s * H);
+    c[i] = make_double2(idx[s] == h ? 1.0 : 0.0, 0.0);
+    if (h == 0) zero_radii[s] = 0.0;
+  }
+}
+
+// workspace: the unit set, one laddered set, the radii (zero) of the fictitious balls
+size_t multipole_field_workspace_bytes(const biem_plan* p, int nb) {
+  return nb <= 0 ? 0 : 2 * align256((size_t)nb * p->H * sizeof(cplx)) + align256((size_t)nb * sizeof(double));
+}
+
+int launch_multipole_field(const biem_plan* p, int nb, int P, const double* d_k, const double* d_src, const int* d_idx, const double* d_points,
+                           int flags, int grad, double* d_out, void* d_work, size_t work_bytes, hipStream_t st) {
+  const char* who = "biem_multipole_field";
+  if (flags & ~BIEM_USCAT_POINTS_BATCHED) { set_error("%s: flags other than BIEM_USCAT_POINTS_BATCHED (%d)", who, flags); return BIEM_ERR_ARG; }
+  if (grad && p->n_end < 2) { set_error("%s: the gradient needs the plan of order n' + 2 of the source's degree n', at least 2 (n_end=%d)", who, p->n_end); return BIEM_ERR_ARG; }
+  if (grad && !p->force_uploaded) { set_error("%s: the plan's force coupling table is not on the device", who); return BIEM_ERR_ARG; }
+  if (nb > 65535) { set_error("%s: more than 65535 systems in one call (%d)", who, nb); return BIEM_ERR_UNSUPPORTED; }
+  if (nb <= 0 || P <= 0) return BIEM_OK;
+  int rc = uscat_covered(p, nb, 1, flags);
+  if (rc != BIEM_OK) {
+    const std::string why = last_error();
+    set_error("%s: the field of the plan of order n_end=%d is not built (%s)", who, p->n_end, why.c_str());
+    return rc == BIEM_ERR_UNSUPPORTED ? rc : BIEM_ERR_ARG;
+  }
+  if (work_bytes < multipole_field_workspace_bytes(p, nb)) { set_error("%s: workspace too small", who); return BIEM_ERR_ARG; }
+  const size_t set = align256((size_t)nb * p->H * sizeof(cplx));
+  cplx* c = (cplx*)d_work;
+  cplx* g = (cplx*)((char*)d_work + set);
+  double* radii = (double*)((char*)d_work + 2 * set);
+  const long long count = (long long)nb * p->H;
+  hipLaunchKernelGGL(k_unit_coef, dim3((unsigned)((count + 255) / 256 < 65536 ? (count + 255) / 256 : 65536)), dim3(256), 0, st, p->H, count, d_idx, c, radii);
+  BIEM_LAUNCHCHK();
+  if (!grad) return uscat_eval_coef(p, nb, 1, P, d_k, d_src, radii, 1, c, d_points, flags, d_out, st);
+  const size_t per = (size_t)P * nb * 2;                     // doubles of one component of the result
+  for (int i = 0; i < p->d; ++i) {
+    // (the set has one entry, of a degree the caller keeps below n_end - 1: the step stays inside the plan)
+    ladder(p, nb, 1, i, p->n_end - 1, d_k, c, g, st);
+    BIEM_LAUNCHCHK();
+    if ((rc = uscat_eval_coef(p, nb, 1, P, d_k, d_src, radii, 1, g, d_points, flags, d_out + (size_t)i * per, st)) != BIEM_OK) return rc;
+  }
   return BIEM_OK;
 }
 

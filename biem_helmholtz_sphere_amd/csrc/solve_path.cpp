@@ -167,6 +167,17 @@ int RhsSource::check(const char* who, const biem_plan* p, int nb, int nrhs) cons
     set_error("%s: n_end=%d exceeds the built table size %d of the point-source right-hand side", who, p->n_end, kMaxRad);
     return BIEM_ERR_UNSUPPORTED;
   }
+  if (kind == MULTIPOLE_SOURCES) {
+    // tree a: the radial row of a (source, ball) pair in LDS, orders < 2 n_end - 1; every other tree: the term lists, built up to half that
+    if (p->tree == TREE_A ? p->n_end > kMaxRad : 2 * p->n_end > kMaxRad) {
+      set_error("%s: n_end=%d exceeds the built table size %d of the multipole right-hand side", who, p->n_end, p->tree == TREE_A ? kMaxRad : kMaxRad / 2);
+      return BIEM_ERR_UNSUPPORTED;
+    }
+    if (p->tree != TREE_A && (!p->lists_built || p->ptr.empty() || !p->d_ptr)) {
+      set_error("%s: the plan has no translation term lists", who);
+      return BIEM_ERR_UNSUPPORTED;
+    }
+  }
   return BIEM_OK;
 }
 
@@ -184,6 +195,9 @@ int RhsSource::launch(const biem_plan* p, int nb, int B, int nrhs, const Boundar
     case POINT_SOURCES:
       return launch_rhs_point_source(p, nb, B, nrhs, k, centers, geom_batched, d_tab, pts, pts_batched, d_f, sys_stride, elem_stride,
                                      rhs_stride, st, slot_order, split, work);
+    case MULTIPOLE_SOURCES:
+      return launch_rhs_multipole(p, nb, B, nrhs, k, centers, geom_batched, d_tab, pts, pts_batched, idx, d_f, sys_stride, elem_stride,
+                                  rhs_stride, st, slot_order, split, work);
   }
   return BIEM_ERR_ARG;
 }

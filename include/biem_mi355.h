@@ -487,6 +487,45 @@ int biem_solve_factored_ps(const biem_plan* plan, int nb, int B, int nrhs, const
                            const double* d_alpha, const double* d_beta, int ab_batched, int per_degree, const double* d_src,
                            int src_batched, double* d_density, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- multipole incidence in closed form: exact right-hand sides for any degree, without samples.  The outgoing
+ *      multipole u_in(x) = h_n'(k |x - s|) Y_h'((x - s)^) at s (orthonormal harmonics, the radial functions of this header), expanded about
+ *      the centre of ball b with t = c_b - s and |t| > rho_b, is a column of the translation operator of the fill:
+ *        u_in(c_b + r) = sum_h (S|R)_{h'->h}(t) j_n(k |r|) Y_h(r^),   f(s, r, b, h) = -gj_{n(h)}(s, b) (S|R)_{h'_r->h}(c_b - s_r),
+ *      gj row 0 of d_tab; (S|R) from the plan's term lists and a table row C_d h_n''(k |t|) Y_l(t^) per (system, source, ball), in 2-D
+ *      from Graf's one term per entry.  d_src as biem_rhs_point_source's; d_idx: the harmonic h' of every source, an index into the
+ *      plan's harmonic axis (biem_plan_labels), int [nrhs] or [nb][nrhs] with src_batched != 0.  h' of degree 0 gives Y_0 times the
+ *      point-source problem.  NOT TESTED HERE: every source strictly outside every ball, 0 <= h' < H (an index outside gives NaN).
+ *      Every element is written by one lane, no atomics: two calls give the same bits.  At most 65535 systems and right-hand sides
+ *      per call (BIEM_ERR_ARG); BIEM_ERR_UNSUPPORTED, nothing launched: n_end above 320 in 2-D, above 160 elsewhere, a plan without
+ *      term lists that is not 2-D.
+ * Workspace: biem_rhs_multipole_workspace_bytes, the table rows of one slice of (systems x right-hand sides): the launcher walks slices
+ * whose table stays under 512 MiB (BIEM_RHS_TABLE_BYTES=n in the environment lowers that, read per call; the result does not depend on
+ * it).  biem_solve_ms / biem_solve_ldlt_ms / biem_solve_factored_ms: the _ps entries with d_idx after src_batched; workspace: the
+ * bytes of biem_solve_workspace_bytes (biem_solve_factored_workspace_bytes) PLUS biem_rhs_multipole_workspace_bytes, at the tail. ---- */
+size_t biem_rhs_multipole_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs, int src_batched, int geom_batched);
+int biem_rhs_multipole(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_centers,
+                       int geom_batched, const double* d_tab, const double* d_src, int src_batched, const int* d_idx, double* d_f,
+                       long long sys_stride, long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream);
+int biem_solve_ms(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_src, int src_batched, const int* d_idx, double* d_density, int* d_info, int chunk, void* d_work,
+                  size_t work_bytes, void* stream);
+int biem_solve_ldlt_ms(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta,
+                       const double* d_centers, const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta,
+                       int ab_batched, int per_degree, const double* d_src, int src_batched, const int* d_idx, double* d_density,
+                       int* d_info, int chunk, void* d_work, size_t work_bytes, void* stream);
+int biem_solve_factored_ms(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k /*c128*/, const double* d_centers, int geom_batched,
+                           const double* d_alpha, const double* d_beta, int ab_batched, int per_degree, const double* d_src,
+                           int src_batched, const int* d_idx, double* d_density, void* d_work, size_t work_bytes, void* stream);
+/* The field of such a source itself, u(x) = h_n'(k_s |x - s_s|) Y_h'((x - s_s)^), one source per system: d_src [nb][d], d_idx [nb] (an
+ * index into the harmonic axis of `plan`), points and flags as biem_uscat (BIEM_USCAT_POINTS_BATCHED only); out [P][nb] complex128.
+ * grad != 0: the Cartesian gradient in the plan's axes, out [d][P][nb]; `plan` is then a plan of order n' + 2 or more (its force
+ * coupling table is built on the first such call).  Every tree the value kernels of biem_uscat cover, the chains included. */
+size_t biem_multipole_field_workspace_bytes(const biem_plan* plan, int nb);
+int biem_multipole_field(biem_plan* plan, int nb, int P, const double* d_k /*c128*/, const double* d_src, const int* d_idx,
+                         const double* d_points, int flags, int grad, double* d_out, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- cross sections: extinction and absorbed power per ball from what the solve already has (no second solve, no
  *      matrix, no workspace).  Real k only, in the far-field normalisation u_scat ~ F(x^) e^{ikr} / r^{(d-1)/2}: "power" is
  *      (1/k) Im oint conj(u) d_n u dS, for a unit plane wave the cross section.  With c_h = density_h blc_n(rho_b), U_h / V_h the
