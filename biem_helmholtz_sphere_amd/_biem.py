@@ -23,13 +23,14 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._arrays import Array, _ptr, _stream_ptr
-from ._fields import (USCAT_GRAD_N_END_MAX, biem_far_pattern, biem_u, biem_u_grad, biem_u_hess, biem_u_interior, biem_u_interior_grad,
+from ._arrays import Array, _host_array, _ptr, _stream_ptr
+from ._coords import canonical_tree
+from ._fields import (USCAT_GRAD_N_END_MAX, _cluster_flat, biem_cluster_coefficients, biem_far_pattern, biem_u, biem_u_grad, biem_u_hess, biem_u_interior, biem_u_interior_grad,
                       biem_u_total, biem_u_total_grad)
-from ._incident import fluid_inclusion_bc, harmonic_labels, max_memory, max_n_end, multipole_source, plane_wave, point_source
+from ._incident import fluid_inclusion_bc, harmonic_labels, max_memory, max_n_end, multipole_source, plane_wave, point_source, regular_wave
 from ._observables import BIEMPower, biem_force, biem_power
 from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_closed_form, _check_incident, _check_multipole_source,
-                        _check_plane_wave_direction, _multipole_source_source,
+                        _check_plane_wave_direction, _multipole_source_source, _regular_wave_source, _RegularWaves,
                         _check_point_source_position, _entry, _factored_source_args, _nrhs, _operator, _pick_systems, _plane_wave_source,
                         _point_source_source, _rhs_project, _sample_ptrs, _source_entry, _source_workspace_bytes, _validate_biem_inputs, _warn_biem_inputs)
 from ._plans import _chain_plan_dim, _plan
@@ -48,7 +49,7 @@ __all__ = [
     "BIEMFactorization", "BIEMKwargs", "BIEMPower", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
     "biem_factorize", "biem_far_pattern", "biem_force", "biem_power", "biem_u", "biem_u_grad", "biem_u_hess", "biem_u_interior",
     "biem_u_interior_grad", "biem_u_total", "biem_u_total_grad", "fluid_inclusion_bc", "harmonic_labels", "max_memory", "max_n_end",
-    "multipole_source", "plane_wave", "point_source",
+    "multipole_source", "plane_wave", "point_source", "regular_wave", "biem_cluster_coefficients",
 ]
 
 _last_solve_stats: dict = {}   # how the last biem() call solved its systems (tests / bench)
@@ -170,6 +171,10 @@ class BIEMResultCalculator:
         """The far-field pattern of the whole cluster about the origin (see :func:`biem_far_pattern`)."""
         return biem_far_pattern(self, directions, per_ball=per_ball)
 
+    def cluster_coefficients(self, *, origin: Array | None = None, n_out: int | None = None) -> Array:
+        """The scattered field of the whole cluster as one outgoing expansion about ``origin`` (see :func:`biem_cluster_coefficients`)."""
+        return biem_cluster_coefficients(self, origin=origin, n_out=n_out)
+
 
 def _reference_matrix(op: _Operator) -> Array:
     """The matrix of every system in the reference's scaling (``BIEMResultCalculator.matrix``), assembled on demand."""
@@ -212,10 +217,15 @@ def _result(op: _Operator, uin, density_t: Optional[torch.Tensor], axes: Optiona
 # the solver (reference :453-819)
 # --------------------------------------------------------------------------------------
 def _closed_form_request(c, k, n_end, uin, uin_grad, plane_wave_direction, point_source_position, multipole_source_position=None,
-                         multipole_source_index=None):
-    """The checks of plane_wave_direction / point_source_position / the multipole_source pair that need no device.  None without any,
-    else (argument name, the checked array on the host - multipoles: the pair (positions, indices) -, the argument as the caller passed
-    it)."""
+                         multipole_source_index=None, regular_wave_origin=None, regular_wave_index=None):
+    """The checks of plane_wave_direction / point_source_position / the multipole_source pair / the regular_wave pair that need no
+    device.  None without any, else (argument name, the checked array on the host - multipoles and regular waves: the pair (positions,
+    indices) -, the argument as the caller passed it)."""
+    if regular_wave_origin is not None or regular_wave_index is not None:
+        checked = _check_multipole_source(c, k, n_end, regular_wave_origin, regular_wave_index, uin, uin_grad, plane_wave_direction,
+                                          point_source_position, "regular_wave_origin", "regular_wave_index",
+                                          (multipole_source_position, multipole_source_index))
+        return "regular_wave_origin", checked, regular_wave_origin
     if multipole_source_position is not None or multipole_source_index is not None:
         checked = _check_multipole_source(c, k, n_end, multipole_source_position, multipole_source_index, uin, uin_grad, plane_wave_direction,
                                           point_source_position)
@@ -237,6 +247,9 @@ def _incident_source(op: _Operator, uin, uin_grad, closed=None):
         _check_incident(op, uin, uin_grad)
         return _boundary_samples(op, uin, uin_grad) + (uin,)
     name, checked, given = closed
+    if name == "regular_wave_origin":
+        arg = given if isinstance(given, torch.Tensor) and given.is_floating_point() else checked[0]
+        return _regular_wave_source(op, checked) + (regular_wave(op.c, k=op.k_given, origin=arg, index=checked[1], n_end=op.n_end)[0],)
     if name == "multipole_source_position":
         arg = given if isinstance(given, torch.Tensor) and given.is_floating_point() else checked[0]
         return _multipole_source_source(op, checked) + (multipole_source(op.c, k=op.k_given, source=arg, index=checked[1], n_end=op.n_end)[0],)
@@ -345,7 +358,8 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
          translational_coefficients_method: Literal["gumerov", "plane_wave", "triplet"] | None = None, chunk: int = 0,
          alpha_n: Array | None = None, beta_n: Array | None = None, plane_wave_direction: Array | None = None,
          point_source_position: Array | None = None, multipole_source_position: Array | None = None,
-         multipole_source_index: Array | int | None = None) -> BIEMResultCalculator:
+         multipole_source_index: Array | int | None = None, regular_wave_origin: Array | None = None,
+         regular_wave_index: Array | int | None = None) -> BIEMResultCalculator:
     r"""Boundary Integral Equation Method (BIEM) for the Helmholtz equation on MI355X.
 
     Same contract as the reference ``biem`` (``_biem.py:453-581``): solves, per leading batch element,
@@ -392,6 +406,13 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     multipole_source's callable.  A general multipole (a dipole along an arbitrary axis) is a linear combination: pass its harmonics as
     right-hand sides and combine the densities.  ``NotImplementedError`` for n_end > 320 in 2-D and n_end > 160 elsewhere.
 
+    ``regular_wave_origin`` / ``regular_wave_index`` (extension, given together, with the shapes and rules of the multipole pair; not
+    together with any other incidence argument): the incident field is the regular wave ``j_n'(k |x - o|) Y_h'((x - o)^)`` about the
+    origin ``o``, :func:`regular_wave` - the basis in which every source-free incident field (a beam given by its beam-shape
+    coefficients, a standing wave) is written.  The right-hand side is exact, ``f = -gj_n (R|R)_{h'->h}(c_b - o)``.  The origin is
+    unrestricted: outside the balls, inside one, or exactly on a ball's centre (nothing is checked, nothing synchronises).  Combine
+    the densities of the harmonics with the field's coefficients; ``fac.tmatrix()`` does so for all of them at once.
+
     Solver: the reference passes every system to a general dense solve (``_biem.py:797``).  Here the system is first brought
     to its complex-symmetric form (real harmonics, symmetric scaling) and factored as U^T U (Cholesky-type, no conjugation)
     without interchanges - half the flops; a system in which a multiplier would exceed 100, or whose factor grew by more than
@@ -401,7 +422,7 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     if translational_coefficients_method not in (None, "gumerov", "plane_wave", "triplet"):
         raise ValueError(f"Invalid translational_coefficients_method: {translational_coefficients_method}")
     closed = _closed_form_request(c, k, n_end, uin, uin_grad, plane_wave_direction, point_source_position, multipole_source_position,
-                                  multipole_source_index)
+                                  multipole_source_index, regular_wave_origin, regular_wave_index)
     op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n, beta_n)
     lib = L.load()
     plan, fl, dev = op.plan, op.fl, op.dev
@@ -499,52 +520,121 @@ class BIEMFactorization:
 
     def solve(self, *, uin: Callable[[Array], Array] | None = None, uin_grad: Callable[[Array], Array] | None = None,
               plane_wave_direction: Array | None = None, point_source_position: Array | None = None,
-              multipole_source_position: Array | None = None, multipole_source_index: Array | int | None = None) -> BIEMResultCalculator:
+              multipole_source_position: Array | None = None, multipole_source_index: Array | int | None = None,
+              regular_wave_origin: Array | None = None, regular_wave_index: Array | int | None = None) -> BIEMResultCalculator:
         """Densities of the incident field (uin, uin_grad), or of plane waves along ``plane_wave_direction`` or of point sources at
         ``point_source_position`` (the monopoles ``h_0(k |x - s|)``, strictly outside every ball) in closed form, against the stored
         factors: ``biem()``'s result for the same field.  Many source positions against one factorisation are right-hand sides of one
         call: a trailing axis of the argument on which the operator has size 1.  ``multipole_source_position`` with
         ``multipole_source_index`` (given together): the outgoing multipoles ``h_n'(k |x - s|) Y_h'((x - s)^)`` in closed form, as in
-        :func:`biem`."""
+        :func:`biem`.  ``regular_wave_origin`` with ``regular_wave_index``: the regular waves ``j_n'(k |x - o|) Y_h'((x - o)^)`` about
+        any origin, as in :func:`biem`."""
         if self._closed:
             raise ValueError("BIEMFactorization is closed")
         op, lib = self._op, L.load()
         closed = _closed_form_request(op.c, op.k_given, op.n_end, uin, uin_grad, plane_wave_direction, point_source_position,
-                                      multipole_source_position, multipole_source_index)
+                                      multipole_source_position, multipole_source_index, regular_wave_origin, regular_wave_index)
         plan, fl, dev = op.plan, op.fl, op.dev
         B, H, nb = fl.B, plan.H, fl.nb
         has_rhs = not (uin is None and uin_grad is None and closed is None)
         density_t = axes = None
         if has_rhs:
             g, axes, uin = _incident_source(op, uin, uin_grad, closed)
-            nrhs = _nrhs(g)
-            density_t = torch.empty((nb, nrhs, B, H), dtype=torch.complex128, device=dev)
-            sp = _stream_ptr(dev)
-            with torch.cuda.device(dev):
-                if nb > 0 and self._factors is None:
-                    _single_ball_density(op, g, self._tab, density_t, sp)
-                elif nb > 0:
-                    n_pad = int(self._factors.shape[-1])
-                    sst = n_pad * n_pad
-                    if self.n_symmetric > 0:
-                        wb = int(lib.biem_solve_factored_workspace_bytes(plan.handle, nb, B, nrhs)) + _source_workspace_bytes(op, g)
-                        work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
-                        entry, what = _source_entry("biem_solve_factored", op, g)
-                        _check_closed_form(g, entry(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab), *_factored_source_args(op, g),
-                                                    *_sample_ptrs(g), _ptr(density_t), _ptr(work), wb, sp), what)
-                        del work
-                    # LU-form systems (runs of consecutive systems): equilibrated right-hand sides in natural order, stored LU, density
-                    ldx = nrhs
-                    for s0, s1 in self._lu_runs:
-                        n = s1 - s0
-                        x = torch.zeros((n, n_pad, ldx), dtype=torch.complex128, device=dev)
-                        xs = n_pad * ldx
-                        _rhs_project(op, n, g, s0, x, xs, ldx, 1, sp, self._tab[s0:s1])
-                        L.check(lib.biem_lu_solve(n, n_pad, nrhs, _ptr(self._factors[s0]), n_pad, sst, _ptr(self._ipiv[s0]), _ptr(x), ldx, xs, sp),
-                                "biem_lu_solve")
-                        L.check(lib.biem_density(plan.handle, n, B, nrhs, _ptr(x), xs, ldx, 1, _ptr(self._tab[s0]), _ptr(density_t[s0]), sp),
-                                "biem_density")
+            density_t = self._densities(g)
         return _result(op, uin, density_t, axes, B > 1 or not has_rhs)
+
+    def _densities(self, g) -> torch.Tensor:
+        """The densities [nb, nrhs, B, H] of the source g of right-hand sides against the stored factors."""
+        op, lib = self._op, L.load()
+        plan, fl, dev = op.plan, op.fl, op.dev
+        B, H, nb = fl.B, plan.H, fl.nb
+        nrhs = _nrhs(g)
+        density_t = torch.empty((nb, nrhs, B, H), dtype=torch.complex128, device=dev)
+        sp = _stream_ptr(dev)
+        with torch.cuda.device(dev):
+            if nb > 0 and self._factors is None:
+                _single_ball_density(op, g, self._tab, density_t, sp)
+            elif nb > 0:
+                n_pad = int(self._factors.shape[-1])
+                sst = n_pad * n_pad
+                if self.n_symmetric > 0:
+                    wb = int(lib.biem_solve_factored_workspace_bytes(plan.handle, nb, B, nrhs)) + _source_workspace_bytes(op, g)
+                    work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+                    entry, what = _source_entry("biem_solve_factored", op, g)
+                    _check_closed_form(g, entry(plan.handle, nb, B, nrhs, _ptr(self._factors), n_pad, sst, _ptr(self._tab), *_factored_source_args(op, g),
+                                                *_sample_ptrs(g), _ptr(density_t), _ptr(work), wb, sp), what)
+                    del work
+                # LU-form systems (runs of consecutive systems): equilibrated right-hand sides in natural order, stored LU, density
+                ldx = nrhs
+                for s0, s1 in self._lu_runs:
+                    n = s1 - s0
+                    x = torch.zeros((n, n_pad, ldx), dtype=torch.complex128, device=dev)
+                    xs = n_pad * ldx
+                    _rhs_project(op, n, g, s0, x, xs, ldx, 1, sp, self._tab[s0:s1])
+                    L.check(lib.biem_lu_solve(n, n_pad, nrhs, _ptr(self._factors[s0]), n_pad, sst, _ptr(self._ipiv[s0]), _ptr(x), ldx, xs, sp),
+                            "biem_lu_solve")
+                    L.check(lib.biem_density(plan.handle, n, B, nrhs, _ptr(x), xs, ldx, 1, _ptr(self._tab[s0]), _ptr(density_t[s0]), sp),
+                            "biem_density")
+        return density_t
+
+    def tmatrix(self, *, origin: Array | None = None, n_out: int | None = None, rhs_chunk: int | None = None) -> Array:
+        r"""The T-matrix of the cluster about ``origin``: ``T`` of shape ``(...(systems), H_out, H)``, complex128, which maps the regular
+        coefficients ``p_h'`` of any incident field ``sum_h' p_h' j_n'(k |x - o|) Y_h'((x - o)^)`` to the outgoing coefficients
+        ``A = T p`` of the scattered field ``sum_h'' A_h'' h_n''(k |x - o|) Y_h''((x - o)^)`` (valid outside the sphere about ``o`` that
+        holds the cluster).  Column h' is :func:`biem_cluster_coefficients` of the solution for the regular wave of index h'
+        (``regular_wave_origin`` / ``regular_wave_index``): H right-hand sides against the stored factors, in chunks of ``rhs_chunk``
+        (default: as many as fit 85 % of the free device memory beside the factors; the result does not depend on it).  ``origin``
+        has shape ``(c_ndim,)`` or ``(c_ndim, ...)`` broadcastable to the axes of the systems (default 0) and may lie anywhere;
+        ``n_out >= n_end`` (default ``n_end``) is the order of the outgoing side, along ``harmonic_labels(c, n_out)``; the columns run
+        along ``harmonic_labels(c, n_end)``.  ``kind="outer"`` only."""
+        if self._closed:
+            raise ValueError("BIEMFactorization is closed")
+        op = self._op
+        if op.kind != "outer":
+            raise ValueError(f"Invalid kind: {op.kind} (kind='inner' has no outgoing expansion: tmatrix needs kind='outer')")
+        tree, _ = canonical_tree(op.c.branching_types_expression_str)
+        plan, fl, dev, batch = op.plan, op.fl, op.dev, tuple(op.batch)
+        nb, B, H, d = fl.nb, fl.B, plan.H, op.c.c_ndim
+        n_end = int(op.n_end)
+        n_out = n_end if n_out is None else int(n_out)
+        if n_out < n_end:
+            raise ValueError(f"n_out={n_out} must be at least n_end={n_end}")
+        if origin is None:
+            O = np.zeros((d,) + (1,) * len(batch))
+        else:
+            O = _host_array(origin).astype(np.float64)
+            if O.ndim < 1 or O.shape[0] != d:
+                raise ValueError(f"origin must have shape ({d},) or ({d}, ...), got {tuple(O.shape)}")
+            if O.ndim == 1:
+                O = O.reshape((d,) + (1,) * len(batch))
+            try:
+                ok = O.ndim == len(batch) + 1 and tuple(np.broadcast_shapes(batch, O.shape[1:])) == batch
+            except ValueError:
+                ok = False
+            if not ok:
+                raise ValueError(f"origin[1:] of shape {tuple(O.shape[1:])} does not broadcast to the batch shape {batch}")
+        O = O[list(op.perm)]                                                   # canonical axes, as the centres
+        obatched = int(any(n != 1 for n in O.shape[1:]))
+        flat = np.moveaxis(np.broadcast_to(O, (d,) + batch), 0, -1).reshape(nb, d) if obatched else O.reshape(1, d)
+        of = torch.as_tensor(np.ascontiguousarray(flat), device=dev)
+        H_out = _plan(tree, n_out, dev).H if n_out != n_end else H
+        if rhs_chunk is None:
+            lib = L.load()
+            with torch.cuda.device(dev):
+                per = (int(lib.biem_solve_factored_workspace_bytes(plan.handle, nb, B, 8)) // 8 if B > 1 else 0) + nb * B * (2 * H + H_out) * 16 + 1
+                rhs_chunk = max(1, min(H, int(0.85 * _available_bytes(dev)) // per)) if nb > 0 else H
+        rhs_chunk = int(rhs_chunk)
+        if rhs_chunk < 1:
+            raise ValueError(f"rhs_chunk={rhs_chunk} must be at least 1")
+        T = torch.empty((nb, H_out, H), dtype=torch.complex128, device=dev)
+        rows = of.shape[0]
+        for h0 in range(0, H, rhs_chunk):
+            n = min(rhs_chunk, H - h0)
+            idx = torch.arange(h0, h0 + n, dtype=torch.int32, device=dev)[None].expand(rows, n).contiguous()
+            g = _RegularWaves(of[:, None, :].expand(rows, n, d).contiguous(), obatched, op.per_degree, idx)
+            A = _cluster_flat(tree, n_end, n_out, fl, of, obatched, self._densities(g), dev)      # [nb, n, H_out]
+            T[:, :, h0:h0 + n] = A.transpose(1, 2)
+        return op.origin.give(T.reshape(batch + (H_out, H)))
 
 
 def biem_factorize(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha: Array | complex = 1.0,

@@ -13,7 +13,7 @@ import torch
 from . import _lib as L
 from ._arrays import Array, _Origin, _host_array, _inverse_perm, _is_complex, _ptr, _result_origin, _shape, _stacked, _stream_ptr, _to_dev
 from ._coords import canonical_tree, n_end_from_harm
-from ._operator import _Flat, _flatten
+from ._operator import _Flat, _RhsAxes, _flatten
 from ._plans import _Plan, _plan
 
 
@@ -351,6 +351,99 @@ def biem_u_total_grad(res: Any, x: Array, /, *, k_interior: Array, density_ratio
         x = _stacked(x)[(...,) + (None,) * len(_shape(res.k))]
     uin = uin_grad(x)
     return _inside_or(inside, outside, uin)
+
+
+def _raised_layout(tree: str, n_end: int, n_out: int, dev: torch.device) -> Tuple[_Plan, torch.Tensor]:
+    """The plan of order n_out >= n_end and, per harmonic of the order-n_end plan, its place on that plan's axis, matched by label (the
+    axis of a larger order does not begin with the smaller one, as _hess_layout)."""
+    big, small = _plan(tree, n_out, dev), _plan(tree, n_end, dev)
+    where = {tuple(lab) + (int(n),): i for i, (lab, n) in enumerate(zip(big.labels.tolist(), big.degrees.tolist()))}
+    idx = [where[tuple(lab) + (int(n),)] for lab, n in zip(small.labels.tolist(), small.degrees.tolist())]
+    return big, torch.as_tensor(idx, dtype=torch.long, device=big.dev)
+
+
+def biem_cluster_coefficients(res: Any, /, *, origin: Array | None = None, n_out: int | None = None, _stage: int = 0) -> Array:
+    r"""Outgoing coefficients of the scattered field of the whole cluster about ``origin``: ``A`` of shape ``(...(first), H_out)``,
+    complex128, the right-hand-side axes of the density included, with
+
+        u_scat(x) = sum_h'' A_h'' h_n''(k |x - o|) Y_h''((x - o)^)    for |x - o| > max_b (|c_b - o| + rho_b),
+        A_h'' = sum_b sum_h (R|R)_{h->h''}(o - c_b) c_{b,h},            c = density x blc (the coefficients of :func:`biem_u`),
+
+    ``h''`` along ``harmonic_labels(c, n_out)``.  ``origin`` has shape ``(c_ndim,)`` or ``(c_ndim, ...)`` broadcastable to the axes of
+    the systems (default: the zero vector) and may lie anywhere; ``n_out`` (default ``n_end``, at least ``n_end``) is the order the
+    expansion is truncated at - the translation of a ball off the origin feeds every degree, so a cluster of radius R about o wants
+    ``n_out`` well above ``k R``.  Axes of the density on which k, eta, the geometry and the origin have size 1 are right-hand sides of
+    one translation table.  ``kind="outer"`` only.  Real and complex k, every tree :func:`biem_u` covers; ``NotImplementedError``
+    above the order of the translation term lists (n_out > 320 in 2-D, > 160 elsewhere).  The result is bit-reproducible."""
+    if res.density is None:
+        raise ValueError("The BIEMResult does not have density.")
+    if res.kind != "outer":
+        raise ValueError(f"Invalid kind: {res.kind} (kind='inner' has no outgoing expansion: cluster_coefficients needs kind='outer')")
+    c = res.c
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    d = c.c_ndim
+    o_origin, dev = _result_origin(res, res.density if origin is None else origin)
+    f64 = torch.float64
+    dens_t = _to_dev(res.density, dev, torch.complex128)
+    H = int(dens_t.shape[-1])
+    n_end = n_end_from_harm(tree, H)
+    n_out = n_end if n_out is None else int(n_out)
+    if n_out < n_end:
+        raise ValueError(f"n_out={n_out} must be at least n_end={n_end}")
+    k_t = _to_dev(res.k, dev, torch.complex128)
+    eta_t = _to_dev(res.eta, dev, f64)
+    cen_t = _to_dev(res.centers, dev, f64)[list(perm)]     # [d, ...(first), B], canonical axes
+    rad_t = _to_dev(res.radii, dev, f64)
+    nd = dens_t.ndim - 2
+    o_t = torch.zeros((d,) + (1,) * nd, dtype=f64, device=dev) if origin is None else _to_dev(_stacked(origin), dev, f64)
+    if o_t.ndim < 1 or o_t.shape[0] != d:
+        raise ValueError(f"origin must have shape ({d},) or ({d}, ...), got {tuple(o_t.shape)}")
+    if o_t.ndim == 1:
+        o_t = o_t.reshape((d,) + (1,) * nd)
+    o_t = o_t[list(perm)]
+    try:
+        batch = tuple(np.broadcast_shapes(tuple(k_t.shape), tuple(eta_t.shape), tuple(cen_t.shape[1:-1]), tuple(rad_t.shape[:-1]),
+                                          tuple(o_t.shape[1:])))
+        batch = (1,) * (nd - len(batch)) + batch
+        full = tuple(np.broadcast_shapes(batch, tuple(dens_t.shape[:-2])))
+        if len(full) != nd:
+            raise ValueError
+    except ValueError as e:
+        raise ValueError("Shapes of origin[1:], the batch and the density are not broadcastable\n"
+                         f"tuple(origin.shape)={tuple(o_t.shape)}\ntuple(density.shape)={tuple(dens_t.shape)}\ntuple(k.shape)={tuple(k_t.shape)}") from e
+    axes = _RhsAxes.of(batch, full)
+    fl = _flatten(batch, torch.movedim(cen_t, 0, -1), rad_t, k_t, eta_t)
+    nb, B, nrhs = fl.nb, fl.B, axes.nrhs
+    obatched = int(any(s != 1 for s in o_t.shape[1:]))
+    of = (torch.movedim(o_t, 0, -1).expand(batch + (d,)).reshape(nb, d) if obatched else o_t.reshape(1, d)).contiguous()
+    out = _cluster_flat(tree, n_end, n_out, fl, of, obatched, axes.lay_out(dens_t.expand(full + (B, H))), dev, int(_stage))
+    return o_origin.give(axes.restore(out).contiguous())
+
+
+def _cluster_flat(tree: str, n_end: int, n_out: int, fl: _Flat, of: torch.Tensor, obatched: int, dens: torch.Tensor, dev: torch.device,
+                  stage: int = 0) -> torch.Tensor:
+    """biem_cluster_coefficients on flattened operands: the densities dens [nb, nrhs, B, H] of order n_end, the origins of [nb or 1, d] in
+    canonical axes; returns [nb, nrhs, H_out].  For n_out > n_end the density goes onto the axis of the larger plan by label."""
+    nb, B, nrhs = fl.nb, fl.B, int(dens.shape[1])
+    if n_out == n_end:
+        plan = _plan(tree, n_end, dev)
+        dens = dens.contiguous()
+    else:
+        plan, idx = _raised_layout(tree, n_end, n_out, dev)
+        small = dens
+        dens = torch.zeros((nb, nrhs, B, plan.H), dtype=torch.complex128, device=dev)
+        dens[..., idx] = small
+    out = torch.empty((nb, nrhs, plan.H), dtype=torch.complex128, device=dev)
+    lib = L.load()
+    with torch.cuda.device(dev):
+        wb = int(lib.biem_cluster_coefficients_workspace_bytes(plan.handle, nb, B, nrhs))
+        work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+        if nb > 0 and nrhs > 0:
+            rc = lib.biem_cluster_coefficients(plan.handle, nb, B, nrhs, n_end, _ptr(fl.k), _ptr(fl.eta), _ptr(fl.centers), _ptr(fl.radii),
+                                               fl.geom_batched, _ptr(of), obatched, _ptr(dens), _ptr(out), stage, _ptr(work), wb,
+                                               _stream_ptr(dev))
+            _check_built(lib, rc, "biem_cluster_coefficients")
+    return out
 
 
 def biem_far_pattern(res: Any, directions: Array, /, per_ball: bool = False) -> Array:

@@ -162,6 +162,23 @@ def multipole_source(c, /, *, k: Array, source: Array, index, n_end: int) -> Tup
     (u, grad u) with point_source's shapes: x of shape (c_ndim, ...(any), ...) gives (...(any), ...) and (c_ndim, ...(any), ...).  Both
     evaluate on the device through ``biem_multipole_field`` (the value kernels of the scattered field on one coefficient; the gradient by
     one step of the coefficient ladder in the plan of order n_end + 1)."""
+    return _expansion_term(c, k, source, index, n_end, "source", regular=False)
+
+
+def regular_wave(c, /, *, k: Array, origin: Array, index, n_end: int) -> Tuple[Callable[[Array], Array], Callable[[Array], Array]]:
+    r"""Regular wave :math:`u(x) = j_{n'}(k\|x - origin\|) Y_{h'}((x - origin)/\|x - origin\|)`, h' = ``index`` a position on the harmonic
+    axis of order ``n_end`` (:func:`harmonic_labels`): the basis in which every source-free solution of the Helmholtz equation is written
+    about ``origin`` (beams by their beam-shape coefficients, standing waves), and the incident field of
+    ``biem(regular_wave_origin=, regular_wave_index=)``.  Normalisation as :func:`multipole_source`, with the regular radial functions
+    j_n = sqrt(pi/2) J_{n+d/2-1}(z) / z^{d/2-1}.
+
+    Arguments, shapes and evaluation as :func:`multipole_source` (``biem_multipole_field`` with the kind-inner value kernels: the same
+    coefficient, the regular radial function).  The field is entire: ``x = origin`` is an ordinary point of value and gradient."""
+    return _expansion_term(c, k, origin, index, n_end, "origin", regular=True)
+
+
+def _expansion_term(c, k, source, index, n_end, sname: str, *, regular: bool):
+    """multipole_source (its argument `sname` = "source") and regular_wave ("origin", regular): one set of checks, one library entry."""
     tree, perm = canonical_tree(c.branching_types_expression_str)
     perm = list(perm)
     n_end = int(n_end)
@@ -174,13 +191,13 @@ def multipole_source(c, /, *, k: Array, source: Array, index, n_end: int) -> Tup
     if i_.size and (int(i_.min()) < 0 or int(i_.max()) >= H):
         raise ValueError(f"index must lie in [0, H) with H={H} harmonics of degree < n_end={n_end}, got values from {int(i_.min())} to {int(i_.max())}")
     if s_.ndim < 1 or s_.shape[0] != c.c_ndim:
-        raise ValueError(f"The first dimension of source must be c.c_ndim={c.c_ndim}, but got shape {tuple(s_.shape)}")
+        raise ValueError(f"The first dimension of {sname} must be c.c_ndim={c.c_ndim}, but got shape {tuple(s_.shape)}")
     if not _bshape_ok(tuple(k_.shape), tuple(s_.shape[1:])) or not _bshape_ok(tuple(i_.shape), tuple(s_.shape[1:])):
-        raise ValueError(f"Shapes of k, index and source[1:] are not broadcastable\n{tuple(k_.shape)=}\n{tuple(i_.shape)=}\n{tuple(s_.shape)=}")
+        raise ValueError(f"Shapes of k, index and {sname}[1:] are not broadcastable\n{tuple(k_.shape)=}\n{tuple(i_.shape)=}\n{tuple(s_.shape)=}")
     if s_.ndim != k_.ndim + 1:
-        raise ValueError(f"source.ndim={s_.ndim} is not k.ndim + 1={k_.ndim + 1}")
+        raise ValueError(f"{sname}.ndim={s_.ndim} is not k.ndim + 1={k_.ndim + 1}")
     nd = k_.ndim
-    raised: dict = {}                          # device index -> the indices on the axis of order n_end + 1 (the gradient's plan)
+    raised: dict = {}                         # device index -> the indices on the axis of order n_end + 1 (the gradient's plan)
 
     def _raised_index(dev) -> np.ndarray:
         key = dev.index
@@ -220,7 +237,8 @@ def multipole_source(c, /, *, k: Array, source: Array, index, n_end: int) -> Tup
         with torch.cuda.device(dev):
             wb = int(lib.biem_multipole_field_workspace_bytes(plan.handle, nb))
             work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
-            L.check(lib.biem_multipole_field(plan.handle, nb, P, _ptr(kf), _ptr(sf), _ptr(jf), _ptr(pts), L.USCAT_POINTS_BATCHED if batched else 0,
+            L.check(lib.biem_multipole_field(plan.handle, nb, P, _ptr(kf), _ptr(sf), _ptr(jf), _ptr(pts),
+                                             (L.USCAT_POINTS_BATCHED if batched else 0) | (L.USCAT_KIND_INNER if regular else 0),
                                              int(grad), _ptr(out), _ptr(work), wb, _stream_ptr(dev)), "biem_multipole_field")
         res = out.reshape(out_shape)
         if grad:

@@ -103,6 +103,13 @@ SIGNATURES = {
     "biem_solve_ms": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _ip, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_ldlt_ms": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _ip, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_factored_ms": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _ip, _dp, _vp, _sz, _vp]),
+    "biem_rhs_regular_wave_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "biem_rhs_regular_wave": (_i, [_vp, _i, _i, _i, _dp, _dp, _i, _dp, _dp, _i, _ip, _dp, _ll, _ll, _ll, _vp, _sz, _vp]),
+    "biem_solve_rw": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _ip, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_solve_ldlt_rw": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _ip, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_solve_factored_rw": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _ip, _dp, _vp, _sz, _vp]),
+    "biem_cluster_coefficients_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "biem_cluster_coefficients": (_i, [_vp, _i, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _dp, _i, _vp, _sz, _vp]),
     "biem_multipole_field_workspace_bytes": (_sz, [_vp, _i]),
     "biem_multipole_field": (_i, [_vp, _i, _i, _dp, _dp, _ip, _dp, _i, _i, _dp, _vp, _sz, _vp]),
     "biem_power": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp, _i, _dp, _dp, _dp, _dp, _dp, _vp]),

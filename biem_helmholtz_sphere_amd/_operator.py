@@ -407,7 +407,20 @@ class _MultipoleSources:
                                                                op.fl.geom_batched))
 
 
-_CLOSED_FORM = (_PlaneWaves, _PointSources, _MultipoleSources)
+@dataclass(frozen=True)
+class _RegularWaves(_MultipoleSources):
+    """Regular waves j_n'(k |x - o|) Y_h'((x - o)^) about the origins `pts` as the source of the right-hand sides, in closed form
+    (biem_rhs_regular_wave): the fields and layouts of _MultipoleSources, whose every use they share; the origins are unrestricted."""
+
+    suffix = "_rw"
+    rhs_entry = "biem_rhs_regular_wave"
+
+    def workspace_bytes(self, op: "_Operator", n: int) -> int:
+        return int(L.load().biem_rhs_regular_wave_workspace_bytes(op.plan.handle, n, op.fl.B, int(self.pts.shape[1]), self.batched,
+                                                                  op.fl.geom_batched))
+
+
+_CLOSED_FORM = (_PlaneWaves, _PointSources, _MultipoleSources)          # (_RegularWaves: a _MultipoleSources)
 
 
 def _check_closed_form(g, rc: int, what: str) -> None:
@@ -492,11 +505,12 @@ def _check_sources_outside(op: _Operator, pts: torch.Tensor, name: str = "point_
                          f"<= radius {float(fl.radii[s if fl.geom_batched else 0, b]):.17g}; {what} must lie strictly outside every ball")
 
 
-def _source_positions(op: _Operator, S: np.ndarray, name: str = "point_source_position"):
+def _source_positions(op: _Operator, S: np.ndarray, name: str = "point_source_position", outside: bool = True):
     """The checked positions S (c_ndim, ...) of the argument `name` laid out as [nb or 1, nrhs, d] in canonical axes, whether they differ
     between the systems, the _RhsAxes of the layout and the full batch shape, as _plane_wave_source.  Every source must lie strictly
     outside every ball (the expansion about a ball's centre converges only there, for kind "inner" and "outer" alike):
-    _check_sources_outside, before any library call."""
+    _check_sources_outside, before any library call - unless `outside` is False (the origins of regular waves lie anywhere: no check, no
+    synchronisation)."""
     batch = op.batch
     try:
         full = tuple(np.broadcast_shapes(batch, S.shape[1:]))
@@ -509,7 +523,8 @@ def _source_positions(op: _Operator, S: np.ndarray, name: str = "point_source_po
     t = torch.as_tensor(np.moveaxis(np.broadcast_to(S, (S.shape[0],) + full), 0, -1).copy(), device=op.dev)
     pts = axes.lay_out(t)                                             # [nb, nrhs, d]
     pts = pts if batched else pts[:1].contiguous()
-    _check_sources_outside(op, pts, name)
+    if outside:
+        _check_sources_outside(op, pts, name)
     return pts, batched, axes, full
 
 
@@ -519,27 +534,31 @@ def _point_source_source(op: _Operator, S: np.ndarray):
     return _PointSources(pts, batched, op.per_degree), axes
 
 
-def _check_multipole_source(c, k, n_end, position, index, uin, uin_grad, plane_wave_direction, point_source_position):
+def _check_multipole_source(c, k, n_end, position, index, uin, uin_grad, plane_wave_direction, point_source_position,
+                            pname: str = "multipole_source_position", iname: str = "multipole_source_index", others=()):
     """The checks of biem(multipole_source_position=, multipole_source_index=) that need no device; returns the positions (float64) and
-    the indices (int32, broadcast to the positions' trailing axes) on the host."""
+    the indices (int32, broadcast to the positions' trailing axes) on the host.  The pair (regular_wave_origin, regular_wave_index)
+    under its names `pname` / `iname` alike, `others` the further incidence arguments it excludes."""
     if position is None or index is None:
-        raise ValueError("multipole_source_position and multipole_source_index must be given together")
-    if uin is not None or uin_grad is not None or plane_wave_direction is not None or point_source_position is not None:
-        raise ValueError("multipole_source_position replaces uin / uin_grad / plane_wave_direction / point_source_position: give one source "
+        raise ValueError(f"{pname} and {iname} must be given together")
+    if (uin is not None or uin_grad is not None or plane_wave_direction is not None or point_source_position is not None
+            or any(o is not None for o in others)):
+        rest = "" if pname == "multipole_source_position" else " / multipole_source_position"
+        raise ValueError(f"{pname} replaces uin / uin_grad / plane_wave_direction / point_source_position{rest}: give one source "
                          "of the incident field, not several")
-    S = _check_source_position("multipole_source_position", c, k, position)
+    S = _check_source_position(pname, c, k, position)
     I = np.asarray(index) if isinstance(index, (int, np.integer)) and not isinstance(index, bool) else _host_array(index)
     if I.dtype.kind not in "iu":
-        raise ValueError(f"multipole_source_index must be an integer or an integer array, got dtype {I.dtype}")
+        raise ValueError(f"{iname} must be an integer or an integer array, got dtype {I.dtype}")
     H = _harm_n_ndim_le(int(n_end), c.c_ndim)
     if I.size and (int(I.min()) < 0 or int(I.max()) >= H):
-        raise ValueError(f"multipole_source_index must lie in [0, H) with H={H} harmonics of degree < n_end={int(n_end)}, "
+        raise ValueError(f"{iname} must lie in [0, H) with H={H} harmonics of degree < n_end={int(n_end)}, "
                          f"got values from {int(I.min())} to {int(I.max())}")
     try:
         I = np.broadcast_to(I, S.shape[1:])
     except ValueError as e:
-        raise ValueError("multipole_source_index is not broadcastable to multipole_source_position.shape[1:]\n"
-                         f"tuple(multipole_source_index.shape)={tuple(I.shape)}\ntuple(multipole_source_position.shape)={tuple(S.shape)}") from e
+        raise ValueError(f"{iname} is not broadcastable to {pname}.shape[1:]\n"
+                         f"tuple({iname}.shape)={tuple(I.shape)}\ntuple({pname}.shape)={tuple(S.shape)}") from e
     return S, I.astype(np.int32)
 
 
@@ -551,6 +570,16 @@ def _multipole_source_source(op: _Operator, checked):
     idx = axes.lay_out(torch.as_tensor(np.broadcast_to(I, full)[..., None].copy(), device=op.dev))[..., 0]      # [nb, nrhs]
     idx = (idx if batched else idx[:1]).to(torch.int32).contiguous()
     return _MultipoleSources(pts, batched, op.per_degree, idx), axes
+
+
+def _regular_wave_source(op: _Operator, checked):
+    """The source of the checked (origins O (c_ndim, ...), indices I O.shape[1:]) of regular waves and the _RhsAxes of its layout, as
+    _multipole_source_source without the containment check: the origin may lie anywhere, a ball's centre included."""
+    S, I = checked
+    pts, batched, axes, full = _source_positions(op, S, "regular_wave_origin", outside=False)
+    idx = axes.lay_out(torch.as_tensor(np.broadcast_to(I, full)[..., None].copy(), device=op.dev))[..., 0]      # [nb, nrhs]
+    idx = (idx if batched else idx[:1]).to(torch.int32).contiguous()
+    return _RegularWaves(pts, batched, op.per_degree, idx), axes
 
 
 def _nrhs(g) -> int:

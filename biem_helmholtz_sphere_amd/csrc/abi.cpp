@@ -650,6 +650,63 @@ int biem_solve_factored_ms(const biem_plan* plan, int nb, int B, int nrhs, const
                              (hipStream_t)stream);
 }
 
+// ---- regular-wave incidence in closed form (kernels_rhs_ms.hip, REG): the sixth source; the _ms entries with origins for sources ----
+size_t biem_rhs_regular_wave_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs, int origin_batched, int geom_batched) {
+  return plan ? rhs_multipole_workspace_bytes(plan, nb, B, nrhs, origin_batched, geom_batched) : 0;
+}
+
+int biem_rhs_regular_wave(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
+                          const double* d_tab, const double* d_origin, int origin_batched, const int* d_idx, double* d_f, long long sys_stride,
+                          long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_centers, "d_centers"); NEED(d_tab, "d_tab"); NEED(d_origin, "d_origin"); NEED(d_idx, "d_idx"); NEED(d_f, "d_f"); NEED(d_work, "d_work");
+  return closed_form_rhs(__func__, RhsSource::regular_waves(d_origin, d_idx, origin_batched, d_k, d_centers, geom_batched), plan, nb, B, nrhs, d_tab,
+                         d_f, sys_stride, elem_stride, rhs_stride, d_work, work_bytes, (hipStream_t)stream);
+}
+
+int biem_solve_rw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_origin, int origin_batched, const int* d_idx, double* d_density, int* d_info, int chunk, void* d_work,
+                  size_t work_bytes, void* stream) {
+  NEED(d_origin, "d_origin"); NEED(d_idx, "d_idx");
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    RhsSource::regular_waves(d_origin, d_idx, origin_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work,
+                    work_bytes, (hipStream_t)stream, false);
+}
+
+int biem_solve_ldlt_rw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                       const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                       const double* d_origin, int origin_batched, const int* d_idx, double* d_density, int* d_info, int chunk, void* d_work,
+                       size_t work_bytes, void* stream) {
+  NEED(d_origin, "d_origin"); NEED(d_idx, "d_idx");
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    RhsSource::regular_waves(d_origin, d_idx, origin_batched, d_k, d_centers, geom_batched), d_density, d_info, chunk, d_work,
+                    work_bytes, (hipStream_t)stream, true);
+}
+
+int biem_solve_factored_rw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k, const double* d_centers, int geom_batched, const double* d_alpha,
+                           const double* d_beta, int ab_batched, int per_degree, const double* d_origin, int origin_batched, const int* d_idx,
+                           double* d_density, void* d_work, size_t work_bytes, void* stream) {
+  NEED(d_origin, "d_origin"); NEED(d_idx, "d_idx");
+  return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                             RhsSource::regular_waves(d_origin, d_idx, origin_batched, d_k, d_centers, geom_batched), d_density, d_work,
+                             work_bytes, (hipStream_t)stream);
+}
+
+// ---- outgoing coefficients of the whole cluster about an origin (kernels_cluster.hip) ----
+size_t biem_cluster_coefficients_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs) {
+  return plan ? cluster_coefficients_workspace_bytes(plan, nb, B, nrhs) : 0;
+}
+
+int biem_cluster_coefficients(const biem_plan* plan, int nb, int B, int nrhs, int n_src, const double* d_k, const double* d_eta,
+                              const double* d_centers, const double* d_radii, int geom_batched, const double* d_origin, int origin_batched,
+                              const double* d_density, double* d_out, int stage, void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_eta, "d_eta"); NEED(d_centers, "d_centers"); NEED(d_radii, "d_radii"); NEED(d_origin, "d_origin");
+  NEED(d_density, "d_density"); NEED(d_out, "d_out"); NEED(d_work, "d_work");
+  return launch_cluster_coefficients(plan, nb, B, nrhs, n_src, d_k, d_eta, d_centers, d_radii, geom_batched, d_origin, origin_batched, d_density,
+                                     d_out, stage, d_work, work_bytes, (hipStream_t)stream);
+}
+
 // the field of the source itself (kernels_ladder.hip): what .uin, utotal and the powers of a closed-form call evaluate
 size_t biem_multipole_field_workspace_bytes(const biem_plan* plan, int nb) { return plan ? multipole_field_workspace_bytes(plan, nb) : 0; }
 

@@ -153,7 +153,23 @@ int launch_rhs_point_source(const biem_plan* p, int nb, int B, int nrhs, const d
 size_t rhs_multipole_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int src_batched, int geom_batched);
 int launch_rhs_multipole(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
                          const double* d_tab, const double* d_src, int src_batched, const int* d_idx, double* d_f, long long sys_stride,
-                         long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work);
+                         long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work,
+                         bool regular = false);
+// regular: the regular wave j_n'(k |x - o_r|) Y_h'((x - o_r)^) about the origins d_src instead, f = -gj_n (R|R)_{h'->h}(c_b - o_r): the same
+// kernels with the regular radial row, workspace and limits as above.  The origin is unrestricted; o_r = c_b gives (R|R)(0) = identity.
+// The two pieces the cluster coefficients (kernels_cluster.hip) share with it: (system, right-hand side) pairs per table slice under the
+// byte cap (BIEM_RHS_TABLE_BYTES), and the regular table rows T[row][H2] = C_d j_n''(k |t|) Y_l(t^) of the rows sr0 B .. of (pairs x balls),
+// t = c_b - src (flip: src - c_b)
+long long rhs_table_slice_pairs(const biem_plan* p, int nb, int B, int nrhs);
+int launch_regular_tables(const biem_plan* p, int B, int nrhs, long long sr0, long long rows, const double* d_k, const double* d_centers,
+                          int geom_batched, const double* d_src, int src_batched, int flip, double* d_T, hipStream_t st);
+// outgoing coefficients of the whole cluster about an origin (kernels_cluster.hip): A[s][r][h''] = sum_b sum_h (R|R)_{h->h''}(o_s - c_b) c[s][r][b][h],
+// c = density * blc.  d_density [nb][nrhs][B][H] in the plan's layout (degrees >= n_src are not read), d_origin [d] or (origin_batched) [nb][d],
+// d_out [nb][nrhs][H]; kind outer.  stage: 0 both, 1 the table rows only, 2 the contraction only (timing; slices then walk one stage)
+size_t cluster_coefficients_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs);
+int launch_cluster_coefficients(const biem_plan* p, int nb, int B, int nrhs, int n_src, const double* d_k, const double* d_eta,
+                                const double* d_centers, const double* d_radii, int geom_batched, const double* d_origin, int origin_batched,
+                                const double* d_density, double* d_out, int stage, void* d_work, size_t work_bytes, hipStream_t st);
 // d_info[s] = code for every system with a (ball, degree) whose symmetric scaling 1 / sqrt(gj gh) is not finite (gj = 0); others untouched
 // (biem_flag_unscalable exposes it for tests)
 int launch_flag_unscalable(const biem_plan* p, int nb, int B, const double* d_tab, int* d_info, int code, hipStream_t st);
@@ -210,7 +226,8 @@ int launch_uscat_hess(const biem_plan* p, int nb, int B, int P, const double* d_
                       double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
 // the field of the outgoing multipole h_n'(k |x - s|) Y_h'((x - s)^) at the points (kernels_ladder.hip): d_src [nb][d], d_idx [nb] into the
 // plan's harmonic axis; out [P][nb], or (grad) its Cartesian gradient [d][P][nb] - p is then a plan of order n' + 2 or more with its force
-// coupling table uploaded.  flags: BIEM_USCAT_POINTS_BATCHED only
+// coupling table uploaded.  flags: BIEM_USCAT_POINTS_BATCHED, and BIEM_USCAT_KIND_INNER for the regular wave j_n' Y_h' about d_src (the
+// kind-inner value kernels on the unit coefficient, the fictitious ball unbounded: every point is an ordinary one, x = d_src included)
 size_t multipole_field_workspace_bytes(const biem_plan* p, int nb);
 int launch_multipole_field(const biem_plan* p, int nb, int P, const double* d_k, const double* d_src, const int* d_idx, const double* d_points,
                            int flags, int grad, double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
@@ -276,10 +293,11 @@ struct BoundaryCoef {
 //   PLANE_WAVES    plane waves along pts = dirs in closed form (launch_rhs_plane_wave: no samples)
 //   POINT_SOURCES  point sources at pts = src in closed form (launch_rhs_point_source)
 //   MULTIPOLE_SOURCES  outgoing multipoles at pts = src of the harmonics idx in closed form (launch_rhs_multipole)
+//   REGULAR_WAVES  regular waves about the origins pts of the harmonics idx in closed form (launch_rhs_multipole, regular)
 // The closed forms read the wavenumbers, centres and ball tables of the call and keep their harmonics in `work`, work_bytes() of them:
 // the caller's workspace, or (set by the whole path) the tail of its own.
 struct RhsSource {
-  enum Kind { SAMPLES, SAMPLES_N, PLANE_WAVES, POINT_SOURCES, MULTIPOLE_SOURCES };
+  enum Kind { SAMPLES, SAMPLES_N, PLANE_WAVES, POINT_SOURCES, MULTIPOLE_SOURCES, REGULAR_WAVES };
   Kind kind;
   const double* g[2] = {nullptr, nullptr};                 // samples: g, or gu and gdn
   const double* pts = nullptr; int pts_batched = 0;        // closed forms: [nrhs][d], or (pts_batched) [nb][nrhs][d], in the plan's axes
@@ -301,8 +319,14 @@ struct RhsSource {
     s.idx = idx;
     return s;
   }
+  static RhsSource regular_waves(const double* origin, const int* idx, int batched, const double* k, const double* centers, int geom_batched) {
+    RhsSource s(REGULAR_WAVES, origin, batched, k, centers, geom_batched);
+    s.idx = idx;
+    return s;
+  }
 
-  bool closed_form() const { return kind == PLANE_WAVES || kind == POINT_SOURCES || kind == MULTIPOLE_SOURCES; }
+  bool translated() const { return kind == MULTIPOLE_SOURCES || kind == REGULAR_WAVES; }   // a column of the translation operator
+  bool closed_form() const { return kind == PLANE_WAVES || kind == POINT_SOURCES || translated(); }
   // the same source for the systems s0 .. of the call
   RhsSource at(const biem_plan* p, int s0, int nrhs, int B) const {
     RhsSource s = *this;
@@ -316,7 +340,7 @@ struct RhsSource {
   size_t work_bytes(const biem_plan* p, int nb, int B, int nrhs) const {
     return kind == PLANE_WAVES ? rhs_plane_wave_workspace_bytes(p, nb, nrhs, pts_batched)
          : kind == POINT_SOURCES ? rhs_point_source_workspace_bytes(p, nb, B, nrhs, pts_batched, geom_batched)
-         : kind == MULTIPOLE_SOURCES ? rhs_multipole_workspace_bytes(p, nb, B, nrhs, pts_batched, geom_batched) : 0;
+         : translated() ? rhs_multipole_workspace_bytes(p, nb, B, nrhs, pts_batched, geom_batched) : 0;
   }
   // what the closed forms cannot take (grid dimensions; the thread-local radial table of a (source, ball) pair): refused under the
   // caller's name `who` before anything is launched

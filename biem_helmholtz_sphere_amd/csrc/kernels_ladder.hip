@@ -81,17 +81,20 @@ int launch_uscat_hess(const biem_plan* p, int nb, int B, int P, const double* d_
 
 // ---- the field of an outgoing multipole h_n'(k |x - s|) Y_h'((x - s)^) itself: the scattered field of one fictitious ball per system at
 // s, radius 0, with the unit coefficient set delta_{h, idx}; its gradient: one ladder step per component, then the value kernels
-// (launch_uscat_hess's route taken once).  c[s][h] = delta_{h, idx[s]}; an index outside [0, H) leaves the set zero
-__global__ void __launch_bounds__(256) k_unit_coef(int H, long long count, const int* __restrict__ idx, cplx* __restrict__ c, double* __restrict__ zero_radii) {
+// (launch_uscat_hess's route taken once).  The regular wave j_n' Y_h' about s (BIEM_USCAT_KIND_INNER): the kind-inner value kernels on the
+// same unit set, the fictitious ball of infinite radius - kind inner masks r > rho only, so every point is an ordinary one, x = s included.
+// c[s][h] = delta_{h, idx[s]}; an index outside [0, H) leaves the set zero
+__global__ void __launch_bounds__(256) k_unit_coef(int H, long long count, const int* __restrict__ idx, cplx* __restrict__ c, double* __restrict__ radii,
+                                                    double radius) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
     const long long s = i / H;
     const int h = (int)(i - s * H);
     c[i] = make_double2(idx[s] == h ? 1.0 : 0.0, 0.0);
-    if (h == 0) zero_radii[s] = 0.0;
+    if (h == 0) radii[s] = radius;
   }
 }
 
-// workspace: the unit set, one laddered set, the radii (zero) of the fictitious balls
+// workspace: the unit set, one laddered set, the radii (zero; regular: infinite) of the fictitious balls
 size_t multipole_field_workspace_bytes(const biem_plan* p, int nb) {
   return nb <= 0 ? 0 : 2 * align256((size_t)nb * p->H * sizeof(cplx)) + align256((size_t)nb * sizeof(double));
 }
@@ -99,7 +102,7 @@ size_t multipole_field_workspace_bytes(const biem_plan* p, int nb) {
 int launch_multipole_field(const biem_plan* p, int nb, int P, const double* d_k, const double* d_src, const int* d_idx, const double* d_points,
                            int flags, int grad, double* d_out, void* d_work, size_t work_bytes, hipStream_t st) {
   const char* who = "biem_multipole_field";
-  if (flags & ~BIEM_USCAT_POINTS_BATCHED) { set_error("%s: flags other than BIEM_USCAT_POINTS_BATCHED (%d)", who, flags); return BIEM_ERR_ARG; }
+  if (flags & ~(BIEM_USCAT_POINTS_BATCHED | BIEM_USCAT_KIND_INNER)) { set_error("%s: flags other than BIEM_USCAT_POINTS_BATCHED and BIEM_USCAT_KIND_INNER (%d)", who, flags); return BIEM_ERR_ARG; }
   if (grad && p->n_end < 2) { set_error("%s: the gradient needs the plan of order n' + 2 of the source's degree n', at least 2 (n_end=%d)", who, p->n_end); return BIEM_ERR_ARG; }
   if (grad && !p->force_uploaded) { set_error("%s: the plan's force coupling table is not on the device", who); return BIEM_ERR_ARG; }
   if (nb > 65535) { set_error("%s: more than 65535 systems in one call (%d)", who, nb); return BIEM_ERR_UNSUPPORTED; }
@@ -116,7 +119,8 @@ int launch_multipole_field(const biem_plan* p, int nb, int P, const double* d_k,
   cplx* g = (cplx*)((char*)d_work + set);
   double* radii = (double*)((char*)d_work + 2 * set);
   const long long count = (long long)nb * p->H;
-  hipLaunchKernelGGL(k_unit_coef, dim3((unsigned)((count + 255) / 256 < 65536 ? (count + 255) / 256 : 65536)), dim3(256), 0, st, p->H, count, d_idx, c, radii);
+  hipLaunchKernelGGL(k_unit_coef, dim3((unsigned)((count + 255) / 256 < 65536 ? (count + 255) / 256 : 65536)), dim3(256), 0, st, p->H, count, d_idx, c, radii,
+                     (flags & BIEM_USCAT_KIND_INNER) ? (double)INFINITY : 0.0);
   BIEM_LAUNCHCHK();
   if (!grad) return uscat_eval_coef(p, nb, 1, P, d_k, d_src, radii, 1, c, d_points, flags, d_out, st);
   const size_t per = (size_t)P * nb * 2;                     // doubles of one component of the result

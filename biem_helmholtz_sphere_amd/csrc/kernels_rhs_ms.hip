@@ -18,6 +18,12 @@
 //
 // Nothing here tests |t| > rho: a source on or inside a sphere gives finite values that mean nothing, t = 0 gives non-finite ones.  An
 // index outside [0, H) gives NaN in its column and reads nothing.  Every element of f is written by one lane, without atomics.
+//
+// Regular waves: u_in(x) = j_n'(k |x - o|) Y_h'((x - o)^) about an origin o is the same column with the regular radial row,
+//   f(s, r, b, h) = -gj_{n(h)}(s, b) (R|R)_{h'_r->h}(c_b - o_r),   (R|R) = (S|R) with j_n'' for h_n'' in T (tree a: J for H in Graf's term):
+// the same kernels with REG = true.  The origin is unrestricted: at t = 0 (o on a centre, the common case) the row is formed from
+// j_l(0) = delta_{l0} j_0(0) and a fixed unit vector, so (R|R)(0) is the identity with exact zeros off the diagonal.
+// launch_regular_tables hands the table stage to the cluster coefficients (kernels_cluster.hip), which take t from the other end (flip).
 #include "common.hpp"
 #include <climits>
 #include <cstdlib>
@@ -34,31 +40,50 @@ __device__ inline MsRow ms_row(long long row, long long sr0, int B, int nrhs) {
   const long long sr = sr0 + row / B;
   return {sr / nrhs, (int)(sr % nrhs), (int)(row % B)};
 }
-// t = c_b - s_r (the sign of a pair table's c_b - c_b'; k_ps_geometry has s - c)
+// t = c_b - s_r (the sign of a pair table's c_b - c_b'; k_ps_geometry has s - c); flip: t = s_r - c_b
 __device__ inline void ms_displacement(const MsRow& w, int d, int B, int nrhs, const double* __restrict__ centers, int geom_batched,
-                                       const double* __restrict__ src, int src_batched, double* t, double* dist) {
+                                       const double* __restrict__ src, int src_batched, double* t, double* dist, bool flip = false) {
   const double* c = centers + ((geom_batched ? w.s * B : 0) + w.b) * d;
   const double* x = src + ((src_batched ? w.s * nrhs : 0) + w.r) * d;
   double r2 = 0.0;
-  for (int i = 0; i < d; ++i) { t[i] = c[i] - x[i]; r2 += t[i] * t[i]; }
+  for (int i = 0; i < d; ++i) { t[i] = flip ? x[i] - c[i] : c[i] - x[i]; r2 += t[i] * t[i]; }
   *dist = sqrt(r2);
+}
+// the radial row of a table at z = k |t|, orders 0 .. nmax, by one lane.  REG: the regular functions alone (sH is not written); at
+// |t| = 0 they are j_l(0) = delta_{l0} j_0(0), written as such - the recurrences divide by z
+template <bool REG>
+__device__ inline void ms_radial_row(int d, int nmax, cplx kk, double dist, cplx* sJ, cplx* sH) {
+  if (REG && dist == 0.0) {
+    const double z0 = radial_z0_at_zero(d);
+    for (int n = 0; n <= nmax; ++n) sJ[n] = make_double2(n == 0 ? z0 : 0.0, 0.0);
+    return;
+  }
+  radial_jh(d, nmax, cscale(kk, dist), sJ, REG ? nullptr : sH);
+}
+// |t| = 0 has no direction: any fixed unit vector does (its harmonics are finite, and only degree 0 meets a nonzero radial value)
+__device__ inline void ms_unit_if_zero(int d, double dist, double* t) {
+  if (dist == 0.0) { t[0] = 1.0; for (int i = 1; i < d; ++i) t[i] = 0.0; }
 }
 
 // plain table rows T[row][H2] = C_d h_n''(k_s |t|) Y_l(t^) of the rows [0, rows) of a slice: one workgroup per row (strided), lane 0 runs the
-// radial recurrence into LDS, then one label per lane, every label from scratch (k_pair_tables' generic branch; chain trees: chain_harmonic)
+// radial recurrence into LDS, then one label per lane, every label from scratch (k_pair_tables' generic branch; chain trees: chain_harmonic).
+// REG: j_n'' for h_n'' (regular waves; the cluster coefficients, which take the displacement from the other end: flip)
+template <bool REG>
 __global__ void __launch_bounds__(256) k_ms_tables(int tree, int d, int n2, int H2, double Cd, const int* __restrict__ labels2,
                                                     const int* __restrict__ deg2, int B, int nrhs, long long sr0, long long rows,
                                                     const cplx* __restrict__ k, const double* __restrict__ centers, int geom_batched,
-                                                    const double* __restrict__ src, int src_batched, cplx* __restrict__ T) {
-  __shared__ cplx sJ[kMaxRad * 2 + 6], sH[kMaxRad * 2 + 6];
+                                                    const double* __restrict__ src, int src_batched, int flip, cplx* __restrict__ T) {
+  __shared__ cplx sJ[kMaxRad * 2 + 6], sH[REG ? 1 : kMaxRad * 2 + 6];
   __shared__ double sC[kChainDimMax], sS[kChainDimMax], sPhi;
+  const cplx* sR = REG ? sJ : sH;
   for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
     const MsRow w = ms_row(row, sr0, B, nrhs);
     double t[kChainDimMax], dist;
-    ms_displacement(w, d, B, nrhs, centers, geom_batched, src, src_batched, t, &dist);
+    ms_displacement(w, d, B, nrhs, centers, geom_batched, src, src_batched, t, &dist, flip != 0);
+    if (REG) ms_unit_if_zero(d, dist, t);
     __syncthreads();                                      // the previous row's tables are no longer read
     if (threadIdx.x == 0) {
-      radial_jh(d, n2 - 1, cscale(k[w.s], dist), sJ, sH);
+      ms_radial_row<REG>(d, n2 - 1, k[w.s], dist, sJ, sH);
       if (tree == TREE_CHAIN) { double phi; chain_angles(d, t, sC, sS, &phi); sPhi = phi; }
     }
     __syncthreads();
@@ -67,14 +92,14 @@ __global__ void __launch_bounds__(256) k_ms_tables(int tree, int d, int n2, int 
       for (int l = threadIdx.x; l < H2; l += 256) {
         double re, im;
         chain_harmonic(d, labels2 + (size_t)l * (d - 1), sC, sS, sPhi, &re, &im);
-        out[l] = cmul(cscale(sH[deg2[l]], Cd), make_double2(re, im));
+        out[l] = cmul(cscale(sR[deg2[l]], Cd), make_double2(re, im));
       }
     } else {
       const Dir dir = make_dir(tree, t);
       for (int l = threadIdx.x; l < H2; l += 256) {
         double re, im;
         harmonic_single(tree, labels2[3 * l], labels2[3 * l + 1], labels2[3 * l + 2], dir, &re, &im);
-        out[l] = cmul(cscale(sH[deg2[l]], Cd), make_double2(re, im));
+        out[l] = cmul(cscale(sR[deg2[l]], Cd), make_double2(re, im));
       }
     }
   }
@@ -110,19 +135,22 @@ __global__ void __launch_bounds__(256) k_rhs_ms(int H, int H2, int n_end, int B,
 
 __device__ inline double sign_even(int e) { return ((e / 2) & 1) ? -1.0 : 1.0; }      // i^e for even e (either sign)
 
-// tree a: one workgroup per (s, r, b) (strided), the radial row h_j(k_s |t|), j < 2 n_end - 1, in LDS, one harmonic per lane
+// tree a: one workgroup per (s, r, b) (strided), the radial row h_j(k_s |t|) (REG: j_j), j < 2 n_end - 1, in LDS, one harmonic per lane
+template <bool REG>
 __global__ void __launch_bounds__(256) k_rhs_ms_2d(int n_end, int H, double Cd, const int* __restrict__ labels, int B, int nrhs, long long rows,
                                                     const cplx* __restrict__ k, const double* __restrict__ centers, int geom_batched,
                                                     const double* __restrict__ src, int src_batched, const int* __restrict__ idx,
                                                     const cplx* __restrict__ tab, cplx* __restrict__ f, long long sys_stride,
                                                     long long elem_stride, long long rhs_stride, const int* __restrict__ hpos, SplitMap sm) {
-  __shared__ cplx sJ[kMaxRad * 2 + 6], sH[kMaxRad * 2 + 6];
+  __shared__ cplx sJ[kMaxRad * 2 + 6], sH[REG ? 1 : kMaxRad * 2 + 6];
+  const cplx* sR = REG ? sJ : sH;
   for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
     const MsRow w = ms_row(row, 0, B, nrhs);
     double t[2], dist;
     ms_displacement(w, 2, B, nrhs, centers, geom_batched, src, src_batched, t, &dist);
+    if (REG) ms_unit_if_zero(2, dist, t);
     __syncthreads();
-    if (threadIdx.x == 0) radial_jh(2, 2 * n_end - 2, cscale(k[w.s], dist), sJ, sH);
+    if (threadIdx.x == 0) ms_radial_row<REG>(2, 2 * n_end - 2, k[w.s], dist, sJ, sH);
     __syncthreads();
     const double phi = atan2(t[1], t[0]);
     const int hp = idx[(src_batched ? w.s * nrhs : 0) + w.r];
@@ -135,7 +163,7 @@ __global__ void __launch_bounds__(256) k_rhs_ms_2d(int n_end, int H, double Cd, 
       double sn, cs;
       sincos((double)mu * phi, &sn, &cs);
       // T'[j] = C_2 h_j / sqrt(2 pi) times the phase, times i^{|m| + |mu| - |m'|} / sqrt(2 pi): k_fill2d's entry
-      const cplx raw = cscale(cmul(cscale(sH[j], Cd * kInvSqrt2Pi), make_double2(cs, sn)), sign_even(am + j - amp) * kInvSqrt2Pi);
+      const cplx raw = cscale(cmul(cscale(sR[j], Cd * kInvSqrt2Pi), make_double2(cs, sn)), sign_even(am + j - amp) * kInvSqrt2Pi);
       const cplx v = ok ? cscale(cmul(gj[am], raw), -1.0) : make_double2(nan(""), nan(""));
       fs[sm.rhs_off(w.b, H, hpos ? hpos[h] : h, elem_stride)] = v;
     }
@@ -156,6 +184,16 @@ long long ms_slice_pairs(const biem_plan* p, int nb, int B, int nrhs) {
 }
 }  // namespace
 
+long long rhs_table_slice_pairs(const biem_plan* p, int nb, int B, int nrhs) { return ms_slice_pairs(p, nb, B, nrhs); }
+
+int launch_regular_tables(const biem_plan* p, int B, int nrhs, long long sr0, long long rows, const double* d_k, const double* d_centers,
+                          int geom_batched, const double* d_src, int src_batched, int flip, double* d_T, hipStream_t st) {
+  hipLaunchKernelGGL(k_ms_tables<true>, dim3(strided_grid(rows)), dim3(256), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2, p->d_deg2,
+                     B, nrhs, sr0, rows, (const cplx*)d_k, d_centers, geom_batched, d_src, src_batched, flip, (cplx*)d_T);
+  BIEM_LAUNCHCHK();
+  return BIEM_OK;
+}
+
 size_t rhs_multipole_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int src_batched, int geom_batched) {
   (void)src_batched; (void)geom_batched;                 // (the wavenumber differs between the systems: a table row per system always)
   if (nb <= 0 || B <= 0 || nrhs <= 0 || p->tree == TREE_A) return 0;
@@ -164,17 +202,19 @@ size_t rhs_multipole_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs
 
 int launch_rhs_multipole(const biem_plan* p, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
                          const double* d_tab, const double* d_src, int src_batched, const int* d_idx, double* d_f, long long sys_stride,
-                         long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work) {
-  if (nrhs < 1) { set_error("biem_rhs_multipole: nrhs < 1"); return BIEM_ERR_ARG; }
+                         long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, void* d_work,
+                         bool regular) {
+  const char* who = regular ? "biem_rhs_regular_wave" : "biem_rhs_multipole";
+  if (nrhs < 1) { set_error("%s: nrhs < 1", who); return BIEM_ERR_ARG; }
   // (nb, nrhs <= 65535, the order limits and the term lists: RhsSource::check has refused the rest)
   if (nb <= 0 || B <= 0) return BIEM_OK;
   const int H = p->H;
   const long long pairs = (long long)nb * nrhs;
-  if (pairs * B > INT_MAX) { set_error("biem_rhs_multipole: %lld (source, ball) pairs in one call, at most %d", pairs * B, INT_MAX); return BIEM_ERR_ARG; }
+  if (pairs * B > INT_MAX) { set_error("%s: %lld (source, ball) pairs in one call, at most %d", who, pairs * B, INT_MAX); return BIEM_ERR_ARG; }
   ProfScope ps(PK_RHS, st, 0.0);
   const int* hpos = slot_order ? p->d_hpos : nullptr;
   if (p->tree == TREE_A) {
-    hipLaunchKernelGGL(k_rhs_ms_2d, dim3(strided_grid(pairs * B)), dim3(256), 0, st, p->n_end, H, p->Cd, p->d_labels, B, nrhs, pairs * B,
+    hipLaunchKernelGGL(regular ? k_rhs_ms_2d<true> : k_rhs_ms_2d<false>, dim3(strided_grid(pairs * B)), dim3(256), 0, st, p->n_end, H, p->Cd, p->d_labels, B, nrhs, pairs * B,
                        (const cplx*)d_k, d_centers, geom_batched, d_src, src_batched, d_idx, (const cplx*)d_tab, (cplx*)d_f, sys_stride,
                        elem_stride, rhs_stride, hpos, split);
     BIEM_LAUNCHCHK();
@@ -184,8 +224,8 @@ int launch_rhs_multipole(const biem_plan* p, int nb, int B, int nrhs, const doub
   cplx* T = (cplx*)d_work;
   for (long long sr0 = 0; sr0 < pairs; sr0 += slice) {
     const long long rows = (pairs - sr0 < slice ? pairs - sr0 : slice) * B;
-    hipLaunchKernelGGL(k_ms_tables, dim3(strided_grid(rows)), dim3(256), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2, p->d_deg2, B,
-                       nrhs, sr0, rows, (const cplx*)d_k, d_centers, geom_batched, d_src, src_batched, T);
+    hipLaunchKernelGGL(regular ? k_ms_tables<true> : k_ms_tables<false>, dim3(strided_grid(rows)), dim3(256), 0, st, p->tree, p->d, p->n2, p->H2,
+                       p->Cd, p->d_labels2, p->d_deg2, B, nrhs, sr0, rows, (const cplx*)d_k, d_centers, geom_batched, d_src, src_batched, 0, T);
     BIEM_LAUNCHCHK();
     hipLaunchKernelGGL(k_rhs_ms, dim3(strided_grid((rows * H + 255) / 256)), dim3(256), 0, st, H, p->H2, p->n_end, B, nrhs, sr0, rows * H, d_idx,
                        src_batched, p->d_ptr, p->d_coef, p->d_tidx16, p->d_deg, T, (const cplx*)d_tab, (cplx*)d_f, sys_stride, elem_stride,

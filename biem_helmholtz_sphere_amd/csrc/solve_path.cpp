@@ -167,10 +167,11 @@ int RhsSource::check(const char* who, const biem_plan* p, int nb, int nrhs) cons
     set_error("%s: n_end=%d exceeds the built table size %d of the point-source right-hand side", who, p->n_end, kMaxRad);
     return BIEM_ERR_UNSUPPORTED;
   }
-  if (kind == MULTIPOLE_SOURCES) {
+  if (translated()) {
     // tree a: the radial row of a (source, ball) pair in LDS, orders < 2 n_end - 1; every other tree: the term lists, built up to half that
     if (p->tree == TREE_A ? p->n_end > kMaxRad : 2 * p->n_end > kMaxRad) {
-      set_error("%s: n_end=%d exceeds the built table size %d of the multipole right-hand side", who, p->n_end, p->tree == TREE_A ? kMaxRad : kMaxRad / 2);
+      set_error("%s: n_end=%d exceeds the built table size %d of the %s right-hand side", who, p->n_end, p->tree == TREE_A ? kMaxRad : kMaxRad / 2,
+                kind == REGULAR_WAVES ? "regular-wave" : "multipole");
       return BIEM_ERR_UNSUPPORTED;
     }
     if (p->tree != TREE_A && (!p->lists_built || p->ptr.empty() || !p->d_ptr)) {
@@ -196,8 +197,9 @@ int RhsSource::launch(const biem_plan* p, int nb, int B, int nrhs, const Boundar
       return launch_rhs_point_source(p, nb, B, nrhs, k, centers, geom_batched, d_tab, pts, pts_batched, d_f, sys_stride, elem_stride,
                                      rhs_stride, st, slot_order, split, work);
     case MULTIPOLE_SOURCES:
+    case REGULAR_WAVES:
       return launch_rhs_multipole(p, nb, B, nrhs, k, centers, geom_batched, d_tab, pts, pts_batched, idx, d_f, sys_stride, elem_stride,
-                                  rhs_stride, st, slot_order, split, work);
+                                  rhs_stride, st, slot_order, split, work, kind == REGULAR_WAVES);
   }
   return BIEM_ERR_ARG;
 }

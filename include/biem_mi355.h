@@ -519,12 +519,53 @@ int biem_solve_factored_ms(const biem_plan* plan, int nb, int B, int nrhs, const
                            const double* d_alpha, const double* d_beta, int ab_batched, int per_degree, const double* d_src,
                            int src_batched, const int* d_idx, double* d_density, void* d_work, size_t work_bytes, void* stream);
 /* The field of such a source itself, u(x) = h_n'(k_s |x - s_s|) Y_h'((x - s_s)^), one source per system: d_src [nb][d], d_idx [nb] (an
- * index into the harmonic axis of `plan`), points and flags as biem_uscat (BIEM_USCAT_POINTS_BATCHED only); out [P][nb] complex128.
- * grad != 0: the Cartesian gradient in the plan's axes, out [d][P][nb]; `plan` is then a plan of order n' + 2 or more (its force
- * coupling table is built on the first such call).  Every tree the value kernels of biem_uscat cover, the chains included. */
+ * index into the harmonic axis of `plan`), points and flags as biem_uscat (BIEM_USCAT_POINTS_BATCHED, BIEM_USCAT_KIND_INNER); out [P][nb]
+ * complex128.  grad != 0: the Cartesian gradient in the plan's axes, out [d][P][nb]; `plan` is then a plan of order n' + 2 or more (its
+ * force coupling table is built on the first such call).  Every tree the value kernels of biem_uscat cover, the chains included.
+ * BIEM_USCAT_KIND_INNER: the regular wave j_n'(k_s |x - o_s|) Y_h'((x - o_s)^) about o = d_src instead (the incident field of
+ * biem_rhs_regular_wave); x = o is an ordinary point. */
 size_t biem_multipole_field_workspace_bytes(const biem_plan* plan, int nb);
 int biem_multipole_field(biem_plan* plan, int nb, int P, const double* d_k /*c128*/, const double* d_src, const int* d_idx,
                          const double* d_points, int flags, int grad, double* d_out, void* d_work, size_t work_bytes, void* stream);
+
+/* ---- regular-wave incidence in closed form: the basis of every source-free incident field.  u_in(x) =
+ *      j_n'(k |x - o|) Y_h'((x - o)^) about an origin o, expanded about the centre of ball b with t = c_b - o, is the same column with
+ *      the regular radial function in the table row:
+ *        u_in(c_b + r) = sum_h (R|R)_{h'->h}(t) j_n(k |r|) Y_h(r^),   f(s, r, b, h) = -gj_{n(h)}(s, b) (R|R)_{h'_r->h}(c_b - o_r).
+ *      Arguments, layouts, limits, workspace and slicing (BIEM_RHS_TABLE_BYTES) are those of biem_rhs_multipole with d_origin for d_src.
+ *      The origin is unrestricted - outside the balls, inside one, or exactly on a centre, where (R|R)(0) is the identity: that ball's
+ *      block is -gj_n delta_{h h'} with exact zeros off the diagonal.  Nothing is non-finite for any origin.  biem_solve_rw /
+ *      biem_solve_ldlt_rw / biem_solve_factored_rw: the _ms entries. ---- */
+size_t biem_rhs_regular_wave_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs, int origin_batched, int geom_batched);
+int biem_rhs_regular_wave(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_centers,
+                          int geom_batched, const double* d_tab, const double* d_origin, int origin_batched, const int* d_idx, double* d_f,
+                          long long sys_stride, long long elem_stride, long long rhs_stride, void* d_work, size_t work_bytes, void* stream);
+int biem_solve_rw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_origin, int origin_batched, const int* d_idx, double* d_density, int* d_info, int chunk, void* d_work,
+                  size_t work_bytes, void* stream);
+int biem_solve_ldlt_rw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta,
+                       const double* d_centers, const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta,
+                       int ab_batched, int per_degree, const double* d_origin, int origin_batched, const int* d_idx, double* d_density,
+                       int* d_info, int chunk, void* d_work, size_t work_bytes, void* stream);
+int biem_solve_factored_rw(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k /*c128*/, const double* d_centers, int geom_batched,
+                           const double* d_alpha, const double* d_beta, int ab_batched, int per_degree, const double* d_origin,
+                           int origin_batched, const int* d_idx, double* d_density, void* d_work, size_t work_bytes, void* stream);
+
+/* ---- the cluster's outgoing coefficients about an origin: the scattered field of all balls as one expansion,
+ *        u_scat(x) = sum_h'' A_h'' h_n''(k |x - o|) Y_h''((x - o)^)  for |x - o| > max_b (|c_b - o| + rho_b),
+ *        A[s][r][h''] = sum_b sum_h (R|R)_{h->h''}(o_s - c_b) c[s][r][b][h],   c = density * blc (biem_uscat's coefficients).
+ *      kind outer.  d_density [nb][nrhs][B][H] on the harmonic axis of `plan`; entries of degree >= n_src (1 <= n_src <= n_end) are not
+ *      read: a density of order n_src placed by label on the axis of a plan of larger order gives the expansion up to that order.
+ *      d_origin [d], or [nb][d] with origin_batched != 0, in the plan's axes; d_out [nb][nrhs][H] complex128.  Every element is written
+ *      by one lane in a fixed order of summation: two calls, any table slicing (BIEM_RHS_TABLE_BYTES) and any nrhs give the same bits
+ *      per right-hand side.  stage: 0; 1 / 2 run the table rows / the contraction alone (timing).  Limits and errors as
+ *      biem_rhs_multipole (n_end above 320 in 2-D, above 160 elsewhere: BIEM_ERR_UNSUPPORTED). ---- */
+size_t biem_cluster_coefficients_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs);
+int biem_cluster_coefficients(const biem_plan* plan, int nb, int B, int nrhs, int n_src, const double* d_k /*c128*/, const double* d_eta,
+                              const double* d_centers, const double* d_radii, int geom_batched, const double* d_origin, int origin_batched,
+                              const double* d_density, double* d_out, int stage, void* d_work, size_t work_bytes, void* stream);
 
 /* ---- cross sections: extinction and absorbed power per ball from what the solve already has (no second solve, no
  *      matrix, no workspace).  Real k only, in the far-field normalisation u_scat ~ F(x^) e^{ikr} / r^{(d-1)/2}: "power" is
