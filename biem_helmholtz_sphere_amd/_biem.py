@@ -27,9 +27,10 @@ from ._arrays import Array, _host_array, _ptr, _stream_ptr
 from ._coords import canonical_tree
 from ._fields import (USCAT_GRAD_N_END_MAX, _cluster_flat, biem_cluster_coefficients, biem_far_pattern, biem_u, biem_u_grad, biem_u_hess, biem_u_interior, biem_u_interior_grad,
                       biem_u_total, biem_u_total_grad)
-from ._incident import fluid_inclusion_bc, harmonic_labels, max_memory, max_n_end, multipole_source, plane_wave, point_source, regular_wave
+from ._incident import (fluid_inclusion_bc, harmonic_labels, max_memory, max_n_end, multipole_expansion, multipole_source, plane_wave,
+                        plane_wave_coefficients, point_source, regular_expansion, regular_wave)
 from ._observables import BIEMPower, biem_force, biem_power
-from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_closed_form, _check_incident, _check_multipole_source,
+from ._operator import (_Operator, _RhsAxes, _ball_tables, _boundary_samples, _check_closed_form, _check_expansion, _check_incident, _check_multipole_source, _expansion_source,
                         _check_plane_wave_direction, _multipole_source_source, _regular_wave_source, _RegularWaves,
                         _check_point_source_position, _entry, _factored_source_args, _nrhs, _operator, _pick_systems, _plane_wave_source,
                         _point_source_source, _rhs_project, _sample_ptrs, _source_entry, _source_workspace_bytes, _validate_biem_inputs, _warn_biem_inputs)
@@ -49,7 +50,8 @@ __all__ = [
     "BIEMFactorization", "BIEMKwargs", "BIEMPower", "BIEMResultCalculator", "BIEMResultCalculatorProtocol", "UinCallable", "biem",
     "biem_factorize", "biem_far_pattern", "biem_force", "biem_power", "biem_u", "biem_u_grad", "biem_u_hess", "biem_u_interior",
     "biem_u_interior_grad", "biem_u_total", "biem_u_total_grad", "fluid_inclusion_bc", "harmonic_labels", "max_memory", "max_n_end",
-    "multipole_source", "plane_wave", "point_source", "regular_wave", "biem_cluster_coefficients",
+    "multipole_source", "plane_wave", "point_source", "regular_wave", "biem_cluster_coefficients", "regular_expansion",
+    "multipole_expansion", "plane_wave_coefficients",
 ]
 
 _last_solve_stats: dict = {}   # how the last biem() call solved its systems (tests / bench)
@@ -217,10 +219,22 @@ def _result(op: _Operator, uin, density_t: Optional[torch.Tensor], axes: Optiona
 # the solver (reference :453-819)
 # --------------------------------------------------------------------------------------
 def _closed_form_request(c, k, n_end, uin, uin_grad, plane_wave_direction, point_source_position, multipole_source_position=None,
-                         multipole_source_index=None, regular_wave_origin=None, regular_wave_index=None):
+                         multipole_source_index=None, regular_wave_origin=None, regular_wave_index=None, regular_wave_coefficients=None,
+                         multipole_source_coefficients=None):
     """The checks of plane_wave_direction / point_source_position / the multipole_source pair / the regular_wave pair that need no
     device.  None without any, else (argument name, the checked array on the host - multipoles and regular waves: the pair (positions,
-    indices) -, the argument as the caller passed it)."""
+    indices), with coefficients the triple (positions, coefficients, n_in) -, the argument as the caller passed it)."""
+    if regular_wave_coefficients is not None:
+        checked = _check_expansion(c, k, regular_wave_origin, regular_wave_coefficients, regular_wave_index,
+                                   (uin, uin_grad, plane_wave_direction, point_source_position, multipole_source_position,
+                                    multipole_source_index, multipole_source_coefficients),
+                                   "regular_wave_origin", "regular_wave_coefficients", "regular_wave_index")
+        return "regular_wave_coefficients", checked, regular_wave_origin
+    if multipole_source_coefficients is not None:
+        checked = _check_expansion(c, k, multipole_source_position, multipole_source_coefficients, multipole_source_index,
+                                   (uin, uin_grad, plane_wave_direction, point_source_position, regular_wave_origin, regular_wave_index),
+                                   "multipole_source_position", "multipole_source_coefficients", "multipole_source_index")
+        return "multipole_source_coefficients", checked, multipole_source_position
     if regular_wave_origin is not None or regular_wave_index is not None:
         checked = _check_multipole_source(c, k, n_end, regular_wave_origin, regular_wave_index, uin, uin_grad, plane_wave_direction,
                                           point_source_position, "regular_wave_origin", "regular_wave_index",
@@ -247,6 +261,12 @@ def _incident_source(op: _Operator, uin, uin_grad, closed=None):
         _check_incident(op, uin, uin_grad)
         return _boundary_samples(op, uin, uin_grad) + (uin,)
     name, checked, given = closed
+    if name in ("regular_wave_coefficients", "multipole_source_coefficients"):
+        regular = name == "regular_wave_coefficients"
+        arg = given if isinstance(given, torch.Tensor) and given.is_floating_point() else checked[0]
+        field = (regular_expansion(op.c, k=op.k_given, origin=arg, coefficients=checked[1]) if regular
+                 else multipole_expansion(op.c, k=op.k_given, source=arg, coefficients=checked[1]))
+        return _expansion_source(op, checked, regular) + (field[0],)
     if name == "regular_wave_origin":
         arg = given if isinstance(given, torch.Tensor) and given.is_floating_point() else checked[0]
         return _regular_wave_source(op, checked) + (regular_wave(op.c, k=op.k_given, origin=arg, index=checked[1], n_end=op.n_end)[0],)
@@ -359,7 +379,8 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
          alpha_n: Array | None = None, beta_n: Array | None = None, plane_wave_direction: Array | None = None,
          point_source_position: Array | None = None, multipole_source_position: Array | None = None,
          multipole_source_index: Array | int | None = None, regular_wave_origin: Array | None = None,
-         regular_wave_index: Array | int | None = None) -> BIEMResultCalculator:
+         regular_wave_index: Array | int | None = None, regular_wave_coefficients: Array | None = None,
+         multipole_source_coefficients: Array | None = None) -> BIEMResultCalculator:
     r"""Boundary Integral Equation Method (BIEM) for the Helmholtz equation on MI355X.
 
     Same contract as the reference ``biem`` (``_biem.py:453-581``): solves, per leading batch element,
@@ -403,15 +424,28 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     ``Y_0 = |S^{d-1}|^{-1/2}``.  The right-hand side is exact, ``f = -gj_n (S|R)_{h'->h}(c_b - s)``: a column of the translation operator
     the matrix is filled with, where the projection of samples aliases as for a point source, worse with every degree.  The axes behave
     as those of point_source_position, every source must lie strictly outside every ball (``ValueError``), ``.uin`` is
-    multipole_source's callable.  A general multipole (a dipole along an arbitrary axis) is a linear combination: pass its harmonics as
-    right-hand sides and combine the densities.  ``NotImplementedError`` for n_end > 320 in 2-D and n_end > 160 elsewhere.
+    multipole_source's callable.  A general multipole (a dipole along an arbitrary axis) is a linear combination: pass its
+    coefficients, ``multipole_source_coefficients`` below.  ``NotImplementedError`` for n_end > 320 in 2-D and n_end > 160 elsewhere.
 
     ``regular_wave_origin`` / ``regular_wave_index`` (extension, given together, with the shapes and rules of the multipole pair; not
     together with any other incidence argument): the incident field is the regular wave ``j_n'(k |x - o|) Y_h'((x - o)^)`` about the
     origin ``o``, :func:`regular_wave` - the basis in which every source-free incident field (a beam given by its beam-shape
     coefficients, a standing wave) is written.  The right-hand side is exact, ``f = -gj_n (R|R)_{h'->h}(c_b - o)``.  The origin is
-    unrestricted: outside the balls, inside one, or exactly on a ball's centre (nothing is checked, nothing synchronises).  Combine
-    the densities of the harmonics with the field's coefficients; ``fac.tmatrix()`` does so for all of them at once.
+    unrestricted: outside the balls, inside one, or exactly on a ball's centre (nothing is checked, nothing synchronises).  A field of
+    several harmonics: ``regular_wave_coefficients`` below; ``fac.tmatrix()`` solves all of them at once.
+
+    ``regular_wave_origin`` / ``regular_wave_coefficients`` and ``multipole_source_position`` / ``multipole_source_coefficients``
+    (extension; the coefficients in place of the index of the same pair, not together with any other incidence argument): the incident
+    field is the whole expansion ``sum_h' p_h' j_n'(k |x - o|) Y_h'((x - o)^)`` (``h_n'`` about the source for the multipole pair) -
+    :func:`regular_expansion` / :func:`multipole_expansion` -, one right-hand side for a beam, a standing wave or the near field of a
+    neighbouring cluster, ``f = -gj_n sum_h' p_h' (R|R)_{h'->h}(c_b - o)``: one solve where the index pair takes one per harmonic, and
+    the only way to ``force()`` of such a field, which is quadratic in it.  The coefficients P are complex of shape
+    ``O.shape[1:] + (H_in,)`` up to broadcasting, the last axis along ``harmonic_labels(c, n_in)``; ``n_in`` is inferred from ``H_in``
+    and is independent of ``n_end`` (a beam about the cluster's origin wants ``n_in`` of the order of ``k R_cluster``).  Trailing axes of
+    O and of P on which the operator has size 1 are right-hand sides; an origin without such axes under coefficients with them is shared
+    by all right-hand sides, whose translation tables are then formed once.  Sources must lie strictly outside every ball
+    (``ValueError``), regular origins anywhere.  ``.uin`` is the expansion's callable.  ``NotImplementedError`` for max(n_in, n_end) above
+    320 in 2-D and above 160 elsewhere.
 
     Solver: the reference passes every system to a general dense solve (``_biem.py:797``).  Here the system is first brought
     to its complex-symmetric form (real harmonics, symmetric scaling) and factored as U^T U (Cholesky-type, no conjugation)
@@ -422,7 +456,8 @@ def biem(c: Any, /, *, centers: Array, radii: Array, k: Array, n_end: int, alpha
     if translational_coefficients_method not in (None, "gumerov", "plane_wave", "triplet"):
         raise ValueError(f"Invalid translational_coefficients_method: {translational_coefficients_method}")
     closed = _closed_form_request(c, k, n_end, uin, uin_grad, plane_wave_direction, point_source_position, multipole_source_position,
-                                  multipole_source_index, regular_wave_origin, regular_wave_index)
+                                  multipole_source_index, regular_wave_origin, regular_wave_index, regular_wave_coefficients,
+                                  multipole_source_coefficients)
     op = _operator(c, centers, radii, k, n_end, alpha, beta, eta, kind, alpha_n, beta_n)
     lib = L.load()
     plan, fl, dev = op.plan, op.fl, op.dev
@@ -521,19 +556,22 @@ class BIEMFactorization:
     def solve(self, *, uin: Callable[[Array], Array] | None = None, uin_grad: Callable[[Array], Array] | None = None,
               plane_wave_direction: Array | None = None, point_source_position: Array | None = None,
               multipole_source_position: Array | None = None, multipole_source_index: Array | int | None = None,
-              regular_wave_origin: Array | None = None, regular_wave_index: Array | int | None = None) -> BIEMResultCalculator:
+              regular_wave_origin: Array | None = None, regular_wave_index: Array | int | None = None,
+              regular_wave_coefficients: Array | None = None, multipole_source_coefficients: Array | None = None) -> BIEMResultCalculator:
         """Densities of the incident field (uin, uin_grad), or of plane waves along ``plane_wave_direction`` or of point sources at
         ``point_source_position`` (the monopoles ``h_0(k |x - s|)``, strictly outside every ball) in closed form, against the stored
         factors: ``biem()``'s result for the same field.  Many source positions against one factorisation are right-hand sides of one
         call: a trailing axis of the argument on which the operator has size 1.  ``multipole_source_position`` with
         ``multipole_source_index`` (given together): the outgoing multipoles ``h_n'(k |x - s|) Y_h'((x - s)^)`` in closed form, as in
         :func:`biem`.  ``regular_wave_origin`` with ``regular_wave_index``: the regular waves ``j_n'(k |x - o|) Y_h'((x - o)^)`` about
-        any origin, as in :func:`biem`."""
+        any origin, as in :func:`biem`.  ``regular_wave_coefficients`` / ``multipole_source_coefficients`` in place of the index of their
+        pair: the whole expansion as one right-hand side, as in :func:`biem`."""
         if self._closed:
             raise ValueError("BIEMFactorization is closed")
         op, lib = self._op, L.load()
         closed = _closed_form_request(op.c, op.k_given, op.n_end, uin, uin_grad, plane_wave_direction, point_source_position,
-                                      multipole_source_position, multipole_source_index, regular_wave_origin, regular_wave_index)
+                                      multipole_source_position, multipole_source_index, regular_wave_origin, regular_wave_index,
+                                      regular_wave_coefficients, multipole_source_coefficients)
         plan, fl, dev = op.plan, op.fl, op.dev
         B, H, nb = fl.B, plan.H, fl.nb
         has_rhs = not (uin is None and uin_grad is None and closed is None)

@@ -20,9 +20,9 @@ from dataclasses import dataclass
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbiem_mi355.so")
-SOURCES = ["abi.cpp", "solve_path.cpp", "plan.cpp", "plan_tree.cpp", "plan_fill.cpp", "kernels_tables.hip", "kernels_fill.hip", "kernels_fill_sym.hip", "kernels_rhs.hip", "kernels_rhs_pw.hip", "kernels_rhs_ps.hip", "kernels_rhs_ms.hip", "kernels_cluster.hip", "kernels_uscat.hip", "kernels_uinterior.hip", "kernels_power.hip", "kernels_force.hip", "kernels_ladder.hip",
+SOURCES = ["abi.cpp", "solve_path.cpp", "plan.cpp", "plan_tree.cpp", "plan_fill.cpp", "kernels_tables.hip", "kernels_fill.hip", "kernels_fill_sym.hip", "kernels_rhs.hip", "kernels_rhs_pw.hip", "kernels_rhs_ps.hip", "kernels_rhs_ms.hip", "kernels_rhs_ex.hip", "kernels_cluster.hip", "kernels_uscat.hip", "kernels_uinterior.hip", "kernels_power.hip", "kernels_force.hip", "kernels_ladder.hip",
            "kernels_gemm3m.hip", "kernels_lu.hip", "kernels_sym.hip", "kernels_trisolve.hip"]
-HEADERS = ["common.hpp", "plan.hpp", "plan_build.hpp", "special.hpp", "fast_layout.hpp", "fill.hpp", "dense.hpp", os.path.join("..", "..", "include", "biem_mi355.h")]
+HEADERS = ["common.hpp", "plan.hpp", "plan_build.hpp", "special.hpp", "fast_layout.hpp", "fill.hpp", "dense.hpp", "rhs_translate.hpp", os.path.join("..", "..", "include", "biem_mi355.h")]
 _MARK = b"BIEM_SRC_HASH="
 
 

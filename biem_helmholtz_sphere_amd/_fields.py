@@ -14,7 +14,7 @@ from . import _lib as L
 from ._arrays import Array, _Origin, _host_array, _inverse_perm, _is_complex, _ptr, _result_origin, _shape, _stacked, _stream_ptr, _to_dev
 from ._coords import canonical_tree, n_end_from_harm
 from ._operator import _Flat, _RhsAxes, _flatten
-from ._plans import _Plan, _plan
+from ._plans import _Plan, _label_positions, _plan
 
 
 # --------------------------------------------------------------------------------------
@@ -356,10 +356,8 @@ def biem_u_total_grad(res: Any, x: Array, /, *, k_interior: Array, density_ratio
 def _raised_layout(tree: str, n_end: int, n_out: int, dev: torch.device) -> Tuple[_Plan, torch.Tensor]:
     """The plan of order n_out >= n_end and, per harmonic of the order-n_end plan, its place on that plan's axis, matched by label (the
     axis of a larger order does not begin with the smaller one, as _hess_layout)."""
-    big, small = _plan(tree, n_out, dev), _plan(tree, n_end, dev)
-    where = {tuple(lab) + (int(n),): i for i, (lab, n) in enumerate(zip(big.labels.tolist(), big.degrees.tolist()))}
-    idx = [where[tuple(lab) + (int(n),)] for lab, n in zip(small.labels.tolist(), small.degrees.tolist())]
-    return big, torch.as_tensor(idx, dtype=torch.long, device=big.dev)
+    big = _plan(tree, n_out, dev)
+    return big, torch.as_tensor(_label_positions(tree, n_end, n_out, dev), dtype=torch.long, device=big.dev)
 
 
 def biem_cluster_coefficients(res: Any, /, *, origin: Array | None = None, n_out: int | None = None, _stage: int = 0) -> Array:

@@ -9,8 +9,8 @@ import torch
 
 from . import _lib as L
 from ._arrays import Array, _bshape_ok, _compute_device, _host_array, _inverse_perm, _is_complex, _like, _ptr, _stream_ptr, _to_dev
-from ._coords import canonical_tree
-from ._plans import _plan
+from ._coords import canonical_tree, harm_count
+from ._plans import _label_positions, _plan
 
 
 # --------------------------------------------------------------------------------------
@@ -177,35 +177,132 @@ def regular_wave(c, /, *, k: Array, origin: Array, index, n_end: int) -> Tuple[C
     return _expansion_term(c, k, origin, index, n_end, "origin", regular=True)
 
 
+def regular_expansion(c, /, *, k: Array, origin: Array, coefficients: Array) -> Tuple[Callable[[Array], Array], Callable[[Array], Array]]:
+    r"""The source-free field :math:`u(x) = \sum_{h'} p_{h'} j_{n'}(k\|x - o\|) Y_{h'}((x - o)/\|x - o\|)` about ``origin`` o: a beam by its
+    beam-shape coefficients, a standing wave, a plane wave by :func:`plane_wave_coefficients` - the incident field of
+    ``biem(regular_wave_origin=, regular_wave_coefficients=)``.  ``coefficients`` is complex of shape ``origin.shape[1:] + (H_in,)`` up to
+    broadcasting, the last axis along ``harmonic_labels(c, n_in)``; ``n_in`` is inferred from ``H_in`` (a length that is no harmonic
+    count of the tree: ``ValueError``).  Normalisation as :func:`regular_wave`.
+
+    Returns (u, grad u) with the shapes of :func:`regular_wave`, evaluated on the device through ``biem_expansion_field`` (the value
+    kernels of the scattered field on the coefficient vector; the gradient by one step of the coefficient ladder in the plan of order
+    n_in + 1).  The field is entire: ``x = origin`` is an ordinary point."""
+    return _expansion_sum(c, k, origin, coefficients, "origin", regular=True)
+
+
+def multipole_expansion(c, /, *, k: Array, source: Array, coefficients: Array) -> Tuple[Callable[[Array], Array], Callable[[Array], Array]]:
+    r"""The outgoing field :math:`u(x) = \sum_{h'} p_{h'} h_{n'}(k\|x - s\|) Y_{h'}((x - s)/\|x - s\|)` radiated from ``source`` s: a general
+    multipole, the field of a neighbouring cluster by its ``cluster_coefficients`` - the incident field of
+    ``biem(multipole_source_position=, multipole_source_coefficients=)``.  Arguments, shapes and evaluation as
+    :func:`regular_expansion`, normalisation as :func:`multipole_source`."""
+    return _expansion_sum(c, k, source, coefficients, "source", regular=False)
+
+
+def plane_wave_coefficients(c, /, *, k: Array, direction: Array, origin: Array, n_in: int) -> Array:
+    r"""Regular coefficients of the plane wave ``e^{i k d.x}`` about ``origin`` o, truncated at order ``n_in``:
+    :math:`p_h = C_d\, i^{n} \overline{Y_h(\hat d)}\, e^{i k \hat d\cdot o}`, ``C_d = (2 pi)^{d/2} sqrt(2 / pi)`` (4 pi in 3-D), along
+    ``harmonic_labels(c, n_in)``; the harmonics by ``biem_harmonics`` on the device.  k has shape (...), direction and origin
+    (c_ndim, ...); the result has shape ``direction.shape[1:] + (H_in,)`` broadcast against k and origin, complex128, a tensor where
+    any input is one, else NumPy.  A beam given by its angular spectrum is a weighted sum of such vectors; the truncation drops what the
+    wave holds in degrees >= n_in, of size ``(k R / 2)^{n_in} / n_in!`` at distance R from o."""
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    n_in = int(n_in)
+    if n_in < 1:
+        raise ValueError(f"n_in must be positive, got {n_in}")
+    tens = [a for a in (direction, origin, k) if isinstance(a, torch.Tensor)]
+    dev = _compute_device(tens[0].device if tens else None)
+    dt, ot, kt = _to_dev(direction, dev, torch.float64), _to_dev(origin, dev, torch.float64), _to_dev(k, dev, torch.complex128)
+    d = c.c_ndim
+    if dt.ndim < 1 or dt.shape[0] != d or ot.ndim < 1 or ot.shape[0] != d:
+        raise ValueError(f"The first dimension of direction and origin must be c.c_ndim={d}, but got shapes {tuple(dt.shape)} and {tuple(ot.shape)}")
+    try:
+        shape = tuple(torch.broadcast_shapes(tuple(dt.shape[1:]), tuple(ot.shape[1:]), tuple(kt.shape)))
+    except RuntimeError as e:
+        raise ValueError(f"Shapes of k, direction[1:] and origin[1:] are not broadcastable\n{tuple(kt.shape)=}\n{tuple(dt.shape)=}\n{tuple(ot.shape)=}") from e
+    dh = dt / torch.linalg.vector_norm(dt, dim=0, keepdim=True)
+    dirs = torch.movedim(dh[list(perm)], 0, -1).contiguous().reshape(-1, d)              # canonical axes, [count, d]
+    plan = _plan(tree, n_in, dev)
+    Y = torch.empty((dirs.shape[0], plan.H), dtype=torch.complex128, device=dev)
+    if dirs.shape[0] > 0:
+        with torch.cuda.device(dev):
+            L.check(L.load().biem_harmonics(plan.handle, int(dirs.shape[0]), _ptr(dirs), _ptr(Y), _stream_ptr(dev)), "biem_harmonics")
+    Cd = (2.0 * math.pi) ** (d / 2.0) * math.sqrt(2.0 / math.pi)
+    phase = torch.as_tensor(1j ** (np.asarray(plan.degrees) % 4), dtype=torch.complex128, device=dev)   # (exact powers of i)
+    ot = ot.reshape((d,) + (1,) * (dh.ndim - ot.ndim) + tuple(ot.shape[1:])) if ot.ndim < dh.ndim else ot
+    p = Cd * phase * torch.conj(Y).reshape(tuple(dt.shape[1:]) + (plan.H,)) * torch.exp(1j * kt * torch.sum(dh * ot, dim=0))[..., None]
+    p = p.expand(shape + (plan.H,)).contiguous()
+    return p.to(tens[0].device) if tens else p.cpu().numpy()
+
+
+def _harmonic_order(c, H_in: int, name: str) -> int:
+    """The order n_in whose harmonic axis has H_in entries; ValueError naming the nearest valid lengths otherwise."""
+    tree = canonical_tree(c.branching_types_expression_str)[0]
+    n = 1
+    while harm_count(tree, n) < H_in:
+        n += 1
+    if H_in < 1 or harm_count(tree, n) != H_in:
+        below = f"{harm_count(tree, n - 1)} (n_in={n - 1}) and " if n > 1 and H_in >= 1 else ""
+        raise ValueError(f"the last axis of {name} has length {H_in}, which is no harmonic count of the tree: the nearest valid lengths are "
+                         f"{below}{harm_count(tree, n)} (n_in={n}); the axis runs along harmonic_labels(c, n_in)")
+    return n
+
+
 def _expansion_term(c, k, source, index, n_end, sname: str, *, regular: bool):
     """multipole_source (its argument `sname` = "source") and regular_wave ("origin", regular): one set of checks, one library entry."""
-    tree, perm = canonical_tree(c.branching_types_expression_str)
-    perm = list(perm)
     n_end = int(n_end)
-    k_ = k if isinstance(k, torch.Tensor) else np.asarray(k)
-    s_ = source if isinstance(source, torch.Tensor) else np.asarray(source, dtype=np.float64)
     i_ = np.asarray(index) if isinstance(index, (int, np.integer)) else _host_array(index)
     if i_.dtype.kind not in "iu":
         raise ValueError(f"index must be an integer or an integer array, got dtype {i_.dtype}")
     H = _harm_n_ndim_le(n_end, c.c_ndim)
     if i_.size and (int(i_.min()) < 0 or int(i_.max()) >= H):
         raise ValueError(f"index must lie in [0, H) with H={H} harmonics of degree < n_end={n_end}, got values from {int(i_.min())} to {int(i_.max())}")
+    tree = canonical_tree(c.branching_types_expression_str)[0]
+
+    def operand(dev, grad: bool, batch, nb):
+        """The indices on the axis of the plan the field runs in: of order n_end, for the gradient of order n_end + 1 (by label)."""
+        idx = _label_positions(tree, n_end, n_end + 1, dev)[i_] if grad else i_
+        return torch.as_tensor(np.ascontiguousarray(np.broadcast_to(idx, batch)).reshape(nb).astype(np.int32), device=dev)
+
+    return _expansion_field(c, k, source, tuple(i_.shape), "index", n_end, sname, regular, "biem_multipole_field", operand)
+
+
+def _expansion_sum(c, k, source, coefficients, sname: str, *, regular: bool):
+    """regular_expansion and multipole_expansion: _expansion_term's checks and evaluation with a coefficient vector for the index."""
+    tree = canonical_tree(c.branching_types_expression_str)[0]
+    pshape = tuple(coefficients.shape) if isinstance(coefficients, torch.Tensor) else tuple(np.shape(coefficients))
+    if len(pshape) < 1:
+        raise ValueError(f"coefficients must have shape {sname}.shape[1:] + (H_in,), got a scalar")
+    n_in = _harmonic_order(c, int(pshape[-1]), "coefficients")
+
+    def operand(dev, grad: bool, batch, nb):
+        """The coefficient vectors [nb, H] on the axis of the plan the field runs in (the gradient: order n_in + 1, placed by label)."""
+        pt = _to_dev(coefficients, dev, torch.complex128)
+        pt = pt.reshape((1,) * (len(batch) + 1 - pt.ndim) + tuple(pt.shape)).expand(tuple(batch) + (pshape[-1],)).reshape(nb, pshape[-1])
+        if not grad:
+            return pt.contiguous()
+        out = torch.zeros((nb, _plan(tree, n_in + 1, dev).H), dtype=torch.complex128, device=dev)
+        out[:, torch.as_tensor(_label_positions(tree, n_in, n_in + 1, dev), device=dev)] = pt
+        return out
+
+    return _expansion_field(c, k, source, pshape[:-1], "coefficients[:-1]", n_in, sname, regular, "biem_expansion_field", operand)
+
+
+def _expansion_field(c, k, source, ishape, iname: str, n_end: int, sname: str, regular: bool, entry: str, operand):
+    """(u, grad u) of a field about `source` whose operand - an index per system (biem_multipole_field) or a coefficient vector
+    (biem_expansion_field), of leading shape `ishape`, made by `operand(dev, grad, batch, nb)` on the axis of order n_end, the gradient's
+    n_end + 1 - takes the place of the density in the value kernels."""
+    tree, perm = canonical_tree(c.branching_types_expression_str)
+    perm = list(perm)
+    k_ = k if isinstance(k, torch.Tensor) else np.asarray(k)
+    s_ = source if isinstance(source, torch.Tensor) else np.asarray(source, dtype=np.float64)
     if s_.ndim < 1 or s_.shape[0] != c.c_ndim:
         raise ValueError(f"The first dimension of {sname} must be c.c_ndim={c.c_ndim}, but got shape {tuple(s_.shape)}")
-    if not _bshape_ok(tuple(k_.shape), tuple(s_.shape[1:])) or not _bshape_ok(tuple(i_.shape), tuple(s_.shape[1:])):
-        raise ValueError(f"Shapes of k, index and {sname}[1:] are not broadcastable\n{tuple(k_.shape)=}\n{tuple(i_.shape)=}\n{tuple(s_.shape)=}")
-    if s_.ndim != k_.ndim + 1:
-        raise ValueError(f"{sname}.ndim={s_.ndim} is not k.ndim + 1={k_.ndim + 1}")
+    if not _bshape_ok(tuple(k_.shape), tuple(s_.shape[1:])) or not _bshape_ok(tuple(ishape), tuple(s_.shape[1:])):
+        raise ValueError(f"Shapes of k, {iname} and {sname}[1:] are not broadcastable\n{tuple(k_.shape)=}\n{tuple(ishape)=}\n{tuple(s_.shape)=}")
+    if s_.ndim != k_.ndim + 1 or len(ishape) > k_.ndim:
+        raise ValueError(f"{sname}.ndim={s_.ndim} is not k.ndim + 1={k_.ndim + 1}" if s_.ndim != k_.ndim + 1 else
+                         f"{iname} has {len(ishape)} axes, more than k.ndim={k_.ndim}")
     nd = k_.ndim
-    raised: dict = {}                         # device index -> the indices on the axis of order n_end + 1 (the gradient's plan)
-
-    def _raised_index(dev) -> np.ndarray:
-        key = dev.index
-        if key not in raised:
-            small, big = _plan(tree, n_end, dev), _plan(tree, n_end + 1, dev)
-            where = {tuple(lab) + (int(n),): j for j, (lab, n) in enumerate(zip(big.labels.tolist(), big.degrees.tolist()))}
-            raised[key] = np.array([where[tuple(lab) + (int(n),)] for lab, n in zip(small.labels.tolist(), small.degrees.tolist())], dtype=np.int64)
-        return raised[key][i_]
 
     def _field(x, grad: bool):
         was_np = not isinstance(x, torch.Tensor)
@@ -218,17 +315,16 @@ def _expansion_term(c, k, source, index, n_end, sname: str, *, regular: bool):
         lead, xb = tuple(xt.shape[1:xt.ndim - nd]), tuple(xt.shape[xt.ndim - nd:])
         st = _to_dev(s_, dev, torch.float64)
         kt = _to_dev(k_, dev, torch.complex128)
-        batch = tuple(np.broadcast_shapes(tuple(kt.shape), tuple(st.shape[1:]), xb))
+        batch = tuple(np.broadcast_shapes(tuple(kt.shape), tuple(st.shape[1:]), xb, tuple(ishape)))
         nb, P = math.prod(batch), math.prod(lead)
         out_shape = ((d,) if grad else ()) + lead + batch
         if nb == 0 or P == 0:
             res = torch.empty(out_shape, dtype=torch.complex128, device=dev)
             return res.cpu().numpy() if was_np else res.to(back)
         plan = _plan(tree, n_end + 1 if grad else n_end, dev)
-        idx = _raised_index(dev) if grad else i_
         kf = kt.expand(batch).reshape(nb).contiguous()
         sf = torch.movedim(st[perm], 0, -1).expand(batch + (d,)).reshape(nb, d).contiguous()
-        jf = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(idx, batch)).reshape(nb).astype(np.int32), device=dev)
+        jf = operand(dev, grad, batch, nb)
         xp = xt[perm]
         batched = any(n != 1 for n in xb)
         pts = (xp.expand((d,) + lead + batch).reshape(d, P, nb) if batched else xp.reshape(d, P)).contiguous()
@@ -237,9 +333,9 @@ def _expansion_term(c, k, source, index, n_end, sname: str, *, regular: bool):
         with torch.cuda.device(dev):
             wb = int(lib.biem_multipole_field_workspace_bytes(plan.handle, nb))
             work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
-            L.check(lib.biem_multipole_field(plan.handle, nb, P, _ptr(kf), _ptr(sf), _ptr(jf), _ptr(pts),
-                                             (L.USCAT_POINTS_BATCHED if batched else 0) | (L.USCAT_KIND_INNER if regular else 0),
-                                             int(grad), _ptr(out), _ptr(work), wb, _stream_ptr(dev)), "biem_multipole_field")
+            L.check(getattr(lib, entry)(plan.handle, nb, P, _ptr(kf), _ptr(sf), _ptr(jf), _ptr(pts),
+                                        (L.USCAT_POINTS_BATCHED if batched else 0) | (L.USCAT_KIND_INNER if regular else 0),
+                                        int(grad), _ptr(out), _ptr(work), wb, _stream_ptr(dev)), entry)
         res = out.reshape(out_shape)
         if grad:
             res = res[_inverse_perm(perm)]                                          # canonical component i is the caller's perm[i]

@@ -108,6 +108,12 @@ SIGNATURES = {
     "biem_solve_rw": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _ip, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_ldlt_rw": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _ip, _dp, _ip, _i, _vp, _sz, _vp]),
     "biem_solve_factored_rw": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _ip, _dp, _vp, _sz, _vp]),
+    "biem_rhs_expansion_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "biem_rhs_expansion": (_i, [_vp, _i, _i, _i, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _vp, _ip, _i, _i, _dp, _ll, _ll, _ll, _i, _vp, _sz, _vp]),
+    "biem_solve_ex": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _i, _dp, _i, _vp, _ip, _i, _i, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_solve_ldlt_ex": (_i, [_vp, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _i, _dp, _i, _vp, _ip, _i, _i, _dp, _ip, _i, _vp, _sz, _vp]),
+    "biem_solve_factored_ex": (_i, [_vp, _i, _i, _i, _dp, _ll, _ll, _dp, _dp, _dp, _i, _dp, _dp, _i, _i, _dp, _i, _i, _dp, _i, _vp, _ip, _i, _i, _dp, _vp, _sz, _vp]),
+    "biem_expansion_field": (_i, [_vp, _i, _i, _dp, _dp, _dp, _dp, _i, _i, _dp, _vp, _sz, _vp]),
     "biem_cluster_coefficients_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "biem_cluster_coefficients": (_i, [_vp, _i, _i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp, _i, _dp, _dp, _i, _vp, _sz, _vp]),
     "biem_multipole_field_workspace_bytes": (_sz, [_vp, _i]),

@@ -13,8 +13,8 @@ import torch
 from . import _lib as L
 from ._arrays import _Origin, _host_array, _inverse_perm, _is_complex, _origin_of, _ptr, _shape, _to_dev
 from ._coords import canonical_tree
-from ._incident import _harm_n_ndim_le
-from ._plans import _Plan, _plan
+from ._incident import _harm_n_ndim_le, _harmonic_order
+from ._plans import _Plan, _label_positions, _plan
 
 
 # --------------------------------------------------------------------------------------
@@ -420,12 +420,45 @@ class _RegularWaves(_MultipoleSources):
                                                                   op.fl.geom_batched))
 
 
-_CLOSED_FORM = (_PlaneWaves, _PointSources, _MultipoleSources)          # (_RegularWaves: a _MultipoleSources)
+@dataclass(frozen=True)
+class _Expansion:
+    """A whole expansion sum_h' p_h' z_n' Y_h' about the origins `pts` (z = j: regular, any origin; z = h: outgoing, origins outside the
+    balls) as the source of the right-hand sides, in closed form (biem_rhs_expansion).  pts [nb or 1, n_origin, d] in canonical axes,
+    n_origin 1 (one origin for all right-hand sides of a system) or nrhs; coef [nb or 1, nrhs, H_list] complex128 along the axis of the
+    list plan `lists`, of order max(n_in, n_end); index_map int32 [H]: where the operator's harmonics lie on that axis."""
+
+    pts: torch.Tensor
+    batched: int
+    per_degree: bool
+    coef: torch.Tensor
+    coef_batched: int
+    lists: Any
+    index_map: torch.Tensor
+    n_in: int
+    regular: bool
+    suffix = "_ex"
+    rhs_entry = "biem_rhs_expansion"
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.pts
+
+    def workspace_bytes(self, op: "_Operator", n: int) -> int:
+        return int(L.load().biem_rhs_expansion_workspace_bytes(self.lists.handle, n, op.fl.B, int(self.pts.shape[1])))
+
+    def source_args(self, s0: int = 0) -> tuple:
+        """What the `_ex` entries take after per_degree, from system s0 on."""
+        return (_ptr(self.pts[s0:] if self.batched else self.pts), self.batched, int(self.pts.shape[1]),
+                _ptr(self.coef[s0:] if self.coef_batched else self.coef), self.coef_batched, self.lists.handle, _ptr(self.index_map),
+                self.n_in, int(self.regular))
+
+
+_CLOSED_FORM = (_PlaneWaves, _PointSources, _MultipoleSources, _Expansion)          # (_RegularWaves: a _MultipoleSources)
 
 
 def _check_closed_form(g, rc: int, what: str) -> None:
     """L.check; for point and multipole sources BIEM_ERR_UNSUPPORTED (the order limits of their tables) as NotImplementedError."""
-    if isinstance(g, (_PointSources, _MultipoleSources)) and rc == L.BIEM_ERR_UNSUPPORTED:
+    if isinstance(g, (_PointSources, _MultipoleSources, _Expansion)) and rc == L.BIEM_ERR_UNSUPPORTED:
         msg = L.load().biem_last_error()
         raise NotImplementedError(msg.decode() if msg else f"{what}: not built for this order")
     L.check(rc, what)
@@ -582,9 +615,77 @@ def _regular_wave_source(op: _Operator, checked):
     return _RegularWaves(pts, batched, op.per_degree, idx), axes
 
 
+def _check_expansion(c, k, position, coefficients, index, others, pname: str, cname: str, iname: str):
+    """The checks of biem(regular_wave_origin=, regular_wave_coefficients=) and of the multipole_source pair under their names that need no
+    device; `others`: every further incidence argument, all of which the pair excludes.  Returns the positions on the host as float64,
+    the coefficients as given and the order n_in of their last axis."""
+    if index is not None:
+        raise ValueError(f"{cname} replaces {iname}: give the index of one harmonic or the coefficients of all, not both")
+    if any(o is not None for o in others):
+        raise ValueError(f"{cname} replaces uin / uin_grad / plane_wave_direction / point_source_position and the other closed forms: give one "
+                         "source of the incident field, not several")
+    if position is None:
+        raise ValueError(f"{pname} and {cname} must be given together")
+    S = _check_source_position(pname, c, k, position)
+    pshape = _shape(coefficients)
+    kind = coefficients.dtype if isinstance(coefficients, torch.Tensor) else np.asarray(coefficients).dtype
+    if isinstance(kind, torch.dtype) and not (kind.is_complex or kind.is_floating_point) or not isinstance(kind, torch.dtype) and kind.kind not in "iufc":
+        raise ValueError(f"{cname} must be a complex (or real) array, got dtype {kind}")
+    if len(pshape) < 1:
+        raise ValueError(f"{cname} must have shape {pname}.shape[1:] + (H_in,), got a scalar")
+    n_in = _harmonic_order(c, int(pshape[-1]), cname)
+    try:
+        lead = np.broadcast_shapes(tuple(S.shape[1:]), tuple(pshape[:-1]))
+        ok = len(lead) == S.ndim - 1
+    except ValueError:
+        ok = False
+    if not ok:
+        raise ValueError(f"{cname}.shape[:-1] is not broadcastable with {pname}.shape[1:]\n"
+                         f"tuple({cname}.shape)={tuple(pshape)}\ntuple({pname}.shape)={tuple(S.shape)}")
+    return S, coefficients, n_in
+
+
+def _expansion_source(op: _Operator, checked, regular: bool):
+    """The source of the checked (origins S (c_ndim, ...), coefficients P (..., H_in), n_in) and the _RhsAxes of its layout: trailing axes
+    of S and of P on which the operator has size 1 are right-hand sides; where S has size 1 on all of them the origin is shared.  The
+    coefficients go onto the axis of the list plan by label."""
+    S, P, n_in = checked
+    pname, cname = ("regular_wave_origin", "regular_wave_coefficients") if regular else ("multipole_source_position", "multipole_source_coefficients")
+    batch, dev, d = op.batch, op.dev, S.shape[0]
+    Pt = _to_dev(P, dev, torch.complex128)
+    Pt = Pt.reshape((1,) * (S.ndim - Pt.ndim) + tuple(Pt.shape))
+    try:
+        full = tuple(np.broadcast_shapes(batch, S.shape[1:], tuple(Pt.shape[:-1])))
+    except ValueError as e:
+        raise ValueError(f"Shapes of the batch, {pname}[1:] and {cname}[:-1] are not broadcastable\n"
+                         f"batch shape={batch}\ntuple({pname}.shape)={tuple(S.shape)}\ntuple({cname}.shape)={tuple(Pt.shape)}") from e
+    axes = _RhsAxes.of(batch, full)
+    shared = all(S.shape[1 + i] == 1 for i in axes.rhs_axes)
+    S = S[list(op.perm)]                                              # canonical component i = the caller's perm[i], as the centres
+    o_full = tuple(1 if (shared and i in axes.rhs_axes) else full[i] for i in range(len(full)))
+    batched = int(any(S.shape[1 + i] != 1 for i in axes.op_axes))
+    t = torch.as_tensor(np.moveaxis(np.broadcast_to(S, (d,) + o_full), 0, -1).copy(), device=dev)
+    pts = _RhsAxes.of(batch, o_full).lay_out(t)                       # [nb, n_origin, d]
+    pts = pts if batched else pts[:1].contiguous()
+    if not regular:
+        _check_sources_outside(op, pts, pname)
+    tree = op.plan.tree
+    n_list = max(n_in, int(op.n_end))
+    lists = _plan(tree, n_list, dev)
+    coef_batched = int(any(Pt.shape[i] != 1 for i in axes.op_axes))
+    placed = torch.zeros(tuple(Pt.shape[:-1]) + (lists.H,), dtype=torch.complex128, device=dev)
+    placed[..., torch.as_tensor(_label_positions(tree, n_in, n_list, dev), device=dev)] = Pt
+    coef = axes.lay_out(placed.expand(full + (lists.H,)))             # [nb, nrhs, H_list]
+    coef = coef if coef_batched else coef[:1].contiguous()
+    index_map = torch.as_tensor(_label_positions(tree, int(op.n_end), n_list, dev).astype(np.int32), device=dev)
+    return _Expansion(pts, batched, op.per_degree, coef, coef_batched, lists, index_map, int(n_in), bool(regular)), axes
+
+
 def _nrhs(g) -> int:
     """Right-hand sides per system of a source: the samples of _boundary_samples (a tensor, or the unmixed pair of the degree-dependent
     case), _PlaneWaves or _PointSources."""
+    if isinstance(g, _Expansion):
+        return int(g.coef.shape[1])
     if isinstance(g, _CLOSED_FORM):
         return int(g.vectors.shape[1])
     return int((g if isinstance(g, torch.Tensor) else next(t for t in g if t is not None)).shape[1])
@@ -593,6 +694,8 @@ def _nrhs(g) -> int:
 def _sample_ptrs(g, s0: int = 0):
     """The source arguments of an entry point from system s0 on: (d_g,) or (d_gu, d_gdn), a missing set as the null pointer; plane
     waves and point sources: (per_degree, d_dirs or d_src, batched); multipoles: d_idx after them."""
+    if isinstance(g, _Expansion):
+        return (int(g.per_degree),) + g.source_args(s0)
     if isinstance(g, _CLOSED_FORM):
         args = (int(g.per_degree), _ptr(g.vectors[s0:] if g.batched else g.vectors), g.batched)
         return args + (_ptr(g.index[s0:] if g.batched else g.index),) if isinstance(g, _MultipoleSources) else args
@@ -603,6 +706,9 @@ def _sample_ptrs(g, s0: int = 0):
 
 def _pick_systems(g, idx: torch.Tensor):
     """The source of the systems idx (a device index tensor) alone."""
+    if isinstance(g, _Expansion):
+        pts, coef = (g.pts[idx].contiguous() if g.batched else g.pts), (g.coef[idx].contiguous() if g.coef_batched else g.coef)
+        return _Expansion(pts, g.batched, g.per_degree, coef, g.coef_batched, g.lists, g.index_map, g.n_in, g.regular)
     if isinstance(g, _CLOSED_FORM):
         if not g.batched:
             return g
@@ -666,7 +772,7 @@ def _rhs_project(op: _Operator, n: int, g, s0: int, f: torch.Tensor, sys_stride:
         work = torch.empty(max(wb, 16), dtype=torch.uint8, device=op.dev)
         rc = getattr(L.load(), g.rhs_entry)(op.plan.handle, n, fl.B, _nrhs(g), _ptr(fl.k[s0:]), _ptr(fl.centers[s0:] if fl.geom_batched else fl.centers),
                                             fl.geom_batched, _ptr(tab), *_sample_ptrs(g, s0)[1:], _ptr(f), sys_stride, elem_stride, rhs_stride,
-                                            _ptr(work), wb, sp)
+                                            *((0,) if isinstance(g, _Expansion) else ()), _ptr(work), wb, sp)      # (expansions: stage 0)
         _check_closed_form(g, rc, g.rhs_entry)
         return
     entry, what = _entry("biem_rhs_project", op.per_degree)

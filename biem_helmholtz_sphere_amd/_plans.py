@@ -65,3 +65,22 @@ def _plan(tree: str, n_end: int, dev: torch.device) -> _Plan:
     if p is None:
         p = _PLANS[key] = _Plan(tree, int(n_end), torch.device("cuda", key[2]))
     return p
+
+
+_POSITIONS: dict = {}
+
+
+def _label_positions(tree: str, n_small: int, n_big: int, dev: torch.device) -> np.ndarray:
+    """Per harmonic of the plan of order n_small its position on the axis of the plan of order n_big >= n_small, matched by label and
+    degree (int64; the axis of a larger order does not begin with the smaller one for every tree)."""
+    small, big = _plan(tree, n_small, dev), _plan(tree, n_big, dev)
+    key = (id(small), id(big))
+    pos = _POSITIONS.get(key)
+    if pos is None:
+        if small is big:
+            pos = np.arange(small.H, dtype=np.int64)
+        else:
+            where = {tuple(lab) + (int(n),): i for i, (lab, n) in enumerate(zip(big.labels.tolist(), big.degrees.tolist()))}
+            pos = np.array([where[tuple(lab) + (int(n),)] for lab, n in zip(small.labels.tolist(), small.degrees.tolist())], dtype=np.int64)
+        _POSITIONS[key] = pos
+    return pos

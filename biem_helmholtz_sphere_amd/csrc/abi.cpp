@@ -693,6 +693,64 @@ int biem_solve_factored_rw(const biem_plan* plan, int nb, int B, int nrhs, const
                              work_bytes, (hipStream_t)stream);
 }
 
+// ---- incident fields by their expansion coefficients (kernels_rhs_ex.hip): the seventh source; whole coefficient vectors against the
+//      columns the _ms / _rw entries take one at a time ----
+#define NEED_EX(who)                                                                                                                      \
+  NEED_AS(who, d_origin, "d_origin"); NEED_AS(who, d_coef, "d_coef"); NEED_DEV_AS(who, list_plan);                                         \
+  if (list_plan != plan) NEED_AS(who, d_map, "d_map")
+#define EX_SOURCE RhsSource::expansion(regular != 0, d_origin, origin_batched, n_origin, d_coef, coef_batched, list_plan, d_map, n_in, d_k, d_centers, geom_batched)
+
+size_t biem_rhs_expansion_workspace_bytes(const biem_plan* list_plan, int nb, int B, int n_origin) {
+  return list_plan ? rhs_expansion_workspace_bytes(list_plan, nb, B, n_origin) : 0;
+}
+
+int biem_rhs_expansion(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_centers, int geom_batched,
+                       const double* d_tab, const double* d_origin, int origin_batched, int n_origin, const double* d_coef, int coef_batched,
+                       const biem_plan* list_plan, const int* d_map, int n_in, int regular, double* d_f, long long sys_stride,
+                       long long elem_stride, long long rhs_stride, int stage, void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_centers, "d_centers"); NEED(d_tab, "d_tab"); NEED(d_f, "d_f"); NEED(d_work, "d_work");
+  NEED_EX(__func__);
+  const RhsSource src = EX_SOURCE;
+  if (const int rc = src.check(__func__, plan, nb, nrhs)) return rc;
+  const size_t need = src.work_bytes(plan, nb, B, nrhs);
+  if (work_bytes < need) { set_error("%s: workspace too small (%zu < %zu)", __func__, work_bytes, need); return BIEM_ERR_ARG; }
+  return launch_rhs_expansion(plan, list_plan, d_map, n_in, regular != 0, nb, B, nrhs, d_k, d_centers, geom_batched, d_tab, d_origin, origin_batched,
+                              n_origin, d_coef, coef_batched, d_f, sys_stride, elem_stride, rhs_stride, (hipStream_t)stream, false, SplitMap(), stage,
+                              d_work);
+}
+
+int biem_solve_ex(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_origin, int origin_batched, int n_origin, const double* d_coef, int coef_batched, const biem_plan* list_plan,
+                  const int* d_map, int n_in, int regular, double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes,
+                  void* stream) {
+  NEED_EX(__func__);
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    EX_SOURCE, d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, false);
+}
+
+int biem_solve_ldlt_ex(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k, const double* d_eta, const double* d_centers,
+                       const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                       const double* d_origin, int origin_batched, int n_origin, const double* d_coef, int coef_batched,
+                       const biem_plan* list_plan, const int* d_map, int n_in, int regular, double* d_density, int* d_info, int chunk,
+                       void* d_work, size_t work_bytes, void* stream) {
+  NEED_EX(__func__);
+  return solve_path(__func__, plan, nb, B, nrhs, d_k, d_eta, d_centers, d_radii, geom_batched, {d_alpha, d_beta, ab_batched, per_degree != 0},
+                    EX_SOURCE, d_density, d_info, chunk, d_work, work_bytes, (hipStream_t)stream, true);
+}
+
+int biem_solve_factored_ex(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k, const double* d_centers, int geom_batched, const double* d_alpha,
+                           const double* d_beta, int ab_batched, int per_degree, const double* d_origin, int origin_batched, int n_origin,
+                           const double* d_coef, int coef_batched, const biem_plan* list_plan, const int* d_map, int n_in, int regular,
+                           double* d_density, void* d_work, size_t work_bytes, void* stream) {
+  NEED_EX(__func__);
+  return solve_factored_path(__func__, plan, nb, B, nrhs, d_F, lda, sys_stride, d_tab, {d_alpha, d_beta, ab_batched, per_degree != 0}, EX_SOURCE,
+                             d_density, d_work, work_bytes, (hipStream_t)stream);
+}
+#undef EX_SOURCE
+#undef NEED_EX
+
 // ---- outgoing coefficients of the whole cluster about an origin (kernels_cluster.hip) ----
 size_t biem_cluster_coefficients_workspace_bytes(const biem_plan* plan, int nb, int B, int nrhs) {
   return plan ? cluster_coefficients_workspace_bytes(plan, nb, B, nrhs) : 0;
@@ -714,7 +772,14 @@ int biem_multipole_field(biem_plan* plan, int nb, int P, const double* d_k, cons
                          int flags, int grad, double* d_out, void* d_work, size_t work_bytes, void* stream) {
   NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_src, "d_src"); NEED(d_idx, "d_idx"); NEED(d_points, "d_points"); NEED(d_out, "d_out"); NEED(d_work, "d_work");
   if (grad) { if (const int rc = build_force_table(__func__, plan)) return rc; }
-  return launch_multipole_field(plan, nb, P, d_k, d_src, d_idx, d_points, flags, grad, d_out, d_work, work_bytes, (hipStream_t)stream);
+  return launch_multipole_field(__func__, plan, nb, P, d_k, d_src, d_idx, nullptr, d_points, flags, grad, d_out, d_work, work_bytes, (hipStream_t)stream);
+}
+
+int biem_expansion_field(biem_plan* plan, int nb, int P, const double* d_k, const double* d_origin, const double* d_coef, const double* d_points,
+                         int flags, int grad, double* d_out, void* d_work, size_t work_bytes, void* stream) {
+  NEED_DEV(plan); NEED(d_k, "d_k"); NEED(d_origin, "d_origin"); NEED(d_coef, "d_coef"); NEED(d_points, "d_points"); NEED(d_out, "d_out"); NEED(d_work, "d_work");
+  if (grad) { if (const int rc = build_force_table(__func__, plan)) return rc; }
+  return launch_multipole_field(__func__, plan, nb, P, d_k, d_origin, nullptr, d_coef, d_points, flags, grad, d_out, d_work, work_bytes, (hipStream_t)stream);
 }
 
 // ---- extinction and absorbed power (kernels_power.hip), radiation force (kernels_force.hip) ----

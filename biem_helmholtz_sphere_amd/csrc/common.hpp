@@ -163,6 +163,23 @@ int launch_rhs_multipole(const biem_plan* p, int nb, int B, int nrhs, const doub
 long long rhs_table_slice_pairs(const biem_plan* p, int nb, int B, int nrhs);
 int launch_regular_tables(const biem_plan* p, int B, int nrhs, long long sr0, long long rows, const double* d_k, const double* d_centers,
                           int geom_batched, const double* d_src, int src_batched, int flip, double* d_T, hipStream_t st);
+// the same rows with the outgoing radial function (regular == false): T[row][H2] = C_d h_n''(k |t|) Y_l(t^)
+int launch_translation_tables(const biem_plan* p, bool regular, int B, int nrhs, long long sr0, long long rows, const double* d_k,
+                              const double* d_centers, int geom_batched, const double* d_src, int src_batched, int flip, double* d_T,
+                              hipStream_t st);
+// incident fields by their expansion coefficients (kernels_rhs_ex.hip): u_in = sum_h' p_h' z_n'(k |x - o|) Y_h'((x - o)^), z = j (regular) or h,
+// f = -gj_n sum_{n(h') < n_in} p_h' (X|R)_{h'->h}(c_b - o), written where launch_rhs_project writes for the solve plan p.  lp: the LIST plan of
+// the same tree, of order max(n_in, n_end) (p itself where n_in <= n_end): its term lists, table labels and harmonic axis, along which
+// d_coef [nrhs][H(lp)] or (coef_batched) [nb][nrhs][H(lp)] lies; d_map [H(p)]: the position of every harmonic of p on that axis (null with
+// lp == p).  d_origin [n_origin][d] or (origin_batched) [nb][n_origin][d], n_origin 1 (one origin for all right-hand sides of a system: the
+// table rows are formed once) or nrhs.  d_work: rhs_expansion_workspace_bytes, the table rows of one slice.  stage: 0; 1 / 2 the table
+// rows / the contraction alone (timing; 1 then 2 is 0 only for a call of one table slice - the workspace holds one).  The count and order limits are RhsSource::check's to refuse (on lp).
+size_t rhs_expansion_workspace_bytes(const biem_plan* lp, int nb, int B, int n_origin);
+int launch_rhs_expansion(const biem_plan* p, const biem_plan* lp, const int* d_map, int n_in, bool regular, int nb, int B, int nrhs,
+                         const double* d_k, const double* d_centers, int geom_batched, const double* d_tab, const double* d_origin,
+                         int origin_batched, int n_origin, const double* d_coef, int coef_batched, double* d_f, long long sys_stride,
+                         long long elem_stride, long long rhs_stride, hipStream_t st, bool slot_order, const SplitMap& split, int stage,
+                         void* d_work);
 // outgoing coefficients of the whole cluster about an origin (kernels_cluster.hip): A[s][r][h''] = sum_b sum_h (R|R)_{h->h''}(o_s - c_b) c[s][r][b][h],
 // c = density * blc.  d_density [nb][nrhs][B][H] in the plan's layout (degrees >= n_src are not read), d_origin [d] or (origin_batched) [nb][d],
 // d_out [nb][nrhs][H]; kind outer.  stage: 0 both, 1 the table rows only, 2 the contraction only (timing; slices then walk one stage)
@@ -228,9 +245,12 @@ int launch_uscat_hess(const biem_plan* p, int nb, int B, int P, const double* d_
 // plan's harmonic axis; out [P][nb], or (grad) its Cartesian gradient [d][P][nb] - p is then a plan of order n' + 2 or more with its force
 // coupling table uploaded.  flags: BIEM_USCAT_POINTS_BATCHED, and BIEM_USCAT_KIND_INNER for the regular wave j_n' Y_h' about d_src (the
 // kind-inner value kernels on the unit coefficient, the fictitious ball unbounded: every point is an ordinary one, x = d_src included)
+// The field of a whole coefficient vector about d_src instead (biem_expansion_field, `who`): d_idx null and d_coef [nb][H] along the
+// plan's harmonic axis, copied where the unit set is written; the gradient reads its degrees < n_end - 1.  One body for both.
 size_t multipole_field_workspace_bytes(const biem_plan* p, int nb);
-int launch_multipole_field(const biem_plan* p, int nb, int P, const double* d_k, const double* d_src, const int* d_idx, const double* d_points,
-                           int flags, int grad, double* d_out, void* d_work, size_t work_bytes, hipStream_t st);
+int launch_multipole_field(const char* who, const biem_plan* p, int nb, int P, const double* d_k, const double* d_src, const int* d_idx,
+                           const double* d_coef, const double* d_points, int flags, int grad, double* d_out, void* d_work, size_t work_bytes,
+                           hipStream_t st);
 // per-lane order ceiling of a tree (kernels_uscat.hip: kFastNendMax*; 0 for the chain trees)
 int uscat_fast_nend_max(int tree);
 // total field inside penetrable fluid balls (kernels_uinterior.hip).  d_kint / d_delta [nb or 1][B] complex; the coefficient step
@@ -294,15 +314,20 @@ struct BoundaryCoef {
 //   POINT_SOURCES  point sources at pts = src in closed form (launch_rhs_point_source)
 //   MULTIPOLE_SOURCES  outgoing multipoles at pts = src of the harmonics idx in closed form (launch_rhs_multipole)
 //   REGULAR_WAVES  regular waves about the origins pts of the harmonics idx in closed form (launch_rhs_multipole, regular)
+//   REGULAR_EXPANSION / MULTIPOLE_EXPANSION  whole coefficient vectors `coef` of regular / outgoing waves about the origins pts
+//                  (launch_rhs_expansion): the columns the two kinds above take one at a time, contracted
 // The closed forms read the wavenumbers, centres and ball tables of the call and keep their harmonics in `work`, work_bytes() of them:
 // the caller's workspace, or (set by the whole path) the tail of its own.
 struct RhsSource {
-  enum Kind { SAMPLES, SAMPLES_N, PLANE_WAVES, POINT_SOURCES, MULTIPOLE_SOURCES, REGULAR_WAVES };
+  enum Kind { SAMPLES, SAMPLES_N, PLANE_WAVES, POINT_SOURCES, MULTIPOLE_SOURCES, REGULAR_WAVES, REGULAR_EXPANSION, MULTIPOLE_EXPANSION };
   Kind kind;
   const double* g[2] = {nullptr, nullptr};                 // samples: g, or gu and gdn
   const double* pts = nullptr; int pts_batched = 0;        // closed forms: [nrhs][d], or (pts_batched) [nb][nrhs][d], in the plan's axes
   const int* idx = nullptr;                                // multipoles: the harmonic of every source, [nrhs] or (pts_batched) [nb][nrhs]
   const double* k = nullptr; const double* centers = nullptr; int geom_batched = 0;
+  // expansions: the coefficient vectors [nrhs][H(lists)] or (coef_batched) [nb][nrhs][H(lists)], the list plan, the map of the solve
+  // plan's harmonics onto its axis (null: the same plan), the order of the coefficients and the origins per system (pts: 1 or nrhs)
+  const double* coef = nullptr; int coef_batched = 0; const biem_plan* lists = nullptr; const int* map = nullptr; int n_in = 0, n_origin = 0;
   void* work = nullptr;
 
   static RhsSource samples(const double* g) { RhsSource s(SAMPLES); s.g[0] = g; return s; }
@@ -325,13 +350,24 @@ struct RhsSource {
     return s;
   }
 
-  bool translated() const { return kind == MULTIPOLE_SOURCES || kind == REGULAR_WAVES; }   // a column of the translation operator
+  static RhsSource expansion(bool regular, const double* origin, int batched, int n_origin, const double* coef, int coef_batched,
+                             const biem_plan* lists, const int* map, int n_in, const double* k, const double* centers, int geom_batched) {
+    RhsSource s(regular ? REGULAR_EXPANSION : MULTIPOLE_EXPANSION, origin, batched, k, centers, geom_batched);
+    s.coef = coef; s.coef_batched = coef_batched; s.lists = lists; s.map = map; s.n_in = n_in; s.n_origin = n_origin;
+    return s;
+  }
+
+  bool expanded() const { return kind == REGULAR_EXPANSION || kind == MULTIPOLE_EXPANSION; }   // a coefficient vector against the columns
+  // columns of the translation operator: the order limits, the term lists and the table rows of `table_plan`
+  bool translated() const { return kind == MULTIPOLE_SOURCES || kind == REGULAR_WAVES || expanded(); }
+  const biem_plan* table_plan(const biem_plan* p) const { return expanded() && lists ? lists : p; }
   bool closed_form() const { return kind == PLANE_WAVES || kind == POINT_SOURCES || translated(); }
   // the same source for the systems s0 .. of the call
   RhsSource at(const biem_plan* p, int s0, int nrhs, int B) const {
     RhsSource s = *this;
     for (const double*& x : s.g) if (x) x += (size_t)s0 * nrhs * B * p->Q * 2;
-    if (pts && pts_batched) s.pts += (size_t)s0 * nrhs * p->d;
+    if (pts && pts_batched) s.pts += (size_t)s0 * (expanded() ? n_origin : nrhs) * p->d;
+    if (coef && coef_batched) s.coef += (size_t)s0 * nrhs * table_plan(p)->H * 2;
     if (idx && pts_batched) s.idx += (size_t)s0 * nrhs;
     if (k) s.k += 2 * (size_t)s0;
     if (centers && geom_batched) s.centers += (size_t)s0 * B * p->d;
@@ -340,6 +376,7 @@ struct RhsSource {
   size_t work_bytes(const biem_plan* p, int nb, int B, int nrhs) const {
     return kind == PLANE_WAVES ? rhs_plane_wave_workspace_bytes(p, nb, nrhs, pts_batched)
          : kind == POINT_SOURCES ? rhs_point_source_workspace_bytes(p, nb, B, nrhs, pts_batched, geom_batched)
+         : expanded() ? rhs_expansion_workspace_bytes(table_plan(p), nb, B, n_origin)
          : translated() ? rhs_multipole_workspace_bytes(p, nb, B, nrhs, pts_batched, geom_batched) : 0;
   }
   // what the closed forms cannot take (grid dimensions; the thread-local radial table of a (source, ball) pair): refused under the

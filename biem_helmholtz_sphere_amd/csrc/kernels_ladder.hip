@@ -83,13 +83,14 @@ int launch_uscat_hess(const biem_plan* p, int nb, int B, int P, const double* d_
 // s, radius 0, with the unit coefficient set delta_{h, idx}; its gradient: one ladder step per component, then the value kernels
 // (launch_uscat_hess's route taken once).  The regular wave j_n' Y_h' about s (BIEM_USCAT_KIND_INNER): the kind-inner value kernels on the
 // same unit set, the fictitious ball of infinite radius - kind inner masks r > rho only, so every point is an ordinary one, x = s included.
-// c[s][h] = delta_{h, idx[s]}; an index outside [0, H) leaves the set zero
-__global__ void __launch_bounds__(256) k_unit_coef(int H, long long count, const int* __restrict__ idx, cplx* __restrict__ c, double* __restrict__ radii,
-                                                    double radius) {
+// A whole expansion about s (biem_expansion_field): the caller's coefficient set in place of the unit one, everything else unchanged.
+// c[s][h] = delta_{h, idx[s]}; an index outside [0, H) leaves the set zero.  idx null: c = coef
+__global__ void __launch_bounds__(256) k_unit_coef(int H, long long count, const int* __restrict__ idx, const cplx* __restrict__ coef,
+                                                    cplx* __restrict__ c, double* __restrict__ radii, double radius) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
     const long long s = i / H;
     const int h = (int)(i - s * H);
-    c[i] = make_double2(idx[s] == h ? 1.0 : 0.0, 0.0);
+    c[i] = idx ? make_double2(idx[s] == h ? 1.0 : 0.0, 0.0) : coef[i];
     if (h == 0) radii[s] = radius;
   }
 }
@@ -99,9 +100,9 @@ size_t multipole_field_workspace_bytes(const biem_plan* p, int nb) {
   return nb <= 0 ? 0 : 2 * align256((size_t)nb * p->H * sizeof(cplx)) + align256((size_t)nb * sizeof(double));
 }
 
-int launch_multipole_field(const biem_plan* p, int nb, int P, const double* d_k, const double* d_src, const int* d_idx, const double* d_points,
-                           int flags, int grad, double* d_out, void* d_work, size_t work_bytes, hipStream_t st) {
-  const char* who = "biem_multipole_field";
+int launch_multipole_field(const char* who, const biem_plan* p, int nb, int P, const double* d_k, const double* d_src, const int* d_idx,
+                           const double* d_coef, const double* d_points, int flags, int grad, double* d_out, void* d_work, size_t work_bytes,
+                           hipStream_t st) {
   if (flags & ~(BIEM_USCAT_POINTS_BATCHED | BIEM_USCAT_KIND_INNER)) { set_error("%s: flags other than BIEM_USCAT_POINTS_BATCHED and BIEM_USCAT_KIND_INNER (%d)", who, flags); return BIEM_ERR_ARG; }
   if (grad && p->n_end < 2) { set_error("%s: the gradient needs the plan of order n' + 2 of the source's degree n', at least 2 (n_end=%d)", who, p->n_end); return BIEM_ERR_ARG; }
   if (grad && !p->force_uploaded) { set_error("%s: the plan's force coupling table is not on the device", who); return BIEM_ERR_ARG; }
@@ -119,13 +120,13 @@ int launch_multipole_field(const biem_plan* p, int nb, int P, const double* d_k,
   cplx* g = (cplx*)((char*)d_work + set);
   double* radii = (double*)((char*)d_work + 2 * set);
   const long long count = (long long)nb * p->H;
-  hipLaunchKernelGGL(k_unit_coef, dim3((unsigned)((count + 255) / 256 < 65536 ? (count + 255) / 256 : 65536)), dim3(256), 0, st, p->H, count, d_idx, c, radii,
+  hipLaunchKernelGGL(k_unit_coef, dim3((unsigned)((count + 255) / 256 < 65536 ? (count + 255) / 256 : 65536)), dim3(256), 0, st, p->H, count, d_idx, (const cplx*)d_coef, c, radii,
                      (flags & BIEM_USCAT_KIND_INNER) ? (double)INFINITY : 0.0);
   BIEM_LAUNCHCHK();
   if (!grad) return uscat_eval_coef(p, nb, 1, P, d_k, d_src, radii, 1, c, d_points, flags, d_out, st);
   const size_t per = (size_t)P * nb * 2;                     // doubles of one component of the result
   for (int i = 0; i < p->d; ++i) {
-    // (the set has one entry, of a degree the caller keeps below n_end - 1: the step stays inside the plan)
+    // (the set's entries are of degrees the caller keeps below n_end - 1 - others are not read -: the step stays inside the plan)
     ladder(p, nb, 1, i, p->n_end - 1, d_k, c, g, st);
     BIEM_LAUNCHCHK();
     if ((rc = uscat_eval_coef(p, nb, 1, P, d_k, d_src, radii, 1, g, d_points, flags, d_out + (size_t)i * per, st)) != BIEM_OK) return rc;

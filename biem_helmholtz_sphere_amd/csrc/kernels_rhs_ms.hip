@@ -25,6 +25,7 @@
 // j_l(0) = delta_{l0} j_0(0) and a fixed unit vector, so (R|R)(0) is the identity with exact zeros off the diagonal.
 // launch_regular_tables hands the table stage to the cluster coefficients (kernels_cluster.hip), which take t from the other end (flip).
 #include "common.hpp"
+#include "rhs_translate.hpp"
 #include <climits>
 #include <cstdlib>
 
@@ -33,37 +34,6 @@ namespace {
 constexpr size_t kRhsTableBytes = (size_t)512 << 20;   // table rows of one slice of (systems x right-hand sides)
 constexpr long long kGridMax = 1 << 20;                // workgroups of a strided launch
 inline unsigned strided_grid(long long groups) { return (unsigned)(groups < kGridMax ? groups : kGridMax); }
-
-// the centre, the source and the system of table row `row` = (sr - sr0) B + b, sr = s nrhs + r
-struct MsRow { long long s; int r, b; };
-__device__ inline MsRow ms_row(long long row, long long sr0, int B, int nrhs) {
-  const long long sr = sr0 + row / B;
-  return {sr / nrhs, (int)(sr % nrhs), (int)(row % B)};
-}
-// t = c_b - s_r (the sign of a pair table's c_b - c_b'; k_ps_geometry has s - c); flip: t = s_r - c_b
-__device__ inline void ms_displacement(const MsRow& w, int d, int B, int nrhs, const double* __restrict__ centers, int geom_batched,
-                                       const double* __restrict__ src, int src_batched, double* t, double* dist, bool flip = false) {
-  const double* c = centers + ((geom_batched ? w.s * B : 0) + w.b) * d;
-  const double* x = src + ((src_batched ? w.s * nrhs : 0) + w.r) * d;
-  double r2 = 0.0;
-  for (int i = 0; i < d; ++i) { t[i] = flip ? x[i] - c[i] : c[i] - x[i]; r2 += t[i] * t[i]; }
-  *dist = sqrt(r2);
-}
-// the radial row of a table at z = k |t|, orders 0 .. nmax, by one lane.  REG: the regular functions alone (sH is not written); at
-// |t| = 0 they are j_l(0) = delta_{l0} j_0(0), written as such - the recurrences divide by z
-template <bool REG>
-__device__ inline void ms_radial_row(int d, int nmax, cplx kk, double dist, cplx* sJ, cplx* sH) {
-  if (REG && dist == 0.0) {
-    const double z0 = radial_z0_at_zero(d);
-    for (int n = 0; n <= nmax; ++n) sJ[n] = make_double2(n == 0 ? z0 : 0.0, 0.0);
-    return;
-  }
-  radial_jh(d, nmax, cscale(kk, dist), sJ, REG ? nullptr : sH);
-}
-// |t| = 0 has no direction: any fixed unit vector does (its harmonics are finite, and only degree 0 meets a nonzero radial value)
-__device__ inline void ms_unit_if_zero(int d, double dist, double* t) {
-  if (dist == 0.0) { t[0] = 1.0; for (int i = 1; i < d; ++i) t[i] = 0.0; }
-}
 
 // plain table rows T[row][H2] = C_d h_n''(k_s |t|) Y_l(t^) of the rows [0, rows) of a slice: one workgroup per row (strided), lane 0 runs the
 // radial recurrence into LDS, then one label per lane, every label from scratch (k_pair_tables' generic branch; chain trees: chain_harmonic).
@@ -133,8 +103,6 @@ __global__ void __launch_bounds__(256) k_rhs_ms(int H, int H2, int n_end, int B,
   }
 }
 
-__device__ inline double sign_even(int e) { return ((e / 2) & 1) ? -1.0 : 1.0; }      // i^e for even e (either sign)
-
 // tree a: one workgroup per (s, r, b) (strided), the radial row h_j(k_s |t|) (REG: j_j), j < 2 n_end - 1, in LDS, one harmonic per lane
 template <bool REG>
 __global__ void __launch_bounds__(256) k_rhs_ms_2d(int n_end, int H, double Cd, const int* __restrict__ labels, int B, int nrhs, long long rows,
@@ -163,7 +131,7 @@ __global__ void __launch_bounds__(256) k_rhs_ms_2d(int n_end, int H, double Cd, 
       double sn, cs;
       sincos((double)mu * phi, &sn, &cs);
       // T'[j] = C_2 h_j / sqrt(2 pi) times the phase, times i^{|m| + |mu| - |m'|} / sqrt(2 pi): k_fill2d's entry
-      const cplx raw = cscale(cmul(cscale(sR[j], Cd * kInvSqrt2Pi), make_double2(cs, sn)), sign_even(am + j - amp) * kInvSqrt2Pi);
+      const cplx raw = cscale(cmul(cscale(sR[j], Cd * kInvSqrt2Pi), make_double2(cs, sn)), ms_sign_even(am + j - amp) * kInvSqrt2Pi);
       const cplx v = ok ? cscale(cmul(gj[am], raw), -1.0) : make_double2(nan(""), nan(""));
       fs[sm.rhs_off(w.b, H, hpos ? hpos[h] : h, elem_stride)] = v;
     }
@@ -186,12 +154,18 @@ long long ms_slice_pairs(const biem_plan* p, int nb, int B, int nrhs) {
 
 long long rhs_table_slice_pairs(const biem_plan* p, int nb, int B, int nrhs) { return ms_slice_pairs(p, nb, B, nrhs); }
 
-int launch_regular_tables(const biem_plan* p, int B, int nrhs, long long sr0, long long rows, const double* d_k, const double* d_centers,
-                          int geom_batched, const double* d_src, int src_batched, int flip, double* d_T, hipStream_t st) {
-  hipLaunchKernelGGL(k_ms_tables<true>, dim3(strided_grid(rows)), dim3(256), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd, p->d_labels2, p->d_deg2,
-                     B, nrhs, sr0, rows, (const cplx*)d_k, d_centers, geom_batched, d_src, src_batched, flip, (cplx*)d_T);
+int launch_translation_tables(const biem_plan* p, bool regular, int B, int nrhs, long long sr0, long long rows, const double* d_k,
+                              const double* d_centers, int geom_batched, const double* d_src, int src_batched, int flip, double* d_T,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(regular ? k_ms_tables<true> : k_ms_tables<false>, dim3(strided_grid(rows)), dim3(256), 0, st, p->tree, p->d, p->n2, p->H2, p->Cd,
+                     p->d_labels2, p->d_deg2, B, nrhs, sr0, rows, (const cplx*)d_k, d_centers, geom_batched, d_src, src_batched, flip, (cplx*)d_T);
   BIEM_LAUNCHCHK();
   return BIEM_OK;
+}
+
+int launch_regular_tables(const biem_plan* p, int B, int nrhs, long long sr0, long long rows, const double* d_k, const double* d_centers,
+                          int geom_batched, const double* d_src, int src_batched, int flip, double* d_T, hipStream_t st) {
+  return launch_translation_tables(p, true, B, nrhs, sr0, rows, d_k, d_centers, geom_batched, d_src, src_batched, flip, d_T, st);
 }
 
 size_t rhs_multipole_workspace_bytes(const biem_plan* p, int nb, int B, int nrhs, int src_batched, int geom_batched) {

@@ -168,13 +168,15 @@ int RhsSource::check(const char* who, const biem_plan* p, int nb, int nrhs) cons
     return BIEM_ERR_UNSUPPORTED;
   }
   if (translated()) {
-    // tree a: the radial row of a (source, ball) pair in LDS, orders < 2 n_end - 1; every other tree: the term lists, built up to half that
-    if (p->tree == TREE_A ? p->n_end > kMaxRad : 2 * p->n_end > kMaxRad) {
-      set_error("%s: n_end=%d exceeds the built table size %d of the %s right-hand side", who, p->n_end, p->tree == TREE_A ? kMaxRad : kMaxRad / 2,
-                kind == REGULAR_WAVES ? "regular-wave" : "multipole");
+    // tree a: the radial row of a (source, ball) pair in LDS, orders < 2 n_end - 1; every other tree: the term lists, built up to half that.
+    // Expansions: the same limits on the plan whose lists and labels they read
+    const biem_plan* t = table_plan(p);
+    const char* what = kind == REGULAR_WAVES ? "regular-wave" : kind == MULTIPOLE_SOURCES ? "multipole" : "expansion";
+    if (t->tree == TREE_A ? t->n_end > kMaxRad : 2 * t->n_end > kMaxRad) {
+      set_error("%s: n_end=%d exceeds the built table size %d of the %s right-hand side", who, t->n_end, t->tree == TREE_A ? kMaxRad : kMaxRad / 2, what);
       return BIEM_ERR_UNSUPPORTED;
     }
-    if (p->tree != TREE_A && (!p->lists_built || p->ptr.empty() || !p->d_ptr)) {
+    if (t->tree != TREE_A && (!t->lists_built || t->ptr.empty() || !t->d_ptr)) {
       set_error("%s: the plan has no translation term lists", who);
       return BIEM_ERR_UNSUPPORTED;
     }
@@ -200,6 +202,11 @@ int RhsSource::launch(const biem_plan* p, int nb, int B, int nrhs, const Boundar
     case REGULAR_WAVES:
       return launch_rhs_multipole(p, nb, B, nrhs, k, centers, geom_batched, d_tab, pts, pts_batched, idx, d_f, sys_stride, elem_stride,
                                   rhs_stride, st, slot_order, split, work, kind == REGULAR_WAVES);
+    case REGULAR_EXPANSION:
+    case MULTIPOLE_EXPANSION:
+      return launch_rhs_expansion(p, table_plan(p), map, n_in, kind == REGULAR_EXPANSION, nb, B, nrhs, k, centers, geom_batched, d_tab, pts,
+                                  pts_batched, n_origin, coef, coef_batched, d_f, sys_stride, elem_stride, rhs_stride, st, slot_order, split, 0,
+                                  work);
   }
   return BIEM_ERR_ARG;
 }

@@ -553,6 +553,58 @@ int biem_solve_factored_rw(const biem_plan* plan, int nb, int B, int nrhs, const
                            const double* d_alpha, const double* d_beta, int ab_batched, int per_degree, const double* d_origin,
                            int origin_batched, const int* d_idx, double* d_density, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- incident fields by their expansion coefficients: beams, standing waves, the near field of a neighbouring cluster
+ *      as ONE right-hand side.  u_in(x) = sum_h' p_h' z_n'(k |x - o|) Y_h'((x - o)^) with z = j (regular != 0; any origin) or z = h (the
+ *      origin strictly outside every ball: NOT TESTED HERE), and
+ *        f(s, r, b, h) = -gj_{n(h)}(s, b) sum_{h' : n(h') < n_in} p[s, r, h'] (X|R)_{h'->h}(c_b - o),   X = R or S:
+ *      the columns biem_rhs_regular_wave / biem_rhs_multipole take one at a time, contracted with whole coefficient vectors.  The order
+ *      n_in of the coefficients is independent of the order of `plan`: `list_plan` is a plan of the same tree of order max(n_in, n_end)
+ *      (`plan` itself where n_in <= n_end) whose term lists, table labels and harmonic axis are read; d_coef [nrhs][H(list_plan)] complex128,
+ *      or [nb][nrhs][H(list_plan)] with coef_batched != 0, lies along that axis (biem_plan_labels; entries of degree >= n_in are not read),
+ *      and d_map [H(plan)] holds the position of every harmonic of `plan` on it, matched by label (may be null with list_plan == plan).
+ *      d_origin [n_origin][d], or [nb][n_origin][d] with origin_batched != 0; n_origin is 1 - one origin for all right-hand sides of a
+ *      system: the table rows are formed once per (system, ball) and a lane applies each translation entry to 8 right-hand sides - or
+ *      nrhs.  f is written where biem_rhs_project writes it for `plan`.  d >= 3: the table row and the coefficient vectors of a workgroup
+ *      sit in LDS while they fit 152 KiB (BIEM_RHS_EX_LDS_BYTES=n in the environment lowers that, read per call), else they are read
+ *      from memory, by the same statements.  Every element is written by one lane in a fixed order of summation (h' ascending, then
+ *      the list's order), no atomics: two calls, any table slicing (BIEM_RHS_TABLE_BYTES), either LDS branch and any nrhs give the
+ *      same bits per right-hand side (within n_origin == 1 and within n_origin == nrhs).  stage: 0; 1 / 2 run the table rows / the
+ *      contraction alone (timing).  Stage 1 then stage 2 is stage 0 only for a call of ONE table slice: the workspace holds one slice,
+ *      so with several stage 1 leaves the last one's rows and stage 2 contracts every slice against those.  Limits and errors as biem_rhs_multipole, applied to list_plan (n_end above 320 in 2-D, above 160
+ *      elsewhere: BIEM_ERR_UNSUPPORTED); BIEM_ERR_ARG for a list plan of another tree or a lower order, n_in outside [1, n_end(list_plan)],
+ *      n_origin neither 1 nor nrhs.
+ * Workspace: biem_rhs_expansion_workspace_bytes, the table rows of one slice of (systems x origins) of list_plan (2-D: none).
+ * biem_solve_ex / biem_solve_ldlt_ex / biem_solve_factored_ex: the _rw entries with (n_origin, d_coef, coef_batched, list_plan, d_map, n_in,
+ * regular) in place of d_idx; workspace: the bytes of biem_solve_workspace_bytes (biem_solve_factored_workspace_bytes) PLUS
+ * biem_rhs_expansion_workspace_bytes, at the tail. ---- */
+size_t biem_rhs_expansion_workspace_bytes(const biem_plan* list_plan, int nb, int B, int n_origin);
+int biem_rhs_expansion(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_centers, int geom_batched,
+                       const double* d_tab, const double* d_origin, int origin_batched, int n_origin, const double* d_coef /*c128*/,
+                       int coef_batched, const biem_plan* list_plan, const int* d_map, int n_in, int regular, double* d_f,
+                       long long sys_stride, long long elem_stride, long long rhs_stride, int stage, void* d_work, size_t work_bytes,
+                       void* stream);
+int biem_solve_ex(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta, const double* d_centers,
+                  const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta, int ab_batched, int per_degree,
+                  const double* d_origin, int origin_batched, int n_origin, const double* d_coef /*c128*/, int coef_batched,
+                  const biem_plan* list_plan, const int* d_map, int n_in, int regular, double* d_density, int* d_info, int chunk,
+                  void* d_work, size_t work_bytes, void* stream);
+int biem_solve_ldlt_ex(const biem_plan* plan, int nb, int B, int nrhs, const double* d_k /*c128*/, const double* d_eta,
+                       const double* d_centers, const double* d_radii, int geom_batched, const double* d_alpha, const double* d_beta,
+                       int ab_batched, int per_degree, const double* d_origin, int origin_batched, int n_origin,
+                       const double* d_coef /*c128*/, int coef_batched, const biem_plan* list_plan, const int* d_map, int n_in, int regular,
+                       double* d_density, int* d_info, int chunk, void* d_work, size_t work_bytes, void* stream);
+int biem_solve_factored_ex(const biem_plan* plan, int nb, int B, int nrhs, const double* d_F, long long lda, long long sys_stride,
+                           const double* d_tab, const double* d_k /*c128*/, const double* d_centers, int geom_batched,
+                           const double* d_alpha, const double* d_beta, int ab_batched, int per_degree, const double* d_origin,
+                           int origin_batched, int n_origin, const double* d_coef /*c128*/, int coef_batched, const biem_plan* list_plan,
+                           const int* d_map, int n_in, int regular, double* d_density, void* d_work, size_t work_bytes, void* stream);
+/* The field of such an expansion itself, one per system: biem_multipole_field with a coefficient vector d_coef [nb][H] complex128 along
+ * the harmonic axis of `plan` in place of the index (one body serves both; workspace: biem_multipole_field_workspace_bytes).  Flags as
+ * there: BIEM_USCAT_KIND_INNER is the regular expansion, where x = o is an ordinary point.  grad != 0: `plan` is a plan of order
+ * n_in + 1 or more, the vector placed on its axis by label; coefficients of degree >= n_end(plan) - 1 are not read. */
+int biem_expansion_field(biem_plan* plan, int nb, int P, const double* d_k /*c128*/, const double* d_origin, const double* d_coef /*c128*/,
+                         const double* d_points, int flags, int grad, double* d_out, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- the cluster's outgoing coefficients about an origin: the scattered field of all balls as one expansion,
  *        u_scat(x) = sum_h'' A_h'' h_n''(k |x - o|) Y_h''((x - o)^)  for |x - o| > max_b (|c_b - o| + rho_b),
  *        A[s][r][h''] = sum_b sum_h (R|R)_{h->h''}(o_s - c_b) c[s][r][b][h],   c = density * blc (biem_uscat's coefficients).
